@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
 """bench.py — graphs/s of the full IG-GCN train step (SGCN over 90-ROI brain graphs + GO-SNP network).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--blocks 5] [--workload full|sgcn|stress]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--blocks 5] [--workload full|sgcn|stress] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     IGCN_BENCH_SWEEP="1,2,4,8" python bench.py ...        one line per N, weak-scaling efficiency vs its own N = 1 run
 
-The timed region (--steps replays between barriers + synchronize) is repeated --blocks times; the line reports the
-MEDIAN block and the spread (`timing`).  The default line also carries the loader-fed step (`pipeline`: host feeder
-thread / device-resident dataset / device GDC one batch ahead on a side stream) and, at N > 1, the distributed step
-taken apart per rank (`distributed_step`).
+The --steps timed steps are split into --blocks blocks of (nearly) equal size, each between barriers + synchronize; the
+line reports the MEDIAN block's milliseconds per step (`ms_per_step`) and the spread (`timing`).  --dump-outputs DIR
+writes what the last timed step handed its caller (loss, updated parameters, gradients, BatchNorm statistics) as
+DIR/<name>.npy, so that two builds can be compared output for output on identical, seeded inputs.  The default line
+also carries the loader-fed step (`pipeline`: host feeder thread / device-resident dataset / device GDC one batch ahead
+on a side stream) and, at N > 1, the distributed step taken apart per rank (`distributed_step`).
 
 Default workload (BASELINE.json configs[2]): full SGCN_GCN_IMGSNP (L=2, hidden=16, R=90, H0=3,
 cross-attention fusion, 3 classes, 3 regression targets), synthetic GO DAG N=3000 pool [1800,800,300,99,1],
@@ -905,7 +907,7 @@ def stress_child(timeout=300):
     """BASELINE configs[4] beside the headline: a short ``--workload stress`` run of this script in a CHILD process
     (its own model, graph capture, in-step rocprofv3 profile and bounded CPU-oracle sample) whose result line is folded
     into the default line as ``stress``.  None (with the reason on stderr) when the child fails: the headline stands."""
-    cmd = [sys.executable, os.path.abspath(__file__), "--workload", "stress", "--steps", "10", "--warmup", "3",
+    cmd = [sys.executable, os.path.abspath(__file__), "--workload", "stress", "--steps", "30", "--warmup", "3",
            "--cpu-baseline-seconds", "8", "--no-stress", "--no-pipeline", "--blocks", "3"]
     # the child profiles into its own directory (a kept parent directory would hand it the parent's kernel summary)
     env = dict(os.environ)
@@ -963,6 +965,40 @@ def self_launch(n):
         print("bench.py: the ranks exited cleanly but printed no result line", file=sys.stderr)
         return 4
     return r.returncode
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def step_outputs(opt, model, data, loss):
+    """What one train step hands its caller, as float32 host arrays: the loss, the parameters Adam just updated, their
+    gradients (zeros for a parameter that took none), the gradient of the node features and the module buffers (BatchNorm
+    running statistics), each group flattened in ``opt.params`` / ``model.buffers()`` order."""
+    def flat(ts):
+        ts = [t.detach().reshape(-1).float() for t in ts]
+        return torch.cat(ts).cpu().numpy() if ts else None
+    out = {"loss": loss.detach().float().reshape(()).cpu().numpy(),
+           "parameters": flat(opt.params),
+           "gradients": flat(p.grad if p.grad is not None else torch.zeros_like(p) for p in opt.params),
+           "x_grad": flat([data.x.grad]) if data.x.grad is not None else None,
+           "buffers": flat(b for b in model.buffers() if b.is_floating_point())}
+    return {k: v for k, v in out.items() if v is not None}
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """Write ``arrays`` as ``out_dir/<name>.npy``.  Past ``limit`` bytes in all, every array gets a share of the limit in
+    proportion to its size and a larger one is replaced by a fixed sample of its flattened elements (seed 0, ascending
+    positions), the same from run to run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > limit:
+            keep = int(a.size * limit / total)
+            if keep < a.size:
+                idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+                a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def sweep(ns):
@@ -1025,7 +1061,7 @@ def main():
         del os.environ["NCCL_DEBUG"]
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--steps", type=int, default=30, help="timed steps in all, split over --blocks blocks")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true", help="skip the roofline measurements (and the profiler child)")
@@ -1041,7 +1077,8 @@ def main():
     ap.add_argument("--no-pipeline", action="store_true",
                     help="skip the loader-fed runs (host feeder thread / device-resident dataset / device GDC)")
     ap.add_argument("--blocks", type=int, default=5,
-                    help="the timed region (--steps steps) is repeated this many times; the median block is reported")
+                    help="the --steps timed steps are split into this many blocks (at most --steps); the median block is "
+                         "reported")
     ap.add_argument("--no-stress", action="store_true",
                     help="default workload only: skip the short configs[4] child run reported as `stress`")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=20.0, help="bound of the CPU-oracle sample")
@@ -1049,9 +1086,13 @@ def main():
                     help="also time the five (layers, hidden) entries of the reference's sweep (main.py:152-154)")
     ap.add_argument("--no-model-sweep", action="store_true", help="skip them in the default line")
     ap.add_argument("--inner-profile", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (loss, parameters, gradients, buffers) as DIR/<name>.npy")
     ap.add_argument("--cpu-baseline-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-baseline-cores", default="", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.cpu_baseline_child:                           # the pinned CPU sample: no GPU call in this process
         cpu_baseline_child(args.workload, args.cpu_baseline_seconds,
@@ -1179,14 +1220,14 @@ def main():
         print(json.dumps({"inner_steps": args.steps, "ms_per_step": round((time.perf_counter() - t0) / args.steps * 1e3, 3)}))
         return
 
-    def timed_block():
-        """EXACTLY --steps steps between barrier + synchronize on both sides; the max over ranks."""
+    def timed_block(n):
+        """EXACTLY n steps between barrier + synchronize on both sides; the max over ranks."""
         torch.cuda.synchronize()
         if world > 1:
             torch.distributed.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        for _ in range(n):
             out = step()
         torch.cuda.synchronize()
         if world > 1:
@@ -1199,13 +1240,17 @@ def main():
             dt = float(t.item())
         return dt, out
 
-    # the timed region is repeated: --blocks blocks of --steps steps each; the line reports the MEDIAN block (and the
-    # spread), so one disturbed block does not decide the headline
-    block_s = []
-    for _ in range(max(1, args.blocks)):
-        dt, loss = timed_block()
-        block_s.append(dt)
-    dt = sorted(block_s)[len(block_s) // 2]
+    # the --steps timed steps are split into blocks (sizes differ by at most one); the line reports the MEDIAN block's
+    # time per step (and the spread), so one disturbed block does not decide the headline
+    n_blocks = max(1, min(args.blocks, args.steps))
+    block_n = [args.steps // n_blocks + (1 if i < args.steps % n_blocks else 0) for i in range(n_blocks)]
+    block_ms = []
+    for n in block_n:
+        dt, loss = timed_block(n)
+        block_ms.append(dt / n * 1e3)
+    ms_per_step = sorted(block_ms)[len(block_ms) // 2]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(opt, model, gstep.data if gstep is not None else data, loss))
     if not bool(torch.isfinite(loss)):
         print("non-finite loss", file=sys.stderr)
         sys.exit(3)
@@ -1278,15 +1323,14 @@ def main():
             "device_us_per_step_by_rank": [round(v, 1) for v in totals], "steps_sampled": 20}
 
     if rank == 0:
-        total_graphs = per_gpu * world * args.steps
         res = {
-            "metric": "graphs/s train step (90-ROI brain + GO-SNP)", "value": round(total_graphs / dt, 1),
+            "metric": "graphs/s train step (90-ROI brain + GO-SNP)", "value": round(per_gpu * world / ms_per_step * 1e3, 1),
             "unit": "graphs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
-            "timing": {"blocks": len(block_s), "steps_per_block": args.steps, "reported": "median block",
-                       "ms_per_step_min": round(min(block_s) / args.steps * 1e3, 3),
-                       "ms_per_step_max": round(max(block_s) / args.steps * 1e3, 3),
-                       "ms_per_step_blocks": [round(b / args.steps * 1e3, 3) for b in block_s]},
+            "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak",
+            "timing": {"blocks": len(block_ms), "steps_per_block": block_n, "reported": "median block",
+                       "ms_per_step_min": round(min(block_ms), 3),
+                       "ms_per_step_max": round(max(block_ms), 3),
+                       "ms_per_step_blocks": [round(b, 3) for b in block_ms]},
             "vs_baseline": None, "dtype": "bf16" if (bf16 and wl["pool"] is not None) else "f32", "data": "synthetic",
             "config": {"workload": wl["name"],
                        "graphs_per_gpu": per_gpu, "global_batch": per_gpu * world,

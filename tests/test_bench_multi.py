@@ -53,7 +53,9 @@ def test_gpus_2_self_launch_rehearsal_on_one_device():
     assert parts["slowest_rank"] in (0, 1) and len(parts["device_us_per_step_by_rank"]) == 2
     for key, vals in parts["per_rank_median_us"].items():
         assert len(vals) == 2 and all(math.isfinite(v) for v in vals), key
-    assert res["timing"]["blocks"] == 5 and len(res["timing"]["ms_per_step_blocks"]) == 5
+    # --steps is the number of timed steps in all: 3 steps over min(--blocks 5, 3) blocks
+    assert res["timing"]["blocks"] == 3 and len(res["timing"]["ms_per_step_blocks"]) == 3
+    assert res["timing"]["steps_per_block"] == [1, 1, 1]
     assert res["timing"]["ms_per_step_min"] <= res["ms_per_step"] <= res["timing"]["ms_per_step_max"]
 
 
