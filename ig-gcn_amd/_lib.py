@@ -9,6 +9,8 @@ import sys
 
 import torch
 
+from . import switches
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libigcn.so")
 
@@ -220,16 +222,9 @@ def load():
     if got != ABI_VERSION:           # a stale libigcn.so would take shifted arguments without a word
         raise IgcnError(f"{LIB_PATH} has ABI revision {got}, this binding is written for {ABI_VERSION}: "
                         "rebuild it with `python ig-gcn_amd/build.py --force`")
-    # the library's A/B switches: read from the environment HERE, once, and handed over (no getenv in a launch path)
-    bits = 0
-    for bit, name in enumerate(("IGCN_NO_TILED_LISTS", "IGCN_PROPAGATE_NO_LDS", "IGCN_SPMM_NO_LDS", "IGCN_GO_ATTN_CM",
-                                "IGCN_DEBUG_REDUCE", "IGCN_ATTN_FP32_CORE", "IGCN_ATTN_BWD_TWICE",
-                                "IGCN_ATTN_EXACT_FP32")):
-        v = os.environ.get(name)
-        if v is not None and (v == "1" or name in ("IGCN_NO_TILED_LISTS", "IGCN_PROPAGATE_NO_LDS", "IGCN_DEBUG_REDUCE", "IGCN_ATTN_FP32_CORE", "IGCN_ATTN_BWD_TWICE")):
-            bits |= 1 << bit
-    lib.igcn_configure(bits, int(os.environ.get("IGCN_GEMM_BN", "0") or 0),
-                       int(os.environ.get("IGCN_ATTN_CHUNK", "0") or 0))
+    # the library's A/B switches (switches.LIBRARY) and knobs: read from the environment HERE, once, and handed over
+    # (no getenv in a launch path)
+    lib.igcn_configure(switches.library_mask(), switches.knob("IGCN_GEMM_BN"), switches.knob("IGCN_ATTN_CHUNK"))
     _lib = lib
     return lib
 

@@ -448,8 +448,7 @@ extern "C" int igcn_attn_core_split_fwd(int B, int D, int H, int Lq, int Lk, con
                                         float* lse, void* stream) {
   int rc = as_check("attn_core_split_fwd", B, D, H, Lq, Lk, q, kv, o, o);
   if (rc) return rc;
-  static const int cap = getenv("IGCN_AS_CHUNK") ? atoi(getenv("IGCN_AS_CHUNK")) : AS_KEY_CHUNK;   // (experiments)
-  const int ch = as_chunk(Lk, cap), ldt = ab_ldt(ch);
+  const int ch = as_chunk(Lk, AS_KEY_CHUNK), ldt = ab_ldt(ch);
   const size_t lds = ((size_t)2 * ch * AB_HD + (size_t)2 * AB_HD * ldt) * 2;
   const int nqt = (Lq + 15) / 16, nw = as_waves(nqt);
   if (lds > 64 * 1024) IGCN_ALLOW_BIG_LDS(k_attn_split_fwd);

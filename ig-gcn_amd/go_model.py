@@ -12,13 +12,12 @@ so checkpoints interchange.  The arithmetic is restructured for the GPU:
 
 Dense read-outs (BatchNorm over nodes, the latent MLP) are small torch ops on the same stream.
 """
-import os
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
+from . import ops, switches
 
 N_SNPS = 54
 
@@ -190,7 +189,7 @@ class Gene_ontology_network(nn.Module):
             # the encoder OUTPUT has three consumers (two read-outs, the decoder): the last layer hands out three
             # aliases and its backward adds their gradients while it loads them — no sum launch, no autograd adds
             fan = 3 if (j == self.n_l - 1 and x.is_cuda and torch.is_grad_enabled()
-                        and os.environ.get("IGCN_NO_GRAD_FAN", "0") != "1") else 1
+                        and not switches.on("IGCN_NO_GRAD_FAN")) else 1
             x = ops.GoAttentionLN.apply(x, self.w_inc[j].weight, self.w_s_loop[j].weight, self.w_att_in[j].weight,
                                         self.w_att_s[j].weight, csr, self.G_B[j].weight, self.G_B[j].bias, keeps[j],
                                         self.pool[j], self.G_B[j].eps, fan)
@@ -200,13 +199,13 @@ class Gene_ontology_network(nn.Module):
         # read-outs (:254-255): BatchNorm1d(n_top) normalises per NODE over (batch, feature); fused kernels
         bn_a, bn_i = self.conc_for_attention[1], self.B[0]
         if ops.node_linear_bn_pair_supported(x, self.conc_for_attention[0].weight, self.conc.weight, None) \
-                and os.environ.get("IGCN_NO_READOUT_PAIR", "0") != "1":
+                and not switches.on("IGCN_NO_READOUT_PAIR"):
             # both read-outs of the encoder output in paired launches.  The encoder output has three consumers (two
             # read-outs, the decoder): their gradients are summed in one launch (ops.GradFan), not by two adds
             x_alias = None
             if x_fan is not None:
                 x_pair, x_alias = x_fan
-            elif x.requires_grad and x.is_cuda and os.environ.get("IGCN_NO_GRAD_FAN", "0") != "1":
+            elif x.requires_grad and x.is_cuda and not switches.on("IGCN_NO_GRAD_FAN"):
                 x_pair, x_alias, x = ops.GradFan.apply(x, 3)
             else:
                 x_pair = x

@@ -10,6 +10,7 @@ import os
 import torch
 
 from . import _lib
+from . import switches
 from ._lib import call, ptr, stream_ptr
 
 
@@ -225,7 +226,7 @@ class GraphPlan:
         ``edge_attr`` as the dense matrix it is.  Decided once, at construction (one host read); ``rebuild`` re-verifies
         every new batch on the device (status bit 2).  IGCN_NO_DENSE_BLOCKS=1 keeps the general kernels."""
         r = self.nodes_per_graph
-        if (not r or self._seg is None or os.environ.get("IGCN_NO_DENSE_BLOCKS", "0") == "1"
+        if (not r or self._seg is None or switches.on("IGCN_NO_DENSE_BLOCKS")
                 or self._seg[3] != r * r or self.n_edges != (self.n_nodes // r) * r * r
                 or not _lib.load().igcn_dense_sgcn_supported(r, 1, 16, 1) or ei.data_ptr() % 16
                 or torch.cuda.is_current_stream_capturing()):
@@ -285,7 +286,7 @@ class GraphPlan:
         # the LDS per-graph build refills ONE cached replica in place (same addresses: capturable); any other build
         # drops the replicas, to be derived again on demand
         keep = (self._seg is not None and not self._tiled and len(self._copies) == 1
-                and os.environ.get("IGCN_PLAN_REPLICATE_LAUNCH", "0") != "1")
+                and not switches.on("IGCN_PLAN_REPLICATE_LAUNCH"))
         if not keep:
             self._copies = {}
         self._build(edge_index.contiguous())
@@ -690,8 +691,8 @@ def sgcn_front_supported(plan, rois, h0, f, layers, snps_feat, snps_logits):
     """The one-launch front of a train step's image branch (igcn_sgcn_front_fwd) covers this batch: what the LDS-resident
     stack covers, on a plan that is built per graph in LDS (not tiled, not dense blocks), with the SNP mask riding along."""
     if (not sgcn_stack_supported(plan, rois, h0, f, layers) or plan._seg is None or plan._tiled
-            or getattr(plan, "dense_blocks", False) or os.environ.get("IGCN_NO_FRONT_FUSED", "0") == "1"
-            or os.environ.get("IGCN_NO_FUSED_SGCN", "0") == "1" or os.environ.get("IGCN_PLAN_REPLICATE_LAUNCH", "0") == "1"):
+            or getattr(plan, "dense_blocks", False) or switches.on("IGCN_NO_FRONT_FUSED")
+            or switches.on("IGCN_NO_FUSED_SGCN") or switches.on("IGCN_PLAN_REPLICATE_LAUNCH")):
         return False
     if snps_feat is None or snps_feat.dim() != 2 or snps_logits is None or snps_feat.shape[1] != snps_logits.numel():
         return False
@@ -913,9 +914,9 @@ def gemm_group(specs, bf16=False, ride=False):
     rounded to bf16 on the way into LDS (igcn_gemm_bf16 semantics) for every member."""
     outs = []
     specs = [tuple(sp) + (0,) * (7 - len(sp)) for sp in specs]
-    if ride and (len(specs) > 4 or os.environ.get("IGCN_NO_GEMM_GROUPS", "0") == "1"):
+    if ride and (len(specs) > 4 or switches.on("IGCN_NO_GEMM_GROUPS")):
         raise _lib.IgcnError("gemm_group(ride=True): at most four products, grouped launches enabled")
-    if len(specs) > 4 or os.environ.get("IGCN_NO_GEMM_GROUPS", "0") == "1":
+    if len(specs) > 4 or switches.on("IGCN_NO_GEMM_GROUPS"):
         for form, a, b, out, bias, final, act in specs:
             if form == "nt":
                 outs.append(gemm_nt(a, b, bias, act, out=out, bf16=bf16))
@@ -1061,7 +1062,7 @@ class LinearPair(torch.autograd.Function):
         lib = _lib.load()
         dy1, dy2 = _f32(dy1), _f32(dy2)
         rows, cols = dy1.shape
-        if (not ctx.bf16 and dy1.is_cuda and dy2.shape == dy1.shape and os.environ.get("IGCN_NO_HEAD_FUSED", "0") != "1"
+        if (not ctx.bf16 and dy1.is_cuda and dy2.shape == dy1.shape and not switches.on("IGCN_NO_HEAD_FUSED")
                 and lib.igcn_head_bwd_supported(rows, cols, x1.shape[1]) and lib.igcn_head_bwd_supported(rows, cols, x2.shape[1])
                 and all(t.is_contiguous() for t in (dy1, dy2, x1, x2, w1, w2))):
             # ReLU mask, bias gradients and the four products in ONE launch, the wide operands read once (igcn_head_bwd_pair)
@@ -1117,7 +1118,7 @@ def _proj_forward(q2, m2, w, bias, d, bf16):
     """q = q2 W_q^T + b_q, k | v = m2 [W_k; W_v]^T + [b_k; b_v] of the packed input projection: one streaming launch
     (igcn_proj_fwd_pair: reduction depth 32, W resident in LDS) when the shape allows it, the grouped GEMM otherwise."""
     lib = _lib.load()
-    if (not bf16 and q2.is_cuda and os.environ.get("IGCN_NO_PROJ_FUSED", "0") != "1" and q2.is_contiguous()
+    if (not bf16 and q2.is_cuda and not switches.on("IGCN_NO_PROJ_FUSED") and q2.is_contiguous()
             and m2.is_contiguous() and w.is_contiguous() and bias.is_contiguous() and q2.shape[0] > 0 and m2.shape[0] > 0
             and lib.igcn_proj_bwd_supported(q2.shape[0], d, d) and lib.igcn_proj_bwd_supported(m2.shape[0], 2 * d, d)):
         q = torch.empty(q2.shape[0], d, dtype=torch.float32, device=q2.device)
@@ -1132,7 +1133,7 @@ def _proj_fused(ctx, dq, dkv, d):
     """The one-pass kernels (igcn_proj_bwd_pair*) cover this backward."""
     lib = _lib.load()
     return bool(ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and not ctx.bf16 and dq.is_cuda
-                and os.environ.get("IGCN_NO_PROJ_FUSED", "0") != "1"
+                and not switches.on("IGCN_NO_PROJ_FUSED")
                 and lib.igcn_proj_bwd_supported(dq.shape[0], d, d) and lib.igcn_proj_bwd_supported(dkv.shape[0], 2 * d, d))
 
 
@@ -1154,7 +1155,7 @@ def _proj_backward(ctx, dq, dkv, q2, m2, w, dw, d, db=None):
                  ptr(db[d:]), d, d, stream_ptr())
         return dquery.view(ctx.shapes[0]), dmem.view(ctx.shapes[1])
     if (ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and not ctx.bf16 and dq.is_cuda
-            and os.environ.get("IGCN_NO_PROJ_FUSED", "0") != "1"
+            and not switches.on("IGCN_NO_PROJ_FUSED")
             and lib.igcn_proj_bwd_supported(dq.shape[0], d, d) and lib.igcn_proj_bwd_supported(dkv.shape[0], 2 * d, d)):
         # input gradient AND weight gradient of a block from ONE pass over its incoming gradient (igcn_proj_bwd): the
         # key | value gradient (52 MB at the bench shape) is read once, not twice
@@ -1430,7 +1431,7 @@ class OutProjHeadInputs(torch.autograd.Function):
 
 
 def outproj_head_inputs_supported(d, width):
-    return relu_owed_supported(d, width) and 512 % d == 0 and os.environ.get("IGCN_NO_OUTPROJ_FUSED", "0") != "1"
+    return relu_owed_supported(d, width) and 512 % d == 0 and not switches.on("IGCN_NO_OUTPROJ_FUSED")
 
 
 def head_inputs_supported(img, cross, latent, x, prob):
@@ -1445,7 +1446,7 @@ def head_inputs_supported(img, cross, latent, x, prob):
 def relu_owed_supported(d, width):
     """HeadInputs can take the ReLU backward and bias gradient of a D-feature layer whose output is its ``cross``
     operand (igcn_head_inputs_bwd_relu): D a power of two in [2, 64] dividing the row width."""
-    return os.environ.get("IGCN_NO_RELU_OWED", "0") != "1" and 2 <= d <= 64 and (d & (d - 1)) == 0 and width % d == 0
+    return not switches.on("IGCN_NO_RELU_OWED") and 2 <= d <= 64 and (d & (d - 1)) == 0 and width % d == 0
 
 
 class SmallLinear(torch.autograd.Function):
@@ -1674,9 +1675,9 @@ class SparseMap(torch.autograd.Function):
     def _use_dense(b, c, csr):
         if c * csr.n_rows * csr.n_cols > SparseMap.DENSE_LIMIT or csr.nnz == 0:
             return False
-        if os.environ.get("IGCN_DENSE_MAPS") == "1":
+        if switches.on("IGCN_DENSE_MAPS"):
             return True
-        if os.environ.get("IGCN_SPARSE_MAPS") == "1":
+        if switches.on("IGCN_SPARSE_MAPS"):
             return False
         return b < SparseMap.SPARSE_MIN_BATCH
 
@@ -1704,7 +1705,7 @@ class SparseMap(torch.autograd.Function):
         # ``x._igcn_grad_rows = (lo, hi)`` (set by the producer of x): only rows [lo, hi) of d x will ever be read — the
         # stacked (plain | masked) SNP batch of a train step, whose plain half is data — and the backward computes only
         # those (the rest of dx stays unwritten)
-        ctx.grad_rows = getattr(x, "_igcn_grad_rows", None) if os.environ.get("IGCN_SNP_GRAD_ALL", "0") != "1" else None
+        ctx.grad_rows = getattr(x, "_igcn_grad_rows", None) if not switches.on("IGCN_SNP_GRAD_ALL") else None
         ctx.csr, ctx.stacked, ctx.nvals = csr, stacked, len(vals)
         ctx.final = _leaves(*vals)
         ctx.dense, ctx.channels = dense, c
@@ -1778,7 +1779,7 @@ class SparseMap(torch.autograd.Function):
                              ptr(csr.row_of), ptr(csr.t_ptr), ptr(csr.t_row), ptr(csr.t_k), ptr(val), ptr(xx), ptr(dyy),
                              ptr(dx_), ptr(dval_), ptr(scratch), stream_ptr())
             if (dval is not None and _DEFER["on"] and ctx.final and csr.nnz > 0
-                    and os.environ.get("IGCN_SPMM_DVAL_NOW", "0") != "1"):
+                    and not switches.on("IGCN_SPMM_DVAL_NOW")):
                 # the value gradients are parameter gradients: queued, and launched together with the other map's at
                 # the end of the backward (each pass alone fills half the chip)
                 if dx is not None:
@@ -1820,7 +1821,7 @@ def _nodes_ln_backward(y, gamma, beta, keep, mean, rstd, pool, final, dz):
     lib = _lib.load()
     scratch = _keep(torch.empty(int(lib.igcn_nodes_ln_bwd_scratch_floats(b, f, n)), dtype=torch.float32,
                                 device=y.device))
-    if _DEFER["on"] and final and os.environ.get("IGCN_LN_AFFINE_NOW", "0") != "1":
+    if _DEFER["on"] and final and not switches.on("IGCN_LN_AFFINE_NOW"):
         # d gamma / d beta are parameter gradients: their pass joins those of the other layers in ONE launch when
         # the backward ends (operands kept alive until then)
         call("igcn_nodes_ln_bwd_dy", b, f, n, pool, ptr(y), ptr(gamma), ptr(beta), ptr(keep), ptr(mean),
@@ -1948,7 +1949,7 @@ class GoAttentionLN(torch.autograd.Function):
         if not gs:
             return none
         fused = bool(lib.igcn_go_attn_ln_fused_ok(n, fin, fout, pool)) and _al16(x, y, gamma, beta, keep, *gs) \
-            and os.environ.get("IGCN_NO_LN_FUSED", "0") != "1"
+            and not switches.on("IGCN_NO_LN_FUSED")
         if len(gs) > 1 and not (fused and len(gs) <= 3):
             # several consumers, no fused path to add them on load: one sum launch (what ops.GradFan does)
             total = torch.empty_like(gs[0])
@@ -2017,7 +2018,7 @@ class GoDecodeLN(torch.autograd.Function):
         lib = _lib.load()
         k = fout * fin
         if lib.igcn_go_decode_ln_fused_ok(nin, nout, fin, fout) and _al16(y, dz, gamma, beta, keep) \
-                and os.environ.get("IGCN_NO_LN_FUSED", "0") != "1":
+                and not switches.on("IGCN_NO_LN_FUSED"):
             dx = torch.empty_like(x)
             dpar = torch.empty(2 * k, dtype=torch.float32, device=x.device)
             dgb = torch.empty(2, nout, dtype=torch.float32, device=x.device)
@@ -2259,7 +2260,7 @@ class LinearBN1d(torch.autograd.Function):
 
 def linear_bn1d_supported(x, weight, groups):
     return (x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and x.is_contiguous() and weight.is_contiguous()
-            and os.environ.get("IGCN_NO_LINEAR_BN_FUSED", "0") != "1"
+            and not switches.on("IGCN_NO_LINEAR_BN_FUSED")
             and _split_k(x.shape[0], weight.shape[0], x.shape[1]) > 1      # (an unsplit product has no slab sum to save)
             and bool(_lib.load().igcn_bn1d_fwd_supported(x.shape[0], groups)))
 
@@ -2457,7 +2458,7 @@ class ProjectedAttention(torch.autograd.Function):
         rows = dq2.shape[0]
         scr = _keep(torch.empty(int(lib.igcn_bias_grad_scratch_floats(rows, 2 * d)), dtype=torch.float32, device=w.device))
         scr2 = _keep(torch.empty(int(lib.igcn_bias_grad_scratch_floats(rows, d)), dtype=torch.float32, device=w.device))
-        if _proj_fused(ctx, dq2, dkv2, d) and os.environ.get("IGCN_NO_PROJ_BIAS_FUSED", "0") != "1":
+        if _proj_fused(ctx, dq2, dkv2, d) and not switches.on("IGCN_NO_PROJ_BIAS_FUSED"):
             dquery, dmem = _proj_backward(ctx, dq2, dkv2, q2, m2, w, dw, d, db)      # bias gradients ride in the pass
             return dquery, dmem, dw, db, None, None
         with _immediate(ctx.final):                                 # d b_q (then d b_k = 0) and d b_v in one launch
@@ -2494,7 +2495,7 @@ class LossHead(torch.autograd.Function):
         # when a backward will follow, the forward writes the gradients for an upstream gradient of ONE as it goes — a
         # train step's d loss / d loss (train._unit_grad, recognised by its address): no backward launch for the loss head
         ctx.unit = None
-        if any(ctx.needs_input_grad) and UNIT_GRAD_PTRS and os.environ.get("IGCN_NO_LOSS_HEAD_FUSED", "0") != "1":
+        if any(ctx.needs_input_grad) and UNIT_GRAD_PTRS and not switches.on("IGCN_NO_LOSS_HEAD_FUSED"):
             f32 = dict(dtype=torch.float32, device=dev)
             unit = (torch.empty(2 * b, c, **f32), torch.empty_like(reg), torch.empty_like(x_hat), torch.empty(4, **f32),
                     torch.empty(1, **f32))
@@ -2562,7 +2563,7 @@ def head_loss_supported(lin_f, w2, reg_f, w2r, keep1, keep2):
     return (lin_f.is_cuda and lin_f.dim() == 2 and lin_f.shape == reg_f.shape and w2.shape[1] == w2r.shape[1] == lin_f.shape[1]
             and lin_f.dtype == torch.float32 and lin_f.is_contiguous() and reg_f.is_contiguous()
             and (keep1 is None) == (keep2 is None) and torch.is_grad_enabled() and bool(UNIT_GRAD_PTRS)
-            and os.environ.get("IGCN_NO_LOSS_HEAD_FUSED", "0") != "1" and os.environ.get("IGCN_NO_HEAD_LOSS_FUSED", "0") != "1"
+            and not switches.on("IGCN_NO_LOSS_HEAD_FUSED") and not switches.on("IGCN_NO_HEAD_LOSS_FUSED")
             and bool(_lib.load().igcn_head_loss_supported(lin_f.shape[1], w2.shape[0], w2r.shape[0])))
 
 

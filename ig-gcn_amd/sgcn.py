@@ -14,13 +14,12 @@ interact at all.
 """
 import math
 
-import os
 
 import torch
 import torch.nn.functional as F
 from torch.nn import Linear, Parameter, init
 
-from . import ops
+from . import ops, switches
 from .sgcn_img_snp import GCNConv, sgcn_stack
 
 
@@ -102,7 +101,7 @@ class SGCN_GCN(torch.nn.Module):
             ew_in = ews[0] if g == 1 else torch.cat(ews, dim=0)
         plan_g = plan.replicate(g)
         xcat = sgcn_stack([self.conv1, *self.convs], x_in, ew_in, plan_g, self.rois,
-                          os.environ.get("IGCN_NO_FUSED_SGCN", "0") != "1")
+                          not switches.on("IGCN_NO_FUSED_SGCN"))
         z = xcat.view(g * bsz, -1)                                    # to_dense_batch == view (:378-381)
         f1 = ops.linear(z, self.lin1.weight, self.lin1.bias, relu=True)
         if self.training and self._dropout_enabled:

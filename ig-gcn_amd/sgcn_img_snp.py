@@ -13,13 +13,12 @@ the two ``x.min().item()`` host syncs of :225,293 are gone (every graph has exac
 to_dense_batch is a view); OrthogonalConstraint uses the Gram identity (B x B instead of (R*D)^2).
 """
 import math
-import os
 
 import torch
 import torch.nn.functional as F
 from torch.nn import Linear, Parameter, init
 
-from . import ops
+from . import ops, switches
 from .go_model import Gene_ontology_network
 
 
@@ -154,7 +153,7 @@ class SGCN_GCN_IMGSNP(torch.nn.Module):
         self.bf16_transforms = bool(kwargs.get("bf16_transforms", False))
         # one LDS-resident kernel per direction for the whole SGCN stack when the batch allows it (small uniform
         # graphs); IGCN_NO_FUSED_SGCN=1 keeps the per-layer kernels (A/B runs, tests of the unfused path)
-        self.fused_sgcn_stack = os.environ.get("IGCN_NO_FUSED_SGCN", "0") != "1"
+        self.fused_sgcn_stack = not switches.on("IGCN_NO_FUSED_SGCN")
         # loss_probability's constants as the dense-block path needs them at FORWARD time (it reduces the mask
         # regulariser inside its first edge pass): (l1_x, ent_x, l1_e, ent_e, eps) — sgcn_hyperparameters.py:18-21;
         # train.losses sets them from the ``hp`` it is given
@@ -324,7 +323,7 @@ class SGCN_GCN_IMGSNP(torch.nn.Module):
         self._dense_reg = None
         self._last_mask_key = self._reg_key(x, edge_weight)
         self._fan_prob = self._fan_snps = None
-        fan = x.is_cuda and torch.is_grad_enabled() and os.environ.get("IGCN_NO_GRAD_FAN", "0") != "1"
+        fan = x.is_cuda and torch.is_grad_enabled() and not switches.on("IGCN_NO_GRAD_FAN")
         prob_m = prob_h = self.prob
         x_m = x_h = x
         convs = [self.conv1, *self.convs]
@@ -333,7 +332,7 @@ class SGCN_GCN_IMGSNP(torch.nn.Module):
             and snps_feat.shape[1] == self.snps_prob.numel()
         xcat = xcat_dense_img = None
         use_dense = (mode is not None and x.is_cuda and (snps_ok or mode == "plain")
-                     and os.environ.get("IGCN_NO_DENSE_BLOCKS") != "1"
+                     and not switches.on("IGCN_NO_DENSE_BLOCKS")
                      and ops.dense_sgcn_supported(plan, self.rois, x.shape[1], convs[0].out_channels, len(convs)))
         if not use_dense:
             plan.flush_pending_check()     # (a dense-block plan's structure check rides in ops.DenseSgcn otherwise)
@@ -345,7 +344,7 @@ class SGCN_GCN_IMGSNP(torch.nn.Module):
         f_conv = convs[0].out_channels
         fp_conv = f_conv if f_conv in _WIDE else next((w for w in _WIDE if w >= f_conv), f_conv)
         use_front = (not use_dense and tuple(explain_flags) == (False, True) and x.is_cuda and snps_ok and fan
-                     and self._reg_hp is not None and os.environ.get("IGCN_NO_MASK_REG_FUSED", "0") != "1"
+                     and self._reg_hp is not None and not switches.on("IGCN_NO_MASK_REG_FUSED")
                      and self.fused_sgcn_stack and not self.bf16_transforms
                      and ops.sgcn_front_supported(plan, self.rois, x.shape[1], fp_conv, len(convs), snps_feat,
                                                   self.snps_prob))
@@ -401,7 +400,7 @@ class SGCN_GCN_IMGSNP(torch.nn.Module):
             # the train step's (plain | masked) pair: cal_probability writes both halves of the stacked batch itself.
             # prob (mask, head inputs, regulariser), data.x (mask, head inputs) and snps_prob (mask, regulariser) each
             # feed several ops: ops.GradFan hands out aliases and sums their gradients in one launch per tensor
-            reg_in_mask = fan and self._reg_hp is not None and os.environ.get("IGCN_NO_MASK_REG_FUSED", "0") != "1"
+            reg_in_mask = fan and self._reg_hp is not None and not switches.on("IGCN_NO_MASK_REG_FUSED")
             if fan and reg_in_mask:
                 # loss_probability AND the SNP mask ride in the mask launch (ops.EdgeMaskStacked with reg_hp /
                 # snps_feat): prob then has two consumers (that op; the head inputs), snps_prob one

@@ -3,7 +3,6 @@ kernel/train_eval_sgcn_img_snps.py:511-548 (two forwards, seven loss terms, back
 graph-batch data parallelism the reference does not have (one process per GPU, one RCCL all-reduce of a
 flat fp32 gradient buffer per step).
 """
-import os
 import sys
 from types import SimpleNamespace
 
@@ -11,6 +10,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
+from . import switches
 from ._lib import call, ptr, stream_ptr
 
 # sgcn_hyperparameters.py:18-23
@@ -394,7 +394,7 @@ def _losses_batched(model, data, lam, hp, temperature, lazy_value=False):
         # (a bf16 heads launch does not carry fp32 products: the batched launch behind the forward stays the better one)
         if z.is_cuda and z.dtype == torch.float32 and z.is_contiguous() and z.shape[0] % 2 == 0 \
                 and not getattr(model, "bf16_transforms", False) \
-                and os.environ.get("IGCN_NO_GRAM_RIDER", "0") != "1" and os.environ.get("IGCN_NO_GEMM_GROUPS", "0") != "1":
+                and not switches.on("IGCN_NO_GRAM_RIDER") and not switches.on("IGCN_NO_GEMM_GROUPS"):
             pre["gram"], pre["hold"] = ops.gram_rider(z.detach(), 2)
 
     # (the fused output-heads + loss launch reads its weights from a cached device vector: uploaded outside captures only)
@@ -416,9 +416,9 @@ def _losses_batched(model, data, lam, hp, temperature, lazy_value=False):
     soft = model.isSoftSimilarity and data.tsne_fdim is not None
     # (the loss head's gradient of these partials for a unit upstream is known here: the Gram loss forward prepares its
     # own backward for it — ops.GramLosses ``expect``)
-    unit = ops.unit_dgram(lam) if (ops.UNIT_GRAD_PTRS and os.environ.get("IGCN_NO_LOSS_HEAD_FUSED", "0") != "1") else None
+    unit = ops.unit_dgram(lam) if (ops.UNIT_GRAD_PTRS and not switches.on("IGCN_NO_LOSS_HEAD_FUSED")) else None
     # (with the output layers left to the loss launch, the Gram loss launch is left to it too: two roles of one grid)
-    job = {} if (isinstance(scores, tuple) and os.environ.get("IGCN_NO_GRAM_LOSS_PAIRED", "0") != "1") else None
+    job = {} if (isinstance(scores, tuple) and not switches.on("IGCN_NO_GRAM_LOSS_PAIRED")) else None
     gram = ops.GramLosses.apply(out_z, None, 2, "partials", (data.tsne_fdim if soft else None, model.rbf_gamma), unit,
                                 pre.get("gram"), job)
     # (rows sum to [2,2] = (consist, orth) per pass)
@@ -546,7 +546,7 @@ def _single_use_parameters(model):
     """True when the step runs both passes as ONE batched sweep (``losses`` picks ``_losses_batched`` /
     ``forward_pair``): every parameter then enters the autograd graph once, which is what deferring the final
     gradient reductions needs (``backward_to_grads``).  IGCN_NO_DEFER=1 switches the deferral off (A/B runs)."""
-    if os.environ.get("IGCN_NO_DEFER", "0") == "1" or not getattr(model, "batched_passes", True):
+    if switches.on("IGCN_NO_DEFER") or not getattr(model, "batched_passes", True):
         return False
     if hasattr(model, "go_network"):
         return hasattr(model, "_forward_grouped") and bool(model.isSoftSimilarity)
@@ -914,7 +914,7 @@ class GraphedTrainStep:
         forget_riders(self.model)                       # (leftovers of a step that failed half way must never launch)
         ensure_unit_grad(self.data.x.device)
         rider = (rebuild and _batched(self.model) and hasattr(self.model, "predraw_dropout")
-                 and os.environ.get("IGCN_NO_DROPOUT_RIDER", "0") != "1")
+                 and not switches.on("IGCN_NO_DROPOUT_RIDER"))
         try:
             if rider:
                 self.model.predraw_dropout(self.data)   # queued: the plan build below carries the mask generation

@@ -138,6 +138,7 @@ def test_model_takes_the_dense_path_and_matches_the_general_kernels(monkeypatch)
     from igcn_amd.sgcn_img_snp import SGCN_GCN_IMGSNP
     from igcn_amd.train import losses
     from _weights import seeded_state
+    from calltrace import record_calls
     pool, rois = (40, 20, 10, 4, 1), 128
     go_snps, adj, pool_dim = synth.go_hierarchy(pool, seed=3)
     a_g, a = synth.go_sparse_inputs(go_snps, adj, "cuda")
@@ -149,11 +150,13 @@ def test_model_takes_the_dense_path_and_matches_the_general_kernels(monkeypatch)
         m._dropout_enabled = False
     graphs = synth.brain_graph_list(6, seed=4, rois=rois, tsne_dim=8, dense=True)
     lam = [1.0, 1.0, 0.5, 1.5e-6, 0.1, 0.2]
-    res = {}
+    res, calls = {}, {}
+    seen = record_calls(monkeypatch)
     for tag in ("dense", "general"):
         if tag == "general":
             monkeypatch.setenv("IGCN_NO_DENSE_BLOCKS", "1")
         for batched in (True, False):
+            seen.clear()
             model.load_state_dict(sd)
             model.zero_grad()
             model.batched_passes = batched
@@ -163,7 +166,9 @@ def test_model_takes_the_dense_path_and_matches_the_general_kernels(monkeypatch)
             loss.backward()
             res[tag, batched] = (float(loss), {k: float(v) for k, v in terms.items()}, data.x.grad.clone(),
                                  {k: p.grad.clone() for k, p in model.named_parameters() if p.grad is not None})
+            calls[tag, batched] = list(seen)
     for batched in (True, False):
+        assert calls["dense", batched] != calls["general", batched]
         ld, td, gxd, gd = res["dense", batched]
         lg, tg, gxg, gg = res["general", batched]
         assert abs(ld - lg) <= 2e-5 * max(1.0, abs(lg)), (ld, lg)

@@ -377,6 +377,7 @@ def test_captured_step_draws_its_dropout_masks_in_the_plan_builds_launch(monkeyp
     from igcn_amd import synth
     from igcn_amd.data import Batch
     from igcn_amd.train import FlatAdam, GraphedTrainStep
+    from calltrace import record_calls
 
     def run():
         torch.manual_seed(77)                                       # (seeds the device-side mask counter too)
@@ -390,10 +391,14 @@ def test_captured_step_draws_its_dropout_masks_in_the_plan_builds_launch(monkeyp
         losses = [float(step()) for _ in range(4)]
         return losses, int(m.go_network.latent[1].num_batches_tracked), m
 
+    seen = record_calls(monkeypatch)
     want, nb_want, _ = run()
+    want_calls = list(seen)
+    seen.clear()
     assert len(set(round(v, 6) for v in want)) > 1                  # the masks differ from replay to replay
     monkeypatch.setenv("IGCN_NO_DROPOUT_RIDER", "1")
     got, nb_got, m = run()
+    assert seen != want_calls                                       # the captured step took the other path
     assert nb_got == nb_want and nb_want >= 8                       # two passes per step, warm-up rolled back or not
     assert all(abs(a - b) <= 1e-6 * max(1.0, abs(b)) for a, b in zip(got, want)), (got, want)
     assert getattr(m.go_network, "_predrawn", None) is None

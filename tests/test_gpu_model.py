@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from conftest import assert_matches, golden_group
+from igcn_amd import switches
 from _weights import seeded_state
 
 pytestmark = pytest.mark.gpu
@@ -852,36 +853,73 @@ def test_deferred_reductions_give_the_same_gradients(golden):
     assert n_grads > 40
 
 
-@pytest.mark.parametrize("switch", ["IGCN_NO_FUSED_SGCN", "IGCN_NO_DEFER", "IGCN_NO_GEMM_GROUPS", "IGCN_NO_READOUT_PAIR",
-                                    "IGCN_LN_AFFINE_NOW", "IGCN_SPMM_DVAL_NOW", "IGCN_NO_PROJ_FUSED", "IGCN_NO_HEAD_FUSED",
-                                    "IGCN_NO_MASK_REG_FUSED", "IGCN_NO_GRAD_FAN", "IGCN_NO_LN_FUSED",
-                                    "IGCN_NO_LOSS_HEAD_FUSED", "IGCN_SPARSE_MAPS", "IGCN_NO_LINEAR_BN_FUSED",
-                                    "IGCN_NO_FRONT_FUSED", "IGCN_NO_HEAD_LOSS_FUSED",
-                                    "IGCN_NO_GRAM_LOSS_PAIRED", "IGCN_NO_RELU_OWED", "IGCN_NO_OUTPROJ_FUSED"])
-def test_every_host_side_switch_gives_the_default_train_step(golden, monkeypatch, switch):
-    """every A/B switch that the Python layer reads selects a second code path — each of them must give
-    the default path's train step (loss, every gradient) on the ``full_b32`` model, so a losing variant cannot rot
-    unnoticed.  (The switches the library reads at load time are covered by test_alternative_kernel_variants_agree.)"""
+# host switches whose second path a full_b32 train step does not reach, with the tests that flip them
+_NOT_IN_THE_TRAIN_STEP = {
+    "IGCN_NO_DENSE_BLOCKS": "complete graphs only: test_gpu_dense.py, test_gpu_ops.py",
+    "IGCN_NO_DROPOUT_RIDER": "captured steps with dropout only: test_gpu_epoch.py",
+    "IGCN_DENSE_MAPS": "a 32-graph step already takes the dense maps: test_gpu_ops.py::test_sparse_map_encode_decode",
+}
+# host switches whose branch needs a wider GO hierarchy than full_b32's: their step runs on full_b32 with this pool
+_POOL_OF = {
+    "IGCN_NO_LINEAR_BN_FUSED": [1800, 800, 300, 99, 1],   # (a split latent product: 400 inputs; full_b32's 80 are not)
+}
+# host switches whose branch a full_b32 train step reaches only on the path of another switch: both runs set that one
+_REACHED_WITH = {
+    "IGCN_LN_AFFINE_NOW": "IGCN_NO_LN_FUSED",          # (the fused LayerNorm backward takes its affine sums itself)
+    "IGCN_SPMM_DVAL_NOW": "IGCN_SPARSE_MAPS",          # (a 32-graph step maps through dense images, no CSR kernel)
+    "IGCN_SNP_GRAD_ALL": "IGCN_SPARSE_MAPS",
+}
+
+
+def _train_step_grads(store, lam):
     from igcn_amd.data import Batch
     from igcn_amd.train import FlatAdam, backward_to_grads, losses, _single_use_parameters
+    model, graphs, _ = _full_model(store)
+    model.train(True)
+    opt = FlatAdam(model.parameters(), lr=1e-3)
+    data = Batch.from_data_list(graphs).to("cuda")
+    opt.zero_grad()
+    loss, terms, _ = losses(model, data, lam)
+    backward_to_grads(loss, opt, data, defer=_single_use_parameters(model))
+    g = {k: p.grad.clone() for k, p in model.named_parameters() if p.grad is not None}
+    g["data.x"] = data.x.grad.clone()
+    return float(loss), g
+
+
+def test_train_step_launches_the_same_calls_every_time(golden, monkeypatch):
+    """The call record the switch test compares is a property of the path alone: two default train steps on fresh
+    models launch the same entry points with the same integer arguments."""
+    from calltrace import record_calls
     store = golden("full_b32")
+    seen = record_calls(monkeypatch)
+    _train_step_grads(store, store["lam"].tolist())
+    first = list(seen)
+    seen.clear()
+    _train_step_grads(store, store["lam"].tolist())
+    assert len(first) > 50 and seen == first
+
+
+@pytest.mark.parametrize("switch", sorted(set(switches.HOST) - set(_NOT_IN_THE_TRAIN_STEP)))
+def test_every_host_side_switch_gives_the_default_train_step(golden, monkeypatch, switch):
+    """every A/B switch that the Python layer reads (switches.HOST) selects a second code path — each of
+    them must give the default path's train step (loss, every gradient) on the ``full_b32`` model (with the GO pool of
+    ``_POOL_OF`` where the branch needs a wider hierarchy), so a losing variant cannot rot unnoticed, and must change the
+    libigcn calls the step launches, so the test sees the path it names.
+    (The switches the library reads at load time are covered by the child-process tests of test_gpu_ops.py.)"""
+    from calltrace import record_calls
+    store = golden("full_b32")
+    if switch in _POOL_OF:
+        store = dict(store, pool=np.array(_POOL_OF[switch]))
     lam = store["lam"].tolist()
-
-    def run():
-        model, graphs, _ = _full_model(store)
-        model.train(True)
-        opt = FlatAdam(model.parameters(), lr=1e-3)
-        data = Batch.from_data_list(graphs).to("cuda")
-        opt.zero_grad()
-        loss, terms, _ = losses(model, data, lam)
-        backward_to_grads(loss, opt, data, defer=_single_use_parameters(model))
-        g = {k: p.grad.clone() for k, p in model.named_parameters() if p.grad is not None}
-        g["data.x"] = data.x.grad.clone()
-        return float(loss), g
-
-    want_loss, want = run()
+    if switch in _REACHED_WITH:
+        monkeypatch.setenv(_REACHED_WITH[switch], "1")
+    seen = record_calls(monkeypatch)
+    want_loss, want = _train_step_grads(store, lam)
+    want_calls = list(seen)
+    seen.clear()
     monkeypatch.setenv(switch, "1")
-    got_loss, got = run()
+    got_loss, got = _train_step_grads(store, lam)
+    assert seen != want_calls, switch + ": the train step launched the default path's calls"
     assert abs(got_loss - want_loss) <= 2e-5 * max(1.0, abs(want_loss)), (switch, got_loss, want_loss)
     assert set(got) == set(want)
     for k, w in want.items():

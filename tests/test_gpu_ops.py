@@ -839,9 +839,14 @@ def test_go_decoder_with_layernorm_backward_in_one_launch(ops, monkeypatch, bsz,
 def test_sparse_map_encode_decode(ops, monkeypatch, bsz, pool, seed, dense):
     """The learnable sparse SNP <-> GO maps in both orientations — encode (C = 2, rows = GO nodes with a few SNPs each,
     plus the root's 54) and decode (C = 1, rows = SNPs with ~5 % of the nodes each) — on the LDS-tiled CSR kernels
-    (default) and as dense image + MFMA GEMMs (IGCN_DENSE_MAPS): outputs and both gradients against fp64.  Batch
-    sizes off the sample-tile sizes (8 / 4) exercise the partial tiles."""
+    (default) and as dense image + MFMA GEMMs (IGCN_DENSE_MAPS, at batch sizes that would take the CSR kernels): outputs
+    and both gradients against fp64.  Batch sizes off the sample-tile sizes (8 / 4) exercise the partial tiles."""
+    from calltrace import record_calls
     monkeypatch.setattr(ops.SparseMap, "DENSE_LIMIT", (1 << 24) if dense else 0)
+    monkeypatch.setattr(ops.SparseMap, "SPARSE_MIN_BATCH", 0)        # every batch size takes the CSR kernels ...
+    if dense:
+        monkeypatch.setenv("IGCN_DENSE_MAPS", "1")                   # ... unless the switch forces the dense image
+    seen = record_calls(monkeypatch)
     a_g, _, _, idx = _hier(pool, seed)
     n = idx["n"]
     gn, gs = idx["gene"]
@@ -877,6 +882,7 @@ def test_sparse_map_encode_decode(ops, monkeypatch, bsz, pool, seed, dense):
     assert_matches(yd, yd_ref.detach().numpy(), TOL, "decode y")
     assert_matches(gd[0], gd_ref[0].numpy(), TOL, "decode dx")
     assert_matches(gd[1], gd_ref[1].numpy(), TOL, "decode dval")
+    assert any(c[0].startswith("igcn_spmm_") for c in seen) != dense
 
 
 def test_adam_matches_torch(ops):
@@ -1278,16 +1284,13 @@ def test_propagate_dense_graph_variants(ops, hint):
     assert_matches(out, want.numpy(), TOL, "out")
 
 
-@pytest.mark.parametrize("g,r,f,density,cross", [(3, 64, 16, 1.0, False), (2, 200, 16, 0.9, False),
-                                                 (2, 130, 8, 1.0, False), (2, 70, 64, 1.0, False),
-                                                 (3, 96, 4, 0.8, False), (2, 128, 32, 1.0, True)])
-def test_propagate_lds_staged_dense_fwd_bwd(ops, monkeypatch, g, r, f, density, cross):
-    """The LDS-staged scatter-aggregate for dense uniform batches (igcn_gcn_propagate_{fwd,bwd} with the
-    nodes_per_graph hint, average in-degree >= 64): forward, dh, dbias and the coefficient gradients against the fp64
-    oracle and against the wave-per-target kernels (IGCN_PROPAGATE_NO_LDS=1).  `density` < 1 gives ragged lists (odd
-    record offsets: the 16-byte record loads start on an even position and mask the neighbour's record); `cross`
-    adds edges BETWEEN graphs, which the staged rows do not cover (global-row fallback)."""
-    from oracle import pyg_ops
+_PROPAGATE_SHAPES = [(3, 64, 16, 1.0, False), (2, 200, 16, 0.9, False), (2, 130, 8, 1.0, False), (2, 70, 64, 1.0, False),
+                     (3, 96, 4, 0.8, False), (2, 128, 32, 1.0, True)]
+
+
+def _propagate_case(g, r, f, density, cross):
+    """edge_index, edge weights, node features, bias and a cotangent of a dense uniform batch (ragged lists below
+    density 1, edges between graphs with ``cross``)."""
     rng = np.random.default_rng(g * 1000 + r + f)
     src, dst = [], []
     for k in range(g):
@@ -1302,26 +1305,68 @@ def test_propagate_lds_staged_dense_fwd_bwd(ops, monkeypatch, g, r, f, density, 
     x = torch.from_numpy(rng.standard_normal((g * r, f))).float()
     b = torch.from_numpy(rng.standard_normal(f)).float()
     cot = torch.from_numpy(rng.standard_normal((g * r, f))).float()
+    return ei, ew, x, b, cot
+
+
+def _propagate_run(ops, ei, ew, x, b, cot, g, r):
+    plan = ops.GraphPlan(ei.cuda(), g * r)
+    plan.nodes_per_graph = r
+    xg, ewg, bg = x.cuda().requires_grad_(True), ew.cuda().requires_grad_(True), b.cuda().requires_grad_(True)
+    coef = ops.GcnNorm.apply(ewg, plan)
+    out = ops.GcnPropagate.apply(xg, coef[0], coef[1], bg, plan, True, coef[2], coef[3])
+    (out * cot.cuda()).sum().backward()
+    return out.detach(), xg.grad, ewg.grad, bg.grad
+
+
+@pytest.mark.parametrize("g,r,f,density,cross", _PROPAGATE_SHAPES)
+def test_propagate_lds_staged_dense_fwd_bwd(ops, g, r, f, density, cross):
+    """The LDS-staged scatter-aggregate for dense uniform batches (igcn_gcn_propagate_{fwd,bwd} with the
+    nodes_per_graph hint, average in-degree >= 64): forward, dh, dbias and the coefficient gradients against the fp64
+    oracle (against the wave-per-target kernels: test_propagate_wave_per_target_kernels_agree).  `density` < 1 gives
+    ragged lists (odd record offsets: the 16-byte record loads start on an even position and mask the neighbour's
+    record); `cross` adds edges BETWEEN graphs, which the staged rows do not cover (global-row fallback)."""
+    from oracle import pyg_ops
+    ei, ew, x, b, cot = _propagate_case(g, r, f, density, cross)
     xd, ewd, bd = x.double().requires_grad_(True), ew.double().requires_grad_(True), b.double().requires_grad_(True)
     want = torch.relu(pyg_ops.gcn_conv(xd, ei, ewd, torch.eye(f, dtype=torch.float64), bd))
     (want * cot.double()).sum().backward()
-
-    def run():
-        plan = ops.GraphPlan(ei.cuda(), g * r)
-        plan.nodes_per_graph = r
-        xg, ewg, bg = x.cuda().requires_grad_(True), ew.cuda().requires_grad_(True), b.cuda().requires_grad_(True)
-        coef = ops.GcnNorm.apply(ewg, plan)
-        out = ops.GcnPropagate.apply(xg, coef[0], coef[1], bg, plan, True, coef[2], coef[3])
-        (out * cot.cuda()).sum().backward()
-        return out.detach(), xg.grad, ewg.grad, bg.grad
-
     assert ei.shape[1] >= 64 * g * r                     # the shape that selects the LDS-staged kernels
-    got = run()
-    monkeypatch.setenv("IGCN_PROPAGATE_NO_LDS", "1")
-    ref = run()
-    for name, a, c, w in zip(("out", "dh", "dew", "dbias"), got, ref, (want.detach(), xd.grad, ewd.grad, bd.grad)):
+    got = _propagate_run(ops, ei, ew, x, b, cot, g, r)
+    for name, a, w in zip(("out", "dh", "dew", "dbias"), got, (want.detach(), xd.grad, ewd.grad, bd.grad)):
         assert_matches(a, w.numpy(), TOL, name + " vs oracle")
-        assert_matches(a, c.cpu().numpy(), 2e-5, name + " vs wave-per-target kernels")
+
+
+_PROPAGATE_SCRIPT = """
+import sys, torch
+sys.path[:0] = [sys.argv[1], sys.argv[2]]
+import igcn_amd
+from igcn_amd import ops
+from test_gpu_ops import _PROPAGATE_SHAPES, _propagate_case, _propagate_run
+out = [[t.cpu() for t in _propagate_run(ops, *_propagate_case(*s), s[0], s[1])] for s in _PROPAGATE_SHAPES]
+torch.save(out, sys.argv[3])
+"""
+
+
+def test_propagate_wave_per_target_kernels_agree(tmp_path):
+    """The shapes of test_propagate_lds_staged_dense_fwd_bwd on the LDS-staged kernels (default) and on the
+    wave-per-target kernels (IGCN_PROPAGATE_NO_LDS=1): the same numbers within 2e-5, and not the same bits, so the
+    switch did change the kernel.  The switch is read once when the library loads, so each variant runs in a child
+    process."""
+    import subprocess
+    import sys
+    from conftest import ROOT
+    outs = {}
+    for tag, extra in (("lds", {}), ("wave", {"IGCN_PROPAGATE_NO_LDS": "1"})):
+        env = {k: v for k, v in os.environ.items() if k != "IGCN_PROPAGATE_NO_LDS"}
+        path = tmp_path / f"{tag}.pt"
+        r = subprocess.run([sys.executable, "-c", _PROPAGATE_SCRIPT, ROOT, os.path.dirname(os.path.abspath(__file__)),
+                            str(path)], env={**env, **extra}, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, (tag, r.stderr[-2000:])
+        outs[tag] = torch.load(path)
+    for shape, got, ref in zip(_PROPAGATE_SHAPES, outs["lds"], outs["wave"]):
+        assert not all(torch.equal(a, c) for a, c in zip(got, ref)), f"{shape}: the switch did not change the kernel"
+        for name, a, c in zip(("out", "dh", "dew", "dbias"), got, ref):
+            assert_matches(a, c.numpy(), 2e-5, f"{shape}: {name} vs wave-per-target kernels")
 
 
 @pytest.mark.parametrize("bsz,lq,lk,d", [(3, 10, 9, 8), (4, 90, 400, 32), (2, 130, 77, 16), (5, 90, 45, 32),
@@ -1413,6 +1458,8 @@ for _ in range(3):
     o = ops.AttentionCore.apply(q, kv, 2)
     gs.append([o.detach()] + list(torch.autograd.grad((o * cot).sum(), [q, kv])))
 assert all(torch.equal(a, b) for g in gs[1:] for a, b in zip(gs[0], g)), "run-to-run bits differ"
+o = ops.AttentionCore.apply(q, kv, 2, True)                 # under bf16 feature transforms
+gs[0] += [o.detach()] + list(torch.autograd.grad((o * cot).sum(), [q, kv]))
 torch.save([t.cpu() for t in gs[0]], sys.argv[1])
 """
     import tempfile
@@ -1420,9 +1467,10 @@ torch.save([t.cpu() for t in gs[0]], sys.argv[1])
     outs = {}
     with tempfile.TemporaryDirectory() as d:
         for tag, extra in (("split", {}), ("exact", {"IGCN_ATTN_EXACT_FP32": "1"}),
-                           ("twice", {"IGCN_ATTN_EXACT_FP32": "1", "IGCN_ATTN_BWD_TWICE": "1"})):
+                           ("twice", {"IGCN_ATTN_EXACT_FP32": "1", "IGCN_ATTN_BWD_TWICE": "1"}),
+                           ("fp32core", {"IGCN_ATTN_FP32_CORE": "1"})):
             env = dict(os.environ)
-            for k in ("IGCN_ATTN_BWD_TWICE", "IGCN_ATTN_EXACT_FP32"):
+            for k in ("IGCN_ATTN_BWD_TWICE", "IGCN_ATTN_EXACT_FP32", "IGCN_ATTN_FP32_CORE"):
                 env.pop(k, None)
             env.update(extra)
             path = os.path.join(d, f"g_{tag}.pt")
@@ -1430,8 +1478,11 @@ torch.save([t.cpu() for t in gs[0]], sys.argv[1])
                                timeout=600)
             assert r.returncode == 0, (tag, r.stderr[-2000:])
             outs[tag] = torch.load(path)
+    # IGCN_ATTN_FP32_CORE=1: bf16 feature transforms keep the fp32 core (the default child's core), not the bf16 one
+    assert all(torch.equal(a, b) for a, b in zip(outs["fp32core"][3:], outs["split"][:3]))
+    assert not any(torch.equal(a, b) for a, b in zip(outs["split"][3:], outs["split"][:3])), "the bf16 core did not run"
     assert torch.equal(outs["exact"][0], outs["twice"][0])                      # (the switch is about the backward)
-    for a, b, nm in zip(outs["exact"][1:], outs["twice"][1:], ("dq", "dkv")):
+    for a, b, nm in zip(outs["exact"][1:3], outs["twice"][1:3], ("dq", "dkv")):
         assert not torch.equal(a, b), nm + ": the switch did not change the kernel"
         assert_matches(a, b.numpy(), 2e-5, nm + " shared vs two-pass", floor=1e-6)
     for a, b, nm, tol_ in zip(outs["split"], outs["exact"], ("o", "dq", "dkv"), (1e-4, 1e-3, 1e-3)):
