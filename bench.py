@@ -2,15 +2,21 @@
 """bench.py — graphs/s of the full IG-GCN train step (SGCN over 90-ROI brain graphs + GO-SNP network).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--blocks 5] [--workload full|sgcn|stress] [--dump-outputs DIR]
+                    [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     IGCN_BENCH_SWEEP="1,2,4,8" python bench.py ...        one line per N, weak-scaling efficiency vs its own N = 1 run
 
 The --steps timed steps are split into --blocks blocks of (nearly) equal size, each between barriers + synchronize; the
 line reports the MEDIAN block's milliseconds per step (`ms_per_step`) and the spread (`timing`).  --dump-outputs DIR
 writes what the last timed step handed its caller (loss, updated parameters, gradients, BatchNorm statistics) as
-DIR/<name>.npy, so that two builds can be compared output for output on identical, seeded inputs.  The default line
-also carries the loader-fed step (`pipeline`: host feeder thread / device-resident dataset / device GDC one batch ahead
-on a side stream) and, at N > 1, the distributed step taken apart per rank (`distributed_step`).
+DIR/<name>.npy, so that two builds can be compared output for output on identical, seeded inputs.
+
+A plain run does only what the headline needs: set-up, graph capture, warm-up, the timed steps, the dump, the line.
+``--full`` adds everything else, each after the timed steps: the loader-fed step (`pipeline`: host feeder thread /
+device-resident dataset / device GDC one batch ahead on a side stream), the roofline fields and the in-step profile
+below, the (layers, hidden) sweep (`model_sweep`), the CPU baseline, the configs[4] child (`stress`) and, at N > 1, the
+distributed step taken apart per rank (`distributed_step`, `config.allreduce_us_per_step`).  The --no-* options trim
+a --full run; --model-sweep, --pipeline and --rotate ask for their own part with or without it.
 
 Default workload (BASELINE.json configs[2]): full SGCN_GCN_IMGSNP (L=2, hidden=16, R=90, H0=3,
 cross-attention fusion, 3 classes, 3 regression targets), synthetic GO DAG N=3000 pool [1800,800,300,99,1],
@@ -21,7 +27,7 @@ in HBM.  Prints ONE JSON line on rank 0.
 ``--workload stress`` = BASELINE configs[4]: 512-ROI dense graphs + 10k-node GO DAG, 32 graphs per GPU, dense
 feature transforms with bf16 operands on the matrix cores (fp32 accumulation); same JSON contract.
 
-Roofline fields (rank 0, N=1):
+Roofline fields (--full, rank 0, N=1):
   roofline        the GCN scatter-aggregate kernel AS THE STEP LAUNCHES IT.  ``us_per_launch`` is the kernel's average
                   duration inside the train step, read from a ``rocprofv3 --kernel-trace --stats`` run of this very
                   command made by this invocation (a child process; the CSV is the one committed under profiles/).
@@ -906,9 +912,9 @@ def step_traffic(workload, kernel_us_per_step):
 def stress_child(timeout=300):
     """BASELINE configs[4] beside the headline: a short ``--workload stress`` run of this script in a CHILD process
     (its own model, graph capture, in-step rocprofv3 profile and bounded CPU-oracle sample) whose result line is folded
-    into the default line as ``stress``.  None (with the reason on stderr) when the child fails: the headline stands."""
+    into the --full line as ``stress``.  None (with the reason on stderr) when the child fails: the headline stands."""
     cmd = [sys.executable, os.path.abspath(__file__), "--workload", "stress", "--steps", "30", "--warmup", "3",
-           "--cpu-baseline-seconds", "8", "--no-stress", "--no-pipeline", "--blocks", "3"]
+           "--full", "--cpu-baseline-seconds", "8", "--no-stress", "--no-pipeline", "--blocks", "3"]
     # the child profiles into its own directory (a kept parent directory would hand it the parent's kernel summary)
     env = dict(os.environ)
     keep = env.pop("IGCN_BENCH_PROFILE_DIR", None)
@@ -1063,6 +1069,10 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30, help="timed steps in all, split over --blocks blocks")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything the headline does not need: loader-fed runs, "
+                         "in-step profile and rooflines, model sweep, CPU baseline, configs[4] child, distributed "
+                         "step per rank")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true", help="skip the roofline measurements (and the profiler child)")
     ap.add_argument("--eager", action="store_true", help="no hipGraph replay of the step")
@@ -1073,18 +1083,19 @@ def main():
     ap.add_argument("--rotate", type=int, default=0,
                     help="time GraphedTrainStep.load + replay over this many distinct device-resident batches")
     ap.add_argument("--pipeline", action="store_true",
-                    help="loader-fed runs: default for the sparse workloads since round 4; forces them for --workload stress")
+                    help="loader-fed runs, also without --full (which has them for the sparse workloads); forces them "
+                         "for --workload stress")
     ap.add_argument("--no-pipeline", action="store_true",
                     help="skip the loader-fed runs (host feeder thread / device-resident dataset / device GDC)")
     ap.add_argument("--blocks", type=int, default=5,
                     help="the --steps timed steps are split into this many blocks (at most --steps); the median block is "
                          "reported")
     ap.add_argument("--no-stress", action="store_true",
-                    help="default workload only: skip the short configs[4] child run reported as `stress`")
+                    help="--full, default workload only: skip the short configs[4] child run reported as `stress`")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=20.0, help="bound of the CPU-oracle sample")
     ap.add_argument("--model-sweep", action="store_true",
                     help="also time the five (layers, hidden) entries of the reference's sweep (main.py:152-154)")
-    ap.add_argument("--no-model-sweep", action="store_true", help="skip them in the default line")
+    ap.add_argument("--no-model-sweep", action="store_true", help="skip them in the --full line")
     ap.add_argument("--inner-profile", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the last timed step's outputs (loss, parameters, gradients, buffers) as DIR/<name>.npy")
@@ -1257,9 +1268,9 @@ def main():
 
     # the distributed step taken apart (two-graph form; an all-reduce captured into the step graph cannot be bracketed):
     # HIP events on the launch stream around [forward..backward + pack] graph | all-reduce | [Adam] graph of extra steps,
-    # the host's enqueue time per step, and the all-reduce alone back to back (no step around it) — per RANK
+    # the host's enqueue time per step, and the all-reduce alone back to back (no step around it) — per RANK (--full)
     allreduce_us, dist_parts = None, None
-    if dist_on and gstep is not None and gstep.g_opt is not None:
+    if args.full and dist_on and gstep is not None and gstep.g_opt is not None:
         def ev():
             return torch.cuda.Event(enable_timing=True)
         recs, host_us = [], []
@@ -1362,11 +1373,11 @@ def main():
             res["rotating_batches"] = {"batches": args.rotate,
                                        "ms_per_step_load_plus_replay": round((time.perf_counter() - t1) / args.steps * 1e3, 3)}
         # (dense 512-ROI subjects are 1.3 MB of edge list each: that dataset is not host-fed per step; --pipeline forces it)
-        if not args.no_pipeline and gstep is not None and world == 1 and wl["pool"] is not None \
-                and (not wl["dense"] or args.pipeline):
+        if (args.full or args.pipeline) and not args.no_pipeline and gstep is not None and world == 1 \
+                and wl["pool"] is not None and (not wl["dense"] or args.pipeline):
             # the loader-fed step (the reference's step starts at `for data in loader: data = data.to(device)`, :515-517)
             res["pipeline"] = pipeline_bench(gstep, wl, device, max(args.steps, 60), args.warmup, res["ms_per_step"])
-        if wl["pool"] is not None and world == 1 and not args.no_roofline:
+        if args.full and wl["pool"] is not None and world == 1 and not args.no_roofline:
             stats = instep_profile(args.workload, bf16)
             dense_rf = dense_roofline(data, wl, stats) if wl["dense"] else None
             standalone = scatter_roofline(data, device, wl, stats) if dense_rf is None else None
@@ -1396,11 +1407,12 @@ def main():
                 if whole is not None:
                     res["roofline_step"] = whole
         if wl["pool"] is not None and world == 1 and not wl["dense"] and gstep is not None \
-                and (args.model_sweep or (args.workload == "full" and not args.no_roofline and not args.no_model_sweep)):
+                and (args.model_sweep or (args.full and args.workload == "full" and not args.no_roofline
+                                          and not args.no_model_sweep)):
             res["model_sweep"] = model_sweep(wl, device, data)
-        if wl["pool"] is not None and world == 1 and not args.no_cpu_baseline:
+        if args.full and wl["pool"] is not None and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(args.workload, seconds=args.cpu_baseline_seconds, device=device)
-        if args.workload == "full" and world == 1 and not args.no_roofline and not args.no_stress:
+        if args.full and args.workload == "full" and world == 1 and not args.no_roofline and not args.no_stress:
             # the device is idle from here on: this process has finished its own measurements
             torch.cuda.synchronize()
             st = stress_child()

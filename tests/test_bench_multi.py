@@ -4,7 +4,8 @@ run that way or under torch.distributed.run).  bench.py then starts its own rank
 * CPU: on a box without N GPUs the command says what is missing and exits 2 (no traceback, no GPU call).
 * GPU: the one-device rehearsal (IGCN_BENCH_ONE_DEVICE=1: both ranks share cuda:0, gradients over gloo) runs the
   multi-rank control flow end to end — rendezvous, parameter broadcast, shard-seeded batches, graphed step around the
-  all-reduce, barrier-bracketed timing, max over ranks, ONE JSON line from rank 0.
+  all-reduce, barrier-bracketed timing, max over ranks, ONE JSON line from rank 0; with --full the line also takes the
+  distributed step apart per rank.
 """
 import json
 import math
@@ -36,7 +37,7 @@ def test_gpus_2_self_launch_rehearsal_on_one_device():
         pytest.skip("needs a GPU")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(IGCN_BENCH_ONE_DEVICE="1", IGCN_BENCH_N1_VALUE="250000")
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-roofline",
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-roofline",
                         "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -70,9 +71,9 @@ def test_sweep_prints_one_line_per_n_and_exchange_form_with_efficiency():
         pytest.skip("needs a GPU")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "IGCN_BENCH_N1_VALUE")}
     env.update(IGCN_BENCH_ONE_DEVICE="1", IGCN_BENCH_SWEEP="1,2")
-    r = subprocess.run([sys.executable, BENCH, "--steps", "3", "--warmup", "1", "--blocks", "2", "--no-roofline",
-                        "--no-cpu-baseline", "--no-pipeline", "--no-stress"], env=env, capture_output=True, text=True,
-                       timeout=900)
+    r = subprocess.run([sys.executable, BENCH, "--steps", "3", "--warmup", "1", "--blocks", "2", "--full",
+                        "--no-roofline", "--no-cpu-baseline", "--no-pipeline", "--no-stress"], env=env,
+                       capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [json.loads(ln) for ln in r.stdout.splitlines() if ln.strip()]
     assert [ln["n_gpus"] for ln in lines] == [1, 2, 2, 2]

@@ -17,7 +17,7 @@ for abl in ${DS_ABL_LIST:-1 2 3 0}; do
   case $abl in [0-9]) def="-DDS_ABL=$abl";; *) def="$abl";; esac
   /opt/rocm/bin/hipcc $FLAGS $def -c ig-gcn_amd/csrc/sgcn_dense.hip -o $O/obj/sgcn_dense.hip.o || exit 1
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $O/obj/*.o -o $LIB || exit 1
-  IGCN_BENCH_PROFILE_DIR=$O/p$abl timeout -k 5 300 python bench.py --workload stress --no-cpu-baseline > $O/bench_$abl.json 2> $O/bench_$abl.err || { cp $O/shipped.so $LIB; exit 1; }
+  IGCN_BENCH_PROFILE_DIR=$O/p$abl timeout -k 5 300 python bench.py --workload stress --full --no-cpu-baseline > $O/bench_$abl.json 2> $O/bench_$abl.err || { cp $O/shipped.so $LIB; exit 1; }
   echo "== DS_ABL=$abl  $(python -c "import json; d=json.load(open('$O/bench_$abl.json')); print(d['ms_per_step'], 'ms/step')")" >> gpurun_out/dense_ablate.txt
   grep -E "k_ds_" $O/p$abl/stress_replay_kernel_stats.csv >> gpurun_out/dense_ablate.txt
   rm -rf $O/p$abl

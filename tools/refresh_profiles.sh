@@ -8,15 +8,15 @@ O=$GRAFT_REPO_ROOT/gpurun_out/refresh
 rm -rf $O
 mkdir -p $O
 cd $GRAFT_REPO_ROOT
-IGCN_BENCH_PROFILE_DIR=$O/full timeout -k 5 600 python bench.py --steps 20 --warmup 5 > $O/${TAG}_bench_full.json 2> $O/full.err
+IGCN_BENCH_PROFILE_DIR=$O/full timeout -k 5 600 python bench.py --steps 20 --warmup 5 --full > $O/${TAG}_bench_full.json 2> $O/full.err
 cp $O/full/full_kernel_stats.csv $O/${TAG}_bench_full_kernel_stats.csv
 cp $O/full/full_replay_kernel_stats.csv $O/${TAG}_bench_full_replay_kernel_stats.csv      # the timed replays only
 cp $O/full/stress_child/stress_replay_kernel_stats.csv $O/${TAG}_bench_full_stress_child_replay_kernel_stats.csv || true
-IGCN_BENCH_PROFILE_DIR=$O/stress timeout -k 5 400 python bench.py --workload stress > $O/${TAG}_bench_stress.json 2> $O/stress.err
+IGCN_BENCH_PROFILE_DIR=$O/stress timeout -k 5 400 python bench.py --workload stress --full > $O/${TAG}_bench_stress.json 2> $O/stress.err
 cp $O/stress/stress_kernel_stats.csv $O/${TAG}_bench_stress_kernel_stats.csv
 cp $O/stress/stress_replay_kernel_stats.csv $O/${TAG}_bench_stress_replay_kernel_stats.csv
 timeout -k 5 300 python bench.py --workload sgcn > $O/${TAG}_bench_sgcn.json 2> $O/sgcn.err
-IGCN_BENCH_GDC_SERIAL=1 timeout -k 5 400 python bench.py --no-roofline --no-cpu-baseline --no-stress > $O/${TAG}_bench_pipeline.json 2> $O/pipeline.err
+IGCN_BENCH_GDC_SERIAL=1 timeout -k 5 400 python bench.py --full --no-roofline --no-cpu-baseline --no-stress > $O/${TAG}_bench_pipeline.json 2> $O/pipeline.err
 rm -rf $O/full $O/stress
 tools/replay_trace.sh refresh/replay_full full 10 > /dev/null
 tools/replay_trace.sh refresh/replay_stress stress 6 > /dev/null
