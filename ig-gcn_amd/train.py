@@ -4,6 +4,7 @@ graph-batch data parallelism the reference does not have (one process per GPU, o
 flat fp32 gradient buffer per step).
 """
 import sys
+import weakref
 from types import SimpleNamespace
 
 import torch
@@ -1193,6 +1194,231 @@ def eval_outputs(model, loader, temperature=None, device=None):
         cols["logp"].append(logp)
         cols["pred"].append(logp.max(1)[1])
     return {k: torch.cat(v) for k, v in cols.items() if v}
+
+
+# the per-row epoch buffers of an Evaluator: name -> (dtype, width attribute; None = one column)
+_EVAL_ROWS = {"logp": (torch.float32, "C"), "pred": (torch.int64, None), "y": (torch.int64, None),
+              "reg": (torch.float32, "NR"), "clini_score": (torch.float32, "NR"), "out_lin": (torch.float32, "F"),
+              "linear_outf": (torch.float32, "H"), "sbjID": (torch.int64, None)}
+_EVAL_FIELDS = ("loss", "accuracy", "auc", "f1", "sensitivity", "specificity")
+_EVALUATORS = weakref.WeakKeyDictionary()      # model -> {(lambda_loss, hp): Evaluator}; an entry dies with its model
+
+
+class _EvalGraph:
+    """One captured evaluation batch: the batched sweep under ``torch.no_grad()`` in eval mode, then igcn_eval_collect.
+    ``plan`` / ``data`` are what ``GraphedTrainStep.load`` reads: its checks and its one-launch hand-over are reused."""
+
+    def __init__(self, ev, data):
+        from . import ops
+        self.data = data
+        self.plan = ops.plan_for(data)
+        self.g = torch.cuda.CUDAGraph()
+        torch.cuda.synchronize()
+        with _capture(self.g):
+            ev._sweep(self.data, self.plan)
+        torch.cuda.synchronize()
+
+    def load(self, batch):
+        GraphedTrainStep.load(self, batch)
+        self.data.sbjID.copy_(batch.sbjID.reshape(self.data.sbjID.shape), non_blocking=True)
+
+
+class Evaluator:
+    """``eval_loss``, ``eval_acc`` and ``eval_scores`` of kernel/train_eval_sgcn_img_snps.py:551-671 in ONE sweep per batch,
+    with the metrics computed on the device.
+
+    Each batch runs the batched route (``_losses_batched``: plain rows [0,B), explain rows [B,2B)) under
+    ``torch.no_grad()`` in eval mode; its last launch, igcn_eval_collect, appends the plain-pass rows, the prediction, the
+    labels, the subject ids and the batch's share of the loss to epoch buffers at a row cursor held in device memory.
+    After the last batch igcn_eval_metrics computes loss, accuracy, AUC, weighted F1, sensitivity, specificity and per
+    target pearson r / r2 / RMSE, read back with one copy.  Like ``EpochTrainer``, every batch signature runs eagerly
+    the first time it is met (the warm-up) and is captured into a hipGraph the second time; the graphs of all shapes
+    write the same buffers through the cursor.  Models that ``_batched`` rejects take an eager forward in front of the
+    same two kernels.
+
+    The buffers hold ``len(loader.dataset)`` rows and grow (dropping the captured graphs, which point at them) when a
+    longer loader comes; ``capacity`` fixes their size instead, and a loader beyond it raises.  The graphs also hold the
+    addresses of the model's parameters and buffers: when any of them has moved since the capture (``FlatAdam`` re-binds
+    every parameter into its flat buffer, ``model.to``, ``load_state_dict(assign=True)``) they are dropped, and each
+    shape is warmed up and captured anew.  Evaluation leaves
+    parameters, module buffers, the optimiser, captured train steps and torch's RNG state as they were, and clears the
+    regulariser the model keeps for ``loss_probability``."""
+
+    def __init__(self, model, lambda_loss=DEFAULT_LAMBDA, hp=HP, temperature=None, capacity=None, max_graphs=4):
+        if not hasattr(model, "go_network"):
+            raise ValueError("Evaluator: SGCN_GCN_IMGSNP models only (SGCN_GCN has its own eval loop)")
+        self._model = weakref.ref(model)             # (kept by ``evaluate`` in a table keyed weakly on the model)
+        self.lam, self.hp, self.temperature = tuple(float(v) for v in lambda_loss), hp, temperature
+        self.C, self.NR = int(model.lin2.weight.shape[0]), int(model.lin2_regr.weight.shape[0])
+        self.F, self.H = int(model.lin1.weight.shape[1]), int(model.lin1.weight.shape[0])
+        self.fixed = capacity is not None
+        if self.fixed and int(capacity) < 1:
+            raise ValueError("Evaluator: capacity must be at least one row")
+        self.capacity = int(capacity) if capacity is not None else 0
+        self.max_graphs = int(max_graphs)
+        self.graphed = _batched(model)
+        self.graphs, self.seen = {}, {}
+        self.storage = None                          # where the model's tensors were when ``graphs`` were captured
+        self.counts = {"eager": 0, "replayed": 0, "captured": 0}
+        self.rows = None
+
+    @property
+    def model(self):
+        return self._model()
+
+    def _reserve(self, need, dev):
+        """Epoch buffers of ``max(need, capacity)`` rows (``capacity`` only when fixed)."""
+        cap = self.capacity if self.fixed else max(int(need), self.capacity)
+        if self.rows is not None and cap == self.capacity:
+            return
+        self.graphs, self.seen = {}, {}              # the captured collects point at the old buffers
+        self.capacity = cap
+        self.rows = {k: torch.zeros((cap,) if w is None else (cap, getattr(self, w)), dtype=dt, device=dev)
+                     for k, (dt, w) in _EVAL_ROWS.items()}
+        self.state = torch.zeros(3, dtype=torch.int64, device=dev)          # cursor, overflow, correct
+        self.loss_sum = torch.zeros(1, dtype=torch.float64, device=dev)
+        self.parts = torch.zeros(2 * max(1, (cap + 255) // 256), dtype=torch.int64, device=dev)
+        self.out = torch.zeros(8 + 3 * self.NR + self.C * self.C, dtype=torch.float64, device=dev)
+
+    def _sweep(self, data, plan=None):
+        """One batch: forward(s), loss, igcn_eval_collect.  ``plan``: the captured batch's static plan, rebuilt in place."""
+        model = self.model
+        forget_riders(model)
+        if plan is not None:
+            data._igcn_plan = plan
+            plan.rebuild(data.edge_index, lazy=True)
+        try:
+            with torch.no_grad():
+                loss, _, outs = losses(model, data, self.lam, self.hp, self.temperature)
+        except BaseException:
+            forget_riders(model)
+            raise
+        logp, _, _, out_lin, lin_f, reg = outs if self.graphed else outs[0]
+        B = int(data.num_graphs)
+        sbj = getattr(data, "sbjID", None)
+        if sbj is None or sbj.numel() != B:
+            raise ValueError("evaluate: every batch must carry sbjID (one id per graph)")
+        logp, reg = logp.reshape(-1, self.C), reg.reshape(-1, self.NR)
+        out_lin, lin_f = out_lin.reshape(-1, self.F), lin_f.reshape(-1, self.H)
+        for name, t in (("logp", logp), ("reg", reg), ("out_lin", out_lin), ("linear_outf", lin_f)):
+            if t.dtype != torch.float32 or t.shape[0] < B:
+                raise _lib.IgcnError(f"evaluate: {name} {tuple(t.shape)} {t.dtype} has no fp32 plain-pass rows [0, {B})")
+        clin = data.clini_score.reshape(B, self.NR).float().contiguous()
+        r = self.rows
+        call("igcn_eval_collect", B, self.C, self.NR, self.F, self.H, ptr(loss.reshape(()).float().contiguous()),
+             ptr(logp.contiguous()), ptr(reg.contiguous()), ptr(out_lin.contiguous()), ptr(lin_f.contiguous()),
+             ptr(data.y.reshape(-1).long().contiguous()), ptr(clin), ptr(sbj.reshape(-1).long().contiguous()), self.capacity,
+             ptr(self.state), ptr(self.loss_sum), ptr(r["logp"]), ptr(r["pred"]), ptr(r["y"]), ptr(r["reg"]),
+             ptr(r["clini_score"]), ptr(r["out_lin"]), ptr(r["linear_outf"]), ptr(r["sbjID"]), stream_ptr())
+        assert_nothing_pending("Evaluator")
+
+    def _batch(self, data):
+        sig = _batch_signature(data)
+        g = self.graphs.get(sig)
+        if g is None and self.graphed and data.x.is_cuda:
+            n = self.seen.get(sig, 0)
+            self.seen[sig] = n + 1
+            if n >= 1 and len(self.graphs) < self.max_graphs:
+                g = self.graphs[sig] = _EvalGraph(self, _clone_batch(data))
+                self.counts["captured"] += 1
+        if g is not None:
+            try:
+                g.load(data)
+            except ValueError:                       # beyond the per-graph sizes the capture was made for
+                g = None
+        if g is None:
+            self.counts["eager"] += 1
+            self._sweep(data)
+            return
+        g.g.replay()
+        self.counts["replayed"] += 1
+
+    def evaluate(self, loader, device=None):
+        """One pass over ``loader``; returns the metrics and the per-row tensors (see ``evaluate``)."""
+        model = self.model
+        dev = next(model.parameters()).device
+        if not hasattr(loader, "dataset"):
+            loader = list(loader)
+        need = len(loader.dataset) if hasattr(loader, "dataset") else sum(int(d.num_graphs) for d in loader)
+        self._reserve(need, dev)
+        storage = tuple(t.data_ptr() for t in (*model.parameters(), *model.buffers()))
+        if storage != self.storage:
+            self.graphs, self.seen = {}, {}          # the captured launches would read the old storage
+            self.storage = storage
+        was = model.training
+        model.eval()
+        n = 0
+        try:
+            self.state.zero_()
+            self.loss_sum.zero_()
+            for data in _batches(loader, device):
+                self._batch(data)
+                n += int(data.num_graphs)
+        finally:
+            model._handoff = type(model._handoff)()     # no later loss_probability is served from an eval batch
+            model.last_edge_prob = None
+            model.train(was)
+        if n == 0:
+            raise ValueError("evaluate: the loader is empty")
+        r = self.rows
+        call("igcn_eval_metrics", min(n, self.capacity), self.C, self.NR, ptr(r["logp"]), ptr(r["pred"]), ptr(r["y"]), ptr(r["reg"]),
+             ptr(r["clini_score"]), ptr(self.state), ptr(self.loss_sum), ptr(self.parts), ptr(self.out), stream_ptr())
+        v = self.out.cpu().numpy()
+        if v[1] != 0:
+            raise _lib.IgcnError(f"evaluate: {n} rows do not fit the epoch buffers ({self.capacity} rows); the batches "
+                                 f"from row {int(v[0])} on were not written")
+        nr, c = self.NR, self.C
+        res = {k: float(x) for k, x in zip(_EVAL_FIELDS, v[2:8])}
+        res["corr"], res["r2"], res["rmse"] = ([float(x) for x in v[8 + j * nr:8 + (j + 1) * nr]] for j in range(3))
+        res["confusion"] = v[8 + 3 * nr:].astype("int64").reshape(c, c)
+        res["n"] = n
+        res.update({k: t[:n].clone() for k, t in r.items()})
+        return res
+
+
+def evaluate(model, loader, lambda_loss=DEFAULT_LAMBDA, hp=HP, temperature=None, device=None, num_classes=None,
+             num_regr=None):
+    """``eval_loss`` (:564-600), ``eval_acc`` (:551-561) and ``eval_scores`` (:602-671) of one loader in ONE sweep per
+    batch (``Evaluator``, kept per model so that every epoch re-uses its captured graphs).  Returns a dict:
+    ``loss``, ``accuracy``, ``auc``, ``f1``, ``sensitivity``, ``specificity`` (floats; the last three 0 unless the model
+    has 2 classes), ``corr`` / ``r2`` / ``rmse`` (one float per regression target), ``confusion`` ([C, C] counts,
+    true-major), ``n`` (rows), and the per-row device tensors ``logp``, ``pred``, ``y``, ``reg``, ``clini_score``,
+    ``out_lin``, ``linear_outf``, ``sbjID``.  Rank-local: under data parallelism the caller shards and gathers.
+    ``temperature`` is passed to the forward, which does not read it (as in the reference)."""
+    if num_classes is not None and int(num_classes) != model.lin2.weight.shape[0]:
+        raise ValueError(f"evaluate: num_classes={num_classes}, the model has {model.lin2.weight.shape[0]} classes")
+    if num_regr is not None and int(num_regr) != model.lin2_regr.weight.shape[0]:
+        raise ValueError(f"evaluate: num_regr={num_regr}, the model has {model.lin2_regr.weight.shape[0]} targets")
+    hp_key = tuple(float(getattr(hp, k)) for k in ("lamda_x_l1", "lamda_e_l1", "lamda_x_ent", "lamda_e_ent", "lamda_mi",
+                                                    "lamda_ce"))
+    key = (tuple(float(v) for v in lambda_loss), hp_key)
+    cache = _EVALUATORS.setdefault(model, {})
+    ev = cache.get(key)
+    if ev is None:
+        ev = cache[key] = Evaluator(model, lambda_loss, hp, temperature)
+    ev.temperature = temperature
+    return ev.evaluate(loader, device)
+
+
+def eval_scores(model, loader, temperature, lambda_loss, criterion_recon, isSoftSimilarity, device, num_classes=2,
+                num_regr=4):
+    """eval_scores() kernel/train_eval_sgcn_img_snps.py:602-671 with its 11-tuple: true_label, pred_label (numpy),
+    accuracy, auc, f1, sensitivity, specificity, all_out_hidden (out_lin), all_out_subid, all_out_linear (CPU tensors),
+    regression_result = (true scores, predicted scores with NaN -> 0, corr, r2, rmse).  The metrics come from the device
+    (``evaluate``), not from sklearn / scipy.  ``criterion_recon`` and ``isSoftSimilarity`` are accepted and unused: the
+    model's own squared error and similarity setting are what the loss takes."""
+    return eval_scores_of(evaluate(model, loader, lambda_loss, HP, temperature, device, num_classes, num_regr))
+
+
+def eval_scores_of(r):
+    """The 11-tuple of ``eval_scores`` from a result of ``evaluate``: a loop that has just evaluated the test loader
+    takes eval_scores from that sweep instead of running another one."""
+    true_clin = r["clini_score"].cpu()
+    pred_clin = r["reg"].cpu()
+    pred_clin = torch.where(torch.isnan(pred_clin), torch.zeros_like(pred_clin), pred_clin)
+    regression = (true_clin.tolist(), pred_clin.tolist(), r["corr"], r["r2"], r["rmse"])
+    return (r["y"].cpu().numpy(), r["pred"].cpu().numpy(), r["accuracy"], r["auc"], r["f1"], r["sensitivity"],
+            r["specificity"], r["out_lin"].cpu(), r["sbjID"].cpu(), r["linear_outf"].cpu(), regression)
 
 
 def output_importance(model):

@@ -31,7 +31,7 @@ extern "C" {
 /* ABI revision: bumped whenever a prototype below changes (argument added, removed or re-ordered).  igcn_version()
  * returns the revision the library was built from; a binding written against a different one must refuse to call
  * (igcn_amd/_lib.py does). */
-#define IGCN_ABI_VERSION 423
+#define IGCN_ABI_VERSION 424
 int igcn_version(void);
 const char* igcn_last_error(void);
 /* A/B switches, set ONCE by the binding when it loads the library (from the IGCN_* environment variables): bit 0 no tiled
@@ -1006,6 +1006,33 @@ int igcn_gdc_topk(int B, int R, int k, double alpha, const float* A, int64_t* ed
  * not read: graph g comes out empty (counts[g] = 0, all its slots padding). */
 int igcn_gdc_topk_of(int B, int R, int k, double alpha, const float* A, int64_t n_subjects, const int64_t* subject,
                      int64_t* edge_index, float* edge_attr, int32_t* counts, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Epoch evaluation on the device (csrc/eval.hip): replaces the per-batch host work of eval_loss :564-600, eval_acc
+ * :551-561 and eval_scores :602-671 (kernel/train_eval_sgcn_img_snps.py) and the sklearn / scipy metrics of :633-667.
+ * igcn_eval_collect: the last launch of one evaluation batch.  Reads the plain-pass rows [0, B) of logp [*, C], reg
+ * [*, NR], out_lin [*, F], lin_f [*, H] (the stacked [2B, *] outputs of the batched sweep, or [B, *]), y [B] int64,
+ * clin [B, NR], sbj [B] int64 and the batch loss (device scalar).  At row cursor c = state[0] it writes rows [c, c + B)
+ * of the epoch buffers (rows_logp [cap, C], rows_pred = argmax(logp) [cap] int64, rows_y, rows_reg / rows_clin [cap, NR],
+ * rows_out_lin [cap, F], rows_lin_f [cap, H], rows_sbj [cap] int64), adds loss * B to loss_sum[0] (fp64) and the correct
+ * count to state[2], then advances the cursor.  If state[1] (overflow) is set or c + B > capacity it writes nothing and
+ * sets state[1] = 1.  state int64 [3] and loss_sum are zeroed by the caller before the first batch.
+ * igcn_eval_metrics: one call after the last batch, over the first n rows (1 <= n <= 65536; C <= 16).  parts: int64
+ * workspace of 2 * ceil(n / 256).  out [8 + 3 NR + C C] fp64 = {rows written (state[0]), overflow (state[1]), loss =
+ * loss_sum / n, accuracy = correct / n, auc, weighted f1, sensitivity, specificity, corr[NR], r2[NR], rmse[NR],
+ * confusion[C][C] (true-major counts)}.  auc / sensitivity / specificity only for C = 2 (else 0): auc is the Mann-Whitney
+ * statistic of logp[:, 1] (ties 1/2; NaN when a class is absent, 0 when a score is NaN, as the reference's except
+ * makes sklearn's error); sensitivity / specificity NaN on a zero denominator.  Per target: predictions' NaN -> 0,
+ * pearsonr (NaN for a constant input), r2_score with force_finite, RMSE.  Integer counts and fixed-order fp64 sums:
+ * bitwise reproducible. */
+int igcn_eval_collect(int B, int C, int NR, int F, int H, const float* loss, const float* logp, const float* reg,
+                      const float* out_lin, const float* lin_f, const int64_t* y, const float* clin, const int64_t* sbj,
+                      int64_t capacity, int64_t* state, double* loss_sum, float* rows_logp, int64_t* rows_pred,
+                      int64_t* rows_y, float* rows_reg, float* rows_clin, float* rows_out_lin, float* rows_lin_f,
+                      int64_t* rows_sbj, void* stream);
+int igcn_eval_metrics(int64_t n, int C, int NR, const float* logp, const int64_t* pred, const int64_t* y,
+                      const float* reg, const float* clin, const int64_t* state, const double* loss_sum, int64_t* parts,
+                      double* out, void* stream);
 
 #ifdef __cplusplus
 }
