@@ -45,6 +45,10 @@ SIGNATURES = {
     "igcn_sgcn_stack_param_floats": (I, [I, I, I]),
     "igcn_sgcn_stack_fwd": (I, [L, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P]),
     "igcn_sgcn_stack_bwd": (I, [L, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "igcn_gat_stack_lds_bytes": (Z, [I, I, I, I, I, I]),
+    "igcn_gat_stack_param_floats": (I, [I, I, I]),
+    "igcn_gat_stack_fwd": (I, [L, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P]),
+    "igcn_gat_stack_bwd": (I, [L, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "igcn_sgcn_front_lds_bytes": (Z, [I, I, I, I, I]),
     "igcn_sgcn_front_fwd": (I, [L, L, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, F, F, F, F, F, P, P, P,
                                 P, P, P, P]),

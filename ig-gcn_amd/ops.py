@@ -687,6 +687,88 @@ def _sgcn_stack_backward(x_in, ew_in, wb, plan, rois, final, dxcat, dxcat2):
     return dx, dew, grads
 
 
+GAT_WIDTHS = (4, 8, 16, 32)
+GAT_MAX_LAYERS = 4
+GAT_MAX_H0 = 8
+GAT_LDS_BYTES = 150 * 1024
+
+
+def gat_stack_limits(plan, rois, h0, f, layers):
+    """None when the LDS-resident GAT stack (igcn_gat_stack_*) covers this batch, else the limit it breaks (a sentence)."""
+    seg = getattr(plan, "_stack_dims", None)
+    if seg is None or seg[0] != rois:
+        return f"needs a per-graph plan of uniform graphs with rois={rois} nodes each"
+    if f not in GAT_WIDTHS:
+        return f"needs a layer width F in {GAT_WIDTHS} (got {f})"
+    if not 1 <= layers <= GAT_MAX_LAYERS:
+        return f"needs 1 <= layers <= {GAT_MAX_LAYERS} (got {layers})"
+    if not 1 <= h0 <= GAT_MAX_H0:
+        return f"needs 1 <= H0 <= {GAT_MAX_H0} input features (got {h0})"
+    need = int(_lib.load().igcn_gat_stack_lds_bytes(rois, seg[1], h0, f, layers, 1))
+    if need > GAT_LDS_BYTES:
+        return (f"needs a graph that fits {GAT_LDS_BYTES // 1024} KB of LDS (rois={rois}, max edges {seg[1]}, F={f}, "
+                f"L={layers}: {need} bytes)")
+    return None
+
+
+def gat_stack_supported(plan, rois, h0, f, layers):
+    """The LDS-resident GAT stack (igcn_gat_stack_*) covers this batch (``gat_stack_limits`` says which limit fails)."""
+    return gat_stack_limits(plan, rois, h0, f, layers) is None
+
+
+class GatStack(torch.autograd.Function):
+    """xcat = cat_l relu(GATConv_l(...)) of kernel/gcn_img_snp.py:217-221 with ifUseGAT (PyG 2.0.2 GATConv(in, F,
+    edge_dim=1)) for a batch of small uniform graphs: one LDS-resident kernel per direction (igcn_gat_stack_*).  ``params``
+    = per layer W [F, Fin], bias [F], att_src [F], att_dst [F], lin_edge [F], att_edge [F]; ``ew_in`` (the scalar edge
+    attributes) is data.  Shapes outside the kernels' coverage raise ValueError: there is no other GAT path."""
+
+    @staticmethod
+    def forward(ctx, x_in, ew_in, plan, rois, *params):
+        x_in, ew_in = _f32(x_in), _f32(ew_in.reshape(-1))
+        params = [_f32(t) for t in params]
+        n, h0 = x_in.shape
+        f, layers = params[0].shape[0], len(params) // 6
+        why = gat_stack_limits(plan, rois, h0, f, layers)
+        if why is not None:
+            raise ValueError(f"GAT stack: {why}")
+        emax = plan._stack_dims[1]
+        xcat = torch.empty(n, layers * f, dtype=torch.float32, device=x_in.device)
+        pp = (ctypes.c_void_p * len(params))(*[t.data_ptr() for t in params])
+        call("igcn_gat_stack_fwd", n // rois, rois, emax, h0, f, layers, ptr(x_in), ptr(ew_in), ptr(plan.src32),
+             ptr(plan.dst32), ptr(plan.tgt_ptr), ptr(plan.tgt_perm), pp, ptr(xcat), ptr(plan.status), stream_ptr())
+        ctx.save_for_backward(x_in, ew_in, *params)
+        ctx.plan, ctx.rois = plan, rois
+        ctx.final = _leaves(*params)
+        return xcat
+
+    @staticmethod
+    def backward(ctx, dxcat):
+        x_in, ew_in, *params = ctx.saved_tensors
+        plan, rois = ctx.plan, ctx.rois
+        n, h0 = x_in.shape
+        f, layers = params[0].shape[0], len(params) // 6
+        dxcat = _f32(dxcat)
+        emax = plan._stack_dims[1]
+        g = n // rois
+        npar = int(_lib.load().igcn_gat_stack_param_floats(h0, f, layers))
+        dx = torch.empty_like(x_in) if ctx.needs_input_grad[0] else None
+        dpar = torch.empty(npar, dtype=torch.float32, device=x_in.device)
+        scratch = _keep(torch.empty(g * npar, dtype=torch.float32, device=x_in.device))
+        pp = (ctypes.c_void_p * len(params))(*[t.data_ptr() for t in params])
+        with _immediate(ctx.final):
+            call("igcn_gat_stack_bwd", g, rois, emax, h0, f, layers, ptr(x_in), ptr(ew_in), ptr(plan.src32),
+                 ptr(plan.dst32), ptr(plan.tgt_ptr), ptr(plan.tgt_perm), ptr(plan.src_ptr), ptr(plan.src_perm), pp,
+                 ptr(dxcat), ptr(dx), ptr(dpar), ptr(scratch), ptr(plan.status), stream_ptr())
+        grads, off = [], 0
+        for l in range(layers):
+            fin = h0 if l == 0 else f
+            for k, shape in enumerate(((f, fin), (f,), (f,), (f,), (f,), (f,))):
+                m = shape[0] * (shape[1] if len(shape) == 2 else 1)
+                grads.append(dpar[off:off + m].view(params[6 * l + k].shape))
+                off += m
+        return (dx, None, None, None, *grads)
+
+
 def sgcn_front_supported(plan, rois, h0, f, layers, snps_feat, snps_logits):
     """The one-launch front of a train step's image branch (igcn_sgcn_front_fwd) covers this batch: what the LDS-resident
     stack covers, on a plan that is built per graph in LDS (not tiled, not dense blocks), with the SNP mask riding along."""

@@ -317,6 +317,32 @@ def losses_sgcn(model, data, hp=HP):
     return hp.lamda_ce * t["ce"] + t["prob"] + hp.lamda_mi * t["mi"], t, (out, out_p)
 
 
+def losses_gcn_img_snp(model, data, lambda_loss=DEFAULT_LAMBDA, hp=HP, temperature=None):
+    """Loss of the unmasked baseline GCN_IMGSNP: train() kernel/train_eval_gcn_img_snps.py:450-484 — ONE forward and five
+    terms (``ce``, ``reg``, ``recon``, ``cluster``, ``orth``); ``lambda_loss[0] == 0`` zeroes ``ce`` AND ``orth`` (:475-478),
+    unlike the sibling's trainer.  Returns (loss, terms dict, outputs)."""
+    lam = lambda_loss
+    o = model(data, temperature, data.x.device)
+    out, snps_hat, out_feat, _, _, reg = o
+    t = {"ce": lam[0] * F.nll_loss(out, data.y.view(-1)),
+         "reg": lam[1] * F.mse_loss(reg.view(-1), data.clini_score.view(-1)),
+         "recon": lam[3] * torch.sum((snps_hat - data.snps_feat) ** 2)}
+    if model.isSoftSimilarity:
+        # consist_loss and OrthogonalConstraint from one Gram matrix of out_z
+        c, orth = model.batch_losses(out_feat, model.laplacian(out_feat.shape[0], data.tsne_fdim))
+        t["cluster"] = lam[4] * c
+    else:
+        orth = None
+        t["cluster"] = 0.0
+        for c in range(2):
+            t["cluster"] = t["cluster"] + lam[4] * model.consist_loss(out_feat[data.clust_y.view(-1) == c])
+    t["orth"] = lam[5] * (orth if orth is not None else model.OrthogonalConstraint(out_feat))
+    if lam[0] == 0:
+        t["ce"], t["orth"] = 0.0, 0.0
+    loss = hp.lamda_ce * t["ce"] + t["reg"] + t["recon"] + t["cluster"] + t["orth"]
+    return loss, t, o
+
+
 def _batched(model):
     """The model takes both passes of a train step in one batched sweep (``_losses_batched``)."""
     return (hasattr(model, "go_network") and getattr(model, "batched_passes", True)
@@ -335,6 +361,8 @@ def losses(model, data, lambda_loss=DEFAULT_LAMBDA, hp=HP, temperature=None, laz
     # so that a process's FIRST evaluation takes the same route — the same rounding — as every later one, whoever calls)
     if data.x.is_cuda and torch.is_grad_enabled():
         ensure_unit_grad(data.x.device)
+    if getattr(model, "single_pass", False):        # GCN_IMGSNP: kernel/train_eval_gcn_img_snps.py's loss
+        return losses_gcn_img_snp(model, data, lambda_loss, hp, temperature)
     if hasattr(model, "_reg_hp"):                    # the dense-block SGCN path reduces loss_probability in its forward
         model._reg_hp = (float(hp.lamda_x_l1), float(hp.lamda_x_ent), float(hp.lamda_e_l1), float(hp.lamda_e_ent), 1e-6)
     if getattr(model, "batched_passes", True) and hasattr(model, "_forward_grouped") and model.isSoftSimilarity:
@@ -1247,6 +1275,8 @@ class Evaluator:
     def __init__(self, model, lambda_loss=DEFAULT_LAMBDA, hp=HP, temperature=None, capacity=None, max_graphs=4):
         if not hasattr(model, "go_network"):
             raise ValueError("Evaluator: SGCN_GCN_IMGSNP models only (SGCN_GCN has its own eval loop)")
+        if getattr(model, "single_pass", False):
+            raise ValueError("Evaluator: SGCN_GCN_IMGSNP models only (GCN_IMGSNP: use eval_loss / eval_acc)")
         self._model = weakref.ref(model)             # (kept by ``evaluate`` in a table keyed weakly on the model)
         self.lam, self.hp, self.temperature = tuple(float(v) for v in lambda_loss), hp, temperature
         self.C, self.NR = int(model.lin2.weight.shape[0]), int(model.lin2_regr.weight.shape[0])

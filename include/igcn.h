@@ -52,6 +52,30 @@ int igcn_configure(unsigned options, int gemm_bn_cap, int attn_chunk_rows);
  * workspace: igcn_graph_plan_workspace_bytes(n_nodes, n_edges) bytes.
  */
 size_t igcn_graph_plan_workspace_bytes(int64_t n_nodes, int64_t n_edges);
+/* ------------------------------------------------------------------------------------------------
+ * The GATConv stack of kernel/gcn_img_snp.py with ifUseGAT (PyG 2.0.2 GATConv(in, F, edge_dim=1): heads 1,
+ * negative_slope 0.2, add_self_loops with fill_value 'mean', bias) x L, each followed by ReLU, + the jumping-knowledge
+ * concatenation, for batches of SMALL UNIFORM graphs: ONE LDS-resident kernel per direction, one workgroup per graph,
+ * on the per-graph plan (src32, dst32, tgt_ptr, tgt_perm; src_ptr, src_perm for the backward).  Per layer and target i:
+ * h = x W^T, z_e = leaky_relu(h[src].att_src + h[i].att_dst + ea_e (lin_edge[:,0].att_edge)) over i's stored incoming
+ * edges with src != dst plus one virtual loop whose ea is the mean of those edges' ea (0 if none), alpha = the edge
+ * softmax over them (max-subtracted, + 1e-16 in the denominator), y_i = relu(sum alpha h[src] + bias).
+ * F in {4,8,16,32}, L <= 4, H0 <= 8 and igcn_gat_stack_lds_bytes(...) <= 150 KB (IGCN_ERR_UNSUPPORTED otherwise).
+ * params: HOST array of 6 L device pointers, per layer W [F, Fin_l] (Fin_0 = H0, then F), bias [F], att_src [F],
+ * att_dst [F], lin_edge [F], att_edge [F].  ew_in [E]: the scalar edge attributes (data, no gradient).
+ * Backward recomputes the forward in LDS; outputs dx_in [N, H0] (or NULL: not computed) and dparams
+ * [igcn_gat_stack_param_floats] = the six gradients of layer 0 in the order above, then layer 1, ... (scratch: n_graphs
+ * * that many floats; the sum over graphs is a final reduction in the sense of igcn_reduce_defer). */
+size_t igcn_gat_stack_lds_bytes(int R, int max_edges, int H0, int F, int L, int backward);
+int igcn_gat_stack_param_floats(int H0, int F, int L);
+int igcn_gat_stack_fwd(int64_t n_graphs, int R, int max_edges, int H0, int F, int L, const float* x_in,
+                       const float* ew_in, const int32_t* src32, const int32_t* dst32, const int32_t* tgt_ptr,
+                       const int32_t* tgt_perm, const float* const* params, float* xcat, int32_t* status, void* stream);
+int igcn_gat_stack_bwd(int64_t n_graphs, int R, int max_edges, int H0, int F, int L, const float* x_in,
+                       const float* ew_in, const int32_t* src32, const int32_t* dst32, const int32_t* tgt_ptr,
+                       const int32_t* tgt_perm, const int32_t* src_ptr, const int32_t* src_perm,
+                       const float* const* params, const float* dxcat, float* dx_in, float* dparams, float* scratch,
+                       int32_t* status, void* stream);
 int igcn_graph_plan_build(int64_t n_nodes, int64_t n_edges, const int64_t* edge_index /*[2,E]*/,
                           int32_t* src32, int32_t* dst32, int32_t* tgt_ptr, int32_t* tgt_perm,
                           int32_t* src_ptr, int32_t* src_perm, int32_t* loop_edge,
