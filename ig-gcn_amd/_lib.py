@@ -14,7 +14,7 @@ from . import switches
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libigcn.so")
 
-ABI_VERSION = 424        # include/igcn.h IGCN_ABI_VERSION this table was written against (tests/test_abi.py compares)
+ABI_VERSION = 425        # include/igcn.h IGCN_ABI_VERSION this table was written against (tests/test_abi.py compares)
 
 P, I, L, F, Z = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
 
@@ -171,6 +171,16 @@ SIGNATURES = {
     "igcn_go_decode_ln_bwd": (I, [I, I, I, I, I] + [P] * 19),
     "igcn_go_decode_bwd_scratch_floats": (Z, [I, I, I, I]),
     "igcn_go_decode_bwd": (I, [I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P]),
+    "igcn_nodes_ln_prelu_fwd": (I, [I, I, I, I, F, P, P, P, P, P, P, P, P, P]),
+    "igcn_nodes_ln_prelu_bwd_scratch_floats": (Z, [I, I, I]),
+    "igcn_nodes_ln_prelu_bwd": (I, [I, I, I, I] + [P] * 13),
+    "igcn_bn_prelu_fwd": (I, [I, I, I, I, P, P, P, P, P, P, I, F, F, P, P, P, P, P, P]),
+    "igcn_bn_prelu_bwd_scratch_floats": (Z, [I, I]),
+    "igcn_bn_prelu_bwd": (I, [I, I, I, I] + [P] * 16),
+    "igcn_guide_gate_supported": (I, [I, I, I]),
+    "igcn_guide_gate_fwd": (I, [I, I, I, I, I, P, P, P, F, P, P, P, P, P, P, P, P, P, P]),
+    "igcn_guide_gate_bwd_scratch_floats": (Z, [I, I, I, I]),
+    "igcn_guide_gate_bwd": (I, [I, I, I, I, I, P, P, P, P, F, P, P, P, P, P, P, P, P, P, P]),
     "igcn_adam_step": (I, [L, P, P, P, P, P, P, F, F, F, F, P]),
     "igcn_adam_step_multi": (I, [I, P, P, P, P, F, F, F, F, P]),
     "igcn_adam_step_ticked": (I, [L, P, P, P, P, P, P, F, F, F, F, P]),

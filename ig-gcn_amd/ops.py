@@ -2788,3 +2788,152 @@ class AttentionCore(torch.autograd.Function):
         call("igcn_attn_core_bf16_bwd" if ctx.core16 else "igcn_attn_core_bwd", b, d, ctx.heads, lq, lk, ptr(q), ptr(kv),
              ptr(o), ptr(lse), ptr(dout), ptr(dq), ptr(dkv), ptr(scratch), stream_ptr())
         return dq, dkv, None, None
+
+
+# =================================================================================================
+# GUIDE_IMGSNP: PReLU forms of the GO normalisation blocks, the image gate + encoder (csrc/guide.hip)
+# =================================================================================================
+class NodesLayerNormPReLU(torch.autograd.Function):
+    """LayerNorm over nodes + PReLU(slope) + node dropout + level pooling (guide_go_model.py:246-251, :273-275)."""
+
+    @staticmethod
+    def forward(ctx, y, gamma, beta, slope, keep, pool, eps):
+        y, gamma, beta, slope = _f32(y), _f32(gamma), _f32(beta), _f32(slope)
+        keep = _f32(keep) if keep is not None else None
+        b, f, n = y.shape
+        z = torch.empty(b, f, n - pool, dtype=torch.float32, device=y.device)
+        mean = torch.empty(b * f, dtype=torch.float32, device=y.device)
+        rstd = torch.empty_like(mean)
+        call("igcn_nodes_ln_prelu_fwd", b, f, n, pool, float(eps), ptr(y), ptr(gamma), ptr(beta), ptr(keep), ptr(slope),
+             ptr(z), ptr(mean), ptr(rstd), stream_ptr())
+        ctx.save_for_backward(y, gamma, beta, slope, keep, mean, rstd)
+        ctx.pool = pool
+        ctx.final = _leaves(gamma, beta, slope)
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        y, gamma, beta, slope, keep, mean, rstd = ctx.saved_tensors
+        b, f, n = y.shape
+        dy = torch.empty_like(y)
+        dgb = torch.empty(2, n, dtype=torch.float32, device=y.device)
+        da = torch.empty(1, dtype=torch.float32, device=y.device)
+        scratch = _keep(torch.empty(int(_lib.load().igcn_nodes_ln_prelu_bwd_scratch_floats(b, f, n)),
+                                    dtype=torch.float32, device=y.device))
+        with _immediate(ctx.final):
+            call("igcn_nodes_ln_prelu_bwd", b, f, n, ctx.pool, ptr(y), ptr(gamma), ptr(beta), ptr(keep), ptr(slope),
+                 ptr(mean), ptr(rstd), ptr(_f32(dz)), ptr(dy), ptr(dgb), ptr(da), ptr(scratch), stream_ptr())
+        return dy, dgb[0], dgb[1], da.view_as(slope), None, None, None
+
+
+def bn_prelu_forward(x, weight, bn, slope, training, keep=None):
+    """y = dropout(PReLU(BatchNorm1d_C(pre))) without autograd (igcn_bn_prelu_fwd): ``weight`` None -> pre = x [B,C];
+    else x [B,F,C] channel-major and pre[b,c,:] = weight x[b,:,c].  Returns (y [B,C,D], save_mean, save_rstd)."""
+    x, slope = _f32(x), _f32(slope)
+    if weight is None:
+        b, c = x.shape
+        f, d = 0, 1
+    else:
+        weight = _f32(weight)
+        b, f, c = x.shape
+        d = weight.shape[0]
+    keep = _f32(keep) if keep is not None else None
+    y = torch.empty(b, c, d, dtype=torch.float32, device=x.device)
+    mean = torch.empty(c, dtype=torch.float32, device=x.device)
+    rstd = torch.empty_like(mean)
+    call("igcn_bn_prelu_fwd", b, c, f, d, ptr(x), ptr(weight), ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean),
+         ptr(bn.running_var), int(training), float(bn.momentum), float(bn.eps), ptr(keep), ptr(slope), ptr(y), ptr(mean),
+         ptr(rstd), stream_ptr())
+    return y, mean, rstd
+
+
+class BatchNormPReLU(torch.autograd.Function):
+    """dropout(PReLU(BatchNorm1d_C(x))) on [B,C] (weight None), or behind a per-node linear F -> 1 on x [B,F,C]
+    (guide_go_model.py:123-136 conc + B, conc_D + B_D; :138-144 latent; guide_img_snp.py:57-66 decoder_i_N).  Output
+    [B,C].  The BatchNorm's running statistics are updated in training mode."""
+
+    @staticmethod
+    def forward(ctx, x, weight, gamma, beta, slope, bn, training, keep):
+        if weight is not None and weight.shape[0] != 1:
+            raise ValueError("BatchNormPReLU: the per-node linear takes gradients with one output per node only")
+        y, mean, rstd = bn_prelu_forward(x, weight, bn, slope, training, keep)
+        ctx.save_for_backward(_f32(x), weight, gamma, beta, slope, keep, mean, rstd)
+        ctx.training = int(training)
+        ctx.final = _leaves(weight, gamma, beta, slope)
+        return y.view(y.shape[0], y.shape[1])
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight, gamma, beta, slope, keep, mean, rstd = ctx.saved_tensors
+        f = 0 if weight is None else x.shape[1]
+        b, c = x.shape[0], x.shape[-1]
+        dx = torch.empty_like(x)
+        dw = torch.empty(1, f, dtype=torch.float32, device=x.device) if f else None
+        dg, db = torch.empty_like(gamma), torch.empty_like(beta)
+        da = torch.empty(1, dtype=torch.float32, device=x.device)
+        scratch = _keep(torch.empty(int(_lib.load().igcn_bn_prelu_bwd_scratch_floats(c, f)), dtype=torch.float32,
+                                    device=x.device))
+        with _immediate(ctx.final):
+            call("igcn_bn_prelu_bwd", b, c, f, ctx.training, ptr(x), ptr(weight), ptr(gamma), ptr(beta), ptr(slope),
+                 ptr(mean), ptr(rstd), ptr(_f32(dy)), ptr(keep), ptr(dx), ptr(dw), ptr(dg), ptr(db), ptr(da),
+                 ptr(scratch), stream_ptr())
+        return dx, dw, dg, db, da.view_as(slope), None, None, None
+
+
+def guide_gate_supported(k, h, l):
+    return bool(_lib.load().igcn_guide_gate_supported(int(k), int(h), int(l)))
+
+
+class GuideGate(torch.autograd.Function):
+    """The image gate and encoder_i_N of GUIDE_IMGSNP (guide_img_snp.py:88-100,112) in one launch per direction:
+    latent_n = W2 (keep * PReLU(W1 (img * z1))) with z1 the hard Gumbel-softmax decision of softmax(bias_n) (training;
+    1 in eval), and imp1 = softmax(bias_n, 1)[:, 1].  ``tau``: 0-d device tensor (read by the kernel) or a number.
+    ``noise`` [B,K,2] replaces the generator's draw; ``state`` (DropoutState) is the generator otherwise.
+    Returns (latent_n [B,L], imp1 [K], gate [B,K,2] = (z1, s0 s1) in training, else None)."""
+
+    @staticmethod
+    def forward(ctx, img, bias, w1, slope, w2, keep, tau, training, noise, state):
+        img, bias, w1, slope, w2 = _f32(img), _f32(bias), _f32(w1), _f32(slope), _f32(w2)
+        keep = _f32(keep) if keep is not None else None
+        noise = _f32(noise) if noise is not None else None
+        b, k = img.shape
+        h, l = w1.shape[0], w2.shape[0]
+        tau_t = None
+        if torch.is_tensor(tau) and tau.is_cuda:
+            tau_t = tau.detach().to(torch.float32).reshape(())
+        tau_v = 0.0 if tau_t is not None else float(tau if tau is not None else 1.0)
+        lat = torch.empty(b, l, dtype=torch.float32, device=img.device)
+        imp1 = torch.empty(k, dtype=torch.float32, device=img.device)
+        gate = torch.empty(b, k, 2, dtype=torch.float32, device=img.device) if training else None
+        call("igcn_guide_gate_fwd", b, k, h, l, int(training), ptr(img), ptr(bias), ptr(tau_t), tau_v, ptr(noise),
+             ptr(state.state) if (training and noise is None) else None, ptr(w1), ptr(slope), ptr(keep), ptr(w2),
+             ptr(lat), ptr(gate), ptr(imp1), stream_ptr())
+        ctx.save_for_backward(img, bias, w1, slope, w2, keep, gate, tau_t)
+        ctx.tau_v, ctx.training = tau_v, int(training)
+        ctx.final = _leaves(bias, w1, slope, w2)
+        if gate is not None:
+            ctx.mark_non_differentiable(gate)
+        return lat, imp1, gate
+
+    @staticmethod
+    def backward(ctx, dlat, dimp1, _dgate):
+        img, bias, w1, slope, w2, keep, gate, tau_t = ctx.saved_tensors
+        b, k = img.shape
+        h, l = w1.shape[0], w2.shape[0]
+        if dlat is None:
+            dlat = torch.zeros(b, l, dtype=torch.float32, device=img.device)
+        dimg = torch.empty_like(img)
+        n = h * k + l * h + 2 * k + 1
+        dpar = torch.empty(n, dtype=torch.float32, device=img.device)
+        scratch = _keep(torch.empty(int(_lib.load().igcn_guide_gate_bwd_scratch_floats(b, k, h, l)), dtype=torch.float32,
+                                    device=img.device))
+        with _immediate(ctx.final):
+            call("igcn_guide_gate_bwd", b, k, h, l, ctx.training, ptr(img), ptr(gate), ptr(bias), ptr(tau_t), ctx.tau_v,
+                 ptr(_f32(dimp1)) if dimp1 is not None else None, ptr(w1), ptr(slope), ptr(keep), ptr(w2),
+                 ptr(_f32(dlat)), ptr(dimg), ptr(dpar), ptr(scratch), stream_ptr())
+        dw1 = dpar[:h * k].view(h, k)
+        dw2 = dpar[h * k:h * k + l * h].view(l, h)
+        o = h * k + l * h
+        dbias = dpar[o:o + 2 * k].view(k, 2)
+        da = dpar[o + 2 * k:o + 2 * k + 1].view_as(slope)
+        return dimg, dbias, dw1, da, dw2, None, None, None, None, None

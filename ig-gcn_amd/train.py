@@ -343,6 +343,32 @@ def losses_gcn_img_snp(model, data, lambda_loss=DEFAULT_LAMBDA, hp=HP, temperatu
     return loss, t, o
 
 
+GUIDE_LAMBDA = (1.0, 1.0, 2.5e-6, 0.2, 0.2)       # kernel/train_eval_guide_img_snps.py:163-164
+GUIDE_PROB_REF, GUIDE_EPS = 0.001, 1e-10          # train()'s prob_ref / eps (:450)
+
+
+def losses_guide(model, data, lambda_loss=None, hp=HP, temperature=None):
+    """Loss of GUIDE_IMGSNP: train() kernel/train_eval_guide_img_snps.py:450-487 — one forward and five terms (``ce``,
+    ``reg``, ``recon``, ``recon_img``, ``sparsity``: the KL term of imp_N[:, 1] against prob_ref); ``lambda_loss`` is
+    indexed [0..4] as there, None (or the library's DEFAULT_LAMBDA, i.e. the caller passed none) is GUIDE's default.
+    Returns (loss, terms dict, outputs)."""
+    lam = GUIDE_LAMBDA if lambda_loss is None or lambda_loss is DEFAULT_LAMBDA else lambda_loss
+    o = model(data, temperature, data.x.device)
+    out, snps_hat, _, _, _, reg, (img, decoded), (p,) = o
+    t = {"ce": lam[0] * F.nll_loss(out, data.y.view(-1)),
+         "reg": lam[1] * F.mse_loss(reg.view(-1), data.clini_score.view(-1)),
+         "recon": lam[2] * torch.sum((snps_hat - data.snps_feat) ** 2),
+         "recon_img": lam[3] * torch.sum((img - decoded) ** 2)}
+    rho = torch.full_like(p, GUIDE_PROB_REF)        # (in fp32 as the reference's FloatTensor: log(rho + eps) rounds alike)
+    s1 = torch.mean(p * (torch.log(p + GUIDE_EPS) - torch.log(rho + GUIDE_EPS)))
+    s2 = torch.mean((1 - p) * (torch.log(1 - p + GUIDE_EPS) - torch.log(1 - rho + GUIDE_EPS))) + s1
+    t["sparsity"] = lam[4] * s2
+    if lam[0] == 0:
+        t["ce"] = 0.0
+    loss = hp.lamda_ce * t["ce"] + t["reg"] + t["recon"] + t["recon_img"] + t["sparsity"]
+    return loss, t, o
+
+
 def _batched(model):
     """The model takes both passes of a train step in one batched sweep (``_losses_batched``)."""
     return (hasattr(model, "go_network") and getattr(model, "batched_passes", True)
@@ -361,6 +387,8 @@ def losses(model, data, lambda_loss=DEFAULT_LAMBDA, hp=HP, temperature=None, laz
     # so that a process's FIRST evaluation takes the same route — the same rounding — as every later one, whoever calls)
     if data.x.is_cuda and torch.is_grad_enabled():
         ensure_unit_grad(data.x.device)
+    if getattr(model, "guide", False):              # GUIDE_IMGSNP: kernel/train_eval_guide_img_snps.py's loss
+        return losses_guide(model, data, lambda_loss, hp, temperature)
     if getattr(model, "single_pass", False):        # GCN_IMGSNP: kernel/train_eval_gcn_img_snps.py's loss
         return losses_gcn_img_snp(model, data, lambda_loss, hp, temperature)
     if hasattr(model, "_reg_hp"):                    # the dense-block SGCN path reduces loss_probability in its forward
@@ -764,7 +792,7 @@ class GraphedTrainStep:
     """
 
     def __init__(self, model, optimizer, data, lambda_loss=DEFAULT_LAMBDA, hp=HP, world_size=1, warmup=3,
-                 distributed=None, comm=None, comm_in_graph=False, max_edges=None, two_buckets=False):
+                 distributed=None, comm=None, comm_in_graph=False, max_edges=None, two_buckets=False, temperature=None):
         """``comm`` (``igcn_amd.comm.Comm``): the gradient all-reduce is igcn_comm_allreduce on the launch stream.
         ``comm_in_graph`` (opt-in): capture it INTO the step graph (one graph: ... pack -> all-reduce -> Adam).  True =
         required (a refused capture raises); None = try — the choice is agreed across ranks (an all-reduce of a flag)
@@ -776,8 +804,11 @@ class GraphedTrainStep:
         ``two_buckets`` (opt-in, distributed steps): THREE graphs — [forward .. the heads' backward + pack of their
         gradients], [the rest of the backward + pack], [Adam] — with the heads' all-reduce (4/5 of the bucket) on a side
         stream beside the second graph and the remainder's behind it (``_TwoBucketExchange``); collectives stay outside
-        the graphs.  Same gradients, bit for bit, as the default form."""
+        the graphs.  Same gradients, bit for bit, as the default form.
+        ``temperature``: passed to ``losses`` (GUIDE_IMGSNP's Gumbel-softmax gate; a 0-d device tensor is read at replay
+        time, a number is baked into the capture); the other models ignore it."""
         self.model, self.opt, self.data, self.world = model, optimizer, data, world_size
+        self.temperature = temperature
         # distributed=True with world_size 1 takes the multi-rank control flow (two graphs around a collective) on
         # a single-rank process group: the rehearsal of the N>1 path that a one-GPU box allows
         self.dist = dist = (world_size > 1 or comm is not None) if distributed is None else bool(distributed)
@@ -805,6 +836,8 @@ class GraphedTrainStep:
         # captured in the middle of an epoch does not shift the masks of every later step against an eager run
         drop = getattr(getattr(model, "go_network", None), "_drop_state", None)
         saved_drop = drop.state.clone() if drop is not None else None
+        gate = getattr(model, "_gate_state", None)                 # (GUIDE_IMGSNP's Gumbel-noise counter: likewise)
+        saved_gate = gate.state.clone() if gate is not None else None
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -834,6 +867,8 @@ class GraphedTrainStep:
             drop_now = getattr(getattr(model, "go_network", None), "_drop_state", None)
             if saved_drop is not None and drop_now is drop:
                 drop.state.copy_(saved_drop)
+            if saved_gate is not None and getattr(model, "_gate_state", None) is gate:
+                gate.state.copy_(saved_gate)
         forget_riders(model)
         opt._has_state = saved_has
         torch.cuda.synchronize()
@@ -962,7 +997,7 @@ class GraphedTrainStep:
             self.data.x.grad = None
             self.model._cut_heads = between is not None
             try:
-                loss, _, _ = losses(self.model, self.data, self.lam, self.hp, lazy_value=True)
+                loss, _, _ = losses(self.model, self.data, self.lam, self.hp, self.temperature, lazy_value=True)
             finally:
                 self.model._cut_heads = False
             if rider:
@@ -1104,8 +1139,9 @@ class EpochTrainer:
     """
 
     def __init__(self, model, optimizer, lambda_loss=DEFAULT_LAMBDA, hp=HP, world_size=1, comm=None, capture_after=1,
-                 max_graphs=4, warmup=2):
+                 max_graphs=4, warmup=2, temperature=None):
         self.model, self.opt, self.lam, self.hp = model, optimizer, lambda_loss, hp
+        self.temperature = temperature
         self.world, self.comm = world_size, comm
         self.capture_after, self.max_graphs, self.warmup = int(capture_after), int(max_graphs), int(warmup)
         self.steps = {}                              # signature -> GraphedTrainStep
@@ -1123,11 +1159,13 @@ class EpochTrainer:
             graphable = data.x.is_cuda and isinstance(self.opt, FlatAdam) and not self.opt.flat_grads
             if graphable and n >= self.capture_after and len(self.steps) < self.max_graphs:
                 g = self.steps[sig] = GraphedTrainStep(self.model, self.opt, _clone_batch(data), self.lam, self.hp,
-                                                       world_size=self.world, comm=self.comm, warmup=self.warmup)
+                                                       world_size=self.world, comm=self.comm, warmup=self.warmup,
+                                                       temperature=self.temperature)
                 self.counts["captured"] += 1
         if g is None:
             self.counts["eager"] += 1
-            return train_step(self.model, self.opt, data, self.lam, self.hp, world_size=self.world, comm=self.comm)
+            return train_step(self.model, self.opt, data, self.lam, self.hp, self.temperature, world_size=self.world,
+                              comm=self.comm)
         g.load(data)
         self.counts["replayed"] += 1
         return g()
@@ -1153,19 +1191,25 @@ def fit_epoch(model, optimizer, loader, temperature=None, lambda_loss=DEFAULT_LA
     """``train(model, optimizer, loader, temperature, lambda_loss, ..., device)`` of the reference (:511-548) as a
     function: the EpochTrainer is kept on the optimiser, so calling this once per epoch — as the reference's epoch
     loop calls ``train`` — re-uses the captured steps."""
-    # (``temperature`` is accepted for the reference's signature and, like the reference's GO network, never read.)
+    # (``temperature`` is read by GUIDE_IMGSNP's gate only; the other models, like the reference's GO network, ignore it.)
     # The captured steps bake the regulariser weights of ``hp`` in as launch arguments: they are part of the key; the
     # model and the communicator are held by weak reference, so an id() recycled after garbage collection cannot alias
     import weakref
     hp_key = tuple(float(getattr(hp, k)) for k in ("lamda_x_l1", "lamda_e_l1", "lamda_x_ent", "lamda_e_ent", "lamda_mi",
                                                     "lamda_ce"))
     key = (id(model), tuple(float(v) for v in lambda_loss), hp_key, world_size, id(comm))
+    if getattr(model, "guide", False):
+        # a device temperature is read at replay time (its address is the key); a number is a launch argument; the
+        # library's default lambda stands for GUIDE's own default (losses_guide)
+        key += (("tensor", temperature.data_ptr()) if torch.is_tensor(temperature) else temperature,
+                lambda_loss is DEFAULT_LAMBDA)
     cache = optimizer.__dict__.setdefault("_igcn_epoch_trainers", {})
     tr = cache.get(key)
     if tr is not None and (tr._model_ref() is not model or (comm is not None and tr._comm_ref() is not comm)):
         tr = None                                             # the id belonged to an object that is gone
     if tr is None:
-        tr = cache[key] = EpochTrainer(model, optimizer, lambda_loss, hp, world_size=world_size, comm=comm)
+        tr = cache[key] = EpochTrainer(model, optimizer, lambda_loss, hp, world_size=world_size, comm=comm,
+                                       temperature=temperature)
         tr._model_ref = weakref.ref(model)
         tr._comm_ref = weakref.ref(comm) if comm is not None else (lambda: None)
     return tr.fit_epoch(loader, device)
@@ -1213,7 +1257,8 @@ def eval_outputs(model, loader, temperature=None, device=None):
     cols = {"logp": [], "pred": [], "reg": [], "out_lin": [], "linear_outf": []}
     for data in _batches(loader, device):
         if hasattr(model, "go_network"):
-            logp, _, _, out_lin, lin_f, reg = model(data, temperature, data.x.device)
+            o = model(data, temperature, data.x.device)     # (the reference's 6-tuple, or GUIDE_IMGSNP's 8-tuple)
+            logp, out_lin, lin_f, reg = o[0], o[3], o[4], o[5]
             cols["reg"].append(reg.reshape(-1, model.num_regr))
             cols["out_lin"].append(out_lin)
             cols["linear_outf"].append(lin_f)
@@ -1277,6 +1322,9 @@ class Evaluator:
             raise ValueError("Evaluator: SGCN_GCN_IMGSNP models only (SGCN_GCN has its own eval loop)")
         if getattr(model, "single_pass", False):
             raise ValueError("Evaluator: SGCN_GCN_IMGSNP models only (GCN_IMGSNP: use eval_loss / eval_acc)")
+        if getattr(model, "guide", False):
+            raise ValueError("Evaluator: SGCN_GCN_IMGSNP models only (GUIDE_IMGSNP: use eval_loss / eval_acc / "
+                             "eval_outputs)")
         self._model = weakref.ref(model)             # (kept by ``evaluate`` in a table keyed weakly on the model)
         self.lam, self.hp, self.temperature = tuple(float(v) for v in lambda_loss), hp, temperature
         self.C, self.NR = int(model.lin2.weight.shape[0]), int(model.lin2_regr.weight.shape[0])

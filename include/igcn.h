@@ -31,7 +31,7 @@ extern "C" {
 /* ABI revision: bumped whenever a prototype below changes (argument added, removed or re-ordered).  igcn_version()
  * returns the revision the library was built from; a binding written against a different one must refuse to call
  * (igcn_amd/_lib.py does). */
-#define IGCN_ABI_VERSION 424
+#define IGCN_ABI_VERSION 425
 int igcn_version(void);
 const char* igcn_last_error(void);
 /* A/B switches, set ONCE by the binding when it loads the library (from the IGCN_* environment variables): bit 0 no tiled
@@ -1057,6 +1057,65 @@ int igcn_eval_collect(int B, int C, int NR, int F, int H, const float* loss, con
 int igcn_eval_metrics(int64_t n, int C, int NR, const float* logp, const int64_t* pred, const int64_t* y,
                       const float* reg, const float* clin, const int64_t* state, const double* loss_sum, int64_t* parts,
                       double* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * GUIDE_IMGSNP (csrc/guide.hip).  nn.PReLU() has one slope a (device float[1], read by the kernels so that a captured
+ * step follows the optimiser): y = u > 0 ? u : a u; du = u > 0 ? dy : a dy; da = sum (u > 0 ? 0 : u dy), dy carrying the
+ * dropout factor behind the activation.  da (dslope, float[1]) and the weight gradients are FINAL reductions of
+ * per-row / per-column partials in a fixed order (queued while igcn_reduce_defer is on; scratch alive until the flush).
+ *
+ * LayerNorm over nodes + PReLU + node dropout + pooling: igcn_nodes_ln_fwd / igcn_nodes_ln_bwd with ReLU replaced by
+ * PReLU — kernel/guide_go_model.py:246-251 (w_act, encoder) and :273-275 (w_act_out, decoder).  Arguments as there plus
+ * the slope; dy [B,f,N], dgb [2,N], dslope [1].  scratch: igcn_nodes_ln_prelu_bwd_scratch_floats(B,f,N). */
+int igcn_nodes_ln_prelu_fwd(int B, int f, int N, int pool, float eps, const float* y, const float* gamma,
+                            const float* beta, const float* keep, const float* slope, float* z, float* mean,
+                            float* rstd, void* stream);
+size_t igcn_nodes_ln_prelu_bwd_scratch_floats(int B, int f, int N);
+int igcn_nodes_ln_prelu_bwd(int B, int f, int N, int pool, const float* y, const float* gamma, const float* beta,
+                            const float* keep, const float* slope, const float* mean, const float* rstd,
+                            const float* dz, float* dy, float* dgb, float* dslope, float* scratch, void* stream);
+/* BatchNorm1d(C) + PReLU (+ dropout keep [B,C], D == 1 only) with groups = 1, optionally behind a per-node linear:
+ *   F == 0: the input is x [B,C] — kernel/guide_go_model.py:138-144 (latent: BN(32), PReLU, Dropout(0.5)),
+ *           kernel/guide_img_snp.py:57-66 (decoder_i_N: BN(32) and BN(hidden_linear), PReLU, Dropout(0.4));
+ *   F >= 1 (<= 8): x [B,F,C] channel-major, W [D,F], pre[b,c,d] = sum_f W[d,f] x[b,f,c] and BatchNorm1d(C) normalises
+ *           each c over (batch, d) — :117-121 (conc_for_attention, D = dim_snps_atten), :123-128 (conc + B, D = 1),
+ *           :130-136 (conc_D + B_D, D = 1).
+ * y [B,C,D]; save_mean / save_rstd [C]; training != 0: batch statistics, running statistics updated (unbiased
+ * variance over B D values).  Backward D == 1 only: dx as x, dW [F] (F >= 1), dgamma / dbeta [C], dslope [1];
+ * scratch igcn_bn_prelu_bwd_scratch_floats(C, F). */
+int igcn_bn_prelu_fwd(int B, int C, int F, int D, const float* x, const float* W, const float* gamma,
+                      const float* beta, float* running_mean, float* running_var, int training, float momentum,
+                      float eps, const float* keep, const float* slope, float* y, float* save_mean, float* save_rstd,
+                      void* stream);
+size_t igcn_bn_prelu_bwd_scratch_floats(int C, int F);
+int igcn_bn_prelu_bwd(int B, int C, int F, int training, const float* x, const float* W, const float* gamma,
+                      const float* beta, const float* slope, const float* save_mean, const float* save_rstd,
+                      const float* dy, const float* keep, float* dx, float* dW, float* dgamma, float* dbeta,
+                      float* dslope, float* scratch, void* stream);
+/* The image gate and encoder_i_N of kernel/guide_img_snp.py:88-100,112 in one launch per direction (one workgroup per
+ * sample).  img [B,K] (K = rois H_0), bias [K,2] (bias_n[0]), W1 [H,K], slope (the encoder's PReLU), keep [B,H] (its
+ * Dropout(0.4)) or NULL, W2 [L,H]; latent [B,L]; imp1 [K] = softmax(bias_n[0], 1)[:, 1].  Temperature: tau (device
+ * float[1]) or, when NULL, tau_value.
+ * Training: per (b, k) logit_j = log softmax(bias[k])_j, s = softmax((logit + g) / tau), z1 = 1 iff s1 > s0 (ties: class
+ * 0), taken as (z1 - s1) + s1 like gumbel_softmax(hard=True); gate [B,K,2] receives (z1, s0 s1).  Eval: z1 = 1, no draw.
+ * The Gumbel noise g of element (b, k, j) sits at flat index i = 2 (b K + k) + j (the reference's [B K, 2] layout):
+ * noise [B,K,2] when given, else drawn from the dropout generator's hash at state[0] = c — the 24-bit draw r(c, i) of
+ * igcn_dropout_masks, u = (r + 1/2) 2^-24, g = -log(-log u) — after which the launch advances state[0] by one (state:
+ * device uint64[igcn_dropout_state_words()], word 1 left at 0).  An eval forward or imposed noise draws nothing.
+ * (u is exact: above 1/2 the kernel forms log u as log1p(-(2^24 - r - 1/2) 2^-24), so r = 2^24 - 1 gives a finite g.)
+ * Backward: dimg [B,K] (written, not added), dparams [H K + L H + 2 K + 1] = (dW1, dW2, d bias [K,2], dslope); d bias is
+ * the straight-through estimator (d z1 reaches s) plus, from dimp1 [K] when not NULL, the gradient reaching imp1.
+ * Limits: igcn_guide_gate_supported(K, H, L) (K <= 1024, H <= 64, L <= 64); B >= 1.
+ * scratch: igcn_guide_gate_bwd_scratch_floats(B, K, H, L). */
+int igcn_guide_gate_supported(int K, int H, int L);
+int igcn_guide_gate_fwd(int B, int K, int H, int L, int training, const float* img, const float* bias, const float* tau,
+                        float tau_value, const float* noise, void* state, const float* W1, const float* slope,
+                        const float* keep, const float* W2, float* latent, float* gate, float* imp1, void* stream);
+size_t igcn_guide_gate_bwd_scratch_floats(int B, int K, int H, int L);
+int igcn_guide_gate_bwd(int B, int K, int H, int L, int training, const float* img, const float* gate,
+                        const float* bias, const float* tau, float tau_value, const float* dimp1, const float* W1,
+                        const float* slope, const float* keep, const float* W2, const float* dlatent, float* dimg,
+                        float* dparams, float* scratch, void* stream);
 
 #ifdef __cplusplus
 }
