@@ -4,6 +4,8 @@ Follows /root/reference/kernel/go_model.py:
   index sets      :42-74  (+ store_ind :161-168)      -> go_index_sets
   parameters      :78-157                              -> go_param_shapes / init_go_state
   forward         :205-287 (helpers :170-201)          -> go_forward
+  activations     nn.ReLU() everywhere (:103,112,117-146) -> relu_act (``act`` of go_forward: the GUIDE network's PReLU
+                  forms, kernel/guide_go_model.py, go through oracle.guide.prelu instead)
 
 Functional over a flat state_dict whose keys equal the reference module's
 (``t.0``, ``w_inc.0.weight``, ``G_B.1.bias``, ``conc_for_attention.1.running_mean`` ...).
@@ -138,8 +140,17 @@ def _row_normalise(row, v, n_rows):
     return v / z.index_select(v.dim() - 1, row)
 
 
-def go_forward(sd, idx, snps, training=False, dropout=True, faithful=False, prefix=""):
-    """go_model.py:205-287.  snps [B,54] -> (latent [B,l], x_D [B,54], atten_out [B,Ntop,d_att])."""
+def relu_act(site, t):
+    """The activation of go_model.py (nn.ReLU): ``site`` is the module key of the activation (unused here)."""
+    return torch.relu(t)
+
+
+def go_forward(sd, idx, snps, training=False, dropout=True, faithful=False, prefix="", act=relu_act, latent_out=True):
+    """go_model.py:205-287.  snps [B,54] -> (latent [B,l], x_D [B,54], atten_out [B,Ntop,d_att]).
+
+    ``act(site, t)``: every activation, ``site`` = its module key without ``prefix`` (``w_act.0``, ``B.1`` ...; the
+    GUIDE network's names, kernel/guide_go_model.py:103-144).  ``latent_out``: the latent MLP ends in BatchNorm
+    ``latent.5`` + activation (go_model.py:144-145); GUIDE's ends at ``latent.4`` (guide_go_model.py:138-144)."""
     g = lambda k: sd[prefix + k]   # noqa: E731
     sdp = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)} if prefix else sd
     n, pool, n_l = idx["n"], idx["pool"], idx["n_l"]
@@ -183,14 +194,14 @@ def go_forward(sd, idx, snps, training=False, dropout=True, faithful=False, pref
                 1, row, alpha.unsqueeze(2) * x_in[:, col, :]) + x_s * v_s
         out = F.layer_norm(out.permute(0, 2, 1), (nj,), g(f"G_B.{j}.weight"), g(f"G_B.{j}.bias"),
                            1e-5).permute(0, 2, 1)
-        out = _node_dropout(torch.relu(out), 0.4, training, dropout)
+        out = _node_dropout(act(f"w_act.{j}", out), 0.4, training, dropout)
         x = out[:, pool[j]:, :]
 
     # read-outs :254-255
     att = x @ g("conc_for_attention.0.weight").t()
-    atten_out = torch.relu(_batch_norm(sdp, "conc_for_attention.1", att, training))
+    atten_out = act("conc_for_attention.2", _batch_norm(sdp, "conc_for_attention.1", att, training))
     inp = (x @ g("conc.weight").t()).squeeze(2)
-    inp_out = _dropout(torch.relu(_batch_norm(sdp, "B.0", inp, training)), 0.5, training, dropout)
+    inp_out = _dropout(act("B.1", _batch_norm(sdp, "B.0", inp, training)), 0.5, training, dropout)
 
     # decoder layers :258-275 (mean aggregation back down the hierarchy)
     for j in range(n_l):
@@ -204,11 +215,11 @@ def go_forward(sd, idx, snps, training=False, dropout=True, faithful=False, pref
         y = agg + self_term
         y = F.layer_norm(y.permute(0, 2, 1), (n_rows,), g(f"G_B_D.{j}.weight"), g(f"G_B_D.{j}.bias"),
                          1e-5).permute(0, 2, 1)
-        x = _node_dropout(torch.relu(y), 0.4, training, dropout)
+        x = _node_dropout(act(f"w_act_out.{j}", y), 0.4, training, dropout)
 
     # gene decoding :278-282
     out_d = (x @ g("conc_D.weight").t()).squeeze(2)
-    out_d = _dropout(torch.relu(_batch_norm(sdp, "B_D.0", out_d, training)), 0.5, training, dropout)
+    out_d = _dropout(act("B_D.1", _batch_norm(sdp, "B_D.0", out_d, training)), 0.5, training, dropout)
     dsn, dn = idx["gene_t"]                      # rows = SNP, cols = GO node
     if faithful:
         w_d = torch.sparse_coo_tensor(torch.stack([dsn, dn]), g("t_D.0"), (N_SNPS, n))
@@ -218,9 +229,10 @@ def go_forward(sd, idx, snps, training=False, dropout=True, faithful=False, pref
 
     # latent projection :138-146,285
     h = inp_out.view(bsz, -1) @ g("latent.0.weight").t()
-    h = _dropout(torch.relu(_batch_norm(sdp, "latent.1", h, training)), 0.5, training, dropout)
-    h = h @ g("latent.4.weight").t()
-    latent = torch.relu(_batch_norm(sdp, "latent.5", h, training))
+    h = _dropout(act("latent.2", _batch_norm(sdp, "latent.1", h, training)), 0.5, training, dropout)
+    latent = h @ g("latent.4.weight").t()
+    if latent_out:
+        latent = act("latent.6", _batch_norm(sdp, "latent.5", latent, training))
     return latent, x_d, atten_out
 
 

@@ -354,3 +354,336 @@ def test_epoch_functions_and_evaluator_refusal(golden):
     assert out["logp"].shape == (16, 3) and out["reg"].shape == (16, 3) and out["linear_outf"].shape == (16, 32)
     with pytest.raises(ValueError, match="GUIDE_IMGSNP"):
         Evaluator(model)
+
+
+# ---- edge sweeps of the three kernel families against float64 torch ---------------------------------------------------
+# Inputs are held off the PReLU kink: an fp32 pre-activation within rounding of 0 may take the other branch, and the
+# derivative jumps there (1 -> a).  _off_kink nudges the shift beta of the affected columns / nodes until no fp64
+# pre-activation lies within KINK of 0; the gate draws its inputs afresh instead.
+KINK = 1e-4
+SWEEP_SLOPES = [0.0, 1.0, 0.25, -0.3, 1.7]
+
+
+def _off_kink(u_of, beta, axis_other):
+    for _ in range(20):
+        near = u_of(beta).abs() < KINK
+        if not bool(near.any()):
+            return beta
+        beta = beta + 4e-3 * near.any(dim=axis_other).double()
+    raise AssertionError("inputs did not leave the PReLU kink")
+
+
+def _ln_u(y, gamma):
+    mu = y.mean(-1, keepdim=True)
+    xh = (y - mu) / torch.sqrt(y.var(-1, unbiased=False, keepdim=True) + 1e-5)
+    return lambda beta: xh * gamma + beta
+
+
+# (b, f, N, pool): rows b f = 1 / 64 / 65 / 1280, N around the 64-node tiles and GD_T = 256 threads, the bench's 1200 /
+# 3000-node layers (20 chunks of GD_RC = 64 rows), pool 0 and pool = N - 1
+LN_SHAPES = [(1, 1, 63, 0), (8, 8, 64, 63), (13, 5, 65, 7), (4, 16, 256, 0), (5, 13, 257, 256), (256, 5, 1200, 800),
+             (256, 5, 3000, 1800), (2, 3, 4100, 100), (1, 1, 4100, 4099)]
+
+
+@pytest.mark.parametrize("a", SWEEP_SLOPES)
+@pytest.mark.parametrize("keep_on", [True, False], ids=["keep", "nokeep"])
+@pytest.mark.parametrize("b,f,n,pool", LN_SHAPES)
+def test_nodes_ln_prelu_sweep_vs_fp64(b, f, n, pool, keep_on, a):
+    from igcn_amd import ops
+    g = torch.Generator().manual_seed(n + 7 * pool + b)
+    y = torch.randn(b, f, n, generator=g, dtype=torch.float64) * 2 + 0.5
+    gamma = 1 + 0.3 * torch.randn(n, generator=g, dtype=torch.float64)
+    beta = _off_kink(_ln_u(y, gamma), 0.2 * torch.randn(n, generator=g, dtype=torch.float64), (0, 1))
+    keep = _keep((b, n), 0.4, g) if keep_on else None
+    slope = torch.tensor([a], dtype=torch.float64)
+    cot = torch.randn(b, f, n - pool, generator=g, dtype=torch.float64)
+    ref = [_leaf(t) for t in (y, gamma, beta, slope)]
+    mu = ref[0].mean(-1, keepdim=True)
+    var = ref[0].var(-1, unbiased=False, keepdim=True)
+    z = _prelu((ref[0] - mu) / torch.sqrt(var + 1e-5) * ref[1] + ref[2], ref[3])
+    if keep_on:
+        z = z * keep.unsqueeze(1)
+    z = z[..., pool:]
+    (z * cot).sum().backward()
+    das = []
+    for _ in range(2):
+        got = [_leaf(t.float().cuda()) for t in (y, gamma, beta, slope)]
+        zg = ops.NodesLayerNormPReLU.apply(*got, keep.float().cuda() if keep_on else None, pool, 1e-5)
+        (zg * cot.float().cuda()).sum().backward()
+        das.append(got[3].grad.clone())
+    assert_matches(zg, z.detach().numpy(), 1e-5, "z")
+    for r, t, w in zip(ref, got, ("dy", "dgamma", "dbeta", "dslope")):
+        assert_matches(t.grad, r.grad.numpy(), 1e-4, w)
+    assert torch.equal(das[0], das[1])
+
+
+def _bn_case(f, b, c, d, seed, training, off_kink=True):
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn((b, c) if f == 0 else (b, f, c), generator=g, dtype=torch.float64) * 1.5 + 0.3
+    w = torch.randn(d, f, generator=g, dtype=torch.float64) if f else None
+    if b == 2 and d == 1:
+        # two samples: (pre_0 - pre_1) / 2 is the column's standard deviation; hold it >= 1/2, away from the
+        # cancellation of two nearly equal numbers (there the fp32 output is ill-conditioned: 1 / |pre_0 - pre_1|)
+        pre = x if f == 0 else torch.einsum("of,bfc->bc", w, x)
+        delta = pre[0] - pre[1]
+        t = torch.where(delta.abs() < 1.0, delta - torch.where(delta >= 0, 1.0, -1.0), torch.zeros_like(delta))
+        if f == 0:
+            x[1] += t
+        else:
+            x[1] += t[None, :] * (w[0] / (w[0] ** 2).sum())[:, None]
+    bn = torch.nn.BatchNorm1d(c).double()
+    with torch.no_grad():
+        bn.weight.copy_(1 + 0.3 * torch.randn(c, generator=g, dtype=torch.float64))
+        bn.running_mean.copy_(0.3 * torch.randn(c, generator=g, dtype=torch.float64))
+        bn.running_var.copy_(0.5 + torch.rand(c, generator=g, dtype=torch.float64))
+        pre = x if f == 0 else torch.einsum("df,bfc->bcd", w, x)
+        if training:
+            m, v = pre.mean((0, -1) if f else 0), pre.var((0, -1) if f else 0, unbiased=False)
+        else:
+            m, v = bn.running_mean, bn.running_var
+        if f:
+            xh = (pre - m[:, None]) / torch.sqrt(v[:, None] + 1e-5)
+            u_of = lambda beta: xh * bn.weight[:, None] + beta[:, None]      # noqa: E731
+            other = (0, 2)
+        else:
+            xh = (pre - m) / torch.sqrt(v + 1e-5)
+            u_of = lambda beta: xh * bn.weight + beta                        # noqa: E731
+            other = (0,)
+        beta = 0.2 * torch.randn(c, generator=g, dtype=torch.float64)
+        bn.bias.copy_(_off_kink(u_of, beta, other) if off_kink else beta)
+    return g, x, w, bn
+
+
+# F = 0 (a column of x), 1, 5 and GD_FMAX = 8 channels of the per-node linear; B = 2 (the smallest batch a training
+# BatchNorm takes), 3, and around the GD_T = 256 threads of a column; C = 1, 32, the bench's 400 (B) and 3000 (B_D)
+@pytest.mark.parametrize("keep_on", [True, False], ids=["keep", "nokeep"])
+@pytest.mark.parametrize("training", [True, False], ids=["train", "eval"])
+@pytest.mark.parametrize("c", [1, 32, 400, 3000])
+@pytest.mark.parametrize("b", [2, 3, 255, 256, 257, 512])
+@pytest.mark.parametrize("f", [0, 1, 5, 8])
+def test_bn_prelu_sweep_vs_fp64(f, b, c, training, keep_on):
+    """Scale-relative bounds of test_bn_prelu_vs_fp64.  Three quantities are sums whose exact value may cancel far below
+    their terms — measured rounding cases, each judged on the scale its terms set (floors, computed in float64):
+    dx, whose exact value in a training BatchNorm over B = 2 samples is O(eps) (x hat = +-1 whatever x is), on the largest
+    gamma rstd e; d W, which in training is orthogonal to W (the BatchNorm is blind to W's scale: exactly 0 at F = 1, and
+    all of it O(eps) at B = 2), on the root-sum-square of its B C summands gamma rstd e x before the batch means cancel
+    them; and d slope on the root-sum-square of its summands u dy."""
+    from igcn_amd import ops
+    a = [0.25, -0.3, 1.7, 0.0][(f + b + c) % 4]
+    g, x, w, bn = _bn_case(f, b, c, 1, 11 * f + b + c, training)
+    bn.train(training)
+    bn_gpu = copy.deepcopy(bn).float().cuda()
+    keep = _keep((b, c), 0.5, g) if keep_on else None
+    slope = torch.tensor([a], dtype=torch.float64)
+    cot = torch.randn(b, c, generator=g, dtype=torch.float64)
+    xr, sr = _leaf(x), _leaf(slope)
+    wr = _leaf(w) if f else None
+    pre = xr if f == 0 else torch.einsum("of,bfc->bc", wr, xr)
+    pre.retain_grad()
+    u = bn(pre)
+    u.retain_grad()
+    out = _prelu(u, sr)
+    if keep_on:
+        out = out * keep
+    (out * cot).sum().backward()
+    with torch.no_grad():
+        up = cot * keep if keep_on else cot
+        gre = u.grad * bn.weight / torch.sqrt((bn.running_var if not training else pre.var(0, unbiased=False)) + 1e-5)
+        fl_dx = float(gre.abs().max())
+        fl_da = float(((u * up)[u <= 0] ** 2).sum().sqrt())
+        fl_dw = float(((gre.unsqueeze(1) * x) ** 2).sum((0, 2)).sqrt().max()) if f else 0.0
+    das = []
+    for _ in range(2):
+        bg = copy.deepcopy(bn_gpu)
+        xg, sg = _leaf(x.float().cuda()), _leaf(slope.float().cuda())
+        wg = _leaf(w.float().cuda()) if f else None
+        og = ops.BatchNormPReLU.apply(xg, wg, bg.weight, bg.bias, sg, bg, training,
+                                      keep.float().cuda() if keep_on else None)
+        (og * cot.float().cuda()).sum().backward()
+        das.append(sg.grad.clone())
+    assert_matches(og, out.detach().numpy(), 1e-5, "y")
+    assert_matches(xg.grad, xr.grad.numpy(), 1e-4, "dx", floor=fl_dx if (training and b == 2) else 0.0)
+    assert_matches(sg.grad, sr.grad.numpy(), 1e-4, "dslope", floor=fl_da)
+    assert_matches(bg.weight.grad, bn.weight.grad.numpy(), 1e-4, "dgamma")
+    assert_matches(bg.bias.grad, bn.bias.grad.numpy(), 1e-4, "dbeta")
+    if f:
+        assert_matches(wg.grad, wr.grad.numpy(), 1e-4, "dW", floor=fl_dw if training else 0.0)
+    assert_matches(bg.running_mean, bn.running_mean.numpy(), 1e-5, "running_mean")
+    assert_matches(bg.running_var, bn.running_var.numpy(), 1e-5, "running_var")
+    assert torch.equal(das[0], das[1])
+
+
+@pytest.mark.parametrize("training", [True, False], ids=["train", "eval"])
+@pytest.mark.parametrize("d", [5, 10, 16, 32])
+def test_node_linear_bn_prelu_wide_sweep_vs_fp64(d, training):
+    """conc_for_attention's form (D > 1) at the bench's n_top = 400 nodes and B = 256: output and running statistics."""
+    from igcn_amd import ops
+    g, x, w, bn = _bn_case(5, 256, 400, d, 90 + d, training, off_kink=False)     # (values only: continuous at the kink)
+    bn.train(training)
+    bn_gpu = copy.deepcopy(bn).float().cuda()
+    with torch.no_grad():
+        out = _prelu(bn(torch.einsum("df,bfc->bcd", w, x)), 0.35)
+    y, _, _ = ops.bn_prelu_forward(x.float().cuda(), w.float().cuda(), bn_gpu, torch.tensor([0.35], device="cuda"),
+                                   training)
+    assert_matches(y, out.numpy(), 1e-5, "y")
+    assert_matches(bn_gpu.running_mean, bn.running_mean.numpy(), 1e-5, "running_mean")
+    assert_matches(bn_gpu.running_var, bn.running_var.numpy(), 1e-5, "running_var")
+
+
+def test_bn_prelu_refusals_launch_nothing():
+    """F = 9 > GD_FMAX, keep with D > 1 and a training call with B D = 1 raise, and nothing is written."""
+    from igcn_amd import _lib, ops
+    from igcn_amd._lib import IgcnError
+
+    def fwd(b, c, f, d, keep, training):
+        x = torch.randn((b, c) if f == 0 else (b, f, c), device="cuda")
+        w = torch.randn(d, f, device="cuda") if f else None
+        bn = torch.nn.BatchNorm1d(c).cuda()
+        y = torch.full((b, c, d), float("nan"), device="cuda")
+        mean, rstd = torch.full((c,), 7.0, device="cuda"), torch.full((c,), 7.0, device="cuda")
+        k = torch.ones(b, c, device="cuda") if keep else None
+        with pytest.raises(IgcnError, match="bn_prelu_fwd"):
+            _lib.call("igcn_bn_prelu_fwd", b, c, f, d, _lib.ptr(x), _lib.ptr(w), _lib.ptr(bn.weight), _lib.ptr(bn.bias),
+                      _lib.ptr(bn.running_mean), _lib.ptr(bn.running_var), int(training), 0.1, 1e-5, _lib.ptr(k),
+                      _lib.ptr(torch.tensor([0.25], device="cuda")), _lib.ptr(y), _lib.ptr(mean), _lib.ptr(rstd),
+                      _lib.stream_ptr())
+        torch.cuda.synchronize()
+        assert bool(torch.isnan(y).all()) and bool((mean == 7).all()) and bool((rstd == 7).all())
+        assert bool((bn.running_mean == 0).all()) and bool((bn.running_var == 1).all())
+
+    fwd(8, 16, 9, 1, False, True)          # F = 9
+    fwd(8, 16, 5, 4, True, True)           # keep with D > 1
+    fwd(1, 16, 0, 1, False, True)          # training, B D = 1
+    fwd(1, 16, 5, 1, False, True)
+    # the backward refuses F = 9 too, before anything is written
+    b, c, f = 8, 16, 9
+    x, w = torch.randn(b, f, c, device="cuda"), torch.randn(1, f, device="cuda")
+    ones = torch.ones(c, device="cuda")
+    dx, dw = torch.full_like(x, float("nan")), torch.full_like(w, float("nan"))
+    dg, db, da = torch.full_like(ones, float("nan")), torch.full_like(ones, float("nan")), torch.full((1,), float("nan"), device="cuda")
+    scratch = torch.full((c * (f + 1) + 64,), float("nan"), device="cuda")
+    with pytest.raises(IgcnError, match="bn_prelu_bwd"):
+        _lib.call("igcn_bn_prelu_bwd", b, c, f, 1, _lib.ptr(x), _lib.ptr(w), _lib.ptr(ones), _lib.ptr(ones),
+                  _lib.ptr(torch.tensor([0.25], device="cuda")), _lib.ptr(ones), _lib.ptr(ones),
+                  _lib.ptr(torch.ones(b, c, device="cuda")), None, _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(dg),
+                  _lib.ptr(db), _lib.ptr(da), _lib.ptr(scratch), _lib.stream_ptr())
+    torch.cuda.synchronize()
+    for t in (dx, dw, dg, db, da, scratch):
+        assert bool(torch.isnan(t).all())
+    # and the autograd entry points
+    bn = torch.nn.BatchNorm1d(16).cuda()
+    with pytest.raises(IgcnError):
+        ops.BatchNormPReLU.apply(torch.randn(8, 9, 16, device="cuda"), torch.randn(1, 9, device="cuda"), bn.weight,
+                                 bn.bias, torch.tensor([0.25], device="cuda"), bn, True, None)
+    with pytest.raises(IgcnError):
+        ops.bn_prelu_forward(torch.randn(8, 5, 16, device="cuda"), torch.randn(4, 5, device="cuda"), bn,
+                             torch.tensor([0.25], device="cuda"), True, torch.ones(8, 16, device="cuda"))
+    with pytest.raises(IgcnError):
+        ops.BatchNormPReLU.apply(torch.randn(1, 16, device="cuda"), None, bn.weight, bn.bias,
+                                 torch.tensor([0.25], device="cuda"), bn, True, None)
+    torch.cuda.synchronize()
+    assert bool((bn.running_mean == 0).all()) and bool((bn.running_var == 1).all())
+
+
+def _gate_case(b, k, h, l, training, seed, tau):
+    """Gate inputs whose fp64 hidden pre-activations all lie off the PReLU kink (by 1e-5 of the largest), and noise
+    whose hard decisions sit 1e-3 (tempered-logit units) off a tie, as tests/golden/make_golden_guide.py moves them."""
+    for s in range(seed, seed + 20):
+        g = torch.Generator().manual_seed(s)
+        img = torch.randn(b, k, generator=g, dtype=torch.float64)
+        bias = 0.1 * (2 * torch.rand(k, 2, generator=g, dtype=torch.float64) - 1)
+        w1 = torch.randn(h, k, generator=g, dtype=torch.float64) / k ** 0.5
+        w2 = torch.randn(l, h, generator=g, dtype=torch.float64) / h ** 0.5
+        keep = _keep((b, h), 0.4, g)
+        noise = torch.from_numpy(guide_ref.gumbel_noise(s, b, k)).double()
+        logit = torch.log(torch.softmax(bias, 1))
+        wt = (logit.unsqueeze(0) + noise) / tau
+        noise[..., 1] += torch.where((wt[..., 1] - wt[..., 0]).abs() < 1e-3, 0.05, 0.0)
+        _, z1 = guide_ref.soft_sample(bias, noise, tau)
+        pre = (img * z1 if training else img) @ w1.t()
+        if not bool(((pre.abs() <= 1e-5 * pre.abs().max()) & (pre != 0)).any()):      # (exact zeros agree)
+            return img, bias, w1, w2, keep, noise
+    raise AssertionError("no gate inputs off the PReLU kink")
+
+
+# K = 1 .. GG_KMAX = 1024 (the LDS row xin[K] full), K < GD_T = 256 and the model's 270; H, L = 1, 32 and their limit 64;
+# B = 1, 8 and 256 workgroups.  Each shape runs in training and eval and in four variants: dropout keep on / off, tau as
+# a device scalar / a number, a cotangent on imp1 (the sparsity term's path into bias_n through the b == 0 block) or not.
+GATE_SHAPES = [(k, h, l, (1, 8, 256)[(i + j + m) % 3]) for i, k in enumerate((1, 64, 255, 270, 1024))
+               for j, h in enumerate((1, 32, 64)) for m, l in enumerate((1, 32, 64))]
+GATE_VARIANTS = {"keep-dev-imp": (True, True, True), "nokeep-num-imp": (False, False, True),
+                 "keep-num-noimp": (True, False, False), "nokeep-dev-noimp": (False, True, False)}
+
+
+@pytest.mark.parametrize("variant", list(GATE_VARIANTS))
+@pytest.mark.parametrize("training", [True, False], ids=["train", "eval"])
+@pytest.mark.parametrize("k,h,l,b", GATE_SHAPES)
+def test_gate_encoder_sweep_vs_fp64(k, h, l, b, training, variant):
+    from igcn_amd import ops
+    keep_on, tau_dev, imp_cot = GATE_VARIANTS[variant]
+    tau = 0.1
+    img, bias, w1, w2, keep, noise = _gate_case(b, k, h, l, training, 1000 * k + 10 * h + l + b, tau)
+    keep = keep if keep_on else None
+    a = torch.tensor([[-0.3, 0.25, 0.0, 1.0, 1.7][(k + h + l) % 5]], dtype=torch.float64)
+    ref = [_leaf(t) for t in (img, bias, w1, a, w2)]
+    lat, imp1 = guide_ref.gate_encoder(*ref[:3], ref[3], ref[4], keep, tau, noise, training)
+    g = torch.Generator().manual_seed(9)
+    c1, c2 = torch.randn(lat.shape, generator=g, dtype=torch.float64), torch.randn(imp1.shape, generator=g, dtype=torch.float64)
+    obj = (lat * c1).sum() + ((imp1 * c2).sum() if imp_cot else 0.0)
+    obj.backward()
+    grads = []
+    for _ in range(2):
+        got = [_leaf(t.float().cuda()) for t in (img, bias, w1, a, w2)]
+        tau_arg = torch.tensor(tau, device="cuda") if tau_dev else tau
+        lg, ig, gate = ops.GuideGate.apply(*got, keep.float().cuda() if keep_on else None, tau_arg, training,
+                                           noise.float().cuda(), None)
+        og = (lg * c1.float().cuda()).sum() + ((ig * c2.float().cuda()).sum() if imp_cot else 0.0)
+        og.backward()
+        grads.append(got[3].grad.clone())
+    assert_matches(lg, lat.detach().numpy(), 1e-4, "latent_n")
+    assert_matches(ig, imp1.detach().numpy(), 1e-5, "imp1")
+    # d bias_n from the gate alone is sum_b s0 s1 img d img / tau, and d img = W1^T dpre an H-term sum that may cancel:
+    # with one summand (B = K = 1) scale-relative turns self-relative.  A measured rounding case: d bias_n is judged on
+    # the scale of those sums' terms, sum_b s0 s1 |img| sum_j |W1[j, k] dpre[b, j]| / tau (float64)
+    fl_b = 0.0
+    if training and not imp_cot:
+        with torch.no_grad():
+            s, z1 = guide_ref.soft_sample(bias, noise, tau)
+            pre = (img * z1) @ w1.t()
+            up = (c1 @ w2) * (keep if keep_on else 1.0)
+            dpre = torch.where(pre > 0, up, a * up)
+            fl_b = float((s[..., 0] * s[..., 1] * img.abs() * (dpre.abs() @ w1.abs())).sum(0).max() / tau)
+    for r, t, w in zip(ref, got, ("d img", "d bias_n", "dW1", "d slope", "dW2")):
+        if r.grad is None:                    # (bias_n in eval with no cotangent on imp1: nothing reaches it)
+            assert not bool(t.grad.abs().max() > 0), w
+            continue
+        assert_matches(t.grad, r.grad.numpy(), 1e-3, w, floor=fl_b if w == "d bias_n" else 0.0)
+    assert torch.equal(grads[0], grads[1])
+    if training:
+        _, z1 = guide_ref.soft_sample(bias, noise, tau)
+        assert torch.equal(gate[..., 0].cpu() > 0.5, z1 > 0.5)
+    else:
+        assert gate is None
+
+
+def test_gate_generator_contract_b256_k1024():
+    """256 workgroups race to advance the counter: one training launch advances it by exactly one, and its draws at
+    K = GG_KMAX = 1024 equal the host rebuild."""
+    from igcn_amd import ops
+    b, k = 256, 1024
+    img, bias, w1, w2, _, _ = _gate_case(b, k, 64, 64, False, 17, 0.1)
+    args = [t.float().cuda() for t in (img, bias, w1)] + [torch.tensor([0.25], device="cuda"), w2.float().cuda()]
+    state = ops.DropoutState("cuda")
+    c0 = int(state.state[0].item())
+    for step in range(3):
+        _, _, gate = ops.GuideGate.apply(*args, None, torch.tensor(0.1, device="cuda"), True, None, state)
+        torch.cuda.synchronize()
+        assert int(state.state[0].item()) == c0 + step + 1 and int(state.state[1].item()) == 0
+        s, z1 = guide_ref.soft_sample(bias, torch.from_numpy(guide_ref.gumbel_noise(c0 + step, b, k)).double(), 0.1)
+        far = (s[..., 1] - s[..., 0]).abs() > 1e-6
+        got = (gate[..., 0] > 0.5).cpu()
+        assert bool(far.float().mean() > 0.99)
+        assert torch.equal(got[far], (z1 > 0.5)[far]), "kernel draws differ from the host rebuild"
+        # the soft part of the gate is the draw's too: s0 s1 of the rebuild
+        prod = (s[..., 0] * s[..., 1]).float()
+        assert_matches(gate[..., 1], prod.numpy(), 1e-4, "s0 s1")
