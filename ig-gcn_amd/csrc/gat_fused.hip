@@ -13,6 +13,10 @@
 // in LDS (keeping every layer's alpha and node logits), then walks the layers top-down: ReLU mask, softmax backward
 // (dz = alpha (dalpha - sum alpha dalpha)), leaky-ReLU slope, the two sources of dh (aggregation by source, the logit
 // terms), the parameter gradients as one row per graph (summed by a final reduction, igcn_reduce_defer) and dx.
+// With the edge attributes trained (SGCN_GAT's masked pass: EW instantiation, igcn_gat_stack_bwd_ew) each thread also
+// owns the stored edges k = tid, tid + 256, ... and adds, layer by layer into its own element of dew,
+//   d ea_k = c_l (dpre_l[k] + dpre_l[Emax + dst_k] / cnt_dst)      (the logit term + the mean-valued virtual loop)
+// with cnt_i = the number of kept (src != dst) edges into i; a stored self-loop gets an exact 0.
 //
 // Preconditions (host wrappers / per-graph plan builder): uniform graphs of R nodes (graph g = nodes [gR, (g+1)R), its
 // edges contiguous in stored order); sums run in list order; no atomics: deterministic.
@@ -35,9 +39,11 @@ __host__ __device__ inline int gt_param_offset(int l, int H0, int F) {
 struct GtLayout {
   int x, esrc, edst, eea, tptr, tk, lea, prm, wt, ce, h, lgs, lgd, alpha, y;   // both directions
   int sptr, sk, dcur, dh, dpre, das, dad, prow, red;                            // backward
+  int icnt;                                                                     // backward with d(edge attribute)
   int total;
 };
 
+// backward: 0 forward, 1 backward, 2 backward with the edge-attribute gradient (1 + one word per node)
 __host__ __device__ inline GtLayout gt_layout(int R, int Emax, int H0, int F, int L, int backward) {
   GtLayout o;
   int p = 0;
@@ -60,7 +66,7 @@ __host__ __device__ inline GtLayout gt_layout(int R, int Emax, int H0, int F, in
   o.lgd = take(LK * R);
   o.alpha = take(LK * EA);
   o.y = take(R * L * F);                           // concatenated layer outputs [R][L F]
-  o.sptr = o.sk = o.dcur = o.dh = o.dpre = o.das = o.dad = o.prow = o.red = 0;
+  o.sptr = o.sk = o.dcur = o.dh = o.dpre = o.das = o.dad = o.prow = o.red = o.icnt = 0;
   if (backward) {
     o.sptr = take(R + 1);                          // by-source list: positions [sptr[n], sptr[n+1]) hold edges sk[.]
     o.sk = take(Emax);
@@ -71,6 +77,7 @@ __host__ __device__ inline GtLayout gt_layout(int R, int Emax, int H0, int F, in
     o.dad = take(R);
     o.prow = take(gt_param_offset(L, H0, F));
     o.red = take(4);
+    if (backward == 2) o.icnt = take(R);           // 1 / (kept incoming edges of node i), 0 for none
   }
   o.total = p;
   return o;
@@ -86,7 +93,8 @@ __device__ __forceinline__ float gt_lrelu(float z) { return z > 0.f ? z : GT_SLO
 
 // Stage graph nb/R: x, edges, lists (by-source too for the backward), parameters; then per-layer c and the loop values.
 // Returns the edge count, or -1 when it exceeds Emax (nothing of LDS beyond the fixed part touched; status bit 1 set).
-template <bool BWD>
+// EW: also keep 1 / cnt of every target (the share of the virtual loop's gradient each kept edge takes).
+template <bool BWD, bool EW = false>
 __device__ int gt_stage(float* lds, const GtLayout& o, int R, int Emax, int H0, int F, int L, int64_t nb,
                         const float* __restrict__ x_in, const float* __restrict__ ew_in,
                         const int32_t* __restrict__ src32, const int32_t* __restrict__ dst32,
@@ -150,6 +158,7 @@ __device__ int gt_stage(float* lds, const GtLayout& o, int R, int Emax, int H0, 
       }
     }
     lds[o.lea + i] = cnt ? s / (float)cnt : 0.f;
+    if (EW) lds[o.icnt + i] = cnt ? 1.f / (float)cnt : 0.f;
   }
   __syncthreads();
   return ne;
@@ -270,24 +279,29 @@ k_gat_stack_fwd(int R, int Emax, int H0, int L, const float* __restrict__ x_in, 
     reinterpret_cast<float4*>(xcat + nb * D)[e] = reinterpret_cast<const float4*>(gt_lds + o.y)[e];
 }
 
-template <int F>
+template <int F, bool EW>
 __global__ void __launch_bounds__(GT_T)
 k_gat_stack_bwd(int R, int Emax, int H0, int L, const float* __restrict__ x_in, const float* __restrict__ ew_in,
                 const int32_t* __restrict__ src32, const int32_t* __restrict__ dst32,
                 const int32_t* __restrict__ tgt_ptr, const int32_t* __restrict__ tgt_perm,
                 const int32_t* __restrict__ src_ptr, const int32_t* __restrict__ src_perm, GtParams prm,
                 const float* __restrict__ dxcat, float* __restrict__ dx_in /*or NULL*/,
-                float* __restrict__ dpar_partial, int P, int32_t* __restrict__ status) {
+                float* __restrict__ dpar_partial, int P, int32_t* __restrict__ status,
+                float* __restrict__ dew /*[sum E], EW only*/) {
   extern __shared__ float gt_lds[];
-  const GtLayout o = gt_layout(R, Emax, H0, F, L, 1);
+  const GtLayout o = gt_layout(R, Emax, H0, F, L, EW ? 2 : 1);
   const int tid = threadIdx.x;
   const int64_t nb = (int64_t)blockIdx.x * R;
   const int D = L * F, EA = Emax + R;
   const int fin_max = F > H0 ? F : H0;
-  if (gt_stage<true>(gt_lds, o, R, Emax, H0, F, L, nb, x_in, ew_in, src32, dst32, tgt_ptr, tgt_perm, src_ptr,
-                     src_perm, prm, status) < 0) {
+  if (gt_stage<true, EW>(gt_lds, o, R, Emax, H0, F, L, nb, x_in, ew_in, src32, dst32, tgt_ptr, tgt_perm, src_ptr,
+                         src_perm, prm, status) < 0) {
     if (dx_in)
       for (int e = tid; e < R * H0; e += GT_T) dx_in[nb * H0 + e] = 0.f;
+    if (EW) {                                         // refused graph: its edges get a defined (zero) gradient too
+      const int32_t eb = tgt_ptr[nb], ne = tgt_ptr[nb + R] - eb;
+      for (int k = tid; k < ne; k += GT_T) dew[eb + k] = 0.f;
+    }
     for (int e = tid; e < P; e += GT_T) dpar_partial[(int64_t)blockIdx.x * P + e] = 0.f;
     return;
   }
@@ -404,6 +418,17 @@ k_gat_stack_bwd(int R, int Emax, int H0, int L, const float* __restrict__ x_in, 
       s = wave_sum(s);
       if (lane == 0) gt_lds[o.red] = s;
     }
+    if (EW) {
+      // d ea of this layer into the thread's own edges (the top layer writes, the others add: no atomics); the
+      // dpre[Emax + dst] / icnt[dst] gathers are indexed LDS reads, same-address lanes broadcast
+      float* dew_g = dew + tgt_ptr[nb];
+      const int ne = tptr[R];
+      for (int k = tid; k < ne; k += GT_T) {
+        const int t = edst[k];
+        const float g = esrc[k] != t ? c * (dpre[k] + dpre[Emax + t] * gt_lds[o.icnt + t]) : 0.f;
+        dew_g[k] = l == L - 1 ? g : dew_g[k] + g;
+      }
+    }
     __syncthreads();
     // (d) dh = (aggregation, by source) + (logit terms); d att_src, d att_dst, d lin_edge, d att_edge
     for (int e = tid; e < R * F; e += GT_T) {
@@ -495,31 +520,33 @@ extern "C" int igcn_gat_stack_fwd(int64_t n_graphs, int R, int max_edges, int H0
   return IGCN_OK;
 }
 
-extern "C" int igcn_gat_stack_bwd(int64_t n_graphs, int R, int max_edges, int H0, int F, int L, const float* x_in,
-                                  const float* ew_in, const int32_t* src32, const int32_t* dst32,
-                                  const int32_t* tgt_ptr, const int32_t* tgt_perm, const int32_t* src_ptr,
-                                  const int32_t* src_perm, const float* const* params, const float* dxcat,
-                                  float* dx_in, float* dparams, float* scratch, int32_t* status, void* stream) {
-  int rc = gt_check("gat_stack_bwd", n_graphs, R, max_edges, H0, F, L, 1);
+// Both backward entry points: EW selects the instantiation that also writes dew (and its LDS layout, code 2).
+template <bool EW>
+static int gt_bwd_launch(const char* nm, int64_t n_graphs, int R, int max_edges, int H0, int F, int L,
+                         const float* x_in, const float* ew_in, const int32_t* src32, const int32_t* dst32,
+                         const int32_t* tgt_ptr, const int32_t* tgt_perm, const int32_t* src_ptr,
+                         const int32_t* src_perm, const float* const* params, const float* dxcat, float* dx_in,
+                         float* dew, float* dparams, float* scratch, int32_t* status, void* stream) {
+  int rc = gt_check(nm, n_graphs, R, max_edges, H0, F, L, EW ? 2 : 1);
   if (rc) return rc;
   IGCN_REQUIRE(x_in && ew_in && src32 && dst32 && tgt_ptr && tgt_perm && src_ptr && src_perm && params && dxcat &&
-                   dparams && scratch,
-               "gat_stack_bwd: null argument");
-  IGCN_REQUIRE(((uintptr_t)dxcat & 15) == 0, "gat_stack_bwd: dxcat must be 16-byte aligned");
+                   dparams && scratch && (dew || !EW),
+               "%s: null argument", nm);
+  IGCN_REQUIRE(((uintptr_t)dxcat & 15) == 0, "%s: dxcat must be 16-byte aligned", nm);
   GtParams prm = {};
   for (int j = 0; j < 6 * L; ++j) {
-    IGCN_REQUIRE(params[j], "gat_stack_bwd: null parameter %d", j);
+    IGCN_REQUIRE(params[j], "%s: null parameter %d", nm, j);
     prm.p[j] = params[j];
   }
-  const size_t lds = igcn_gat_stack_lds_bytes(R, max_edges, H0, F, L, 1);
+  const size_t lds = igcn_gat_stack_lds_bytes(R, max_edges, H0, F, L, EW ? 2 : 1);
   const int P = igcn_gat_stack_param_floats(H0, F, L);
   hipStream_t st = (hipStream_t)stream;
 #define GT_BWD(FV)                                                                                                \
   {                                                                                                               \
-    if (lds > 64 * 1024) IGCN_ALLOW_BIG_LDS((k_gat_stack_bwd<FV>));                                               \
-    hipLaunchKernelGGL((k_gat_stack_bwd<FV>), dim3((unsigned)n_graphs), dim3(GT_T), lds, st, R, max_edges, H0, L,  \
-                       x_in, ew_in, src32, dst32, tgt_ptr, tgt_perm, src_ptr, src_perm, prm, dxcat, dx_in,       \
-                       scratch, P, status);                                                                       \
+    if (lds > 64 * 1024) IGCN_ALLOW_BIG_LDS((k_gat_stack_bwd<FV, EW>));                                           \
+    hipLaunchKernelGGL((k_gat_stack_bwd<FV, EW>), dim3((unsigned)n_graphs), dim3(GT_T), lds, st, R, max_edges,    \
+                       H0, L, x_in, ew_in, src32, dst32, tgt_ptr, tgt_perm, src_ptr, src_perm, prm, dxcat, dx_in, \
+                       scratch, P, status, dew);                                                                  \
   }
   switch (F) {
     case 4: GT_BWD(4) break;
@@ -528,6 +555,27 @@ extern "C" int igcn_gat_stack_bwd(int64_t n_graphs, int R, int max_edges, int H0
     default: GT_BWD(32) break;
   }
 #undef GT_BWD
-  IGCN_CHECK_LAUNCH("gat_stack_bwd");
+  IGCN_CHECK_LAUNCH(nm);
   return igcn_launch_reduce_rows_final(scratch, n_graphs, P, P, dparams, st);
+}
+
+extern "C" int igcn_gat_stack_bwd(int64_t n_graphs, int R, int max_edges, int H0, int F, int L, const float* x_in,
+                                  const float* ew_in, const int32_t* src32, const int32_t* dst32,
+                                  const int32_t* tgt_ptr, const int32_t* tgt_perm, const int32_t* src_ptr,
+                                  const int32_t* src_perm, const float* const* params, const float* dxcat,
+                                  float* dx_in, float* dparams, float* scratch, int32_t* status, void* stream) {
+  return gt_bwd_launch<false>("gat_stack_bwd", n_graphs, R, max_edges, H0, F, L, x_in, ew_in, src32, dst32, tgt_ptr,
+                              tgt_perm, src_ptr, src_perm, params, dxcat, dx_in, nullptr, dparams, scratch, status,
+                              stream);
+}
+
+// The same backward with d(loss)/d(ew_in) as one more output: dew [sum E], every element written (0 at stored loops).
+extern "C" int igcn_gat_stack_bwd_ew(int64_t n_graphs, int R, int max_edges, int H0, int F, int L, const float* x_in,
+                                     const float* ew_in, const int32_t* src32, const int32_t* dst32,
+                                     const int32_t* tgt_ptr, const int32_t* tgt_perm, const int32_t* src_ptr,
+                                     const int32_t* src_perm, const float* const* params, const float* dxcat,
+                                     float* dx_in, float* dew, float* dparams, float* scratch, int32_t* status,
+                                     void* stream) {
+  return gt_bwd_launch<true>("gat_stack_bwd_ew", n_graphs, R, max_edges, H0, F, L, x_in, ew_in, src32, dst32, tgt_ptr,
+                             tgt_perm, src_ptr, src_perm, params, dxcat, dx_in, dew, dparams, scratch, status, stream);
 }

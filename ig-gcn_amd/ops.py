@@ -693,8 +693,10 @@ GAT_MAX_H0 = 8
 GAT_LDS_BYTES = 150 * 1024
 
 
-def gat_stack_limits(plan, rois, h0, f, layers):
-    """None when the LDS-resident GAT stack (igcn_gat_stack_*) covers this batch, else the limit it breaks (a sentence)."""
+def gat_stack_limits(plan, rois, h0, f, layers, ew_grad=False):
+    """None when the LDS-resident GAT stack (igcn_gat_stack_*) covers this batch, else the limit it breaks (a sentence).
+    ``ew_grad``: the edge attributes take a gradient (igcn_gat_stack_bwd_ew, whose LDS layout has one more word per
+    node)."""
     seg = getattr(plan, "_stack_dims", None)
     if seg is None or seg[0] != rois:
         return f"needs a per-graph plan of uniform graphs with rois={rois} nodes each"
@@ -704,7 +706,7 @@ def gat_stack_limits(plan, rois, h0, f, layers):
         return f"needs 1 <= layers <= {GAT_MAX_LAYERS} (got {layers})"
     if not 1 <= h0 <= GAT_MAX_H0:
         return f"needs 1 <= H0 <= {GAT_MAX_H0} input features (got {h0})"
-    need = int(_lib.load().igcn_gat_stack_lds_bytes(rois, seg[1], h0, f, layers, 1))
+    need = int(_lib.load().igcn_gat_stack_lds_bytes(rois, seg[1], h0, f, layers, 2 if ew_grad else 1))
     if need > GAT_LDS_BYTES:
         return (f"needs a graph that fits {GAT_LDS_BYTES // 1024} KB of LDS (rois={rois}, max edges {seg[1]}, F={f}, "
                 f"L={layers}: {need} bytes)")
@@ -719,16 +721,21 @@ def gat_stack_supported(plan, rois, h0, f, layers):
 class GatStack(torch.autograd.Function):
     """xcat = cat_l relu(GATConv_l(...)) of kernel/gcn_img_snp.py:217-221 with ifUseGAT (PyG 2.0.2 GATConv(in, F,
     edge_dim=1)) for a batch of small uniform graphs: one LDS-resident kernel per direction (igcn_gat_stack_*).  ``params``
-    = per layer W [F, Fin], bias [F], att_src [F], att_dst [F], lin_edge [F], att_edge [F]; ``ew_in`` (the scalar edge
-    attributes) is data.  Shapes outside the kernels' coverage raise ValueError: there is no other GAT path."""
+    = per layer W [F, Fin], bias [F], att_src [F], att_dst [F], lin_edge [F], att_edge [F]; ``ew_in`` = the scalar edge
+    attributes.  Where they require a gradient (SGCN_GAT's masked pass: edge_weight * edge_prob) the backward is
+    igcn_gat_stack_bwd_ew, which also returns d(loss)/d(ew_in) — through the logit term and through the mean-valued added
+    self-loop, 0 at stored self-loops; where they are data it is igcn_gat_stack_bwd.  ``plan`` may be the batched plan
+    ``plan.replicate(g)`` of g stacked passes.  Shapes outside the kernels' coverage raise ValueError: there is no other
+    GAT path."""
 
     @staticmethod
     def forward(ctx, x_in, ew_in, plan, rois, *params):
+        ctx.ew_shape = ew_in.shape
         x_in, ew_in = _f32(x_in), _f32(ew_in.reshape(-1))
         params = [_f32(t) for t in params]
         n, h0 = x_in.shape
         f, layers = params[0].shape[0], len(params) // 6
-        why = gat_stack_limits(plan, rois, h0, f, layers)
+        why = gat_stack_limits(plan, rois, h0, f, layers, ew_grad=ctx.needs_input_grad[1])
         if why is not None:
             raise ValueError(f"GAT stack: {why}")
         emax = plan._stack_dims[1]
@@ -755,10 +762,17 @@ class GatStack(torch.autograd.Function):
         dpar = torch.empty(npar, dtype=torch.float32, device=x_in.device)
         scratch = _keep(torch.empty(g * npar, dtype=torch.float32, device=x_in.device))
         pp = (ctypes.c_void_p * len(params))(*[t.data_ptr() for t in params])
+        dew = torch.empty_like(ew_in) if ctx.needs_input_grad[1] else None      # the kernel writes every element
         with _immediate(ctx.final):
-            call("igcn_gat_stack_bwd", g, rois, emax, h0, f, layers, ptr(x_in), ptr(ew_in), ptr(plan.src32),
-                 ptr(plan.dst32), ptr(plan.tgt_ptr), ptr(plan.tgt_perm), ptr(plan.src_ptr), ptr(plan.src_perm), pp,
-                 ptr(dxcat), ptr(dx), ptr(dpar), ptr(scratch), ptr(plan.status), stream_ptr())
+            if dew is None:
+                call("igcn_gat_stack_bwd", g, rois, emax, h0, f, layers, ptr(x_in), ptr(ew_in), ptr(plan.src32),
+                     ptr(plan.dst32), ptr(plan.tgt_ptr), ptr(plan.tgt_perm), ptr(plan.src_ptr), ptr(plan.src_perm), pp,
+                     ptr(dxcat), ptr(dx), ptr(dpar), ptr(scratch), ptr(plan.status), stream_ptr())
+            else:
+                call("igcn_gat_stack_bwd_ew", g, rois, emax, h0, f, layers, ptr(x_in), ptr(ew_in), ptr(plan.src32),
+                     ptr(plan.dst32), ptr(plan.tgt_ptr), ptr(plan.tgt_perm), ptr(plan.src_ptr), ptr(plan.src_perm), pp,
+                     ptr(dxcat), ptr(dx), ptr(dew), ptr(dpar), ptr(scratch), ptr(plan.status), stream_ptr())
+                dew = dew.view(ctx.ew_shape)
         grads, off = [], 0
         for l in range(layers):
             fin = h0 if l == 0 else f
@@ -766,7 +780,7 @@ class GatStack(torch.autograd.Function):
                 m = shape[0] * (shape[1] if len(shape) == 2 else 1)
                 grads.append(dpar[off:off + m].view(params[6 * l + k].shape))
                 off += m
-        return (dx, None, None, None, *grads)
+        return (dx, dew, None, None, *grads)
 
 
 def sgcn_front_supported(plan, rois, h0, f, layers, snps_feat, snps_logits):

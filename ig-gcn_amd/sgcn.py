@@ -1,6 +1,9 @@
-"""Drop-in ``SGCN_GCN`` — the image-only sibling of the hot path (reference kernel/sgcn.py:272-388) on the
-same kernels: masks (igcn_edge_mask_*), one gcn_norm per pass, MFMA feature transforms, scatter-aggregate,
-the (R*D -> hidden_linear -> classes) head on the split-K GEMM, and the mask regulariser as one reduction.
+"""Drop-ins for the image-only models of the reference's kernel/sgcn.py: ``SGCN_GCN`` (:272-388) and its attention twin
+``SGCN_GAT`` (:154-270).
+
+``SGCN_GCN`` — the image-only sibling of the hot path on the same kernels: masks (igcn_edge_mask_*), one gcn_norm per
+pass, MFMA feature transforms, scatter-aggregate, the (R*D -> hidden_linear -> classes) head on the split-K GEMM, and
+the mask regulariser as one reduction.
 
 Same constructor signature (``dataset`` is accepted and ignored exactly as in the reference), the same
 ``forward(data, isExplain=False) -> log_softmax [B, C]``, ``cal_probability`` (:321), ``loss_probability``
@@ -11,6 +14,14 @@ inputs (the reference hard-codes 90 at :285, i.e. it only works for rois=90; ide
 ``forward_pair`` runs the plain and the masked pass of train() (kernel/train_eval_sgcn.py:303-306) as one
 sweep over a 2-copy block-diagonal batch — there is no BatchNorm in this model, so the two passes do not
 interact at all.
+
+``SGCN_GAT`` is the same model with PyG GATConv(in, hidden, edge_dim=1) layers (``gcn_img_snp.GATConv``): masks, head,
+regulariser and the stacked pair are shared (``_ImageOnly``), the graph stack is the LDS-resident GAT stack
+(ops.GatStack: one kernel per direction for both passes).  The masked pass's edge attribute ``edge_weight * edge_prob``
+is trained through it: igcn_gat_stack_bwd_ew returns d(loss)/d(edge attribute) — ``prob_bias`` gets its only task
+gradient there.  The constructor reads ``dataset.num_features`` / ``dataset.num_classes`` (:163,168) and sizes ``lin1``
+with the reference's literal 90 (:167).  Shapes outside the GAT stack raise ValueError; there is no second GAT path.
+GATConv parity rests on the restatement of PyG 2.0.2's GATConv in tests/golden/gat_standin.py (PyG itself is unpinned).
 """
 import math
 
@@ -20,18 +31,20 @@ import torch.nn.functional as F
 from torch.nn import Linear, Parameter, init
 
 from . import ops, switches
-from .sgcn_img_snp import GCNConv, masked_inputs, sgcn_stack
+from .gcn_img_snp import ROIS_REF, GATConv, gat_stack
+from .sgcn_img_snp import GCNConv, _grid_width, masked_inputs, sgcn_stack
 
 
-class SGCN_GCN(torch.nn.Module):
-    def __init__(self, dataset, num_layers, hidden, *args, hidden_linear=64, rois=90, H_0=3, num_features=3,
-                 num_classes=2, **kwargs):
-        super().__init__()
+class _ImageOnly(torch.nn.Module):
+    """What SGCN_GCN and SGCN_GAT share: the mask parameters, cal_probability / loss_probability, the head, and the
+    plain / masked / stacked-pair forward around the subclass's graph stack (``_stack``)."""
+
+    def _build(self, conv, num_features, num_classes, num_layers, hidden, hidden_linear, rois, H_0, lin1_rois):
         self.input = None
         self.rois, self.prob_dim = rois, H_0
-        self.conv1 = GCNConv(num_features, hidden)
-        self.convs = torch.nn.ModuleList(GCNConv(hidden, hidden) for _ in range(num_layers - 1))
-        self.lin1 = Linear(rois * num_layers * hidden, hidden_linear)
+        self.conv1 = conv(num_features, hidden)
+        self.convs = torch.nn.ModuleList(conv(hidden, hidden) for _ in range(num_layers - 1))
+        self.lin1 = Linear(lin1_rois * num_layers * hidden, hidden_linear)
         self.lin2 = Linear(hidden_linear, num_classes)
         self.prob = Parameter(torch.empty(rois, H_0))
         self.prob_bias = Parameter(torch.empty(H_0 * 2, 1))
@@ -39,6 +52,7 @@ class SGCN_GCN(torch.nn.Module):
         self._init_masks()
         self._dropout_enabled = True
         self.batched_passes = True
+        self.last_edge_prob = None
 
     def _init_masks(self):
         with torch.no_grad():
@@ -54,13 +68,13 @@ class SGCN_GCN(torch.nn.Module):
         self._init_masks()
 
     def cal_probability(self, x, edge_index, edge_weight, plan=None):
-        """:321-332 -> (x*prob, edge_weight*e, prob, e)."""
+        """:321-332 (SGCN_GAT: :198-209) -> (x*prob, edge_weight*e, prob, e)."""
         plan = plan if plan is not None else ops.GraphPlan(edge_index, x.shape[0])
         xm, ewm, e = ops.EdgeMask.apply(x, self.prob, self.prob_bias, edge_weight, plan, self.rois)
         return xm, ewm, self.prob, e
 
     def loss_probability(self, x, edge_index, edge_weight, hp, eps=1e-6, plan=None, edge_prob=None):
-        """:334-358 (no SNP term; node-mask L1 = sum|sigmoid(prob)| / rois)."""
+        """:334-358 (SGCN_GAT: :211-233) (no SNP term; node-mask L1 = sum|sigmoid(prob)| / rois)."""
         if edge_prob is None:
             _, _, _, edge_prob = self.cal_probability(x, edge_index, edge_weight, plan=plan)
         none = self.prob.new_empty(0)
@@ -68,7 +82,7 @@ class SGCN_GCN(torch.nn.Module):
                                          hp.lamda_e_l1, hp.lamda_e_ent, eps)
 
     def forward(self, data, isExplain=False):
-        """:360-388."""
+        """:360-388 (SGCN_GAT: :235-267)."""
         return self._forward_grouped(data, (bool(isExplain),))[0]
 
     def forward_pair(self, data):
@@ -76,6 +90,12 @@ class SGCN_GCN(torch.nn.Module):
         return self._forward_grouped(data, (False, True))
 
     def _forward_grouped(self, data, explain_flags):
+        # nothing of the last forward outlives this one: its edge mask holds that step's whole autograd graph.  Seen with
+        # SGCN_GAT: a step captured right after an eager one (train.EpochTrainer) crashed at the end of the capture, after
+        # torch's warning that an AccumulateGrad node of an earlier iteration, kept alive, sat on another stream; with the
+        # mask dropped here the same run passes.  SGCN_GCN runs this same code (tests/test_gpu_sgcn_gat.py runs both
+        # through fit_epoch)
+        self.last_edge_prob = None
         x = data.x
         x.requires_grad = True                                         # :362 — populates data.x.grad
         self.input = x
@@ -85,11 +105,11 @@ class SGCN_GCN(torch.nn.Module):
         bsz, g = n // self.rois, len(explain_flags)
         plan = ops.plan_for(data)
         plan.flush_pending_check()
+        self._check_stack(plan, x, explain_flags)
         # the train step's (plain | masked) pair: the mask launch writes both halves of the stacked batch itself
         stacked = tuple(explain_flags) == (False, True) and x.is_cuda
         x_in, ew_in, _, self.last_edge_prob = masked_inputs(self, data, plan, explain_flags, stacked)
-        xcat = sgcn_stack([self.conv1, *self.convs], x_in, ew_in, plan.replicate(g), self.rois,
-                          not switches.on("IGCN_NO_FUSED_SGCN"))
+        xcat = self._stack(x_in, ew_in, plan.replicate(g))
         z = xcat.view(g * bsz, -1)                                    # to_dense_batch == view (:378-381)
         f1 = ops.linear(z, self.lin1.weight, self.lin1.bias, relu=True)
         if self.training and self._dropout_enabled:
@@ -97,5 +117,37 @@ class SGCN_GCN(torch.nn.Module):
         logp = F.log_softmax(ops.linear(f1, self.lin2.weight, self.lin2.bias), dim=-1)
         return [logp[k * bsz:(k + 1) * bsz] for k in range(g)] if g > 1 else [logp]
 
+    def _check_stack(self, plan, x, explain_flags):
+        pass
+
     def __repr__(self):
         return self.__class__.__name__
+
+
+class SGCN_GCN(_ImageOnly):
+    def __init__(self, dataset, num_layers, hidden, *args, hidden_linear=64, rois=90, H_0=3, num_features=3,
+                 num_classes=2, **kwargs):
+        super().__init__()
+        self._build(GCNConv, num_features, num_classes, num_layers, hidden, hidden_linear, rois, H_0, rois)
+
+    def _stack(self, x_in, ew_in, plan_g):
+        return sgcn_stack([self.conv1, *self.convs], x_in, ew_in, plan_g, self.rois,
+                          not switches.on("IGCN_NO_FUSED_SGCN"))
+
+
+class SGCN_GAT(_ImageOnly):
+    def __init__(self, dataset, num_layers, hidden, *args, hidden_linear=64, rois=90, H_0=3, **kwargs):
+        super().__init__()
+        self._build(lambda i, o: GATConv(i, o, edge_dim=1), dataset.num_features, dataset.num_classes, num_layers,
+                    hidden, hidden_linear, rois, H_0, ROIS_REF)
+
+    def _check_stack(self, plan, x, explain_flags):
+        """Refuse, before any launch, what the GAT stack does not cover (the sentence of ops.gat_stack_limits)."""
+        why = ops.gat_stack_limits(plan, self.rois, x.shape[1], _grid_width(self.conv1.out_channels),
+                                   1 + len(self.convs),
+                                   ew_grad=torch.is_grad_enabled() and any(explain_flags))
+        if why is not None:
+            raise ValueError(f"GAT stack: {why}")
+
+    def _stack(self, x_in, ew_in, plan_g):
+        return gat_stack([self.conv1, *self.convs], x_in, ew_in, plan_g, self.rois)

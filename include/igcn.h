@@ -31,7 +31,7 @@ extern "C" {
 /* ABI revision: bumped whenever a prototype below changes (argument added, removed or re-ordered).  igcn_version()
  * returns the revision the library was built from; a binding written against a different one must refuse to call
  * (igcn_amd/_lib.py does). */
-#define IGCN_ABI_VERSION 425
+#define IGCN_ABI_VERSION 426
 int igcn_version(void);
 const char* igcn_last_error(void);
 /* A/B switches, set ONCE by the binding when it loads the library (from the IGCN_* environment variables): bit 0 no tiled
@@ -62,7 +62,7 @@ size_t igcn_graph_plan_workspace_bytes(int64_t n_nodes, int64_t n_edges);
  * softmax over them (max-subtracted, + 1e-16 in the denominator), y_i = relu(sum alpha h[src] + bias).
  * F in {4,8,16,32}, L <= 4, H0 <= 8 and igcn_gat_stack_lds_bytes(...) <= 150 KB (IGCN_ERR_UNSUPPORTED otherwise).
  * params: HOST array of 6 L device pointers, per layer W [F, Fin_l] (Fin_0 = H0, then F), bias [F], att_src [F],
- * att_dst [F], lin_edge [F], att_edge [F].  ew_in [E]: the scalar edge attributes (data, no gradient).
+ * att_dst [F], lin_edge [F], att_edge [F].  ew_in [E]: the scalar edge attributes (igcn_gat_stack_bwd: data, no gradient).
  * Backward recomputes the forward in LDS; outputs dx_in [N, H0] (or NULL: not computed) and dparams
  * [igcn_gat_stack_param_floats] = the six gradients of layer 0 in the order above, then layer 1, ... (scratch: n_graphs
  * * that many floats; the sum over graphs is a final reduction in the sense of igcn_reduce_defer). */
@@ -76,6 +76,18 @@ int igcn_gat_stack_bwd(int64_t n_graphs, int R, int max_edges, int H0, int F, in
                        const int32_t* tgt_perm, const int32_t* src_ptr, const int32_t* src_perm,
                        const float* const* params, const float* dxcat, float* dx_in, float* dparams, float* scratch,
                        int32_t* status, void* stream);
+/* The same backward when the edge attributes are trained: kernel/sgcn.py:235-267 (SGCN_GAT.forward) passes edge_attr =
+ * edge_weight * edge_prob to every GATConv of the masked pass, and kernel/train_eval_sgcn.py:305-308 backpropagates
+ * through it into prob_bias / prob.  One more output dew [sum E] = d(loss)/d(ew_in), every element written: for a stored
+ * edge k with src != dst and target i, sum_l c_l (dpre_l[k] + dpre_l[loop of i] / cnt_i) with c_l = lin_edge_l .
+ * att_edge_l, dpre the gradient of the pre-leaky-ReLU logits and cnt_i the number of such edges into i (the logit term
+ * and the 'mean' fill value of the added self-loop); exactly 0 for a stored self-loop (PyG removes it).  Same kernel
+ * template, one workgroup per graph, no atomics; LDS: igcn_gat_stack_lds_bytes(..., backward = 2). */
+int igcn_gat_stack_bwd_ew(int64_t n_graphs, int R, int max_edges, int H0, int F, int L, const float* x_in,
+                          const float* ew_in, const int32_t* src32, const int32_t* dst32, const int32_t* tgt_ptr,
+                          const int32_t* tgt_perm, const int32_t* src_ptr, const int32_t* src_perm,
+                          const float* const* params, const float* dxcat, float* dx_in, float* dew, float* dparams,
+                          float* scratch, int32_t* status, void* stream);
 int igcn_graph_plan_build(int64_t n_nodes, int64_t n_edges, const int64_t* edge_index /*[2,E]*/,
                           int32_t* src32, int32_t* dst32, int32_t* tgt_ptr, int32_t* tgt_perm,
                           int32_t* src_ptr, int32_t* src_perm, int32_t* loop_edge,
