@@ -14,7 +14,7 @@ from . import switches
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libigcn.so")
 
-ABI_VERSION = 426        # include/igcn.h IGCN_ABI_VERSION this table was written against (tests/test_abi.py compares)
+ABI_VERSION = 427        # include/igcn.h IGCN_ABI_VERSION this table was written against (tests/test_abi.py compares)
 
 P, I, L, F, Z = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
 
@@ -45,6 +45,10 @@ SIGNATURES = {
     "igcn_sgcn_stack_param_floats": (I, [I, I, I]),
     "igcn_sgcn_stack_fwd": (I, [L, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P]),
     "igcn_sgcn_stack_bwd": (I, [L, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "igcn_sgcn_ori_lds_bytes": (Z, [I, I, I, I, I, I]),
+    "igcn_sgcn_ori_param_floats": (I, [I, I, I]),
+    "igcn_sgcn_ori_fwd": (I, [L, I, I, I, I, I] + [P] * 15),
+    "igcn_sgcn_ori_bwd": (I, [L, I, I, I, I, I] + [P] * 22),
     "igcn_gat_stack_lds_bytes": (Z, [I, I, I, I, I, I]),
     "igcn_gat_stack_param_floats": (I, [I, I, I]),
     "igcn_gat_stack_fwd": (I, [L, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P]),

@@ -687,6 +687,82 @@ def _sgcn_stack_backward(x_in, ew_in, wb, plan, rois, final, dxcat, dxcat2):
     return dx, dew, grads
 
 
+def sgcn_ori_supported(plan, rois, h0, f1, f3):
+    """The LDS-resident SGCN_Ori stack (igcn_sgcn_ori_*) covers this batch: per-graph plan of uniform graphs, 1 <= h0 <= 8,
+    1 <= f1, f3 <= 32 (any width, not only the grid), and the graph fits LDS in both directions."""
+    seg = getattr(plan, "_stack_dims", None)
+    if seg is None or seg[0] != rois or not (1 <= h0 <= 8) or not (1 <= f1 <= 32) or not (1 <= f3 <= 32):
+        return False
+    lib = _lib.load()
+    return int(lib.igcn_sgcn_ori_lds_bytes(rois, seg[1], h0, f1, f3, 1)) <= 150 * 1024
+
+
+class TapGrads:
+    """Where ops.SgcnOriStack's backward leaves d(loss)/d(acts) [N, F3] (``grads``; None until a backward has run): the
+    gradient at SGCN_Ori's Grad-CAM tap, written by the backward kernel itself — no second launch, nothing that waits
+    for the device.  ``sink`` (a callable or None) is told, with this object, each time a backward fills it: a model
+    that ran several forwards learns which of them fired last, as the reference's hooks overwrite one attribute."""
+
+    def __init__(self, sink=None):
+        self.grads, self.sink = None, sink
+
+    def publish(self, grads):
+        self.grads = grads
+        if self.sink is not None:
+            self.sink(self)
+
+
+class SgcnOriStack(torch.autograd.Function):
+    """(z, acts) of kernel/sgcn.py:120-138 for a batch of small uniform graphs, one LDS-resident kernel per direction
+    (igcn_sgcn_ori_*): acts = conv3(relu(conv1(x))) before its ReLU [N, F3], z [B, rois*F1 + rois*F3] = the head's input
+    cat(z1, z2).  Both outputs take gradients; the backward also hands d(loss)/d(acts) to ``tap`` (a TapGrads, or None)."""
+
+    @staticmethod
+    def forward(ctx, x_in, ew_in, plan, rois, tap, w1, b1, w3, b3):
+        x_in, ew_in = _f32(x_in), _f32(ew_in)
+        wb = [_f32(t) for t in (w1, b1, w3, b3)]
+        n, h0 = x_in.shape
+        f1, f3 = wb[0].shape[0], wb[2].shape[0]
+        if wb[0].shape[1] != h0 or wb[2].shape[1] != f1:
+            raise ValueError(f"SgcnOriStack: W1 {tuple(wb[0].shape)} / W3 {tuple(wb[2].shape)} do not chain from H0={h0}")
+        g = n // rois
+        z = torch.empty(g, rois * (f1 + f3), dtype=torch.float32, device=x_in.device)
+        acts = torch.empty(n, f3, dtype=torch.float32, device=x_in.device)
+        call("igcn_sgcn_ori_fwd", g, rois, plan._stack_dims[1], h0, f1, f3, ptr(x_in), ptr(ew_in), ptr(plan.src32),
+             ptr(plan.dst32), ptr(plan.tgt_ptr), ptr(plan.tgt_perm), ptr(plan.loop_edge), *[ptr(t) for t in wb], ptr(z),
+             ptr(acts), ptr(plan.status), stream_ptr())
+        ctx.save_for_backward(x_in, ew_in, *wb)
+        ctx.plan, ctx.rois, ctx.tap = plan, rois, tap
+        ctx.final = _leaves(*wb)
+        ctx.set_materialize_grads(False)
+        return z, acts
+
+    @staticmethod
+    def backward(ctx, dz, dacts_in):
+        x_in, ew_in, *wb = ctx.saved_tensors
+        plan, rois = ctx.plan, ctx.rois
+        n, h0 = x_in.shape
+        f1, f3 = wb[0].shape[0], wb[2].shape[0]
+        g = n // rois
+        dz = _f32(dz) if dz is not None else torch.zeros(g, rois * (f1 + f3), dtype=torch.float32, device=x_in.device)
+        dacts_in = _f32(dacts_in) if dacts_in is not None else None
+        lib = _lib.load()
+        npar = int(lib.igcn_sgcn_ori_param_floats(h0, f1, f3))
+        dx, dew = torch.empty_like(x_in), torch.empty_like(ew_in)
+        dacts = torch.empty(n, f3, dtype=torch.float32, device=x_in.device) if ctx.tap is not None else None
+        dpar = torch.empty(npar, dtype=torch.float32, device=x_in.device)
+        scratch = _keep(torch.empty(g * npar, dtype=torch.float32, device=x_in.device))
+        with _immediate(ctx.final):
+            call("igcn_sgcn_ori_bwd", g, rois, plan._stack_dims[1], h0, f1, f3, ptr(x_in), ptr(ew_in), ptr(plan.src32),
+                 ptr(plan.dst32), ptr(plan.tgt_ptr), ptr(plan.tgt_perm), ptr(plan.src_ptr), ptr(plan.src_perm),
+                 ptr(plan.loop_edge), *[ptr(t) for t in wb], ptr(dz), ptr(dacts_in), ptr(dacts), ptr(dx), ptr(dew),
+                 ptr(dpar), ptr(scratch), ptr(plan.status), stream_ptr())
+        if ctx.tap is not None:
+            ctx.tap.publish(dacts)
+        o1, o2, o3 = f1 * h0, f1 * h0 + f1, f1 * h0 + f1 + f3 * f1
+        return (dx, dew, None, None, None, dpar[:o1].view(f1, h0), dpar[o1:o2], dpar[o2:o3].view(f3, f1), dpar[o3:])
+
+
 GAT_WIDTHS = (4, 8, 16, 32)
 GAT_MAX_LAYERS = 4
 GAT_MAX_H0 = 8

@@ -1,5 +1,5 @@
-"""Drop-ins for the image-only models of the reference's kernel/sgcn.py: ``SGCN_GCN`` (:272-388) and its attention twin
-``SGCN_GAT`` (:154-270).
+"""Drop-ins for the image-only models of the reference's kernel/sgcn.py: ``SGCN_GCN`` (:272-388), its attention twin
+``SGCN_GAT`` (:154-270) and the original ``SGCN_Ori`` (:11-151), the one model that fills the Grad-CAM surface.
 
 ``SGCN_GCN`` â€” the image-only sibling of the hot path on the same kernels: masks (igcn_edge_mask_*), one gcn_norm per
 pass, MFMA feature transforms, scatter-aggregate, the (R*D -> hidden_linear -> classes) head on the split-K GEMM, and
@@ -22,6 +22,15 @@ is trained through it: igcn_gat_stack_bwd_ew returns d(loss)/d(edge attribute) â
 gradient there.  The constructor reads ``dataset.num_features`` / ``dataset.num_classes`` (:163,168) and sizes ``lin1``
 with the reference's literal 90 (:167).  Shapes outside the GAT stack raise ValueError; there is no second GAT path.
 GATConv parity rests on the restatement of PyG 2.0.2's GATConv in tests/golden/gat_standin.py (PyG itself is unpinned).
+
+``SGCN_Ori(H_0, H_1, H_2, H_3)`` â€” conv1 (H_0 -> H_1), ReLU, conv3 (H_1 -> H_3) whose PRE-ReLU output is
+``final_conv_acts``, ReLU, and the head fc1 -> ReLU -> bn1 -> Dropout(0.5) -> fc2 -> ReLU -> bn2 -> Dropout(0.7) -> fc3
+(ReLU in front of BatchNorm, :143-147) on cat(z1, z2), two node-major blocks.  The graph stack is one LDS-resident
+kernel per direction (ops.SgcnOriStack: two independent widths, the tap and its gradient leave the kernels directly);
+``IGCN_NO_FUSED_SGCN=1``, or a batch that kernel does not cover, takes gcn_norm once + (transform, aggregate) per layer.
+``final_conv_grads`` is d(loss)/d(final_conv_acts) after a backward (the reference fills it through a hook, :71-72,125).
+``conv2`` exists for its state_dict keys only (:121 is commented out in the reference) and ``fc1`` takes
+``rois*H_3 + rois*H_2`` inputs (:20): a forward with H_1 != H_2 raises ValueError.
 """
 import math
 
@@ -151,3 +160,110 @@ class SGCN_GAT(_ImageOnly):
 
     def _stack(self, x_in, ew_in, plan_g):
         return gat_stack([self.conv1, *self.convs], x_in, ew_in, plan_g, self.rois)
+
+
+class SGCN_Ori(_ImageOnly):
+    def __init__(self, H_0, H_1, H_2, H_3, class_num=2, hidden_size=64, rois=90):
+        super().__init__()
+        self.input = None
+        self.final_conv_acts = None
+        self.final_conv_pair_acts = None
+        self._tap, self._fired = None, None
+        self.rois, self.prob_dim = rois, H_0
+        self.dim1, self.dim2, self.dim3 = rois * H_3 + rois * H_2, 64, 16              # :20-22
+        self.conv1 = GCNConv(H_0, H_1)
+        self.conv2 = GCNConv(H_1, H_2)                                   # unused by forward (:121), kept for its keys
+        self.conv3 = GCNConv(H_1, H_3)
+        self.fc1 = Linear(self.dim1, self.dim2)
+        self.bn1 = torch.nn.BatchNorm1d(self.dim2)
+        self.fc2 = Linear(self.dim2, self.dim3)
+        self.bn2 = torch.nn.BatchNorm1d(self.dim3)
+        self.fc3 = Linear(self.dim3, class_num)
+        self.prob = Parameter(torch.empty(rois, H_0))
+        self.prob_bias = Parameter(torch.empty(H_0 * 2, 1))
+        self.edge_prob = Parameter(torch.empty(rois, rois))               # unused by forward (as in the reference)
+        self._init_masks()
+        self._dropout_enabled = True
+        self.batched_passes = True
+        self.last_edge_prob = None
+
+    def reset_parameters(self):
+        for m in (self.conv1, self.conv2, self.conv3, self.fc1, self.fc2, self.fc3, self.bn1, self.bn2):
+            m.reset_parameters()
+        self._init_masks()
+
+    @property
+    def final_conv_grads(self):
+        """d(loss)/d(final_conv_acts) of the last backward (None before one).  After ``forward_pair`` it is the PLAIN
+        pass's, as the reference's two calls leave it: both hooks write the attribute and the plain pass's fires last."""
+        tap = self._fired
+        if tap is None or tap.grads is None:
+            return None
+        return tap.grads[:tap.grads.shape[0] // tap.passes]
+
+    def _tap_fired(self, tap):
+        self._fired = tap
+
+    @property
+    def final_conv_pair(self):
+        """((acts, grads) of pass 0, (acts, grads) of pass 1) of the last ``forward_pair`` â€” one entry after a single
+        pass; ``grads`` is None until a backward has run."""
+        if self.final_conv_pair_acts is None:
+            return None
+        g = None if self._tap is None else self._tap.grads
+        n = self.final_conv_pair_acts[0].shape[0]
+        return tuple((a, None if g is None else g[i * n:(i + 1) * n]) for i, a in enumerate(self.final_conv_pair_acts))
+
+    def _graph_stack(self, x_in, ew_in, plan_g, tap):
+        """(z [passes*B, rois*H_1 + rois*H_3], acts [passes*N, H_3]) of :120-138."""
+        w1, b1, w3, b3 = self.conv1.lin.weight, self.conv1.bias, self.conv3.lin.weight, self.conv3.bias
+        if (not switches.on("IGCN_NO_FUSED_SGCN") and x_in.is_cuda
+                and ops.sgcn_ori_supported(plan_g, self.rois, x_in.shape[1], w1.shape[0], w3.shape[0])):
+            return ops.SgcnOriStack.apply(x_in, ew_in, plan_g, self.rois, tap, w1, b1, w3, b3)
+        what, wloop, tstream, sstream = ops.GcnNorm.apply(ew_in, plan_g)          # once for both layers
+        h1 = ops.GcnPropagate.apply(ops.linear(x_in, w1), what, wloop, b1, plan_g, True, tstream, sstream)
+        acts = ops.GcnPropagate.apply(ops.linear(h1, w3), what, wloop, b3, plan_g, False, tstream, sstream)
+        if acts.requires_grad:
+            acts.register_hook(tap.publish)                                # stores a reference: nothing waits
+        g = x_in.shape[0] // self.rois
+        return torch.cat((h1.view(g, -1), torch.relu(acts).view(g, -1)), 1), acts
+
+    def _bn(self, x, bn, groups, p):
+        keep = None
+        if self.training and self._dropout_enabled:
+            keep = F.dropout(torch.ones_like(x), p, True)                  # the factors {0, 1/(1-p)}, applied by the kernel
+        return ops.BatchNorm1dGrouped.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, self.training,
+                                            bn.momentum, bn.eps, 0, groups, keep)
+
+    def _forward_grouped(self, data, explain_flags):
+        if self.conv2.out_channels != self.conv1.out_channels:
+            raise ValueError(f"SGCN_Ori: fc1 takes rois*H_3 + rois*H_2 inputs (kernel/sgcn.py:20) but the forward feeds it "
+                             f"rois*H_3 + rois*H_1: H_1={self.conv1.out_channels} != H_2={self.conv2.out_channels}")
+        # nothing of the last forward outlives this one (see _ImageOnly._forward_grouped): the tap is a node of that
+        # step's autograd graph, and a step captured right after an eager one must not find that graph alive.  What a
+        # backward has published (final_conv_grads) is a plain tensor and stays until the next backward replaces it.
+        self.last_edge_prob = None
+        self.final_conv_acts = self.final_conv_pair_acts = self._tap = None
+        x = data.x
+        x.requires_grad = True                                         # :113 â€” populates data.x.grad
+        self.input = x
+        n = x.shape[0]
+        if n % self.rois:
+            raise ValueError(f"every graph must have exactly rois={self.rois} nodes (got {n} nodes)")
+        bsz, g = n // self.rois, len(explain_flags)
+        plan = ops.plan_for(data)
+        plan.flush_pending_check()
+        stacked = tuple(explain_flags) == (False, True) and x.is_cuda
+        x_in, ew_in, _, self.last_edge_prob = masked_inputs(self, data, plan, explain_flags, stacked)
+        tap = ops.TapGrads(self._tap_fired)
+        tap.passes = g
+        z, acts = self._graph_stack(x_in, ew_in, plan.replicate(g), tap)
+        self._tap = tap
+        self.final_conv_pair_acts = tuple(acts[k * n:(k + 1) * n] for k in range(g))
+        self.final_conv_acts = self.final_conv_pair_acts[-1]           # the reference's last call (the masked pass) wins
+        h = self._bn(ops.linear(z, self.fc1.weight, self.fc1.bias, relu=True), self.bn1, g, 0.5)       # :143-144
+        h = self._bn(ops.linear(h, self.fc2.weight, self.fc2.bias, relu=True), self.bn2, g, 0.7)       # :145-146
+        if self.training:
+            torch._foreach_add_([bn.num_batches_tracked for bn in (self.bn1, self.bn2)], g)
+        logp = F.log_softmax(ops.linear(h, self.fc3.weight, self.fc3.bias), dim=-1)
+        return [logp[k * bsz:(k + 1) * bsz] for k in range(g)] if g > 1 else [logp]

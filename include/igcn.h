@@ -31,7 +31,7 @@ extern "C" {
 /* ABI revision: bumped whenever a prototype below changes (argument added, removed or re-ordered).  igcn_version()
  * returns the revision the library was built from; a binding written against a different one must refuse to call
  * (igcn_amd/_lib.py does). */
-#define IGCN_ABI_VERSION 426
+#define IGCN_ABI_VERSION 427
 int igcn_version(void);
 const char* igcn_last_error(void);
 /* A/B switches, set ONCE by the binding when it loads the library (from the IGCN_* environment variables): bit 0 no tiled
@@ -286,6 +286,33 @@ int igcn_sgcn_front_fwd(int64_t n_nodes, int64_t n_edges, int n_graphs, int R, i
                         float* ew_in, float* e, const float* snps_logits, int n_snps, float l1_x, float ent_x, float l1_e,
                         float ent_e, float eps, float* reg_partial, const float* snps_feat, float* snps_full,
                         const float* const* W /*HOST [L]*/, const float* const* b /*HOST [L]*/, float* xcat, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * SGCN_Ori's graph stack (kernel/sgcn.py:111-148: conv1, ReLU, conv3, the Grad-CAM tap, ReLU, final_z), LDS-resident
+ * like igcn_sgcn_stack_* and on the same per-graph plan, with two layers of INDEPENDENT width: per graph
+ *   h1 = relu(GCNConv1(x)) [R, F1],  acts = GCNConv3(h1) [R, F3] (no ReLU: final_conv_acts, :124),  h3 = relu(acts);
+ * gcn_norm runs once.  Row g of z [n_graphs, R*F1 + R*F3] = [h1 of graph g node-major | h3 of graph g node-major]: the
+ * reference's final_z (:128-138) written in place; acts [n_graphs*R, F3].  1 <= H0 <= 8, 1 <= F1, F3 <= 32 (any value:
+ * a width is rounded up to a multiple of 4 inside LDS only) and igcn_sgcn_ori_lds_bytes(...) <= 150 KB, otherwise
+ * IGCN_ERR_UNSUPPORTED.  W1 [F1, H0], b1 [F1], W3 [F3, F1], b3 [F3].  A graph with more than max_edges edges sets status
+ * bit 1 and leaves its outputs unwritten.
+ * Backward recomputes the forward in LDS: dx_in [N, H0], dew_in [E] (every element written), dparams
+ * [igcn_sgcn_ori_param_floats] = dW1 | db1 | dW3 | db3 (scratch: n_graphs * that many floats; the sum over graphs is a
+ * final reduction in the sense of igcn_reduce_defer), and dacts [n_graphs*R, F3] (or NULL) = d(loss)/d(acts): dz's h3
+ * block where acts > 0 and exactly 0 elsewhere — what the reference's hook stores as final_conv_grads (:71-72,125).
+ * dacts_in (or NULL): a gradient the caller holds on acts itself, added at the tap (and then part of dacts). */
+size_t igcn_sgcn_ori_lds_bytes(int R, int max_edges, int H0, int F1, int F3, int backward);
+int igcn_sgcn_ori_param_floats(int H0, int F1, int F3);
+int igcn_sgcn_ori_fwd(int64_t n_graphs, int R, int max_edges, int H0, int F1, int F3, const float* x_in,
+                      const float* ew_in, const int32_t* src32, const int32_t* dst32, const int32_t* tgt_ptr,
+                      const int32_t* tgt_perm, const int32_t* loop_edge, const float* W1, const float* b1,
+                      const float* W3, const float* b3, float* z, float* acts, int32_t* status, void* stream);
+int igcn_sgcn_ori_bwd(int64_t n_graphs, int R, int max_edges, int H0, int F1, int F3, const float* x_in,
+                      const float* ew_in, const int32_t* src32, const int32_t* dst32, const int32_t* tgt_ptr,
+                      const int32_t* tgt_perm, const int32_t* src_ptr, const int32_t* src_perm,
+                      const int32_t* loop_edge, const float* W1, const float* b1, const float* W3, const float* b3,
+                      const float* dz, const float* dacts_in, float* dacts, float* dx_in, float* dew_in,
+                      float* dparams, float* scratch, int32_t* status, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Backward of a bias-free projection y = x W^T (x [M, K], W [N, K]) in ONE pass over the gradient G = dL/dy [M, N]:
