@@ -14,7 +14,7 @@ from . import switches
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libigcn.so")
 
-ABI_VERSION = 427        # include/igcn.h IGCN_ABI_VERSION this table was written against (tests/test_abi.py compares)
+ABI_VERSION = 428        # include/igcn.h IGCN_ABI_VERSION this table was written against (tests/test_abi.py compares)
 
 P, I, L, F, Z = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
 
@@ -135,6 +135,8 @@ SIGNATURES = {
     "igcn_mask_reg_blocks": (I, [L]),
     "igcn_mask_reg_fwd": (I, [L, L, L, P, P, P, F, F, F, F, F, P, P, P]),
     "igcn_mask_reg_bwd": (I, [L, L, L, P, P, P, F, F, F, F, F, P, P, P, P, P]),
+    "igcn_mask_reg3_fwd": (I, [L, L, L, P, P, P, F, F, F, F, F, F, F, P, P, P]),
+    "igcn_mask_reg3_bwd": (I, [L, L, L, P, P, P, F, F, F, F, F, F, F, P, P, P, P, P]),
     "igcn_rbf_laplacian": (I, [I, I, F, P, P, P]),
     "igcn_gram_loss_fwd": (I, [I, I, I, P, P, P, P, P]),
     "igcn_gram_loss_bwd": (I, [I, I, P, P, P, P, P]),
@@ -202,6 +204,10 @@ SIGNATURES = {
     "igcn_head_loss_gram_fwd": (I, [I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, F, F, P, P, P, P, P, P, P, P, P,
                                     I, I, I, P, P, I, F, P, P, P, P, P]),
     "igcn_loss_final": (I, [P, I, P, I, P, I, P, P, P]),
+    "igcn_cluster_head_loss_supported": (I, [I, I, I]),
+    "igcn_cluster_head_loss_blocks": (I, [I, I]),
+    "igcn_cluster_head_loss_fwd": (I, [I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, F, F, F, I, P, P, P, P, P, P, P, P, P]),
+    "igcn_cluster_loss_final": (I, [P, I, P, I, P, P, P]),
     "igcn_reduce_flush": (I, [P]),
     "igcn_reduce_flush_tick": (I, [P, P]),
     "igcn_comm_unique_id_bytes": (I, []),

@@ -13,6 +13,7 @@ struct MaskRegArgs {
   const float *prob, *e, *snps;
   int64_t n_prob, n_edge, n_snps;
   float l1_x, ent_x, l1_e, ent_e, eps;
+  float l1_s, ent_s;                       // the snps group's own weights (igcn_mask_reg3_*; = l1_x, ent_x otherwise)
 };
 
 __device__ __forceinline__ float reg_term(float p, float l1, float ent, float eps) {
@@ -36,7 +37,7 @@ __global__ void __launch_bounds__(256) k_mask_reg_fwd(MaskRegArgs a, float* __re
       acc += reg_term(a.e[i - a.n_prob], a.l1_e, a.ent_e, a.eps) / (float)a.n_edge;
     } else {
       const float p = 1.f / (1.f + expf(-a.snps[i - a.n_prob - a.n_edge]));
-      acc += reg_term(p, a.l1_x, a.ent_x, a.eps) / (float)a.n_snps;
+      acc += reg_term(p, a.l1_s, a.ent_s, a.eps) / (float)a.n_snps;
     }
   }
   acc = block_sum_all(acc, red);
@@ -58,7 +59,7 @@ __global__ void k_mask_reg_bwd(MaskRegArgs a, const float* __restrict__ gout, fl
   } else {
     const int64_t k = i - a.n_prob - a.n_edge;
     const float p = 1.f / (1.f + expf(-a.snps[k]));
-    dsnps[k] = g * reg_grad(p, a.l1_x, a.ent_x, a.eps) * p * (1.f - p) / (float)a.n_snps;
+    dsnps[k] = g * reg_grad(p, a.l1_s, a.ent_s, a.eps) * p * (1.f - p) / (float)a.n_snps;
   }
 }
 
@@ -73,11 +74,18 @@ extern "C" int igcn_mask_reg_blocks(int64_t n_total) {
 
 // loss == NULL: the block partials stay in scratch and their consumer sums them (igcn_loss_head_fwd, prob_rows):
 // one launch less on the step's critical path.
-extern "C" int igcn_mask_reg_fwd(int64_t n_prob, int64_t n_edge, int64_t n_snps, const float* prob, const float* e,
-                                 const float* snps, float l1_x, float ent_x, float l1_e, float ent_e, float eps,
-                                 float* loss /*[1] or NULL*/, float* scratch /*[1024]*/, void* stream) {
+// igcn_mask_reg3_*: the snps group with weights l1_s, ent_s of its own — the cluster-label model's loss_probability
+// (kernel/sgcn_img_snp_clusterlabel.py:114-144) normalises prob's L1 term by its rows and snps_prob's by one row, i.e.
+// l1 = lamda_x_l1 H_0 and l1_s = lamda_x_l1 54 against the means taken here.  Same kernels, block count and scratch.
+extern "C" int igcn_mask_reg3_fwd(int64_t n_prob, int64_t n_edge, int64_t n_snps, const float* prob, const float* e,
+                                  const float* snps, float l1_x, float ent_x, float l1_e, float ent_e, float l1_s,
+                                  float ent_s, float eps, float* loss /*[1] or NULL*/, float* scratch /*[1024]*/,
+                                  void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  MaskRegArgs a{prob, e, snps, n_prob, n_edge, n_snps, l1_x, ent_x, l1_e, ent_e, eps};
+  IGCN_REQUIRE(n_prob >= 0 && n_edge >= 0 && n_snps >= 0 && scratch && (n_prob == 0 || prob) && (n_edge == 0 || e) &&
+                   (n_snps == 0 || snps),
+               "mask_reg_fwd: bad arguments");
+  MaskRegArgs a{prob, e, snps, n_prob, n_edge, n_snps, l1_x, ent_x, l1_e, ent_e, eps, l1_s, ent_s};
   const int blocks = igcn_mask_reg_blocks(n_prob + n_edge + n_snps);
   hipLaunchKernelGGL(k_mask_reg_fwd, dim3((unsigned)blocks), dim3(256), 0, st, a, scratch);
   IGCN_CHECK_LAUNCH("mask_reg_fwd");
@@ -85,12 +93,41 @@ extern "C" int igcn_mask_reg_fwd(int64_t n_prob, int64_t n_edge, int64_t n_snps,
   return igcn_launch_reduce_rows(scratch, blocks, 1, 1, loss, 0, st);
 }
 
+extern "C" int igcn_mask_reg_fwd(int64_t n_prob, int64_t n_edge, int64_t n_snps, const float* prob, const float* e,
+                                 const float* snps, float l1_x, float ent_x, float l1_e, float ent_e, float eps,
+                                 float* loss /*[1] or NULL*/, float* scratch /*[1024]*/, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  MaskRegArgs a{prob, e, snps, n_prob, n_edge, n_snps, l1_x, ent_x, l1_e, ent_e, eps, l1_x, ent_x};
+  const int blocks = igcn_mask_reg_blocks(n_prob + n_edge + n_snps);
+  hipLaunchKernelGGL(k_mask_reg_fwd, dim3((unsigned)blocks), dim3(256), 0, st, a, scratch);
+  IGCN_CHECK_LAUNCH("mask_reg_fwd");
+  if (loss == nullptr) return IGCN_OK;
+  return igcn_launch_reduce_rows(scratch, blocks, 1, 1, loss, 0, st);
+}
+
+extern "C" int igcn_mask_reg3_bwd(int64_t n_prob, int64_t n_edge, int64_t n_snps, const float* prob, const float* e,
+                                  const float* snps, float l1_x, float ent_x, float l1_e, float ent_e, float l1_s,
+                                  float ent_s, float eps, const float* gout /*[1] device*/, float* dprob, float* de,
+                                  float* dsnps, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  IGCN_REQUIRE(n_prob >= 0 && n_edge >= 0 && n_snps >= 0 && gout && (n_prob == 0 || (prob && dprob)) &&
+                   (n_edge == 0 || (e && de)) && (n_snps == 0 || (snps && dsnps)),
+               "mask_reg_bwd: bad arguments");
+  MaskRegArgs a{prob, e, snps, n_prob, n_edge, n_snps, l1_x, ent_x, l1_e, ent_e, eps, l1_s, ent_s};
+  const int64_t total = n_prob + n_edge + n_snps;
+  if (total == 0) return IGCN_OK;
+  hipLaunchKernelGGL(k_mask_reg_bwd, dim3((unsigned)igcn_cdiv(total, 256)), dim3(256), 0, st, a, gout, dprob, de,
+                     dsnps);
+  IGCN_CHECK_LAUNCH("mask_reg_bwd");
+  return IGCN_OK;
+}
+
 extern "C" int igcn_mask_reg_bwd(int64_t n_prob, int64_t n_edge, int64_t n_snps, const float* prob, const float* e,
                                  const float* snps, float l1_x, float ent_x, float l1_e, float ent_e, float eps,
                                  const float* gout /*[1] device*/, float* dprob, float* de, float* dsnps,
                                  void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  MaskRegArgs a{prob, e, snps, n_prob, n_edge, n_snps, l1_x, ent_x, l1_e, ent_e, eps};
+  MaskRegArgs a{prob, e, snps, n_prob, n_edge, n_snps, l1_x, ent_x, l1_e, ent_e, eps, l1_x, ent_x};
   const int64_t total = n_prob + n_edge + n_snps;
   if (total == 0) return IGCN_OK;
   hipLaunchKernelGGL(k_mask_reg_bwd, dim3((unsigned)igcn_cdiv(total, 256)), dim3(256), 0, st, a, gout, dprob, de,

@@ -2470,6 +2470,36 @@ class MaskRegulariser(torch.autograd.Function):
         return dprob, de, dsnps, None, None, None, None, None, None
 
 
+class MaskRegulariser3(torch.autograd.Function):
+    """MaskRegulariser with weights (l1_s, ent_s) of its own for the ``snps_prob`` group (igcn_mask_reg3_*): the
+    cluster-label model's loss_probability (kernel/sgcn_img_snp_clusterlabel.py:114-144) normalises the L1 terms of
+    ``prob`` and ``snps_prob`` differently.  Same launches, block count and ``partials`` mode as MaskRegulariser."""
+
+    @staticmethod
+    def forward(ctx, prob, e, snps_prob, l1_x, ent_x, l1_e, ent_e, l1_s, ent_s, eps, partials=False):
+        prob, e, snps_prob = _f32(prob), _f32(e), _f32(snps_prob)
+        dev = prob.device
+        scratch = torch.empty(1024, dtype=torch.float32, device=dev)
+        ctx.hp = (float(l1_x), float(ent_x), float(l1_e), float(ent_e), float(l1_s), float(ent_s), float(eps))
+        loss = None if partials else torch.empty(1, dtype=torch.float32, device=dev)
+        call("igcn_mask_reg3_fwd", prob.numel(), e.numel(), snps_prob.numel(), ptr(prob), ptr(e), ptr(snps_prob),
+             *ctx.hp, ptr(loss), ptr(scratch), stream_ptr())
+        ctx.save_for_backward(prob, e, snps_prob)
+        ctx.partials = partials
+        if partials:
+            return scratch[:int(_lib.load().igcn_mask_reg_blocks(prob.numel() + e.numel() + snps_prob.numel()))]
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, gout):
+        prob, e, snps_prob = ctx.saved_tensors
+        gout = _f32(gout[:1] if ctx.partials else gout).reshape(1)     # partials: the same scalar in every element
+        dprob, de, dsnps = torch.empty_like(prob), torch.empty_like(e), torch.empty_like(snps_prob)
+        call("igcn_mask_reg3_bwd", prob.numel(), e.numel(), snps_prob.numel(), ptr(prob), ptr(e), ptr(snps_prob),
+             *ctx.hp, ptr(gout), ptr(dprob), ptr(de), ptr(dsnps), stream_ptr())
+        return dprob, de, dsnps, None, None, None, None, None, None, None, None
+
+
 def rbf_laplacian(tsne, n, gamma, device):
     """Lap = diag(W1) - W with W = exp(-gamma*cdist(t,t)^2) (util/image_cluster.py:15-31); tsne None -> W = 1."""
     lap = torch.empty(n, n, dtype=torch.float32, device=device)
@@ -2833,6 +2863,116 @@ class HeadLoss(torch.autograd.Function):
         dw2r, db2r = dwb[o1:o1 + nr * k].view(nr, k), dwb[o1 + nr * k:]
         return (dx1, None, dw2, db2 if has_b2 else None, dx2, None, dw2r, db2r if has_b2r else None, None, None, dxhat, None,
                 dgram, dprob, None, None, None, None, None)
+
+
+_CLUSTER_WTS = {}
+
+
+def _cluster_loss_weights(hp_ce, hp_mi, lambda0, b, predict, dev):
+    """{hp_ce, hp_mi, lambda0, B, predict_cluster} as a cached DEVICE vector (igcn_cluster_loss_final reads its weights from
+    memory, as igcn_loss_final does); None inside a capture that has not seen them."""
+    key = (float(hp_ce), float(hp_mi), float(lambda0), int(b), bool(predict), str(dev))
+    t = _CLUSTER_WTS.get(key)
+    if t is None:
+        if torch.cuda.is_current_stream_capturing():
+            return None
+        t = _CLUSTER_WTS[key] = torch.tensor([key[0], key[1], key[2], float(b), 1.0 if predict else 0.0],
+                                             dtype=torch.float32, device=dev)
+    return t
+
+
+def cluster_head_loss_supported(f1, w1, f2, w2, keep1, keep2):
+    """The fused two-head + loss launch (igcn_cluster_head_loss_fwd) covers these layers, and a unit upstream gradient is
+    what the backward will bring (train._unit_grad has registered its scalar)."""
+    return (f1.is_cuda and f1.dim() == 2 and f1.shape == f2.shape and w1.shape[1] == w2.shape[1] == f1.shape[1]
+            and f1.shape[0] % 2 == 0 and f1.shape[0] > 0
+            and f1.dtype == torch.float32 and f1.is_contiguous() and f2.is_contiguous()
+            and (keep1 is None) == (keep2 is None) and torch.is_grad_enabled() and bool(UNIT_GRAD_PTRS)
+            and not switches.on("IGCN_NO_HEAD_LOSS_FUSED")
+            and bool(_lib.load().igcn_cluster_head_loss_supported(f1.shape[1], w1.shape[0], w2.shape[0])))
+
+
+class ClusterHeadLoss(torch.autograd.Function):
+    """lin2_classify | lin2_cluster -> both log_softmaxes -> the four cross-entropy terms and the reconstruction term of
+    the cluster-label trainer (kernel/train_eval_sgcn_clusterlabel.py:376-393) AND their backward for an upstream gradient
+    of one, in ONE multi-workgroup launch (igcn_cluster_head_loss_fwd) — the sibling of HeadLoss.
+    Returns (loss, terms [6] = {ce, ce_cluster, mi, mi_cluster, prob, recon}, log_softmax classify [2B, C1], log_softmax
+    cluster [2B, C2]); the last three are not differentiable.  ``lazy``: as HeadLoss — the loss value's last step
+    (igcn_cluster_loss_final) is issued by the backward and joins the deferred flush."""
+
+    @staticmethod
+    def forward(ctx, f1, keep1, w1, b1, f2, keep2, w2, b2, y, clust_y, x_hat, snps, prob, hp_ce, hp_mi, lambda0,
+                predict_cluster=True, lazy=False):
+        f = lambda t: _f32(t) if t is not None else None               # noqa: E731
+        f1, keep1, w1, b1, f2, keep2, w2, b2, x_hat, snps, prob = (
+            f(t) for t in (f1, keep1, w1, b1, f2, keep2, w2, b2, x_hat, snps, prob))
+        y, clust_y = y.contiguous(), clust_y.contiguous()
+        rows, k = f1.shape
+        b, c1, c2, s = rows // 2, w1.shape[0], w2.shape[0], snps.shape[1]
+        if y.dtype != torch.int64 or clust_y.dtype != torch.int64 or y.numel() != b or clust_y.numel() != b \
+                or rows != 2 * b or f2.shape != f1.shape or x_hat.shape != (2 * b, s) or prob.numel() == 0 \
+                or snps.shape[0] != b or w1.shape[1] != k or w2.shape[1] != k:
+            raise _lib.IgcnError("cluster head loss: inconsistent shapes")
+        dev = f1.device
+        lib = _lib.load()
+        if not lib.igcn_cluster_head_loss_supported(k, c1, c2):
+            raise _lib.IgcnError(f"cluster head loss: K/4 a power of two <= 64 and C1, C2 <= 4 (K={k} C1={c1} C2={c2})")
+        wts = _cluster_loss_weights(hp_ce, hp_mi, lambda0, b, predict_cluster, dev)
+        if wts is None:
+            raise _lib.IgcnError("cluster head loss: the loss weights must be uploaded outside a capture "
+                                 "(ops._cluster_loss_weights)")
+        f32 = dict(dtype=torch.float32, device=dev)
+        nblk = int(lib.igcn_cluster_head_loss_blocks(b, k))
+        out8 = torch.empty(8, **f32)
+        logp1, logp2 = torch.empty(2 * b, c1, **f32), torch.empty(2 * b, c2, **f32)
+        dx1, dx2, dxhat = torch.empty_like(f1), torch.empty_like(f2), torch.empty_like(x_hat)
+        parts = torch.empty(nblk, 5, **f32)
+        wcols = c1 * k + c1 + c2 * k + c2
+        wpart = torch.empty(nblk, wcols, **f32)
+        dprob = torch.empty(1, **f32)
+        call("igcn_cluster_head_loss_fwd", b, k, c1, c2, s, ptr(f1), ptr(keep1), ptr(w1), ptr(b1), ptr(f2), ptr(keep2),
+             ptr(w2), ptr(b2), ptr(y), ptr(clust_y), ptr(x_hat), ptr(snps), float(hp_ce), float(hp_mi), float(lambda0),
+             1 if predict_cluster else 0, ptr(logp1), ptr(logp2), ptr(dx1), ptr(dx2), ptr(dxhat), ptr(parts), ptr(wpart),
+             ptr(dprob), stream_ptr())
+        ctx.final = (parts, prob, wts, out8) if lazy else None
+        if not lazy:
+            call("igcn_cluster_loss_final", ptr(parts), nblk, ptr(prob), prob.numel(), ptr(wts), ptr(out8), stream_ptr())
+        ctx.unit = (dx1, dx2, dxhat, dprob, wpart)
+        ctx.cfg = (b, k, c1, c2, nblk, b1 is not None, b2 is not None)
+        ctx.prob_shape = tuple(prob.shape)
+        ctx.w_final = (_leaves(w1, b1), _leaves(w2, b2))
+        loss, terms = out8[0], out8[1:7]
+        ctx.mark_non_differentiable(terms, logp1, logp2)
+        ctx.set_materialize_grads(False)
+        return loss, terms, logp1, logp2
+
+    @staticmethod
+    def backward(ctx, gout, _gt=None, _g1=None, _g2=None):
+        b, k, c1, c2, nblk, has_b1, has_b2 = ctx.cfg
+        dx1, dx2, dxhat, dprob, wpart = ctx.unit
+        if ctx.final is not None:                    # the loss value: now, i.e. into the flush when the stream defers
+            parts, prob, wts, out8 = ctx.final
+            call("igcn_cluster_loss_final", ptr(parts), nblk, ptr(prob), prob.numel(), ptr(wts), ptr(out8), stream_ptr())
+            _keep(parts)
+        wcols = c1 * k + c1 + c2 * k + c2
+        dwb = _keep(torch.empty(wcols, dtype=torch.float32, device=dx1.device))       # (kept until the flush: HeadLoss)
+        _keep(wpart)
+        o1, o2 = c1 * k + c1, c2 * k + c2
+        gout = _f32(gout).reshape(1)
+        unit = gout.data_ptr() in UNIT_GRAD_PTRS
+        # (another upstream gradient scales the sums below: they are then needed here, not at the flush)
+        with _immediate(ctx.w_final[0] and unit):
+            call("igcn_reduce_rows_final", ptr(wpart), nblk, wcols, o1, ptr(dwb), stream_ptr())
+        with _immediate(ctx.w_final[1] and unit):
+            call("igcn_reduce_rows_final", wpart.data_ptr() + 4 * o1, nblk, wcols, o2, ptr(dwb[o1:]), stream_ptr())
+        if not unit:                                 # every gradient is linear in the upstream one
+            dx1, dx2, dxhat, dprob, dwb = (t * gout for t in (dx1, dx2, dxhat, dprob, dwb))
+        ps = ctx.prob_shape
+        dprob = dprob.view(()) if ps == () else dprob.expand(ps)
+        dw1, db1 = dwb[:c1 * k].view(c1, k), dwb[c1 * k:o1]
+        dw2, db2 = dwb[o1:o1 + c2 * k].view(c2, k), dwb[o1 + c2 * k:]
+        return (dx1, None, dw1, db1 if has_b1 else None, dx2, None, dw2, db2 if has_b2 else None, None, None, dxhat, None,
+                dprob, None, None, None, None, None)
 
 
 # =================================================================================================

@@ -354,8 +354,13 @@ class SGCN_GCN_IMGSNP(torch.nn.Module):
         if not (self.training and self._dropout_enabled) or not data.x.is_cuda:
             return
         gb = groups * (data.x.shape[0] // self.rois)
+        self.go_network.predraw_dropout(gb, data.x.device, self._head_dropout(gb), groups)
+
+    def _head_dropout(self, rows):
+        """[(shape, p), ...]: the two heads' dropout sites (:300, :303) for a sweep of ``rows`` samples, drawn by the GO
+        network's mask launch (``extra_dropout``)."""
         hl = self.lin1.weight.shape[0]
-        self.go_network.predraw_dropout(gb, data.x.device, [((gb, hl), 0.5), ((gb, hl), 0.3)], groups)
+        return [((rows, hl), 0.5), ((rows, hl), 0.3)]
 
     def _forward_grouped(self, data, temperature, device, explain_flags, split=True, raw_scores=False, on_out_z=None,
                          heads_to_loss=False):
@@ -384,8 +389,7 @@ class SGCN_GCN_IMGSNP(torch.nn.Module):
             img_out = ops.GraphPool.apply(img.xcat, self.rois)
         else:
             img_out = (img.xcat if img.xcat_img is None else img.xcat_img).view(g * bsz, -1)
-        hl = self.lin1.weight.shape[0]
-        head_drop = [((g * bsz, hl), 0.5), ((g * bsz, hl), 0.3)] if (self.training and self._dropout_enabled) else []
+        head_drop = self._head_dropout(g * bsz) if (self.training and self._dropout_enabled) else []
         latent, x_hat, _, atten_out = self.go_network(img.snps_in, temperature, device, groups=g, extra_dropout=head_drop)
         out_z, out_lin, feat = self._fusion(data, img, img_out, batch_x, latent, atten_out, bsz, g)
         if on_out_z is not None:

@@ -369,10 +369,70 @@ def losses_guide(model, data, lambda_loss=None, hp=HP, temperature=None):
     return loss, t, o
 
 
+CLUSTER_LAMBDA0 = 1e-5                            # kernel/train_eval_sgcn_clusterlabel.py:188
+CLUSTER_TERMS = ("ce", "ce_cluster", "mi", "mi_cluster", "prob", "recon")
+
+
+def _cluster_lambda0(lambda_loss):
+    """``lambda0`` of the cluster-label trainer from what a caller of ``losses`` / ``train_step`` passed as ``lambda_loss``:
+    a number, or None / the library's DEFAULT_LAMBDA (the caller passed none) for the trainer's own default."""
+    return CLUSTER_LAMBDA0 if lambda_loss is None or lambda_loss is DEFAULT_LAMBDA else float(lambda_loss)
+
+
+def losses_clusterlabel(model, data, lambda0=CLUSTER_LAMBDA0, hp=HP, temperature=None, lazy_value=False):
+    """Loss of SGCN_GCN_CLUSTERLABEL: train() kernel/train_eval_sgcn_clusterlabel.py:375-393 — the plain and the masked
+    pass, two classification heads each, six terms (``ce``, ``ce_cluster``, ``mi``, ``mi_cluster``, ``prob``, ``recon``):
+    ``hp.lamda_ce (ce + ce_cluster)/2 + hp.lamda_mi (mi + mi_cluster)/2 + prob + recon``, or ``hp.lamda_ce ce +
+    hp.lamda_mi mi + prob + recon`` when the model does not predict the cluster.  The per-cluster ``consist_loss`` of
+    :386-388 is weighted by ``lambda1 = 0`` (:191) and never added to the loss (:391,393): it is not computed (its
+    boolean-mask indexing could not be captured either).  Inside a train step on the GPU the output layers, the
+    log-softmaxes, five of the terms and their backward are one launch (ops.ClusterHeadLoss; ``lazy_value`` as in
+    ``losses``); otherwise (eval, IGCN_NO_HEAD_LOSS_FUSED=1, refused shapes) the same terms through torch.
+    Returns (loss, terms dict, outputs = (log_softmax classify, log_softmax cluster, x_hat, out_z), stacked pass-major
+    for the batched sweep, one tuple per pass otherwise)."""
+    from . import ops
+    lam0 = _cluster_lambda0(lambda0)
+    dev = data.x.device
+    y, cy = data.y.view(-1), data.clust_y.view(-1)
+    predict = bool(model.isPredictCluster)
+    if getattr(model, "batched_passes", True):
+        b = int(data.num_graphs)
+        # (the fused launch reads its weights from a cached device vector: uploaded outside captures only)
+        heads = (data.x.is_cuda and torch.is_grad_enabled()
+                 and ops._cluster_loss_weights(hp.lamda_ce, hp.lamda_mi, lam0, b, predict, dev) is not None)
+        o = model._forward_grouped(data, temperature, dev, (False, True), split=False, heads_to_loss=heads)
+        if isinstance(o[0], tuple):
+            (_, f1, keep1, f2, keep2), _, x_hat, out_z = o
+            prob = model.loss_probability(data.x, data.edge_index, data.edge_attr, hp, edge_prob=model.last_edge_prob,
+                                          partials=True)
+            loss, terms, logp, logp_c = ops.ClusterHeadLoss.apply(
+                f1, keep1, model.lin2_classify.weight, model.lin2_classify.bias, f2, keep2, model.lin2_cluster.weight,
+                model.lin2_cluster.bias, y, cy, x_hat, data.snps_feat, prob, hp.lamda_ce, hp.lamda_mi, lam0, predict,
+                bool(lazy_value))
+            return loss, dict(zip(CLUSTER_TERMS, terms.unbind(0))), (logp, logp_c, x_hat, out_z)
+        outs = o
+        (out, out_p), (out_c, out_c_p), (xh, xh_p) = ((t[:b], t[b:]) for t in o[:3])
+    else:
+        o1 = model(data, temperature, dev)
+        o2 = model(data, temperature, dev, isExplain=True)
+        outs = (o1, o2)
+        (out, out_c, xh, _), (out_p, out_c_p, xh_p, _) = o1, o2
+    t = {"ce": F.nll_loss(out, y), "ce_cluster": F.nll_loss(out_c, cy),
+         "mi": F.nll_loss(out_p, y), "mi_cluster": F.nll_loss(out_c_p, cy),
+         "prob": model.loss_probability(data.x, data.edge_index, data.edge_attr, hp, edge_prob=model.last_edge_prob),
+         "recon": lam0 * (torch.sum((xh - data.snps_feat) ** 2) + torch.sum((xh_p - data.snps_feat) ** 2)) / 2}
+    if predict:
+        loss = hp.lamda_ce * (t["ce"] + t["ce_cluster"]) / 2 + hp.lamda_mi * (t["mi"] + t["mi_cluster"]) / 2
+    else:
+        loss = hp.lamda_ce * t["ce"] + hp.lamda_mi * t["mi"]
+    return loss + t["prob"] + t["recon"], t, outs
+
+
 def _batched(model):
-    """The model takes both passes of a train step in one batched sweep (``_losses_batched``)."""
+    """The model takes both passes of a train step in one batched sweep (``_losses_batched`` / ``losses_clusterlabel``)."""
     return (hasattr(model, "go_network") and getattr(model, "batched_passes", True)
-            and hasattr(model, "_forward_grouped") and model.isSoftSimilarity)
+            and hasattr(model, "_forward_grouped")
+            and bool(model.isSoftSimilarity or getattr(model, "clusterlabel", False)))
 
 
 def losses(model, data, lambda_loss=DEFAULT_LAMBDA, hp=HP, temperature=None, lazy_value=False):
@@ -391,6 +451,8 @@ def losses(model, data, lambda_loss=DEFAULT_LAMBDA, hp=HP, temperature=None, laz
         return losses_guide(model, data, lambda_loss, hp, temperature)
     if getattr(model, "single_pass", False):        # GCN_IMGSNP: kernel/train_eval_gcn_img_snps.py's loss
         return losses_gcn_img_snp(model, data, lambda_loss, hp, temperature)
+    if getattr(model, "clusterlabel", False):       # SGCN_GCN_CLUSTERLABEL: kernel/train_eval_sgcn_clusterlabel.py's loss
+        return losses_clusterlabel(model, data, lambda_loss, hp, temperature, lazy_value)
     if hasattr(model, "_reg_hp"):                    # the dense-block SGCN path reduces loss_probability in its forward
         model._reg_hp = (float(hp.lamda_x_l1), float(hp.lamda_x_ent), float(hp.lamda_e_l1), float(hp.lamda_e_ent), 1e-6)
     if getattr(model, "batched_passes", True) and hasattr(model, "_forward_grouped") and model.isSoftSimilarity:
@@ -606,7 +668,7 @@ def _single_use_parameters(model):
     if switches.on("IGCN_NO_DEFER") or not getattr(model, "batched_passes", True):
         return False
     if hasattr(model, "go_network"):
-        return hasattr(model, "_forward_grouped") and bool(model.isSoftSimilarity)
+        return hasattr(model, "_forward_grouped") and bool(model.isSoftSimilarity or getattr(model, "clusterlabel", False))
     return hasattr(model, "forward_pair")
 
 
@@ -640,7 +702,7 @@ def _two_buckets_possible(model, optimizer):
     """The two-bucket exchange needs the table-mode optimiser, the batched sweep with deferred reductions and a model whose
     heads can be cut off (SGCN_GCN_IMGSNP)."""
     return (hasattr(model, "head_parameters") and not getattr(optimizer, "flat_grads", True)
-            and _single_use_parameters(model))
+            and not getattr(model, "clusterlabel", False) and _single_use_parameters(model))
 
 
 class _TwoBucketExchange:
@@ -1197,7 +1259,10 @@ def fit_epoch(model, optimizer, loader, temperature=None, lambda_loss=DEFAULT_LA
     import weakref
     hp_key = tuple(float(getattr(hp, k)) for k in ("lamda_x_l1", "lamda_e_l1", "lamda_x_ent", "lamda_e_ent", "lamda_mi",
                                                     "lamda_ce"))
-    key = (id(model), tuple(float(v) for v in lambda_loss), hp_key, world_size, id(comm))
+    if getattr(model, "clusterlabel", False):       # (the cluster trainer's ``lambda0``: one number)
+        key = (id(model), _cluster_lambda0(lambda_loss), hp_key, world_size, id(comm))
+    else:
+        key = (id(model), tuple(float(v) for v in lambda_loss), hp_key, world_size, id(comm))
     if getattr(model, "guide", False):
         # a device temperature is read at replay time (its address is the key); a number is a launch argument; the
         # library's default lambda stands for GUIDE's own default (losses_guide)
@@ -1236,15 +1301,23 @@ def eval_loss(model, loader, lambda_loss=DEFAULT_LAMBDA, hp=HP, temperature=None
 
 @torch.no_grad()
 def eval_acc(model, loader, temperature=None, device=None):
-    """eval_acc() kernel/train_eval_sgcn_img_snps.py:551-561 / kernel/train_eval_sgcn.py:316-325."""
+    """eval_acc() kernel/train_eval_sgcn_img_snps.py:551-561 / kernel/train_eval_sgcn.py:316-325; for
+    SGCN_GCN_CLUSTERLABEL the pair (accuracy of the diagnosis head, accuracy of the cluster-label head) of
+    kernel/train_eval_sgcn_clusterlabel.py:434-447."""
     model.eval()
-    correct, count = None, 0
+    pair = getattr(model, "clusterlabel", False)
+    correct, correct_c, count = None, None, 0
     for data in _batches(loader, device):
         out = model(data, temperature, data.x.device) if hasattr(model, "go_network") else model(data)
         logp = out[0] if isinstance(out, tuple) else out
         hit = logp.max(1)[1].eq(data.y.view(-1)).sum()
         correct = hit if correct is None else correct + hit
+        if pair:
+            hit_c = out[1].max(1)[1].eq(data.clust_y.view(-1)).sum()
+            correct_c = hit_c if correct_c is None else correct_c + hit_c
         count += data.num_graphs
+    if pair:
+        return int(correct) / count, int(correct_c) / count
     return int(correct) / count
 
 
@@ -1256,7 +1329,13 @@ def eval_outputs(model, loader, temperature=None, device=None):
     model.eval()
     cols = {"logp": [], "pred": [], "reg": [], "out_lin": [], "linear_outf": []}
     for data in _batches(loader, device):
-        if hasattr(model, "go_network"):
+        if getattr(model, "clusterlabel", False):
+            # SGCN_GCN_CLUSTERLABEL's 4-tuple (kernel/train_eval_sgcn_clusterlabel.py:449-470 collects both heads)
+            logp, logp_c, _, out_z = model(data, temperature, data.x.device)
+            cols.setdefault("logp_cluster", []).append(logp_c)
+            cols.setdefault("pred_cluster", []).append(logp_c.max(1)[1])
+            cols["out_lin"].append(out_z)
+        elif hasattr(model, "go_network"):
             o = model(data, temperature, data.x.device)     # (the reference's 6-tuple, or GUIDE_IMGSNP's 8-tuple)
             logp, out_lin, lin_f, reg = o[0], o[3], o[4], o[5]
             cols["reg"].append(reg.reshape(-1, model.num_regr))
@@ -1324,6 +1403,9 @@ class Evaluator:
             raise ValueError("Evaluator: SGCN_GCN_IMGSNP models only (GCN_IMGSNP: use eval_loss / eval_acc)")
         if getattr(model, "guide", False):
             raise ValueError("Evaluator: SGCN_GCN_IMGSNP models only (GUIDE_IMGSNP: use eval_loss / eval_acc / "
+                             "eval_outputs)")
+        if getattr(model, "clusterlabel", False):
+            raise ValueError("Evaluator: SGCN_GCN_IMGSNP models only (SGCN_GCN_CLUSTERLABEL: use eval_loss / eval_acc / "
                              "eval_outputs)")
         self._model = weakref.ref(model)             # (kept by ``evaluate`` in a table keyed weakly on the model)
         self.lam, self.hp, self.temperature = tuple(float(v) for v in lambda_loss), hp, temperature
@@ -1463,6 +1545,9 @@ def evaluate(model, loader, lambda_loss=DEFAULT_LAMBDA, hp=HP, temperature=None,
     true-major), ``n`` (rows), and the per-row device tensors ``logp``, ``pred``, ``y``, ``reg``, ``clini_score``,
     ``out_lin``, ``linear_outf``, ``sbjID``.  Rank-local: under data parallelism the caller shards and gathers.
     ``temperature`` is passed to the forward, which does not read it (as in the reference)."""
+    if getattr(model, "clusterlabel", False):       # (before the heads are looked at: this model has other ones)
+        raise ValueError("evaluate: SGCN_GCN_IMGSNP models only (SGCN_GCN_CLUSTERLABEL: use eval_loss / eval_acc / "
+                         "eval_outputs)")
     if num_classes is not None and int(num_classes) != model.lin2.weight.shape[0]:
         raise ValueError(f"evaluate: num_classes={num_classes}, the model has {model.lin2.weight.shape[0]} classes")
     if num_regr is not None and int(num_regr) != model.lin2_regr.weight.shape[0]:

@@ -31,7 +31,7 @@ extern "C" {
 /* ABI revision: bumped whenever a prototype below changes (argument added, removed or re-ordered).  igcn_version()
  * returns the revision the library was built from; a binding written against a different one must refuse to call
  * (igcn_amd/_lib.py does). */
-#define IGCN_ABI_VERSION 427
+#define IGCN_ABI_VERSION 428
 int igcn_version(void);
 const char* igcn_last_error(void);
 /* A/B switches, set ONCE by the binding when it loads the library (from the IGCN_* environment variables): bit 0 no tiled
@@ -719,6 +719,16 @@ int igcn_mask_reg_fwd(int64_t n_prob, int64_t n_edge, int64_t n_snps, const floa
 int igcn_mask_reg_bwd(int64_t n_prob, int64_t n_edge, int64_t n_snps, const float* prob, const float* e,
                       const float* snps, float l1_x, float ent_x, float l1_e, float ent_e, float eps,
                       const float* gout, float* dprob, float* de, float* dsnps, void* stream);
+/* The same with weights l1_s, ent_s of its own for the snps group (the cluster-label model's loss_probability,
+ * kernel/sgcn_img_snp_clusterlabel.py:114-144, whose L1 terms of prob and snps_prob are normalised differently: l1_x =
+ * lamda_x_l1 H_0, l1_s = lamda_x_l1 54 against the means taken here).  Same loss == NULL mode, block count and scratch;
+ * with l1_s = l1_x, ent_s = ent_x the same bits as igcn_mask_reg_{fwd,bwd}. */
+int igcn_mask_reg3_fwd(int64_t n_prob, int64_t n_edge, int64_t n_snps, const float* prob, const float* e,
+                       const float* snps, float l1_x, float ent_x, float l1_e, float ent_e, float l1_s, float ent_s,
+                       float eps, float* loss, float* scratch, void* stream);
+int igcn_mask_reg3_bwd(int64_t n_prob, int64_t n_edge, int64_t n_snps, const float* prob, const float* e,
+                       const float* snps, float l1_x, float ent_x, float l1_e, float ent_e, float l1_s, float ent_s,
+                       float eps, const float* gout, float* dprob, float* de, float* dsnps, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Batch-level losses from ONE Gram matrix G = s s^T [B,B] of the fused features s [B, R*D]:
@@ -1043,6 +1053,31 @@ int igcn_head_loss_gram_fwd(int B, int K, int C, int NR, int S, const float* x1,
                             void* stream);
 int igcn_loss_final(const float* parts, int nparts, const float* gram, int gram_rows, const float* prob, int prob_rows,
                     const float* wts, float* out, void* stream);
+/* THE TWO CLASSIFICATION HEADS AND THE LOSS OF THE CLUSTER-LABEL TRAINER AS ONE LAUNCH (kernel/sgcn_img_snp_clusterlabel.py
+ * :217-228 lin2_classify / lin2_cluster / both log_softmaxes on the stacked sweep; train() of
+ * kernel/train_eval_sgcn_clusterlabel.py:376-393) with their BACKWARD for an upstream gradient of one — the sibling of
+ * igcn_head_loss_fwd.  x1 / x2 [2B, K] = the heads' hidden features, pass-major (keep1 / keep2 [2B, K]: dropout factors, or
+ * NULL), W1 [C1, K] + b1 = lin2_classify, W2 [C2, K] + b2 = lin2_cluster, y / clust_y [B] int64, x_hat [2B, S], snps [B, S];
+ * K / 4 a power of two <= 64, C1, C2 <= 4 (igcn_cluster_head_loss_supported).
+ *   loss = hp_ce (ce + ce_cluster)/2 + hp_mi (mi + mi_cluster)/2 + prob + lambda0 (sse_plain + sse_masked)/2
+ *   predict_cluster == 0:  loss = hp_ce ce + hp_mi mi + prob + recon; logp2 is still written, dx2 and the W2 | b2 part of
+ *   wpart are exact zeros.
+ * Outputs: logp1 [2B, C1], logp2 [2B, C2]; dx1 / dx2 [2B, K], dxhat [2B, S]; parts [blocks, 5] = partial sums of (ce,
+ * ce_cluster, mi, mi_cluster, sse); wpart [blocks, C1 K + C1 + C2 K + C2] = per-workgroup partial rows of (dW1 | db1 | dW2 |
+ * db2) for igcn_reduce_rows_final; dprob [1]  (blocks = igcn_cluster_head_loss_blocks(B, K)).  No atomics, fixed-order sums.
+ * A label outside its classes poisons its term with NaN (as igcn_head_loss_fwd).
+ * igcn_cluster_loss_final: the loss VALUE from parts [nparts, 5] and the regulariser (prob [prob_rows], possibly the
+ * un-reduced partials of igcn_mask_reg3_fwd); wts [5] DEVICE floats = {hp_ce, hp_mi, lambda0, B, predict_cluster}; out [8] =
+ * loss, ce, ce_cluster, mi, mi_cluster, prob, recon, 0.  Joins the deferred flush exactly as igcn_loss_final does. */
+int igcn_cluster_head_loss_supported(int K, int C1, int C2);
+int igcn_cluster_head_loss_blocks(int B, int K);
+int igcn_cluster_head_loss_fwd(int B, int K, int C1, int C2, int S, const float* x1, const float* keep1, const float* W1,
+                               const float* b1, const float* x2, const float* keep2, const float* W2, const float* b2,
+                               const int64_t* y, const int64_t* clust_y, const float* x_hat, const float* snps, float hp_ce,
+                               float hp_mi, float lambda0, int predict_cluster, float* logp1, float* logp2, float* dx1,
+                               float* dx2, float* dxhat, float* parts, float* wpart, float* dprob, void* stream);
+int igcn_cluster_loss_final(const float* parts, int nparts, const float* prob, int prob_rows, const float* wts, float* out,
+                            void* stream);
 /* igcn_loss_head_fwd that also writes the gradients igcn_loss_head_bwd would return for gout = 1 (each element's gradient
  * is known where its forward term is computed): a train step, whose d loss / d loss is one, then has no backward launch
  * for the loss head.  dlogp [2B,C] (of the raw scores when from_logits), dreg [2B,NR], dxhat [2B,S], dgram [4], dprob [1]. */
