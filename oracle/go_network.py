@@ -16,6 +16,7 @@ sparse matrix per sample and layer) and is what bench.py times as the CPU baseli
 import torch
 import torch.nn.functional as F
 
+from .dropout import is_feed
 from .pyg_ops import scatter_sum_dim1
 
 N_SNPS = 54
@@ -122,15 +123,21 @@ def _batch_norm(sd, name, x, training):
                         sd[name + ".weight"], sd[name + ".bias"], training, 0.1, 1e-5)
 
 
-def _node_dropout(x, p, training, enabled):
-    """nn.Dropout2d on a 3-D [B,N,f] tensor: zeroes whole nodes (dim-1 slices) per sample."""
+def _node_dropout(x, p, training, enabled, site=None):
+    """nn.Dropout2d on a 3-D [B,N,f] tensor: zeroes whole nodes (dim-1 slices) per sample.  ``enabled``: True / False,
+    or an oracle.dropout.MaskFeed whose [B,N] factors of ``site`` are applied instead of drawn ones."""
     if not (training and enabled):
         return x
+    if is_feed(enabled):
+        return x * enabled.take(site, x.shape[:2], p, x).unsqueeze(2)
     keep = torch.bernoulli(torch.full((x.shape[0], x.shape[1], 1), 1.0 - p, dtype=x.dtype))
     return x * keep / (1.0 - p)
 
 
-def _dropout(x, p, training, enabled):
+def _dropout(x, p, training, enabled, site=None):
+    """F.dropout(x, p) in training mode; with a MaskFeed as ``enabled``, x times the feed's factors of ``site``."""
+    if training and is_feed(enabled):
+        return x * enabled.take(site, x.shape, p, x)
     return F.dropout(x, p, True) if (training and enabled) else x
 
 
@@ -149,7 +156,9 @@ def go_forward(sd, idx, snps, training=False, dropout=True, faithful=False, pref
     """go_model.py:205-287.  snps [B,54] -> (latent [B,l], x_D [B,54], atten_out [B,Ntop,d_att]).
 
     ``act(site, t)``: every activation, ``site`` = its module key without ``prefix`` (``w_act.0``, ``B.1`` ...; the
-    GUIDE network's names, kernel/guide_go_model.py:103-144).  ``latent_out``: the latent MLP ends in BatchNorm
+    GUIDE network's names, kernel/guide_go_model.py:103-144).  ``dropout``: True (draw), False, or an
+    oracle.dropout.MaskFeed — every dropout site then takes its factors by that same module key (node sites [B,N], the
+    pooled-away nodes of an encoder level included).  ``latent_out``: the latent MLP ends in BatchNorm
     ``latent.5`` + activation (go_model.py:144-145); GUIDE's ends at ``latent.4`` (guide_go_model.py:138-144)."""
     g = lambda k: sd[prefix + k]   # noqa: E731
     sdp = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)} if prefix else sd
@@ -194,14 +203,14 @@ def go_forward(sd, idx, snps, training=False, dropout=True, faithful=False, pref
                 1, row, alpha.unsqueeze(2) * x_in[:, col, :]) + x_s * v_s
         out = F.layer_norm(out.permute(0, 2, 1), (nj,), g(f"G_B.{j}.weight"), g(f"G_B.{j}.bias"),
                            1e-5).permute(0, 2, 1)
-        out = _node_dropout(act(f"w_act.{j}", out), 0.4, training, dropout)
+        out = _node_dropout(act(f"w_act.{j}", out), 0.4, training, dropout, f"w_act.{j}")
         x = out[:, pool[j]:, :]
 
     # read-outs :254-255
     att = x @ g("conc_for_attention.0.weight").t()
     atten_out = act("conc_for_attention.2", _batch_norm(sdp, "conc_for_attention.1", att, training))
     inp = (x @ g("conc.weight").t()).squeeze(2)
-    inp_out = _dropout(act("B.1", _batch_norm(sdp, "B.0", inp, training)), 0.5, training, dropout)
+    inp_out = _dropout(act("B.1", _batch_norm(sdp, "B.0", inp, training)), 0.5, training, dropout, "B.1")
 
     # decoder layers :258-275 (mean aggregation back down the hierarchy)
     for j in range(n_l):
@@ -215,11 +224,11 @@ def go_forward(sd, idx, snps, training=False, dropout=True, faithful=False, pref
         y = agg + self_term
         y = F.layer_norm(y.permute(0, 2, 1), (n_rows,), g(f"G_B_D.{j}.weight"), g(f"G_B_D.{j}.bias"),
                          1e-5).permute(0, 2, 1)
-        x = _node_dropout(act(f"w_act_out.{j}", y), 0.4, training, dropout)
+        x = _node_dropout(act(f"w_act_out.{j}", y), 0.4, training, dropout, f"w_act_out.{j}")
 
     # gene decoding :278-282
     out_d = (x @ g("conc_D.weight").t()).squeeze(2)
-    out_d = _dropout(act("B_D.1", _batch_norm(sdp, "B_D.0", out_d, training)), 0.5, training, dropout)
+    out_d = _dropout(act("B_D.1", _batch_norm(sdp, "B_D.0", out_d, training)), 0.5, training, dropout, "B_D.1")
     dsn, dn = idx["gene_t"]                      # rows = SNP, cols = GO node
     if faithful:
         w_d = torch.sparse_coo_tensor(torch.stack([dsn, dn]), g("t_D.0"), (N_SNPS, n))
@@ -229,7 +238,7 @@ def go_forward(sd, idx, snps, training=False, dropout=True, faithful=False, pref
 
     # latent projection :138-146,285
     h = inp_out.view(bsz, -1) @ g("latent.0.weight").t()
-    h = _dropout(act("latent.2", _batch_norm(sdp, "latent.1", h, training)), 0.5, training, dropout)
+    h = _dropout(act("latent.2", _batch_norm(sdp, "latent.1", h, training)), 0.5, training, dropout, "latent.2")
     latent = h @ g("latent.4.weight").t()
     if latent_out:
         latent = act("latent.6", _batch_norm(sdp, "latent.5", latent, training))

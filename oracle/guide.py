@@ -20,6 +20,7 @@ import torch
 import torch.nn.functional as F
 
 from . import go_network as G
+from .dropout import is_feed
 
 LAMBDA = (1.0, 1.0, 2.5e-6, 0.2, 0.2)        # kernel/train_eval_guide_img_snps.py:163-164
 PROB_REF, EPS = 0.001, 1e-10                 # train()'s prob_ref / eps (:450)
@@ -72,6 +73,8 @@ def gate(bias, noise, tau, b):
 def model_forward(sd, cfg, idx, data, tau=None, noise=None, training=False, dropout=False):
     """GUIDE_IMGSNP.forward :78-135.  cfg: SimpleNamespace(rois); data: x [B*rois, H_0] (every graph has rois nodes:
     to_dense_batch :86-89 is a reshape), snps_feat.  ``noise`` [B, K, 2]: the gate's Gumbel noise (training needs it).
+    ``dropout``: True (draw), False, or an oracle.dropout.MaskFeed (the GO network's sites, ``encoder_i_N.1``,
+    ``decoder_i_N.1``, ``decoder_i_N.5``, ``lin1``, ``lin1_regr``).
     Returns the reference's 8-tuple (log_softmax, x_hat, latent, latent, linear_outf, our_reg, [img_out, decoded],
     [imp_N[:, 1]])."""
     x = data.x
@@ -87,19 +90,19 @@ def model_forward(sd, cfg, idx, data, tau=None, noise=None, training=False, drop
         x_in = img
     latent_g, x_hat, _ = go_forward(sd, idx, data.snps_feat, training, dropout, prefix="go_network.")     # :105
     h = prelu("encoder_i_N.1", x_in @ sd["encoder_i_N.0.weight"].t(), sd["encoder_i_N.1.weight"])           # :49-55,110
-    h = G._dropout(h, 0.4, training, dropout)
+    h = G._dropout(h, 0.4, training, dropout, "encoder_i_N.1")
     latent_n = h @ sd["encoder_i_N.3.weight"].t()
     latent = (latent_g + latent_n) / 2                                        # :113
     d = prelu("decoder_i_N.1", _batch_norm(sd, "decoder_i_N.0", latent, training), sd["decoder_i_N.1.weight"])  # :57-66
-    d = G._dropout(d, 0.4, training, dropout) @ sd["decoder_i_N.3.weight"].t()
+    d = G._dropout(d, 0.4, training, dropout, "decoder_i_N.1") @ sd["decoder_i_N.3.weight"].t()
     d = prelu("decoder_i_N.5", _batch_norm(sd, "decoder_i_N.4", d, training), sd["decoder_i_N.5.weight"])
-    decoded = G._dropout(d, 0.4, training, dropout) @ sd["decoder_i_N.7.weight"].t()
+    decoded = G._dropout(d, 0.4, training, dropout, "decoder_i_N.5") @ sd["decoder_i_N.7.weight"].t()
     if training:
         _count_batches(sd, MODEL_BNS)
     lin_f = torch.relu(latent @ sd["lin1.weight"].t() + sd["lin1.bias"])     # :127-133
-    logits = G._dropout(lin_f, 0.5, training, dropout) @ sd["lin2.weight"].t() + sd["lin2.bias"]
+    logits = G._dropout(lin_f, 0.5, training, dropout, "lin1") @ sd["lin2.weight"].t() + sd["lin2.bias"]
     r = torch.relu(latent @ sd["lin1_regr.weight"].t() + sd["lin1_regr.bias"])
-    reg = G._dropout(r, 0.3, training, dropout) @ sd["lin2_regr.weight"].t() + sd["lin2_regr.bias"]
+    reg = G._dropout(r, 0.3, training, dropout, "lin1_regr") @ sd["lin2_regr.weight"].t() + sd["lin2_regr.bias"]
     return F.log_softmax(logits, dim=-1), x_hat, latent, latent, lin_f, reg, [img, decoded], [imp[:, 1]]
 
 
@@ -115,6 +118,8 @@ def train_losses(sd, cfg, idx, data, tau, noise, lam=LAMBDA, dropout=False):
     """train() :460-483 (model in training mode; criterion_recon = MSELoss(reduction='none')).
     Returns (loss, dict of the five terms, outputs)."""
     outs = model_forward(sd, cfg, idx, data, tau, noise, training=True, dropout=dropout)
+    if is_feed(dropout):
+        dropout.close()                                                       # (every mask of the launch was consumed)
     logp, x_hat, _, _, _, reg, (img, decoded), prob = outs
     s2 = 0.0
     for p in prob:

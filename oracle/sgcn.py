@@ -13,7 +13,9 @@ import torch
 import torch.nn.functional as F
 
 from .pyg_ops import gcn_conv, to_dense_batch
-from .sgcn_img_snp import HP, edge_and_region_masks
+from .dropout import is_feed
+from .go_network import _dropout
+from .sgcn_img_snp import HP, edge_and_region_masks, pass_feeds
 
 
 def loss_probability(sd, x, edge_index, edge_weight, rois, hp=HP, eps=1e-6):
@@ -29,6 +31,7 @@ def loss_probability(sd, x, edge_index, edge_weight, rois, hp=HP, eps=1e-6):
 
 
 def model_forward(sd, rois, data, is_explain=False, training=False, dropout=True):
+    """``dropout``: True (draw), False, or an oracle.dropout.MaskFeed with the factors of site ``lin1``."""
     x, ei, batch, ew = data.x, data.edge_index, data.batch, data.edge_attr
     if is_explain:
         xm, ewm, _ = edge_and_region_masks(sd, x, ei, ew, rois)
@@ -43,14 +46,17 @@ def model_forward(sd, rois, data, is_explain=False, training=False, dropout=True
     dense, _ = to_dense_batch(xcat, batch, float(xcat.min()) - 1)
     z = dense.reshape(dense.shape[0], -1)
     h = torch.relu(z @ sd["lin1.weight"].t() + sd["lin1.bias"])
-    h = F.dropout(h, 0.5, True) if (training and dropout) else h
+    h = _dropout(h, 0.5, training, dropout, "lin1")
     return F.log_softmax(h @ sd["lin2.weight"].t() + sd["lin2.bias"], dim=-1)
 
 
 def train_losses(sd, rois, data, hp=HP, training=True, dropout=True):
     y = data.y.view(-1)
-    out = model_forward(sd, rois, data, False, training, dropout)
-    out_p = model_forward(sd, rois, data, True, training, dropout)
+    d1, d2 = pass_feeds(dropout, y.numel())        # (a MaskFeed: rows [0, B) for the plain pass, [B, 2B) for the masked one)
+    out = model_forward(sd, rois, data, False, training, d1)
+    out_p = model_forward(sd, rois, data, True, training, d2)
+    if is_feed(dropout) and training:
+        dropout.close()
     t = {"ce": F.nll_loss(out, y), "mi": F.nll_loss(out_p, y),
          "prob": loss_probability(sd, data.x, data.edge_index, data.edge_attr, rois, hp)}
     return hp.lamda_ce * t["ce"] + t["prob"] + hp.lamda_mi * t["mi"], t, (out, out_p)

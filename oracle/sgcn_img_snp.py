@@ -21,6 +21,7 @@ import torch
 import torch.nn.functional as F
 
 from . import go_network as G
+from .dropout import is_feed
 from .pyg_ops import gcn_conv, global_pools, to_dense_batch
 
 HP = SimpleNamespace(lamda_x_l1=0.1, lamda_e_l1=0.1, lamda_x_ent=0.1, lamda_e_ent=0.1,
@@ -100,7 +101,8 @@ def model_forward(sd, cfg, go_idx, data, is_explain=False, training=False, dropo
     """SGCN_GCN_IMGSNP.forward :207-307.
 
     cfg: SimpleNamespace(num_layers, rois[, image_only, snps_only, use_prob4regr]) ; data: object with x, edge_index, edge_attr,
-    batch, snps_feat.  Returns the reference 6-tuple.
+    batch, snps_feat.  ``dropout``: True (draw), False, or an oracle.dropout.MaskFeed holding this pass's factors (the GO
+    network's sites, ``lin1``, ``lin1_regr``).  Returns the reference 6-tuple.
     """
     x, ei, batch, ew, snps = data.x, data.edge_index, data.batch, data.edge_attr, data.snps_feat
     rois = cfg.rois
@@ -140,7 +142,7 @@ def model_forward(sd, cfg, go_idx, data, is_explain=False, training=False, dropo
         out_z = (img_out + out_cross) / 2
         out_lin = torch.cat([out_z, latent], dim=-1)
     lin_f = torch.relu(out_lin @ sd["lin1.weight"].t() + sd["lin1.bias"])
-    h = F.dropout(lin_f, 0.5, True) if (training and dropout) else lin_f
+    h = G._dropout(lin_f, 0.5, training, dropout, "lin1")
     logits = h @ sd["lin2.weight"].t() + sd["lin2.bias"]
     if getattr(cfg, "use_prob4regr", True) and not snps_only:
         xd, _ = to_dense_batch(data.x, batch, float(data.x.min()) - 1)        # :293-297 (isuseProb4Regr)
@@ -149,17 +151,27 @@ def model_forward(sd, cfg, go_idx, data, is_explain=False, training=False, dropo
     else:
         feat = out_lin
     r = torch.relu(feat @ sd["lin1_regr.weight"].t() + sd["lin1_regr.bias"])
-    r = F.dropout(r, 0.3, True) if (training and dropout) else r
+    r = G._dropout(r, 0.3, training, dropout, "lin1_regr")
     reg = r @ sd["lin2_regr.weight"].t() + sd["lin2_regr.bias"]
     return F.log_softmax(logits, dim=-1), x_hat, out_z, out_lin, lin_f, reg
 
 
+def pass_feeds(dropout, b):
+    """``dropout`` per pass of a train step: a MaskFeed is split into rows [0, B) | [B, 2B), True / False serve both."""
+    return (dropout.rows(0, b), dropout.rows(b, 2 * b)) if is_feed(dropout) else (dropout, dropout)
+
+
 def train_losses(sd, cfg, go_idx, data, lam=None, dropout=True, faithful=False):
-    """The loss of train() :521-543 (model in training mode).  Returns (loss, dict of terms)."""
+    """The loss of train() :521-543 (model in training mode).  ``dropout``: True, False, or an oracle.dropout.MaskFeed
+    of 2B rows per site — the plain pass takes rows [0, B), the masked pass rows [B, 2B) — which must be used up.
+    Returns (loss, dict of terms, outputs)."""
     lam = DEFAULT_LAMBDA if lam is None else lam
     y = data.y.view(-1)
-    o1 = model_forward(sd, cfg, go_idx, data, False, True, dropout, faithful)
-    o2 = model_forward(sd, cfg, go_idx, data, True, True, dropout, faithful)
+    d1, d2 = pass_feeds(dropout, y.numel())
+    o1 = model_forward(sd, cfg, go_idx, data, False, True, d1, faithful)
+    o2 = model_forward(sd, cfg, go_idx, data, True, True, d2, faithful)
+    if is_feed(dropout):
+        dropout.close()
     clin = data.clini_score.view(-1)
     t = {}
     t["ce"] = lam[0] * F.nll_loss(o1[0], y)

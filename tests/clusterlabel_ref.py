@@ -1,7 +1,8 @@
 """CPU restatement (TEST INFRASTRUCTURE ONLY) of what SGCN_GCN_CLUSTERLABEL adds to the shared body of the family —
 kernel/sgcn_img_snp_clusterlabel.py:114-144 (loss_probability with its own normalisations), :217-228 (the two
 classification heads) and train() of kernel/train_eval_sgcn_clusterlabel.py:375-393 (the six-term loss) — functional over
-a flat state_dict with the reference's key names, in whatever dtype the state has (the tests use float64).  The masks,
+a flat state_dict with the reference's key names, in whatever dtype the state has (the tests use float64); dropout is
+off unless the caller asks for it or feeds the masks (oracle.dropout.MaskFeed).  The masks,
 GCNConv, the GO network and the attention are ``oracle``'s.
 
 Also the float64 references of the two new launches: ``head_loss`` (igcn_cluster_head_loss_fwd) and ``mask_reg3``
@@ -41,8 +42,10 @@ def param_shapes(num_layers, hidden, h0=1, num_features=1, l_dim=32, num_classes
     return shp
 
 
-def model_forward(sd, rois, go_idx, data, is_explain=False, training=False, predict=True, faithful=False):
-    """forward :157-228 with isCrossAtten=True, dropout off.  Returns the reference's 4-tuple."""
+def model_forward(sd, rois, go_idx, data, is_explain=False, training=False, predict=True, faithful=False, dropout=False):
+    """forward :157-228 with isCrossAtten=True.  ``dropout``: False (off), True (drawn, as the reference does), or an
+    oracle.dropout.MaskFeed holding this pass's factors: the GO network's sites and the two heads' (:221,225, both
+    p = 0.5), ``lin1_classify`` and ``lin1_cluster``.  Returns the reference's 4-tuple."""
     x, ei, batch, ew, snps = data.x, data.edge_index, data.batch, data.edge_attr, data.snps_feat
     if is_explain:
         xm, ewm, _, snpsm = OS.edge_and_region_masks(sd, x, ei, ew, rois, snps)
@@ -57,13 +60,15 @@ def model_forward(sd, rois, go_idx, data, is_explain=False, training=False, pred
     dense, _ = to_dense_batch(xcat, batch, float(xcat.min()) - 1)
     bsz = dense.shape[0]
     img_out = dense.reshape(bsz, -1)
-    latent, x_hat, atten_out = G.go_forward(sd, go_idx, snpsm, training, False, faithful, prefix="go_network.")
+    latent, x_hat, atten_out = G.go_forward(sd, go_idx, snpsm, training, dropout, faithful, prefix="go_network.")
     cross = torch.relu(OS._mha(sd, dense, atten_out)).reshape(bsz, -1)
     out_z = torch.cat([(img_out + cross) / 2, latent], dim=-1)                            # :208
     z_cluster = out_z if predict else torch.zeros_like(out_z)                              # :217-220
     h_cluster = torch.relu(z_cluster @ sd["lin1_cluster.weight"].t() + sd["lin1_cluster.bias"])
+    h_cluster = G._dropout(h_cluster, 0.5, training, dropout, "lin1_cluster")
     s_cluster = h_cluster @ sd["lin2_cluster.weight"].t() + sd["lin2_cluster.bias"]
     h = torch.relu(out_z @ sd["lin1_classify.weight"].t() + sd["lin1_classify.bias"])
+    h = G._dropout(h, 0.5, training, dropout, "lin1_classify")
     s = h @ sd["lin2_classify.weight"].t() + sd["lin2_classify.bias"]
     return F.log_softmax(s, dim=-1), F.log_softmax(s_cluster, dim=-1), x_hat, out_z
 
@@ -93,11 +98,16 @@ def combine(t, predict, hp=HP):
     return hp.lamda_ce * t["ce"] + hp.lamda_mi * t["mi"] + t["prob"] + t["recon"]
 
 
-def train_losses(sd, rois, go_idx, data, lambda0=LAMBDA0, predict=True, hp=HP, faithful=False):
-    """The loss of train() :375-393 (model in training mode, dropout off).  Returns (loss, terms, (o1, o2))."""
+def train_losses(sd, rois, go_idx, data, lambda0=LAMBDA0, predict=True, hp=HP, faithful=False, dropout=False):
+    """The loss of train() :375-393 (model in training mode).  ``dropout``: False, True, or an oracle.dropout.MaskFeed of
+    2B rows per site (plain pass rows [0, B), masked pass rows [B, 2B)), which must be used up.
+    Returns (loss, terms, (o1, o2))."""
     y, cy = data.y.view(-1), data.clust_y.view(-1)
-    o1 = model_forward(sd, rois, go_idx, data, False, True, predict, faithful)
-    o2 = model_forward(sd, rois, go_idx, data, True, True, predict, faithful)
+    d1, d2 = OS.pass_feeds(dropout, y.numel())
+    o1 = model_forward(sd, rois, go_idx, data, False, True, predict, faithful, d1)
+    o2 = model_forward(sd, rois, go_idx, data, True, True, predict, faithful, d2)
+    if OS.is_feed(dropout):
+        dropout.close()
     t = {"ce": F.nll_loss(o1[0], y), "ce_cluster": F.nll_loss(o1[1], cy),
          "mi": F.nll_loss(o2[0], y), "mi_cluster": F.nll_loss(o2[1], cy),
          "prob": loss_probability(sd, data.x, data.edge_index, data.edge_attr, rois, hp),

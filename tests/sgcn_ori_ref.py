@@ -3,7 +3,8 @@ in the dtype of its inputs (the tests use float64).  ``sd``: name -> tensor with
 
   stack(...)            :120-138   h1 = relu(conv1), acts = conv3(h1) (the Grad-CAM tap, pre-ReLU), z = cat(z1, z2)
   model_forward(...)    :111-148   masks (cal_probability :74-85 = oracle.sgcn_img_snp.edge_and_region_masks), the stack,
-                                   fc1 -> ReLU -> bn1 -> fc2 -> ReLU -> bn2 -> fc3 -> log_softmax (dropout off)
+                                   fc1 -> ReLU -> bn1 -> fc2 -> ReLU -> bn2 -> fc3 -> log_softmax (dropout off, or with
+                                   the factors a run recorded: ``keeps``)
   loss_probability      :87-109    = oracle.sgcn.loss_probability (the same formula as SGCN_GCN's)
   train_losses(...)                train() kernel/train_eval_sgcn.py:303-308
   param_shapes(...)                the reference's state_dict keys and shapes
@@ -37,8 +38,10 @@ def _bn(x, sd, name, training, stats):
     return (x - mean) / torch.sqrt(var + 1e-5) * sd[name + ".weight"] + sd[name + ".bias"]
 
 
-def model_forward(sd, rois, data, is_explain=False, training=False, stats=None, taps=None):
-    """log_softmax [B, C], dropout off.  ``taps`` (a dict or None) receives final_conv_acts (retaining its gradient)."""
+def model_forward(sd, rois, data, is_explain=False, training=False, stats=None, taps=None, keeps=None):
+    """log_softmax [B, C].  ``taps`` (a dict or None) receives final_conv_acts (retaining its gradient).  ``keeps``: None
+    (dropout off) or the two factor tensors of Dropout(0.5) behind bn1 [B, 64] and Dropout(0.7) behind bn2 [B, 16] (:144,
+    :146), {0, 1 / (1 - p)}, as a training run of the HIP model recorded them."""
     x, ei, ew = data.x, data.edge_index, data.edge_attr
     if is_explain:
         x, ew, _ = edge_and_region_masks(sd, x, ei, ew, rois)
@@ -48,7 +51,13 @@ def model_forward(sd, rois, data, is_explain=False, training=False, stats=None, 
             acts.retain_grad()
         taps["acts"] = acts
     h = _bn(torch.relu(z @ sd["fc1.weight"].t() + sd["fc1.bias"]), sd, "bn1", training, stats)
+    if keeps is not None:
+        assert keeps[0].shape == h.shape, (keeps[0].shape, h.shape)
+        h = h * keeps[0].to(h.dtype)
     h = _bn(torch.relu(h @ sd["fc2.weight"].t() + sd["fc2.bias"]), sd, "bn2", training, stats)
+    if keeps is not None:
+        assert keeps[1].shape == h.shape, (keeps[1].shape, h.shape)
+        h = h * keeps[1].to(h.dtype)
     return F.log_softmax(h @ sd["fc3.weight"].t() + sd["fc3.bias"], dim=-1)
 
 

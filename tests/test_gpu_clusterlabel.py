@@ -5,7 +5,8 @@
   * the model against the fixture captured from the reference (tests/golden/clusterlabel.npz): eval, training mode, one
     train step — through the fused launch and under IGCN_NO_HEAD_LOSS_FUSED=1 — and forward_pair against two forwards;
   * GraphedTrainStep against eager train_step, fit_epoch against the eager loop, eval_acc's pair;
-  * dropout on: fresh masks per replay, nothing left queued after a step, also one that raised half way."""
+  * dropout on: the step's loss, terms and gradients against the float64 restatement fed the step's own masks by site
+    name; fresh masks per replay, nothing left queued after a step, also one that raised half way."""
 import copy
 import itertools
 
@@ -14,6 +15,7 @@ import pytest
 import torch
 
 import clusterlabel_ref as REF
+import dropout_cases as DC
 from conftest import assert_matches
 from test_gpu_model import grad_floor
 
@@ -402,6 +404,75 @@ def test_train_step_vs_reference_golden(golden, monkeypatch, tag, route):
             solid = torch.zeros_like(solid)
         assert float(diff[solid].max() if solid.any() else 0.0) <= 5e-5, "param " + k
         assert float(diff.max()) <= 2.01 * lr, "param (noise-level grads) " + k
+
+
+@pytest.mark.parametrize("tag", DC.CLUSTER_TAGS)
+@pytest.mark.parametrize("route", ["fused", "unfused"])
+def test_train_losses_with_dropout_vs_oracle_under_the_steps_own_masks(golden, monkeypatch, tag, route):
+    """Dropout ON (the first 8 graphs of the fixture's training batch): the step's one mask launch — 2B rows per site —
+    is recorded, equals oracle.dropout.masks(recorded sites, counter) bit for bit, and clusterlabel_ref.train_losses takes
+    those factors by site name.  The two head sites, lin1_classify and lin1_cluster, have one shape and one p: only their
+    POSITION in the launch tells them apart, and only the values — the loss, the six terms at 1e-4, every gradient at
+    1e-3 — tell whether each head got its own.  Negative controls (values only): the oracle under the masks of
+    counter + 1, and under the two head masks swapped, is dropout_cases.MARGIN away."""
+    from igcn_amd.train import losses
+    from oracle import dropout as OD
+    from oracle import sgcn_img_snp as OS
+    store = golden("clusterlabel")
+    model, graphs, cfg = _model(store, tag, dropout=True)
+    model.train(True)
+    if route == "unfused":
+        monkeypatch.setenv("IGCN_NO_HEAD_LOSS_FUSED", "1")
+    b = DC.CLUSTER_B
+    data = _batch(graphs["train"][:b])
+    counter = int(DC.set_counter(model.go_network).state[0].item())
+    with monkeypatch.context() as mp:
+        drawn = DC.recorded_masks(mp)
+        seen = [c[0] for c in _run_traced(mp, lambda: losses(model, data, hp=REF.HP))]
+    loss, terms, _ = _run_traced.result
+    loss.backward()
+    assert (("igcn_cluster_head_loss_fwd" in seen) == (route == "fused")), seen
+    assert len(drawn.calls) == 1 and not drawn.calls[0][2]
+    sites, arrays = drawn.calls[0][0], drawn.arrays(0)
+    assert sites[-2:] == [((2 * b, 64), 0.5), ((2 * b, 64), 0.5)], sites[-2:]
+    DC.assert_masks_rebuilt(sites, arrays, counter, f"{tag}/{route}")
+    assert int(model.go_network._drop_state.state[0].item()) == counter + 1
+    names = OD.go_site_names(2, OD.CLUSTER_HEADS)
+    _, idx, sd, _ = REF.fixture_setup(store, tag)
+
+    def oracle(factors, grad):
+        with torch.set_grad_enabled(grad):
+            st = OS.make_leaf_state(sd, torch.float64)
+            dd = DC.cpu_batch(graphs["train"][:b])
+            out = REF.train_losses(st, cfg.rois, idx, dd, cfg.lambda0, cfg.predict, dropout=OD.feed_of(sites, factors, names))
+        return st, dd, out
+    st, dd, (ref_loss, ref_terms, _) = oracle(arrays, True)
+    ref_loss.backward()
+    ref = float(ref_loss)
+    print(f"\n[{tag}/{route}] loss {float(loss):.6f}, oracle {ref:.6f}")
+    assert abs(float(loss) - ref) <= DC.LOSS_TOL * max(1.0, abs(ref)), (float(loss), ref)
+    assert sorted(terms) == sorted(REF.TERMS)
+    for k, v in terms.items():
+        r = float(ref_terms[k])
+        assert abs(float(v) - r) <= DC.LOSS_TOL * max(1.0, abs(r)), (k, float(v), r)
+    params = dict(model.named_parameters())
+    wg = {k: v.grad.numpy() for k, v in st.items() if v.requires_grad and v.grad is not None}
+    assert_matches(data.x.grad, dd.x.grad.numpy(), 1e-3, "grad data.x")
+    for k, w in wg.items():
+        g = params[k].grad
+        if g is None:                        # (lin*_cluster without isPredictCluster: no gradient here, zeros there)
+            assert not np.abs(w).max() > 0, k
+            continue
+        assert_matches(g, w, 1e-3, "grad " + k, floor=grad_floor(wg, k, 1e-5))
+    own = (loss, terms)
+    gap_next = DC.gap(own, oracle(OD.masks(sites, counter + 1), False)[2][:2])
+    print(f"[control] HIP loss against the oracle under the masks of counter + 1: {gap_next:.5f} (margin {DC.MARGIN})")
+    assert gap_next > DC.MARGIN, gap_next
+    if cfg.predict:
+        swapped = arrays[:-2] + [arrays[-1], arrays[-2]]
+        gap_heads = DC.gap(own, oracle(swapped, False)[2][:2], "terms")
+        print(f"[control] a term under swapped head masks: {gap_heads:.5f}")
+        assert gap_heads > DC.MARGIN, gap_heads
 
 
 @pytest.mark.parametrize("tag", ["h0_1", "h0_3"])

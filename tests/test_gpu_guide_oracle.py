@@ -2,7 +2,8 @@
 at the shapes it runs: 90 ROIs, H_0 3, hidden_linear 32, the bench's 3000-node GO DAG (1800, 800, 300, 99, 1); hidden 16
 at B = 256 graphs (the captured step of tools/guide_bench.py) and hidden 10 at B = 32.
 
-Training mode, dropout off, the gate's Gumbel noise imposed (guide_ref.gumbel_noise, moved 1e-3 off a hard-decision tie):
+Training mode, the gate's Gumbel noise imposed; dropout off — and, in one configuration of its own (hidden 10, B = 8), ON
+with the oracle fed the masks the step drew (oracle.dropout.MaskFeed, the five sites of this model by name).  Gumbel noise (guide_ref.gumbel_noise, moved 1e-3 off a hard-decision tie):
 the five loss terms and the loss to 1e-4, every gradient (data.x included) to 1e-3 on the scales of
 tests/test_gpu_guide.py's fixture test.  An fp32 pre-activation within rounding of a PReLU's kink may take the other
 branch, where the derivative jumps (1 -> a): the model's slopes are set to seeded positive values, so that the HIP path's
@@ -21,6 +22,7 @@ import numpy as np
 import pytest
 import torch
 
+import dropout_cases as DC
 import guide_ref
 from conftest import assert_matches, relu_forced
 from _weights import seeded_state
@@ -52,9 +54,17 @@ def _need_gpu():
 _SETUP = {}
 
 
+DROPOUT = "h10_b8_dropout"          # dropout on: dropout_cases.GUIDE (its own seed), not part of CONFIGS
+
+
 def _setup(tag):
     """(model on cuda, float32 state, index sets, graphs, noise [B, K, 2]) of a configuration; built once per module."""
     if tag in _SETUP:
+        return _SETUP[tag]
+    if tag == DROPOUT:
+        g = DC.GUIDE
+        assert (g["pool"], g["rois"], g["h0"], g["hidden_linear"], g["tau"]) == (POOL, ROIS, H0, HL, TAU)
+        _SETUP[tag] = DC.guide_setup(g["hidden"], g["bsz"], g["seed"], "cuda")
         return _SETUP[tag]
     from igcn_amd import synth
     from igcn_amd.guide_img_snp import GUIDE_IMGSNP
@@ -81,12 +91,12 @@ def _setup(tag):
     return _SETUP[tag]
 
 
-def _fresh(tag):
+def _fresh(tag, dropout=False):
     model, sd, idx, graphs, noise = _setup(tag)
     model.load_state_dict(sd)
     model.zero_grad(set_to_none=True)
-    model._dropout_enabled = False
-    model.go_network._dropout_enabled = False
+    model._dropout_enabled = dropout
+    model.go_network._dropout_enabled = dropout
     return model, sd, idx, graphs, noise
 
 
@@ -95,7 +105,8 @@ def _named(o):
 
 
 class _recorded_prelus:
-    """Record the outputs of the HIP path's PReLU launches (dropout off: the PReLU itself), in call order."""
+    """Record the outputs of the HIP path's PReLU launches, in call order (dropout off: the PReLU itself; dropout on: the
+    PReLU times the site's factors — a dropped entry shows nothing and goes into ``decisions``' skip mask)."""
 
     def __init__(self, monkeypatch):
         from igcn_amd import ops
@@ -117,8 +128,10 @@ class _recorded_prelus:
         monkeypatch.setattr(ops, "NodesLayerNormPReLU", LN)
         monkeypatch.setattr(ops, "bn_prelu_forward", bn)
 
-    def decisions(self):
-        """site -> (bool tensor of u > 0 in the oracle's layout, entries nothing downstream reads or None)."""
+    def decisions(self, dropped=None):
+        """site -> (bool tensor of u > 0 in the oracle's layout, entries nothing downstream reads or None).  ``dropped``
+        {site: bool array, True = zero factor}: [B, N] for the LayerNorm sites (whole nodes), the site's shape otherwise."""
+        dropped = dropped or {}
         assert len(self.ln) == len(LN_SITES) and len(self.bn) == len(BN_SITES), (len(self.ln), len(self.bn))
         out = {}
         for site, (z, pool) in zip(LN_SITES, self.ln):           # HIP [B, f, N - pool] -> oracle [B, N, f]
@@ -127,10 +140,13 @@ class _recorded_prelus:
             want[:, pool:, :] = (z > 0).permute(0, 2, 1).cpu()
             skip = torch.zeros_like(want)
             skip[:, :pool, :] = True                              # pooled-away nodes
+            if site in dropped:
+                skip |= torch.from_numpy(dropped[site]).unsqueeze(2)
             out[site] = (want, skip)
         for site, y in zip(BN_SITES, self.bn):                    # HIP [B, C, D] -> [B, C, D] (D > 1) or [B, C]
             w = (y > 0).cpu()
-            out[site] = (w if w.shape[-1] > 1 else w[..., 0], None)
+            w = w if w.shape[-1] > 1 else w[..., 0]
+            out[site] = (w, torch.from_numpy(dropped[site]).reshape(w.shape) if site in dropped else None)
         return out
 
 
@@ -218,6 +234,83 @@ def test_model_train_vs_fp64_oracle(tag, monkeypatch):
     for k, p in params.items():                # nothing the oracle leaves without a gradient gets one here
         if k not in wg:
             assert p.grad is None or not bool(p.grad.abs().max() > 0), "unexpected grad " + k
+
+
+def test_model_train_with_dropout_vs_fp64_oracle_under_the_steps_own_masks(monkeypatch):
+    """Dropout on in the model and in its GO network (hidden 10, B = 8, the module's pool): the one mask launch of the
+    forward is recorded, equals oracle.dropout.masks(recorded sites, counter) bit for bit, and the oracle takes those
+    factors by site name — the GO network's seven sites and encoder_i_N.1, decoder_i_N.1, decoder_i_N.5 (p = 0.4), lin1
+    (0.5), lin1_regr (0.3).  The five terms and the loss at 1e-4, every gradient at 1e-3 on the floors of the dropout-off
+    test; PReLU decisions of dropped entries are skipped (a PReLU output times a zero factor shows nothing), MAX_FLIPS and
+    BAND as everywhere.  Negative control: the oracle under the masks of counter + 1 is dropout_cases.MARGIN away."""
+    from igcn_amd.data import Batch
+    from igcn_amd.train import GUIDE_LAMBDA, losses
+    from oracle import dropout as OD
+    from oracle import guide as OGD
+    from oracle import sgcn_img_snp as OS
+    model, sd, idx, graphs, noise = _fresh(DROPOUT, dropout=True)
+    model.train()
+    model._gate_noise = torch.from_numpy(noise).cuda()
+    data = Batch.from_data_list(graphs).to("cuda")
+    rec = _recorded_prelus(monkeypatch)
+    counter = int(DC.set_counter(model.go_network).state[0].item())
+    with monkeypatch.context() as mp:
+        drawn = DC.recorded_masks(mp)
+        loss, terms, outs = losses(model, data, temperature=torch.tensor(TAU, device="cuda"))
+    loss.backward()
+    model._gate_noise = None
+    torch.cuda.synchronize()
+    assert len(drawn.calls) == 1 and not drawn.calls[0][2]
+    sites, arrays = drawn.calls[0][0], drawn.arrays(0)
+    DC.assert_masks_rebuilt(sites, arrays, counter, "GUIDE_IMGSNP")
+    assert int(model.go_network._drop_state.state[0].item()) == counter + 1
+    names = OD.go_site_names(2, OD.GUIDE_EXTRA)
+    zero = {n: a == 0 for n, a in zip(names, arrays)}
+    dropped = {("go_network." + n if n in OD.go_site_names(2) else n): z for n, z in zero.items()}
+    t0 = time.perf_counter()
+    sdo = OS.make_leaf_state(sd, torch.float64)
+    cpu = OGD.batch_data(Batch.from_data_list(graphs))
+    imp = _imposed_prelus(monkeypatch, rec.decisions(dropped))
+    lin_f = _named(outs)["lin_f"]
+    noise64 = torch.from_numpy(noise).double()
+    with relu_forced({0: (lin_f > 0).cpu()}, band=BAND) as rf:
+        loss_o, terms_o, outs_o = OGD.train_losses(sdo, SimpleNamespace(rois=ROIS), idx, cpu, TAU, noise64, GUIDE_LAMBDA,
+                                                   dropout=OD.feed_of(sites, arrays, names))
+    loss_o.backward()
+    print(f"\n[{DROPOUT}] oracle {time.perf_counter() - t0:.1f} s; imposed {imp.flips} of {imp.total} PReLU decisions "
+          f"and {rf.flips} of {lin_f.numel()} lin1 ReLU decisions")
+    assert imp.mismatch == 0 and rf.mismatch_outside == 0, (imp.mismatch, rf.mismatch_outside)
+    assert imp.flips + rf.flips <= MAX_FLIPS, (imp.flips, rf.flips)
+    for k in TERMS:
+        ref = float(terms_o[k].detach())
+        assert abs(float(terms[k]) - ref) <= 1e-4 * max(1.0, abs(ref)), (k, float(terms[k]), ref)
+    ref = float(loss_o.detach())
+    assert abs(float(loss) - ref) <= 1e-4 * max(1.0, abs(ref)), (float(loss), ref)
+    want = _named(outs_o)
+    for n, o in _named(outs).items():
+        assert_matches(o, want[n].detach().numpy(), 1e-4, n)
+    assert_matches(data.x.grad, cpu.x.grad.numpy(), 1e-3, "grad data.x")
+    params = dict(model.named_parameters())
+    wg = {k: v.grad.numpy() for k, v in sdo.items() if v.requires_grad and v.grad is not None}
+    go_scale = max(float(np.abs(w).max()) for k, w in wg.items() if k.startswith("go_network."))
+    for k, w in wg.items():                    # the floors of test_model_train_vs_fp64_oracle
+        assert params[k].grad is not None, k
+        floor = 1e-5
+        sib = wg.get(k[:-5] + ".weight") if k.endswith(".bias") else None
+        if sib is not None:
+            floor = max(floor, 0.5 * float(np.abs(sib).max()))
+        if k.startswith("go_network."):
+            floor = max(floor, go_scale)
+        assert_matches(params[k].grad, w, 1e-3, "grad " + k, floor=floor)
+    # negative control (values only): the same HIP loss against the oracle under the NEXT launch's masks
+    monkeypatch.undo()
+    with torch.no_grad():
+        other = OGD.train_losses(OS.make_leaf_state(sd, torch.float64), SimpleNamespace(rois=ROIS), idx,
+                                 OGD.batch_data(Batch.from_data_list(graphs)), TAU, noise64, GUIDE_LAMBDA,
+                                 dropout=OD.feed_of(sites, OD.masks(sites, counter + 1), names))[:2]
+    gap = DC.gap((loss, terms), other)
+    print(f"[control] HIP loss against the oracle under the masks of counter + 1: {gap:.5f} (margin {DC.MARGIN})")
+    assert gap > DC.MARGIN, gap
 
 
 @pytest.mark.parametrize("tag", list(CONFIGS))

@@ -5,12 +5,14 @@ mode normalises with BatchNorm over 3-8 samples, which amplifies fp32 rounding (
 far from the reference's own fp32 numbers, see test_oracle_golden.py), hence the looser bound there.
 """
 import ast
+import time
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
+import dropout_cases as DC
 from conftest import assert_matches, golden_group
 from igcn_amd import switches
 from _weights import seeded_state
@@ -296,11 +298,22 @@ def test_full_model_vs_oracle_larger(bsz, pool, explain):
 
 def train_mode_vs_oracle(monkeypatch, rois, pool, bsz, dense=False, bf16=False, maps=("sparse", "default"),
                          graph_seed=78, go_seed=1, tol=1e-4, gtol=1e-3, max_flips=40, band=2e-5, formulations=(True, False),
-                         layers=2, hidden=16, h0=3):
-    """TRAINING mode (batch statistics in every BatchNorm, dropout off) of the HIP model against the fp64 oracle: the
-    seven loss terms of train() at ``tol`` and every gradient at ``gtol``, for the step formulations ``formulations``
-    (True: both passes as one 2B-sample sweep; False: two forward() calls).  Returns the number of imposed ReLU
-    decisions.
+                         layers=2, hidden=16, h0=3, dropout=False, controls=False):
+    """TRAINING mode (batch statistics in every BatchNorm) of the HIP model against the fp64 oracle: the seven loss
+    terms of train() at ``tol`` and every gradient at ``gtol``, for the step formulations ``formulations`` (True: both
+    passes as one 2B-sample sweep; False: two forward() calls).  Returns the number of imposed ReLU decisions.
+
+    ``dropout=False``: every dropout switched off.  ``dropout=True``: as the model trains — the mask generator's stream
+    counter is set to dropout_cases.COUNTER, what ``ops.dropout_masks`` returned is recorded, required equal bit for bit
+    to oracle.dropout.masks(recorded sites, counter) (the stacked sweep: one draw of 2B rows; two forward() calls: two
+    draws, counters c and c + 1) and fed to the oracle by site NAME (oracle.dropout.MaskFeed, which refuses a shape or a p
+    other than the oracle site's own and masks left over): a site given another site's mask, another p, the other pass's
+    rows, the pooled node range, or a mask applied in one direction only moves the terms or the gradients.  A dropped
+    entry (a whole node at the LayerNorm sites) reads "not positive" in the fused kernels' outputs whatever the
+    pre-activation was: its ReLU decision is unobservable and irrelevant (value and gradient are zero either way) and is
+    ignored.  ``controls`` (with the stacked sweep): the negative controls — the oracle under the masks of counter c + 1
+    is dropout_cases.MARGIN away from the HIP loss, and so is a term under the two passes' row ranges swapped (values
+    only; tests/test_oracle_dropout.py measures both gaps on the oracle).
 
     ReLU decisions.  tools/relu_margin.py at the default shapes: B.0's smallest pre-activation is 1.5e-6 of its layer's
     scale; fp32 puts it on the other side of zero, and d B.0.bias[node] — a 32-term sum of scale 7e-4 — moves by one
@@ -313,7 +326,7 @@ def train_mode_vs_oracle(monkeypatch, rois, pool, bsz, dense=False, bf16=False, 
     from igcn_amd.data import Batch
     from igcn_amd.sgcn_img_snp import SGCN_GCN_IMGSNP
     from igcn_amd.train import losses
-    from oracle import go_network as OG, sgcn_img_snp as OS
+    from oracle import dropout as OD, go_network as OG, sgcn_img_snp as OS
     lam = [1.0, 1.0, 0.5, 1.5e-6, 0.1, 0.2]
     go_snps, adj, pool_dim = synth.go_hierarchy(pool, seed=go_seed)
     a_g, a = synth.go_sparse_inputs(go_snps, adj, "cuda")
@@ -323,7 +336,7 @@ def train_mode_vs_oracle(monkeypatch, rois, pool, bsz, dense=False, bf16=False, 
     sd = seeded_state({k: v.shape for k, v in model.state_dict().items()}, 5)
     model.load_state_dict(sd)
     for m in (model, model.go_network):
-        m._dropout_enabled = False
+        m._dropout_enabled = bool(dropout)
     graphs = synth.brain_graph_list(bsz, seed=graph_seed, rois=rois, h0=h0, tsne_dim=16, dense=dense)
     # oracle, fp64, training mode
     a_g_c, a_c = synth.go_sparse_inputs(go_snps, adj)
@@ -340,6 +353,7 @@ def train_mode_vs_oracle(monkeypatch, rois, pool, bsz, dense=False, bf16=False, 
         model.zero_grad()
         model.batched_passes = batched
         data = Batch.from_data_list(graphs).to("cuda")
+        counter = None
         with monkeypatch.context() as mp:
             for cls in classes:
                 def wrapped(*a, _cls=cls, _apply=cls.apply):
@@ -347,8 +361,21 @@ def train_mode_vs_oracle(monkeypatch, rois, pool, bsz, dense=False, bf16=False, 
                     seen.setdefault(_cls.__name__, []).append(out)
                     return out
                 mp.setattr(cls, "apply", wrapped)
+            if dropout:
+                counter = int(DC.set_counter(model.go_network).state[0].item())
+                drawn = DC.recorded_masks(mp)
             loss, terms, _ = losses(model, data, lam)
         loss.backward()
+        masks = None
+        if dropout:
+            # one launch for the stacked sweep, one per forward() otherwise; each advances the counter by one
+            assert len(drawn.calls) == (1 if batched else 2) and not any(c[2] for c in drawn.calls), drawn.calls
+            masks = []
+            for k, (sites, _, _) in enumerate(drawn.calls):
+                arrays = drawn.arrays(k)
+                DC.assert_masks_rebuilt(sites, arrays, counter + k, f"batched={batched}, launch {k}")
+                masks.append((sites, arrays))
+            assert int(model.go_network._drop_state.state[0].item()) == counter + len(masks)
         params = dict(model.named_parameters())
         grads = {k: params[k].grad for k in params if params[k].grad is not None}
         grads["data.x"] = data.x.grad
@@ -409,7 +436,18 @@ def train_mode_vs_oracle(monkeypatch, rois, pool, bsz, dense=False, bf16=False, 
             forced[base + 9], forced[base + 10] = hb[0][p_] > 0, hb[1][p_] > 0
             forced[base + 11] = None                                  # out_proj + ReLU: fused in the GEMM epilogue
             forced[base + 12], forced[base + 13] = lp[0][p_] > 0, lp[1][p_] > 0
-        return loss, terms, grads, forced, ignore
+            if masks is not None:
+                # factors of this pass: rows [p B, (p + 1) B) of the stacked draw, or the p-th draw.  In the launch's order:
+                # 2 encoder + 2 decoder LayerNorm sites [B, nodes], inp_out, out_D, the latent hidden layer, the two heads
+                # (applied to the heads' ReLU outputs inside the loss launch: those decisions stay observable)
+                arrays = masks[0][1] if batched else masks[p_][1]
+                rows = slice(p_ * bsz, (p_ + 1) * bsz) if batched else slice(None)
+                zero = [torch.from_numpy(a[rows] == 0) for a in arrays]
+                for site, z in ((base + 2, zero[0]), (base + 3, zero[1]), (base + 6, zero[2]), (base + 7, zero[3])):
+                    z = z.unsqueeze(2).expand_as(forced[site])
+                    ignore[site] = z | ignore[site] if site in ignore else z
+                ignore[base + 5], ignore[base + 8], ignore[base + 9] = zero[4], zero[5], zero[6]
+        return loss, terms, grads, forced, ignore, (counter, masks)
 
     flips_seen = 0
     for mp_ in maps:
@@ -418,15 +456,23 @@ def train_mode_vs_oracle(monkeypatch, rois, pool, bsz, dense=False, bf16=False, 
         else:
             monkeypatch.delenv("IGCN_SPARSE_MAPS", raising=False)
         for batched in formulations:
-            loss, terms, got, forced, ignore = hip_run(batched)
+            loss, terms, got, forced, ignore, (counter, masks) = hip_run(batched)
+            feed = False
+            if dropout:
+                heads = OD.go_site_names(2, OD.HEADS)
+                feed = OD.feed_of(*masks[0], heads) if batched else OD.stack_rows(masks, heads)
+            t0 = time.perf_counter()
             st = OS.make_leaf_state(sd, dtype=torch.float64)
             dd = Batch.from_data_list(graphs)
             dd.x = dd.x.double().requires_grad_(True)
             dd.edge_attr, dd.snps_feat = dd.edge_attr.double(), dd.snps_feat.double()
             dd.tsne_fdim, dd.clini_score = dd.tsne_fdim.double(), dd.clini_score.double()
             with relu_forced(forced, band=band, ignore=ignore) as rf:
-                ref_loss, ref_terms, _ = OS.train_losses(st, cfg, idx, dd, lam, dropout=False)
+                ref_loss, ref_terms, _ = OS.train_losses(st, cfg, idx, dd, lam, dropout=feed)
             ref_loss.backward()
+            if dropout:
+                print(f"\n[pool {sum(pool)}, B = {bsz}, batched={batched}] oracle {time.perf_counter() - t0:.1f} s; imposed "
+                      f"{rf.flips} ReLU decisions (cap {max_flips})")
             assert rf.mismatch_outside == 0, (mp_, batched, rf.mismatch_outside)     # decisions agree outside the band
             assert rf.flips <= max_flips, rf.flips
             flips_seen += rf.flips
@@ -439,6 +485,19 @@ def train_mode_vs_oracle(monkeypatch, rois, pool, bsz, dense=False, bf16=False, 
             for k, w in want.items():
                 assert_matches(got[k], w.numpy(), gtol, f"grad {k} (maps={mp_}, batched={batched}, "
                                                         f"{rf.flips} imposed decisions)", floor=1e-6)
+            if controls and dropout and batched:
+                sites, arrays = masks[0]
+                own = (loss, terms)
+
+                def other(factors):
+                    with torch.no_grad():
+                        return OS.train_losses(OS.make_leaf_state(sd, dtype=torch.float64), cfg, idx, DC.cpu_batch(graphs), lam,
+                                               dropout=OD.feed_of(sites, factors, heads))[:2]
+                gap_next = DC.gap(own, other(OD.masks(sites, counter + 1)))
+                gap_rows = DC.gap(own, other([np.concatenate([a[bsz:], a[:bsz]]) for a in arrays]), "terms")
+                print(f"[controls] HIP loss against the oracle under the masks of counter + 1: {gap_next:.5f}; a term under "
+                      f"swapped row ranges: {gap_rows:.5f} (margin {DC.MARGIN})")
+                assert gap_next > DC.MARGIN and gap_rows > DC.ROWS_MARGIN, (gap_next, gap_rows)
     return flips_seen
 
 
@@ -463,6 +522,65 @@ def test_train_mode_multifusion_vs_oracle(monkeypatch, layers, hidden):
 
 
 # ---- the image-only sibling SGCN_GCN (kernel/sgcn.py:272-388; BASELINE configs[0]/[1]) -------------------------
+@pytest.mark.parametrize("pool,batched", [(DC.SMALL_POOL, True), (DC.SMALL_POOL, False), (DC.LARGE_POOL, True)])
+def test_train_mode_with_dropout_vs_oracle_under_the_steps_own_masks(monkeypatch, pool, batched):
+    """Dropout ON, as the model trains: R = 90, L = 2, h = 16, H_0 = 3, B = 8 — both step formulations on the 500-node GO
+    DAG, and the stacked sweep on the 3000-node DAG, where the LDS-resident GO kernels carry the factors — against the
+    fp64 oracle fed the masks this very step drew (see train_mode_vs_oracle): the seven loss terms at 1e-4, every
+    gradient and data.x.grad at 1e-3, the recorded masks equal to the host-rebuilt ones bit for bit.  The first case also
+    runs the negative controls."""
+    c = DC.HEADLINE
+    train_mode_vs_oracle(monkeypatch, c["rois"], pool, c["bsz"], maps=("default",), graph_seed=c["graph_seed"],
+                         go_seed=c["go_seed"], formulations=(batched,), layers=c["layers"], hidden=c["hidden"], h0=c["h0"],
+                         dropout=True, controls=(pool == DC.SMALL_POOL and batched))
+
+
+def test_captured_step_replays_the_masks_of_its_counter_vs_oracle(monkeypatch):
+    """GraphedTrainStep with dropout on (headline model, 500-node DAG, B = 8, FlatAdam(lr=0): the parameters stay put).
+    The capture queues its mask job as a rider of the plan build's launch; the tensors that call returned are the static
+    buffers every replay fills.  For each of two replays: the counter read before it gives, rebuilt on the host, exactly
+    what the buffers hold after it, and the replay's loss is the oracle's under those masks; the counters of the two
+    replays differ by one launch's advance."""
+    from igcn_amd import synth
+    from igcn_amd.data import Batch
+    from igcn_amd.train import FlatAdam, GraphedTrainStep
+    from oracle import dropout as OD, go_network as OG, sgcn_img_snp as OS
+    c = DC.HEADLINE
+    model, go_snps, adj = DC.headline_model(DC.SMALL_POOL, "cuda")
+    model.train()
+    sd = seeded_state({k: v.shape for k, v in model.state_dict().items()}, c["state_seed"])
+    model.load_state_dict(sd)
+    graphs = synth.brain_graph_list(c["bsz"], seed=c["graph_seed"], rois=c["rois"], h0=c["h0"], tsne_dim=16)
+    static = Batch.from_data_list(graphs).to("cuda")
+    static.x.requires_grad_(True)
+    opt = FlatAdam(model.parameters(), lr=0.0)
+    state = DC.set_counter(model.go_network).state
+    with monkeypatch.context() as mp:
+        drawn = DC.recorded_masks(mp)
+        step = GraphedTrainStep(model, opt, static, DC.LAM, warmup=2)
+    sites, buffers, ride = drawn.calls[-1]                     # the capture's own call: static tensors
+    assert ride and len(drawn.calls) == 3, [c_[2] for c_ in drawn.calls]
+    assert model.go_network._drop_state.state is state and int(state[0].item()) == DC.COUNTER    # warm-up rolled back
+    idx = OG.go_index_sets(*synth.go_sparse_inputs(go_snps, adj), list(DC.SMALL_POOL), 2)
+    cfg = SimpleNamespace(num_layers=c["layers"], rois=c["rois"], image_only=False, rbf_gamma=0.01)
+    counters, losses_seen = [], []
+    for _ in range(2):
+        counters.append(int(state[0].item()))
+        loss = float(step())
+        torch.cuda.synchronize()
+        arrays = [t.detach().cpu().numpy() for t in buffers]
+        DC.assert_masks_rebuilt(sites, arrays, counters[-1], f"replay at counter {counters[-1]}")
+        with torch.no_grad():
+            ref = float(OS.train_losses(OS.make_leaf_state(sd, dtype=torch.float64), cfg, idx, DC.cpu_batch(graphs), DC.LAM,
+                                        dropout=OD.feed_of(sites, arrays, OD.go_site_names(2, OD.HEADS)))[0])
+        assert abs(loss - ref) <= DC.LOSS_TOL * max(1.0, abs(ref)), (counters[-1], loss, ref)
+        losses_seen.append(loss)
+    assert counters[1] == counters[0] + 1 and int(state[0].item()) == counters[1] + 1
+    assert losses_seen[0] != losses_seen[1]
+    for k, p in model.named_parameters():
+        assert torch.equal(p.detach().cpu(), sd[k]), k
+
+
 def _sgcn_model(store):
     from igcn_amd import synth
     from igcn_amd.sgcn import SGCN_GCN

@@ -967,6 +967,48 @@ def test_batchnorm1d_grouped(ops, bsz, c, training, relu, groups):
     assert_matches(rvg, rv.numpy(), TOL, "running_var")
 
 
+@pytest.mark.parametrize("c", [5, 32])
+@pytest.mark.parametrize("rows", [2, 3, 33])
+@pytest.mark.parametrize("groups", [1, 2])
+@pytest.mark.parametrize("p", [0.5, 0.7])
+def test_batchnorm1d_grouped_without_relu_applies_the_dropout_factors(ops, p, groups, rows, c):
+    """``keep`` with the ReLU flag 0 — how the image-only heads call the op (sgcn.py ``_bn``: Dropout(0.5) behind bn1,
+    Dropout(0.7) behind bn2) — against float64, forward and backward: factors {0, fp32(1 / (1 - p))}, ``rows`` samples per
+    group (2 and 3: the smallest batches; 33: past one wavefront's rows), C = 5 (odd) and 32.
+
+    dx of a training-mode BatchNorm is a cancelling sum, rstd gamma (g - mean(g) - xhat mean(g xhat)) with g = dy keep —
+    at 2 rows per group all that is left of it is of the order eps rstd^2 of its summands — so fp32 leaves an error
+    relative to the SUMMANDS: dx is judged on the scale max|gamma| max(rstd) max|g| of the float64 evaluation."""
+    rng = np.random.default_rng(1000 * rows + 10 * c + groups)
+    bsz = rows * groups
+    x = torch.from_numpy(rng.standard_normal((bsz, c)) * 1.5 + 0.2).float()
+    gamma = torch.from_numpy(1 + 0.2 * rng.standard_normal(c)).float()
+    beta = torch.from_numpy(0.2 * rng.standard_normal(c)).float()
+    scale = np.float32(1.0) / (np.float32(1.0) - np.float32(p))
+    keep = torch.from_numpy(np.where(rng.random((bsz, c)) < p, np.float32(0.0), scale).astype(np.float32))
+    assert 0 < int((keep == 0).sum()) < keep.numel()
+    rm0, rv0 = torch.from_numpy(0.1 * rng.standard_normal(c)).float(), torch.from_numpy(1 + rng.random(c)).float()
+    cot = torch.from_numpy(rng.standard_normal((bsz, c))).float()
+    ref_in = [t.double().requires_grad_(True) for t in (x, gamma, beta)]
+    rm, rv = rm0.double().clone(), rv0.double().clone()
+    parts = [torch.nn.functional.batch_norm(ref_in[0][g * rows:(g + 1) * rows], rm, rv, ref_in[1], ref_in[2], True, 0.1, 1e-5)
+             for g in range(groups)]
+    y_ref = torch.cat(parts) * keep.double()
+    g_ref = torch.autograd.grad((y_ref * cot.double()).sum(), ref_in)
+    rstd = torch.stack([(x[g * rows:(g + 1) * rows].double().var(0, unbiased=False) + 1e-5).rsqrt() for g in range(groups)])
+    dx_scale = float(gamma.abs().max()) * float(rstd.max()) * float((cot * keep).abs().max())
+    dev = [t.cuda().requires_grad_(True) for t in (x, gamma, beta)]
+    rmg, rvg = rm0.cuda(), rv0.cuda()
+    y = ops.BatchNorm1dGrouped.apply(dev[0], dev[1], dev[2], rmg, rvg, True, 0.1, 1e-5, 0, groups, keep.cuda())
+    g = torch.autograd.grad((y * cot.cuda()).sum(), dev)
+    assert_matches(y, y_ref.detach().numpy(), TOL, "y")
+    assert bool((y.cpu()[keep == 0] == 0).all())
+    for got, want, nm, floor in zip(g, g_ref, ("dx", "dgamma", "dbeta"), (dx_scale, 1e-6, 1e-6)):
+        assert_matches(got, want.numpy(), 3e-4, nm, floor=floor)
+    assert_matches(rmg, rm.numpy(), TOL, "running_mean")
+    assert_matches(rvg, rv.numpy(), TOL, "running_var")
+
+
 def test_plan_replicate_equals_plan_of_the_doubled_graph(ops):
     rng = np.random.default_rng(0)
     n, e = 90 * 4, 270 * 4

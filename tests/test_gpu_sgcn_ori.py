@@ -324,6 +324,53 @@ def test_both_routes_vs_fp64_in_eval_mode(monkeypatch, golden, route, explain):
         assert_matches(p.grad, w.numpy(), 1e-3, "grad " + k, floor=1e-4)
 
 
+def test_train_mode_with_dropout_vs_fp64_under_the_recorded_factors(monkeypatch, golden):
+    """TRAINING mode with dropout ON at B = 6, masked pass: the two ``keep`` tensors ``_bn`` hands ops.BatchNorm1dGrouped
+    (ReLU flag 0) are recorded at the op's ``apply`` — Dropout(0.5) behind bn1, Dropout(0.7) behind bn2: their non-zero
+    value is 1 / (1 - p) of the right p — and the float64 restatement multiplies by them at the same two places: logp at
+    1e-4, every gradient at 1e-3 (the bounds of the eval-mode check above)."""
+    from igcn_amd import ops
+    from igcn_amd.data import Batch
+    store = golden("sgcn_ori")
+    model, graphs, seed = _model(store, "h32_5", bsz=6, train=True)
+    model._dropout_enabled = True
+    torch.manual_seed(seed)
+    data = _batch(graphs)
+    keeps = []
+    real = ops.BatchNorm1dGrouped.apply
+
+    def spy(*a):
+        assert a[8] == 0 and a[10] is not None                    # ReLU flag 0, factors present
+        keeps.append(a[10].detach().cpu())
+        return real(*a)
+    sd = {k: (v.detach().cpu().double().requires_grad_(True) if v.dtype.is_floating_point and "running_" not in k
+              else v.detach().cpu().clone()) for k, v in model.state_dict(keep_vars=True).items()}
+    with monkeypatch.context() as mp:
+        mp.setattr(ops.BatchNorm1dGrouped, "apply", spy)
+        out = model(data, True)
+    cot = _probe([out], 4)[0]
+    (out * cot.cuda()).sum().backward()
+    assert [tuple(k.shape) for k in keeps] == [(6, 64), (6, 16)]
+    for k, p in zip(keeps, (0.5, 0.7)):
+        vals = np.unique(k.numpy())
+        assert len(vals) == 2 and vals[0] == 0.0 and abs(float(vals[1]) - 1.0 / (1.0 - p)) <= 1e-6 / (1.0 - p), (p, vals)
+    dcpu = Batch.from_data_list(graphs)
+    dcpu.x = dcpu.x.double().requires_grad_(True)
+    dcpu.edge_attr = dcpu.edge_attr.double()
+    taps = {}
+    ref = REF.model_forward(sd, 90, dcpu, True, training=True, taps=taps, keeps=keeps)
+    (ref * cot.double()).sum().backward()
+    assert_matches(out, ref.detach().numpy(), 1e-4, "logp")
+    assert_matches(model.final_conv_grads, taps["acts"].grad.numpy(), 1e-3, "final_conv_grads")
+    assert_matches(data.x.grad, dcpu.x.grad.numpy(), 1e-3, "grad data.x")
+    for k, p in model.named_parameters():
+        w = sd[k].grad
+        if w is None:
+            assert p.grad is None or not bool(p.grad.abs().max() > 0), k
+            continue
+        assert_matches(p.grad, w.numpy(), 1e-3, "grad " + k, floor=1e-4)
+
+
 @pytest.mark.parametrize("tag", TAGS)
 @pytest.mark.parametrize("mode", ["eval", "train"])
 @pytest.mark.parametrize("explain", [False, True])
