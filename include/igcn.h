@@ -934,6 +934,13 @@ int igcn_go_decode_bwd(int B, int Nin, int Nout, int fin, int fout, const int32_
  * `lr` is a DEVICE float[1] read by the kernel at run time: the reference's schedule
  * (`param_group['lr'] = lr_decay_factor * param_group['lr']`, kernel/train_eval_sgcn_img_snps.py:169-171) writes that
  * scalar, and a launch captured into a hipGraph sees the new rate at its next replay.
+ * The update, with t = *step after the increment and g = grad * grad_scale (scaled BEFORE it is squared):
+ *   m = beta1 m + (1 - beta1) g ;  v = beta2 v + (1 - beta2) g^2
+ *   param -= lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+ * — eps is added AFTER the second moment's bias correction (torch.optim.Adam's placement), not to sqrt(v).  beta1, beta2,
+ * eps and grad_scale are taken as given in float: 1 - beta2 is 1 - float(0.999), which moves exp_avg_sq by 1.3e-5 relative
+ * and the update by at most 2e-5 of its scale from torch's double-valued betas (tests/test_adam_reference.py).  All forms
+ * below compute this one expression in fp32 (tests/test_gpu_adam.py holds each to the fp64 evaluation of it).
  */
 int igcn_adam_step(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
                    int32_t* step, const float* lr, float beta1, float beta2, float eps, float grad_scale,

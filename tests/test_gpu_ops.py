@@ -886,6 +886,9 @@ def test_sparse_map_encode_decode(ops, monkeypatch, bsz, pool, seed, dense):
 
 
 def test_adam_matches_torch(ops):
+    """Five steps beside fp32 torch.optim.Adam on three tiny tensors: a smoke check of the default route.  What pins the
+    kernels — every form, chunk seams, misaligned gradients, grad_scale, eps, large t, against an fp64 oracle at the scale of
+    one update — is tests/test_gpu_adam.py."""
     from igcn_amd.train import FlatAdam
     rng = np.random.default_rng(0)
     ps = [torch.nn.Parameter(torch.from_numpy(rng.standard_normal(s)).float().cuda()) for s in ((7, 5), (33,), (2, 3, 4))]
