@@ -1,7 +1,7 @@
 // The GATConv stack of one brain graph, LDS-resident: L x (PyG 2.0.2 GATConv(heads=1, edge_dim=1, add_self_loops,
 // fill_value='mean'), ReLU) + the jumping-knowledge concatenation of kernel/gcn_img_snp.py:217-221 with ifUseGAT as ONE
-// kernel per direction, one 256-thread workgroup per graph — the GAT twin of k_sgcn_stack_{fwd,bwd}
-// (csrc/sgcn_fused.hip).
+// kernel per direction, one 256-thread workgroup per graph.  The staged graph (its LDS layout and loader) is
+// csrc/gcn_lds.h, shared with the GCN stacks; the edge array there called ew holds this stack's edge attribute ea.
 //
 // One layer, for a target i with incoming list E(i) (stored self-loops skipped: src == dst) plus one virtual loop whose
 // edge value is the mean of ea over E(i) (0 for an empty list):
@@ -21,6 +21,7 @@
 // Preconditions (host wrappers / per-graph plan builder): uniform graphs of R nodes (graph g = nodes [gR, (g+1)R), its
 // edges contiguous in stored order); sums run in list order; no atomics: deterministic.
 #include "common.h"
+#include "gcn_lds.h"
 
 #define GT_T 256
 #define GT_MAXL 4
@@ -37,8 +38,9 @@ __host__ __device__ inline int gt_param_offset(int l, int H0, int F) {
 }
 
 struct GtLayout {
-  int x, esrc, edst, eea, tptr, tk, lea, prm, wt, ce, h, lgs, lgd, alpha, y;   // both directions
-  int sptr, sk, dcur, dh, dpre, das, dad, prow, red;                            // backward
+  GraphLds t;                                                                   // the staged graph
+  int lea, prm, wt, ce, h, lgs, lgd, alpha, y;                                  // both directions
+  int dcur, dh, dpre, das, dad, prow, red;                                      // backward
   int icnt;                                                                     // backward with d(edge attribute)
   int total;
 };
@@ -51,12 +53,7 @@ __host__ __device__ inline GtLayout gt_layout(int R, int Emax, int H0, int F, in
   const int fin_max = F > H0 ? F : H0;
   const int EA = Emax + R;                         // alpha / dpre: stored edge k at k, node i's virtual loop at Emax + i
   const int LK = backward ? L : 1;                 // the backward keeps every layer's logits and alpha
-  o.x = take(R * H0);
-  o.esrc = take(Emax);                             // per stored edge: local endpoints and value
-  o.edst = take(Emax);
-  o.eea = take(Emax);
-  o.tptr = take(R + 1);                            // by-target list: positions [tptr[i], tptr[i+1]) hold edges tk[.]
-  o.tk = take(Emax);
+  graph_lds_layout(o.t, R, Emax, H0, take);
   o.lea = take(R);                                 // the virtual loop's edge value (mean of the kept incoming ea)
   o.prm = take(gt_param_offset(L, H0, F));         // every layer's parameters as stored
   o.wt = take(L * F * fin_max);                    // W_l transposed [fin][F]: the F lanes of a node read consecutive words
@@ -66,10 +63,9 @@ __host__ __device__ inline GtLayout gt_layout(int R, int Emax, int H0, int F, in
   o.lgd = take(LK * R);
   o.alpha = take(LK * EA);
   o.y = take(R * L * F);                           // concatenated layer outputs [R][L F]
-  o.sptr = o.sk = o.dcur = o.dh = o.dpre = o.das = o.dad = o.prow = o.red = o.icnt = 0;
+  o.dcur = o.dh = o.dpre = o.das = o.dad = o.prow = o.red = o.icnt = 0;
   if (backward) {
-    o.sptr = take(R + 1);                          // by-source list: positions [sptr[n], sptr[n+1]) hold edges sk[.]
-    o.sk = take(Emax);
+    graph_lds_layout_bwd(o.t, R, Emax, take);
     o.dcur = take(R * F);                          // d(layer output), masked by the ReLU
     o.dh = take(R * F);
     o.dpre = take(EA);                             // d(pre-activation logit) per edge / virtual loop
@@ -92,7 +88,7 @@ extern "C" int igcn_gat_stack_param_floats(int H0, int F, int L) { return gt_par
 __device__ __forceinline__ float gt_lrelu(float z) { return z > 0.f ? z : GT_SLOPE * z; }
 
 // Stage graph nb/R: x, edges, lists (by-source too for the backward), parameters; then per-layer c and the loop values.
-// Returns the edge count, or -1 when it exceeds Emax (nothing of LDS beyond the fixed part touched; status bit 1 set).
+// Returns the edge count, or -1 for a refused graph (graph_lds_load: nothing of LDS touched; status bit 1 set).
 // EW: also keep 1 / cnt of every target (the share of the virtual loop's gradient each kept edge takes).
 template <bool BWD, bool EW = false>
 __device__ int gt_stage(float* lds, const GtLayout& o, int R, int Emax, int H0, int F, int L, int64_t nb,
@@ -102,28 +98,13 @@ __device__ int gt_stage(float* lds, const GtLayout& o, int R, int Emax, int H0, 
                         const int32_t* __restrict__ src_ptr, const int32_t* __restrict__ src_perm,
                         const GtParams& prm, int32_t* __restrict__ status) {
   const int tid = threadIdx.x;
-  const int32_t eb = tgt_ptr[nb];
-  const int ne = tgt_ptr[nb + R] - eb;
-  if (ne > Emax) {
-    if (tid == 0 && status) atomicOr(status, 2);
-    return -1;
-  }
-  int32_t* esrc = reinterpret_cast<int32_t*>(lds + o.esrc);
-  int32_t* edst = reinterpret_cast<int32_t*>(lds + o.edst);
-  int32_t* tptr = reinterpret_cast<int32_t*>(lds + o.tptr);
-  int32_t* tk = reinterpret_cast<int32_t*>(lds + o.tk);
-  for (int i = tid; i < R * H0; i += GT_T) lds[o.x + i] = x_in[nb * H0 + i];
-  for (int k = tid; k < ne; k += GT_T) {
-    esrc[k] = src32[eb + k] - (int32_t)nb;
-    edst[k] = dst32[eb + k] - (int32_t)nb;
-    lds[o.eea + k] = ew_in[eb + k];
-    tk[k] = tgt_perm[eb + k] - eb;
-    if (BWD) reinterpret_cast<int32_t*>(lds + o.sk)[k] = src_perm[eb + k] - eb;
-  }
-  for (int i = tid; i <= R; i += GT_T) {
-    tptr[i] = tgt_ptr[nb + i] - eb;
-    if (BWD) reinterpret_cast<int32_t*>(lds + o.sptr)[i] = src_ptr[nb + i] - eb;
-  }
+  int32_t eb;
+  const int ne = graph_lds_load<BWD>(lds, o.t, R, Emax, H0, nb, x_in, ew_in, src32, dst32, tgt_ptr, tgt_perm, src_ptr,
+                                     src_perm, status, eb, GT_T);
+  if (ne < 0) return -1;
+  const int32_t* src = lds_i32(lds, o.t.src);
+  const int32_t* tptr = lds_i32(lds, o.t.tptr);
+  const int32_t* tperm = lds_i32(lds, o.t.tperm);
   const int fin_max = F > H0 ? F : H0;
   const int P = gt_param_offset(L, H0, F);
   for (int j = tid; j < P; j += GT_T) {
@@ -151,9 +132,9 @@ __device__ int gt_stage(float* lds, const GtLayout& o, int R, int Emax, int H0, 
     float s = 0.f;
     int cnt = 0;
     for (int p = tptr[i]; p < tptr[i + 1]; ++p) {
-      const int k = tk[p];
-      if (esrc[k] != i) {
-        s += lds[o.eea + k];
+      const int k = tperm[p];
+      if (src[k] != i) {
+        s += lds[o.t.ew + k];
         ++cnt;
       }
     }
@@ -172,15 +153,15 @@ __device__ void gt_layer_fwd(float* lds, const GtLayout& o, int R, int Emax, int
   const int tid = threadIdx.x;
   constexpr int FQ = F / 4;
   const int fin = l == 0 ? H0 : F, D = L * F;
-  const float* xin = l == 0 ? lds + o.x : lds + o.y + (l - 1) * F;
+  const float* xin = l == 0 ? lds + o.t.x : lds + o.y + (l - 1) * F;
   const int ldx = l == 0 ? H0 : D;
   const int fin_max = F > H0 ? F : H0;
   const float* wt = lds + o.wt + l * F * fin_max;
   const float* pb = lds + o.prm + gt_param_offset(l, H0, F) + F * fin;      // b | att_src | att_dst | le | ae
   float* H = lds + o.h;
-  const int32_t* esrc = reinterpret_cast<const int32_t*>(lds + o.esrc);
-  const int32_t* tptr = reinterpret_cast<const int32_t*>(lds + o.tptr);
-  const int32_t* tk = reinterpret_cast<const int32_t*>(lds + o.tk);
+  const int32_t* src = lds_i32(lds, o.t.src);
+  const int32_t* tptr = lds_i32(lds, o.t.tptr);
+  const int32_t* tperm = lds_i32(lds, o.t.tperm);
   for (int e = tid; e < R * FQ; e += GT_T) {
     const int i = e / FQ, q = e - i * FQ;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -211,15 +192,15 @@ __device__ void gt_layer_fwd(float* lds, const GtLayout& o, int R, int Emax, int
     float m = zl;
     const int p0 = tptr[i], p1 = tptr[i + 1];
     for (int p = p0; p < p1; ++p) {
-      const int k = tk[p], s = esrc[k];
-      if (s != i) m = fmaxf(m, gt_lrelu(lgs[s] + zd + lds[o.eea + k] * c));
+      const int k = tperm[p], s = src[k];
+      if (s != i) m = fmaxf(m, gt_lrelu(lgs[s] + zd + lds[o.t.ew + k] * c));
     }
     float sum = 0.f;
     for (int p = p0; p < p1; ++p) {                   // list order, the virtual loop last (PyG appends the loops)
-      const int k = tk[p], s = esrc[k];
+      const int k = tperm[p], s = src[k];
       float ev = 0.f;
       if (s != i) {
-        ev = __expf(gt_lrelu(lgs[s] + zd + lds[o.eea + k] * c) - m);
+        ev = __expf(gt_lrelu(lgs[s] + zd + lds[o.t.ew + k] * c) - m);
         sum += ev;
       }
       alpha[k] = ev;
@@ -228,7 +209,7 @@ __device__ void gt_layer_fwd(float* lds, const GtLayout& o, int R, int Emax, int
     sum += el;
     const float den = sum + 1e-16f;
     for (int p = p0; p < p1; ++p) {
-      const int k = tk[p];
+      const int k = tperm[p];
       alpha[k] = alpha[k] / den;
     }
     alpha[Emax + i] = el / den;
@@ -239,7 +220,7 @@ __device__ void gt_layer_fwd(float* lds, const GtLayout& o, int R, int Emax, int
     const int i = e / FQ, q = e - i * FQ;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int p = tptr[i]; p < tptr[i + 1]; ++p) {
-      const int k = tk[p], s = esrc[k];
+      const int k = tperm[p], s = src[k];
       if (s == i) continue;
       const float a = alpha[k];
       const float4 h4 = *reinterpret_cast<const float4*>(H + s * F + q * 4);
@@ -308,12 +289,12 @@ k_gat_stack_bwd(int R, int Emax, int H0, int L, const float* __restrict__ x_in, 
   for (int l = 0; l < L; ++l)
     gt_layer_fwd<F>(gt_lds, o, R, Emax, H0, L, l, gt_lds + o.lgs + l * R, gt_lds + o.lgd + l * R,
                     gt_lds + o.alpha + l * EA);
-  const int32_t* esrc = reinterpret_cast<const int32_t*>(gt_lds + o.esrc);
-  const int32_t* edst = reinterpret_cast<const int32_t*>(gt_lds + o.edst);
-  const int32_t* tptr = reinterpret_cast<const int32_t*>(gt_lds + o.tptr);
-  const int32_t* tk = reinterpret_cast<const int32_t*>(gt_lds + o.tk);
-  const int32_t* sptr = reinterpret_cast<const int32_t*>(gt_lds + o.sptr);
-  const int32_t* sk = reinterpret_cast<const int32_t*>(gt_lds + o.sk);
+  const int32_t* src = lds_i32(gt_lds, o.t.src);
+  const int32_t* dst = lds_i32(gt_lds, o.t.dst);
+  const int32_t* tptr = lds_i32(gt_lds, o.t.tptr);
+  const int32_t* tperm = lds_i32(gt_lds, o.t.tperm);
+  const int32_t* sptr = lds_i32(gt_lds, o.t.sptr);
+  const int32_t* sperm = lds_i32(gt_lds, o.t.sperm);
   float* H = gt_lds + o.h;
   float* dcur = gt_lds + o.dcur;
   float* dH = gt_lds + o.dh;
@@ -324,7 +305,7 @@ k_gat_stack_bwd(int R, int Emax, int H0, int L, const float* __restrict__ x_in, 
   constexpr int FQ = F / 4;
   for (int l = L - 1; l >= 0; --l) {
     const int fin = l == 0 ? H0 : F;
-    const float* xin = l == 0 ? gt_lds + o.x : gt_lds + o.y + (l - 1) * F;
+    const float* xin = l == 0 ? gt_lds + o.t.x : gt_lds + o.y + (l - 1) * F;
     const int ldx = l == 0 ? H0 : D;
     const float* wt = gt_lds + o.wt + l * F * fin_max;
     const float* W = gt_lds + o.prm + gt_param_offset(l, H0, F);             // [F][fin] as stored
@@ -366,7 +347,7 @@ k_gat_stack_bwd(int R, int Emax, int H0, int L, const float* __restrict__ x_in, 
       const float* dy = dcur + i * F;
       float sa = 0.f;
       for (int p = p0; p < p1; ++p) {
-        const int k = tk[p], s = esrc[k];
+        const int k = tperm[p], s = src[k];
         float da = 0.f;
         if (s != i) {
 #pragma unroll
@@ -383,11 +364,11 @@ k_gat_stack_bwd(int R, int Emax, int H0, int L, const float* __restrict__ x_in, 
       const float zd = lgd[i];
       float sd = 0.f;
       for (int p = p0; p < p1; ++p) {
-        const int k = tk[p], s = esrc[k];
+        const int k = tperm[p], s = src[k];
         float g = 0.f;
         if (s != i) {
           const float dz = alpha[k] * (dpre[k] - sa);
-          g = lgs[s] + zd + gt_lds[o.eea + k] * c > 0.f ? dz : GT_SLOPE * dz;
+          g = lgs[s] + zd + gt_lds[o.t.ew + k] * c > 0.f ? dz : GT_SLOPE * dz;
           sd += g;
         }
         dpre[k] = g;
@@ -401,7 +382,7 @@ k_gat_stack_bwd(int R, int Emax, int H0, int L, const float* __restrict__ x_in, 
     // (c) d a_s by source; d bias; d c (one wave)
     for (int n = tid; n < R; n += GT_T) {
       float s = 0.f;
-      for (int q = sptr[n]; q < sptr[n + 1]; ++q) s += dpre[sk[q]];     // stored loops carry an exact 0
+      for (int q = sptr[n]; q < sptr[n + 1]; ++q) s += dpre[sperm[q]];     // stored loops carry an exact 0
       das[n] = s + dpre[Emax + n];
     }
     for (int f = tid; f < F; f += GT_T) {
@@ -413,7 +394,7 @@ k_gat_stack_bwd(int R, int Emax, int H0, int L, const float* __restrict__ x_in, 
       const int lane = tid - (GT_T - IGCN_WAVE);
       const int ne = tptr[R];
       float s = 0.f;
-      for (int k = lane; k < ne; k += IGCN_WAVE) s += dpre[k] * gt_lds[o.eea + k];
+      for (int k = lane; k < ne; k += IGCN_WAVE) s += dpre[k] * gt_lds[o.t.ew + k];
       for (int i = lane; i < R; i += IGCN_WAVE) s += dpre[Emax + i] * gt_lds[o.lea + i];
       s = wave_sum(s);
       if (lane == 0) gt_lds[o.red] = s;
@@ -424,8 +405,8 @@ k_gat_stack_bwd(int R, int Emax, int H0, int L, const float* __restrict__ x_in, 
       float* dew_g = dew + tgt_ptr[nb];
       const int ne = tptr[R];
       for (int k = tid; k < ne; k += GT_T) {
-        const int t = edst[k];
-        const float g = esrc[k] != t ? c * (dpre[k] + dpre[Emax + t] * gt_lds[o.icnt + t]) : 0.f;
+        const int t = dst[k];
+        const float g = src[k] != t ? c * (dpre[k] + dpre[Emax + t] * gt_lds[o.icnt + t]) : 0.f;
         dew_g[k] = l == L - 1 ? g : dew_g[k] + g;
       }
     }
@@ -435,7 +416,7 @@ k_gat_stack_bwd(int R, int Emax, int H0, int L, const float* __restrict__ x_in, 
       const int n = e / F, f = e - n * F;
       float s = 0.f;
       for (int q = sptr[n]; q < sptr[n + 1]; ++q) {
-        const int k = sk[q], t = edst[k];
+        const int k = sperm[q], t = dst[k];
         if (t != n) s += alpha[k] * dcur[t * F + f];
       }
       s += alpha[Emax + n] * dcur[n * F + f];

@@ -13,7 +13,24 @@
 // Preconditions (checked by the host wrappers / guaranteed by the per-graph plan builders): a block-diagonal batch of
 // uniform graphs (R nodes each, graph g = nodes [gR, (g+1)R), its edges contiguous in stored order), edge lists
 // from the graph plan.  Sums run in the plan's stable (reference scatter) order; no atomics: deterministic.
+//
+// The staged graph's LDS layout, gcn_norm (lists and backward) and the list walks of a layer are csrc/gcn_lds.h, shared
+// with the other LDS stacks; what is here is this stack's own: the register-batched staging, the transforms, the
+// parameter gradients and the front kernel's plan build and masks.
 #include "common.h"
+
+// phase stamps for tools/sgcn_probe.py and tools/front_probe.py (-DSF_PROBE_ON); gcn_lists of csrc/gcn_lds.h stamps too
+#ifdef SF_PROBE_ON
+__device__ long long sf_probe_buf[8 * 16];
+#define SF_PROBE(i) do { if (threadIdx.x == 0 && blockIdx.x < 8) sf_probe_buf[blockIdx.x * 16 + (i)] = wall_clock64(); } while (0)
+extern "C" int igcn_debug_sf_probe(long long* out) {
+  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(sf_probe_buf), sizeof(long long) * 8 * 16);
+}
+#else
+#define SF_PROBE(i)
+#endif
+#define GCN_LDS_PROBE(i) SF_PROBE(i)
+#include "gcn_lds.h"
 
 // threads per workgroup (= per graph).  The kernels are chains of ~20 barrier-separated phases over ~1.5 k work items;
 // measured at the bench shape (512 graphs, hot): forward 16.7 / 12.6 / 12.3 us and backward 52 / 40 / 53 us with
@@ -30,10 +47,12 @@ struct SfParams {
 
 // LDS carve-out shared by both kernels (all offsets in 4-byte words)
 struct SfLayout {
-  int x, dis, wl, wloop, ew, what, src, dst, tptr, tperm, wallT, act, wall, loop, tsrc, twhat;   // forward part
-  int ycat;                                                                             // [R][L*F] layer outputs
-  int sptr, sperm, g, dh, dx, dwhat, dwloop, ddeg, red, dycat, prow, bdst, bwhat, v1, v2;   // backward part
-  int fprob, fct, fcs, fsperm, fe;                                                       // front part (k_sgcn_front_fwd)
+  GraphLds t;                                      // the staged graph
+  GcnNormLds n;                                    // gcn_norm: coefficients, lists, backward
+  int wallT, act, wall;                            // forward part
+  int ycat;                                        // [R][L*F] layer outputs
+  int g, dh, dx, red, dycat, prow;                 // backward part
+  int fprob, fct, fcs, fsperm, fe;                 // front part (k_sgcn_front_fwd)
   int total;
 };
 
@@ -44,30 +63,34 @@ __host__ __device__ inline SfLayout sf_layout(int R, int Emax, int H0, int F, in
   int p = 0;
   auto take = [&](int n) { int q = p; p += (n + 3) & ~3; return q; };
   const int fin_max = F > H0 ? F : H0;
-  o.x = take(R * H0);
-  o.dis = take(R);
-  o.wl = take(R);
-  o.wloop = take(R);
-  o.ew = take(Emax);
-  o.what = take(Emax);
-  o.src = take(Emax);
-  o.dst = take(Emax);
-  o.tptr = take(R + 1);
-  o.tperm = take(Emax);
-  o.tsrc = take(Emax + 4);                         // by-TARGET order: source node and coefficient of every list entry
-  o.twhat = take(Emax + 4);                        // (+4: the 4-wide list walk may read past the end; never used)
+  // The two shared structs, filled HERE and not by graph_lds_layout / gcn_norm_layout: the order of the blocks is
+  // part of this kernel's speed (the same code over the shared functions' order: backward 26.0 -> 26.9 us at the
+  // bench shape, docs/LABLOG.md section C), so the hot kernel keeps the order it was tuned in.
+  o.t.x = take(R * H0);
+  o.n.dis = take(R);
+  o.n.wl = take(R);
+  o.n.wloop = take(R);
+  o.t.ew = take(Emax);
+  take(Emax);     // reserved (once the by-edge coefficients): LDS per workgroup decides how many graphs share a CU
+  o.t.src = take(Emax);
+  o.t.dst = take(Emax);
+  o.t.tptr = take(R + 1);
+  o.t.tperm = take(Emax);
+  o.n.tsrc = take(Emax + 4);                       // (+4: the 4-wide list walk may read past the end; never used)
+  o.n.twhat = take(Emax + 4);
   // every layer's weights, fetched with the graph (one round trip): wallT = W_l TRANSPOSED (Wt[fi][fo]: the F lanes of
   // a node read consecutive words in the transforms) | b_l; wall = W_l [fo][fi] as stored (backward: dX = dH W)
   o.wallT = take(L * (F * fin_max + F));
   o.wall = take(backward ? L * (F * fin_max + F) : 0);
-  o.loop = take(R);
+  o.n.loop = take(R);
   // activations: the transforms H_l (the forward keeps the current one only, the backward all of them) and the
   // concatenated layer outputs Y [R][L*F], which leave for HBM in ONE coalesced pass at the end — a store in front of
   // a barrier makes the whole workgroup wait for its acknowledgement, so nothing is stored before the last barrier
   o.act = take((backward ? L : 1) * R * F);
   o.ycat = take(R * L * F);
-  o.sptr = o.sperm = o.g = o.dh = o.dx = o.dwhat = o.dwloop = o.ddeg = o.red = o.dycat = o.prow = o.bdst = o.bwhat = 0;
-  o.v1 = o.v2 = 0;
+  o.g = o.dh = o.dx = o.red = o.dycat = o.prow = 0;
+  o.t.sptr = o.t.sperm = 0;
+  o.n.bdst = o.n.bwhat = o.n.dwhat = o.n.dwloop = o.n.ddeg = o.n.v1 = o.n.v2 = 0;
   o.fprob = o.fct = o.fcs = o.fsperm = o.fe = 0;
   if (front) {
     o.fprob = take(R * H0);
@@ -77,22 +100,22 @@ __host__ __device__ inline SfLayout sf_layout(int R, int Emax, int H0, int F, in
     o.fe = take(Emax);
   }
   if (backward) {
-    o.sptr = take(R + 1);
-    o.sperm = take(Emax);
+    o.t.sptr = take(R + 1);
+    o.t.sperm = take(Emax);
     o.g = take(R * F);
     o.dh = take(R * F);
-    // gcn_norm backward: per-position products (by-source / by-target order) — in G / dH, dead by then, when they fit
-    o.v1 = Emax <= R * F ? o.g : take(Emax);
-    o.v2 = Emax <= R * F ? o.dh : take(Emax);
+    // gcn_norm backward's per-position products go into G / dH, dead by then, when they fit
+    o.n.v1 = Emax <= R * F ? o.g : take(Emax);
+    o.n.v2 = Emax <= R * F ? o.dh : take(Emax);
     o.dx = take(R * fin_max);
-    o.dwhat = take(Emax);
-    o.dwloop = take(R);
-    o.ddeg = take(R);
+    o.n.dwhat = take(Emax);
+    o.n.dwloop = take(R);
+    o.n.ddeg = take(R);
     o.red = take(SF_TB + (SF_TB > F * fin_max ? SF_TB : F * fin_max));
     o.dycat = take(R * L * F);
     o.prow = take(L * (F * fin_max + F));
-    o.bdst = take(Emax + 4);                       // by-SOURCE order: target node and coefficient of every list entry
-    o.bwhat = take(Emax + 4);
+    o.n.bdst = take(Emax + 4);
+    o.n.bwhat = take(Emax + 4);
   }
   o.total = p;
   return o;
@@ -102,24 +125,11 @@ extern "C" size_t igcn_sgcn_stack_lds_bytes(int R, int max_edges, int H0, int F,
   return (size_t)sf_layout(R, max_edges, H0, F, L, backward).total * 4;
 }
 
-// stage the graph: node features, edges (local endpoints, weights), lists, and the gcn_norm coefficients
-#ifdef SF_PROBE_ON
-__device__ long long sf_probe_buf[8 * 16];
-#define SF_PROBE(i) do { if (threadIdx.x == 0 && blockIdx.x < 8) sf_probe_buf[blockIdx.x * 16 + (i)] = wall_clock64(); } while (0)
-extern "C" int igcn_debug_sf_probe(long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(sf_probe_buf), sizeof(long long) * 8 * 16);
-}
-#else
-#define SF_PROBE(i)
-#endif
-
-template <bool BWD>
-__device__ __forceinline__ void sf_lists(float* lds, const SfLayout& o, int R, int ne, int32_t eb);
-
-// Returns the graph's edge count, or -1 (nothing staged beyond the fixed-size arrays) when it exceeds Emax.  The loads
-// whose size is fixed by R go out FIRST, together with the two pointer words that give the graph's edge range: the
-// edge arrays then follow one round trip later instead of two (the range used to be fetched, and waited for, in front
-// of everything).
+// Stage the graph: node features, edges (local endpoints, weights), lists, and the gcn_norm coefficients (gcn_lists).
+// Returns the graph's edge count, or -1 (nothing staged beyond the fixed-size arrays) when it exceeds Emax.
+// Its own load sequence, not graph_lds_load's: the loads whose size is fixed by R go out FIRST, together with the two
+// pointer words that give the graph's edge range: the edge arrays then follow one round trip later instead of two
+// (the range used to be fetched, and waited for, in front of everything).
 template <bool BWD>
 __device__ __forceinline__ int sf_stage(float* lds, const SfLayout& o, int R, int Emax, int H0, int64_t nb,
                                         const float* __restrict__ x_in, const float* __restrict__ ew_in,
@@ -157,10 +167,10 @@ __device__ __forceinline__ int sf_stage(float* lds, const SfLayout& o, int R, in
     const float* src = wsrc(tid + j * (int)blockDim.x, wd[j], wdT[j]);
     wv[j] = src ? *src : 0.f;
   }
-  int32_t* ssrc = reinterpret_cast<int32_t*>(lds + o.src);
-  int32_t* sdst = reinterpret_cast<int32_t*>(lds + o.dst);
-  int32_t* stptr = reinterpret_cast<int32_t*>(lds + o.tptr);
-  int32_t* stperm = reinterpret_cast<int32_t*>(lds + o.tperm);
+  int32_t* ssrc = lds_i32(lds, o.t.src);
+  int32_t* sdst = lds_i32(lds, o.t.dst);
+  int32_t* stptr = lds_i32(lds, o.t.tptr);
+  int32_t* stperm = lds_i32(lds, o.t.tperm);
   // ONE batch of loads per thread, parked in registers: x, the loop edges, the list pointers — and, as soon as the
   // (scalar) edge range has arrived, this thread's edge of every edge array; only then the LDS stores.  The vector
   // loads of the first group are still in flight when the second group goes out: one round trip, not two.
@@ -205,97 +215,39 @@ __device__ __forceinline__ int sf_stage(float* lds, const SfLayout& o, int R, in
   }
 #pragma unroll
   for (int j = 0; j < 4; ++j)
-    if (tid + j * bd < nx) lds[o.x + tid + j * bd] = xv[j];
-  for (int i = tid + 4 * bd; i < nx; i += bd) lds[o.x + i] = x_in[nb * H0 + i];
-  for (int i = tid; i < R; i += bd) reinterpret_cast<int32_t*>(lds + o.loop)[i] = i == tid ? lp : loop_edge[nb + i];
+    if (tid + j * bd < nx) lds[o.t.x + tid + j * bd] = xv[j];
+  for (int i = tid + 4 * bd; i < nx; i += bd) lds[o.t.x + i] = x_in[nb * H0 + i];
+  for (int i = tid; i < R; i += bd) lds_i32(lds, o.n.loop)[i] = i == tid ? lp : loop_edge[nb + i];
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int i = tid + j * bd;
     if (i <= R) {
       stptr[i] = tp[j] - eb;
-      if (BWD) reinterpret_cast<int32_t*>(lds + o.sptr)[i] = sp[j] - eb;
+      if (BWD) lds_i32(lds, o.t.sptr)[i] = sp[j] - eb;
     }
   }
   for (int i = tid + 2 * bd; i <= R; i += bd) {
     stptr[i] = tgt_ptr[nb + i] - eb;
-    if (BWD) reinterpret_cast<int32_t*>(lds + o.sptr)[i] = src_ptr[nb + i] - eb;
+    if (BWD) lds_i32(lds, o.t.sptr)[i] = src_ptr[nb + i] - eb;
   }
   if (tid < ne) {
     ssrc[tid] = es - (int32_t)nb;
     sdst[tid] = ed - (int32_t)nb;
-    lds[o.ew + tid] = ev;
+    lds[o.t.ew + tid] = ev;
     stperm[tid] = et - eb;                         // by-target position eb + k holds edge tgt_perm[.] of this graph
-    if (BWD) reinterpret_cast<int32_t*>(lds + o.sperm)[tid] = ep - eb;
+    if (BWD) lds_i32(lds, o.t.sperm)[tid] = ep - eb;
   }
   for (int k = tid + bd; k < ne; k += bd) {
     ssrc[k] = src32[eb + k] - (int32_t)nb;
     sdst[k] = dst32[eb + k] - (int32_t)nb;
-    lds[o.ew + k] = ew_in[eb + k];
+    lds[o.t.ew + k] = ew_in[eb + k];
     stperm[k] = tgt_perm[eb + k] - eb;
-    if (BWD) reinterpret_cast<int32_t*>(lds + o.sperm)[k] = src_perm[eb + k] - eb;
+    if (BWD) lds_i32(lds, o.t.sperm)[k] = src_perm[eb + k] - eb;
   }
   __syncthreads();
   SF_PROBE(1);
-  sf_lists<BWD>(lds, o, R, ne, eb);
+  gcn_lists<BWD>(lds, o.t, o.n, R, ne, eb, bd);
   return ne;
-}
-
-// From the staged graph (local endpoints, weights, by-target pointers / permutation, loop edges — by-source ones too for
-// the backward) to the lists every layer walks.  Ends WITHOUT a barrier: the caller's next __syncthreads() orders the
-// coefficient arrays before their first use.
-template <bool BWD>
-__device__ __forceinline__ void sf_lists(float* lds, const SfLayout& o, int R, int ne, int32_t eb) {
-  const int tid = threadIdx.x;
-  int32_t* ssrc = reinterpret_cast<int32_t*>(lds + o.src);
-  int32_t* sdst = reinterpret_cast<int32_t*>(lds + o.dst);
-  int32_t* stptr = reinterpret_cast<int32_t*>(lds + o.tptr);
-  int32_t* stperm = reinterpret_cast<int32_t*>(lds + o.tperm);
-  // gcn_norm (PyG: drop stored loops, add one loop per node whose weight is the LAST stored loop's or 1), with the
-  // list entries laid out in BY-TARGET order (tsrc, twhat): every later walk of a target's list reads two consecutive
-  // arrays instead of chasing permutation -> edge -> endpoint.  Three short phases with a thread per list POSITION
-  // (360 of them) or per node — a thread per node walking its list through the permutation was a serial chain of
-  // dependent LDS reads on 90 of the 512 threads.
-  int32_t* stsrc = reinterpret_cast<int32_t*>(lds + o.tsrc);
-  for (int p = tid; p < ne; p += (int)blockDim.x) {
-    const int k = stperm[p];
-    const int sk = ssrc[k];
-    stsrc[p] = sk;
-    lds[o.twhat + p] = sk != sdst[k] ? lds[o.ew + k] : 0.f;      // stored loops are replaced by the added loop
-  }
-  __syncthreads();
-  for (int i = tid; i < R; i += (int)blockDim.x) {
-    float deg = 0.f;
-    for (int p = stptr[i]; p < stptr[i + 1]; ++p) deg += lds[o.twhat + p];     // list order (loops add an exact 0)
-    const int32_t le = reinterpret_cast<const int32_t*>(lds + o.loop)[i];
-    const float lw = le >= 0 ? lds[o.ew + (le - eb)] : 1.f;
-    deg += lw;
-    float d = 1.0f / sqrtf(deg);
-    if (deg == 0.f) d = 0.f;
-    lds[o.dis + i] = d;
-    lds[o.wl + i] = lw;
-    lds[o.wloop + i] = d * lw * d;
-  }
-  __syncthreads();
-  SF_PROBE(2);
-  for (int p = tid; p < ne; p += (int)blockDim.x)
-    lds[o.twhat + p] = lds[o.dis + stsrc[p]] * lds[o.twhat + p] * lds[o.dis + sdst[stperm[p]]];
-  if (BWD) {
-    for (int k = tid; k < ne; k += (int)blockDim.x) {
-      const int s = ssrc[k], t = sdst[k];
-      lds[o.what + k] = s != t ? lds[o.dis + s] * lds[o.ew + k] * lds[o.dis + t] : 0.f;
-    }
-    // the transposed lists (edges out of a source) in BY-SOURCE order, for dH = A_hat^T G
-    const int32_t* ssptr = reinterpret_cast<const int32_t*>(lds + o.sptr);
-    const int32_t* ssperm = reinterpret_cast<const int32_t*>(lds + o.sperm);
-    int32_t* sbdst = reinterpret_cast<int32_t*>(lds + o.bdst);
-    (void)ssptr;
-    for (int p = tid; p < ne; p += (int)blockDim.x) {  // a thread per list POSITION (the source of position p is the
-      const int k = ssperm[p];                          // source of the edge stored there)
-      const int i = ssrc[k], t = sdst[k];
-      sbdst[p] = t;
-      lds[o.bwhat + p] = t != i ? lds[o.dis + i] * lds[o.ew + k] * lds[o.dis + t] : 0.f;
-    }
-  }
 }
 
 // H = X W^T (X [R, fin], row stride ldx, at `xin`), then Y = relu(A_hat H + b) (row stride ldy): one layer, out of LDS
@@ -306,8 +258,8 @@ __device__ __forceinline__ void sf_layer(float* lds, const SfLayout& o, int R, i
   // Wt = the layer's weights TRANSPOSED in LDS (Wt[fi][fo], staged that way with the graph: the F lanes of a node
   // read consecutive words, not a stride-fin column), bt = its bias
   const int tid = threadIdx.x;
-  const int32_t* stptr = reinterpret_cast<const int32_t*>(lds + o.tptr);
-  const int32_t* stsrc = reinterpret_cast<const int32_t*>(lds + o.tsrc);
+  const int32_t* stptr = lds_i32(lds, o.t.tptr);
+  const int32_t* stsrc = lds_i32(lds, o.n.tsrc);
   // work item = (node, output quad): every LDS access moves 16 bytes (one weight-row quad serves four FMAs, one
   // gathered activation quad four more) — with one item per output word the phase is bound by the LDS instruction
   // rate, two 4-byte reads per FMA.  Dot products fully unrolled: the reads of an item are issued together.
@@ -345,24 +297,9 @@ __device__ __forceinline__ void sf_layer(float* lds, const SfLayout& o, int R, i
   __syncthreads();
   for (int e = tid; e < R * FQ; e += (int)blockDim.x) {
     const int i = e / FQ, q = e - i * FQ;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    const int p1 = stptr[i + 1];
-    for (int p = stptr[i]; p < p1; p += 4) {                 // stored order of the target's edges (reference order),
-      int sj[4];                                             // four entries per step: their reads overlap
-      float wj[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        sj[j] = stsrc[p + j];
-        wj[j] = lds[o.twhat + p + j];
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (p + j < p1) {
-          const float4 h4 = *reinterpret_cast<const float4*>(H + sj[j] * F + q * 4);
-          acc.x += wj[j] * h4.x; acc.y += wj[j] * h4.y; acc.z += wj[j] * h4.z; acc.w += wj[j] * h4.w;
-        }
-    }
-    const float wl = lds[o.wloop + i];
+    // stored order of the target's edges (reference order)
+    float4 acc = gcn_walk4(stsrc, lds + o.n.twhat, stptr[i], stptr[i + 1], H, F, q);
+    const float wl = lds[o.n.wloop + i];
     const float4 hs = *reinterpret_cast<const float4*>(H + i * F + q * 4);
     const float4 b4 = *reinterpret_cast<const float4*>(bt + q * 4);
     acc.x = fmaxf(acc.x + wl * hs.x + b4.x, 0.f);            // + self loop, + bias in the reference's order, ReLU
@@ -395,7 +332,7 @@ k_sgcn_stack_fwd(int R, int Emax, int H0, int L, const float* __restrict__ x_in,
   for (int l = 0; l < L; ++l) {
     // layer l owns columns [l F, (l+1) F) of the concatenated output rows and reads the columns of layer l-1
     const float* wl = sf_lds + o.wallT + l * (F * (F > H0 ? F : H0) + F);
-    sf_layer<F>(sf_lds, o, R, l == 0 ? H0 : F, l == 0 ? sf_lds + o.x : Y + (l - 1) * F, l == 0 ? H0 : D, H, Y + l * F, D,
+    sf_layer<F>(sf_lds, o, R, l == 0 ? H0 : F, l == 0 ? sf_lds + o.t.x : Y + (l - 1) * F, l == 0 ? H0 : D, H, Y + l * F, D,
                 wl, wl + F * (l == 0 ? H0 : F));
     SF_PROBE(4 + l);
   }
@@ -477,14 +414,14 @@ k_sgcn_front_fwd(int R, int Emax, int H0, int L, const SfFront fr, SfParams prm,
     return;
   }
   const int32_t eb = (int32_t)eb64;
-  int32_t* ssrc = reinterpret_cast<int32_t*>(lds + o.src);
-  int32_t* sdst = reinterpret_cast<int32_t*>(lds + o.dst);
-  int32_t* stptr = reinterpret_cast<int32_t*>(lds + o.tptr);
-  int32_t* stperm = reinterpret_cast<int32_t*>(lds + o.tperm);
-  int32_t* sloop = reinterpret_cast<int32_t*>(lds + o.loop);
-  int32_t* ct = reinterpret_cast<int32_t*>(lds + o.fct);
-  int32_t* cs = reinterpret_cast<int32_t*>(lds + o.fcs);
-  int32_t* ssperm = reinterpret_cast<int32_t*>(lds + o.fsperm);
+  int32_t* ssrc = lds_i32(lds, o.t.src);
+  int32_t* sdst = lds_i32(lds, o.t.dst);
+  int32_t* stptr = lds_i32(lds, o.t.tptr);
+  int32_t* stperm = lds_i32(lds, o.t.tperm);
+  int32_t* sloop = lds_i32(lds, o.n.loop);
+  int32_t* ct = lds_i32(lds, o.fct);
+  int32_t* cs = lds_i32(lds, o.fcs);
+  int32_t* ssperm = lds_i32(lds, o.fsperm);
   // ---- stage: one batch of loads per thread (edge endpoints, weight; node features and mask factors are on their way)
   int64_t es[2] = {0, 0}, ed[2] = {0, 0};
   float ev[2] = {0.f, 0.f};
@@ -522,7 +459,7 @@ k_sgcn_front_fwd(int R, int Emax, int H0, int L, const SfFront fr, SfParams prm,
       if (s < 0 || s >= R || d < 0 || d >= R) { bad = true; s = 0; d = 0; }
       ssrc[k] = (int32_t)s;
       sdst[k] = (int32_t)d;
-      lds[o.ew + k] = ev[j];
+      lds[o.t.ew + k] = ev[j];
     }
   }
   for (int k = tid + 2 * bd; k < ne; k += bd) {                   // graphs with more than 2 * 512 edges
@@ -530,15 +467,15 @@ k_sgcn_front_fwd(int R, int Emax, int H0, int L, const SfFront fr, SfParams prm,
     if (s < 0 || s >= R || d < 0 || d >= R) { bad = true; s = 0; d = 0; }
     ssrc[k] = (int32_t)s;
     sdst[k] = (int32_t)d;
-    lds[o.ew + k] = fr.ew[eb64 + k];
+    lds[o.t.ew + k] = fr.ew[eb64 + k];
   }
   if (bad) atomicOr(fr.status, 1);                                 // an edge leaves its graph: not a PyG batch
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int i = tid + j * bd;
-    if (i < nx) lds[o.x + i] = xv[j] * pv[j];                      // the masked copy's x * prob (plain: x * 1 = x)
+    if (i < nx) lds[o.t.x + i] = xv[j] * pv[j];                      // the masked copy's x * prob (plain: x * 1 = x)
   }
-  for (int i = tid + 4 * bd; i < nx; i += bd) lds[o.x + i] = fr.x[nb * H0 + i] * (copy ? fr.prob[i] : 1.f);
+  for (int i = tid + 4 * bd; i < nx; i += bd) lds[o.t.x + i] = fr.x[nb * H0 + i] * (copy ? fr.prob[i] : 1.f);
   __syncthreads();
   SF_PROBE(1);
   // ---- plan: histograms by target / by source, last stored loop per node
@@ -583,31 +520,31 @@ k_sgcn_front_fwd(int R, int Emax, int H0, int L, const SfFront fr, SfParams prm,
     ssperm[cs[ks] + rs] = k;
     if (copy) {
       float z = 0.f;
-      for (int h = 0; h < H0; ++h) z += lds[o.x + ks * H0 + h] * pbv[h];
-      for (int h = 0; h < H0; ++h) z += lds[o.x + kd * H0 + h] * pbv[H0 + h];
+      for (int h = 0; h < H0; ++h) z += lds[o.t.x + ks * H0 + h] * pbv[h];
+      for (int h = 0; h < H0; ++h) z += lds[o.t.x + kd * H0 + h] * pbv[H0 + h];
       const float p = 1.f / (1.f + expf(-z));
       lds[o.fe + k] = p;
       racc += em_reg_term(p, fr.l1_e, fr.ent_e, fr.eps) / (float)fr.n_edges;
     }
   }
   for (int i = tid; i <= R; i += bd) stptr[i] = ct[i];
-  for (int i = tid; i < R; i += bd) {                              // (sf_lists reads batch-global loop edge ids)
+  for (int i = tid; i < R; i += bd) {                              // (gcn_lists reads batch-global loop edge ids)
     const int32_t l = sloop[i];
     sloop[i] = l >= 0 ? eb + l : -1;
   }
   __syncthreads();
   SF_PROBE(3);
   if (copy)
-    for (int k = tid; k < ne; k += bd) lds[o.ew + k] = lds[o.ew + k] * lds[o.fe + k];     // ew * e
+    for (int k = tid; k < ne; k += bd) lds[o.t.ew + k] = lds[o.t.ew + k] * lds[o.fe + k];     // ew * e
   __syncthreads();
-  sf_lists<false>(lds, o, R, ne, eb);
+  gcn_lists<false>(lds, o.t, o.n, R, ne, eb, bd);
   SF_PROBE(4);          // (the first barrier inside sf_layer orders its lists before their use)
   float* H = lds + o.act;
   float* Y = lds + o.ycat;
   const int D = L * F;
   for (int l = 0; l < L; ++l) {
     const float* wl = lds + o.wallT + l * wstride;
-    sf_layer<F>(lds, o, R, l == 0 ? H0 : F, l == 0 ? lds + o.x : Y + (l - 1) * F, l == 0 ? H0 : D, H, Y + l * F, D, wl,
+    sf_layer<F>(lds, o, R, l == 0 ? H0 : F, l == 0 ? lds + o.t.x : Y + (l - 1) * F, l == 0 ? H0 : D, H, Y + l * F, D, wl,
                 wl + F * (l == 0 ? H0 : F));
   }
   SF_PROBE(5);
@@ -622,7 +559,7 @@ k_sgcn_front_fwd(int R, int Emax, int H0, int L, const SfFront fr, SfParams prm,
         for (int i = tid; i < fr.n_snps; i += bd)
           racc += em_reg_term(1.f / (1.f + expf(-fr.snps_logits[i])), fr.l1_x, fr.ent_x, fr.eps) / (float)fr.n_snps;
     }
-    racc = block_sum_all(racc, lds + o.dis);                       // (dis is dead behind the last layer)
+    racc = block_sum_all(racc, lds + o.n.dis);                       // (dis is dead behind the last layer)
     if (tid == 0) fr.reg_partial[g] = racc;
   }
   SF_PROBE(6);
@@ -630,9 +567,9 @@ k_sgcn_front_fwd(int R, int Emax, int H0, int L, const SfFront fr, SfParams prm,
   const int64_t nbo = (int64_t)copy * fr.n_nodes + nb, ebo = (int64_t)copy * fr.n_edges + eb64;
   for (int q = tid; q < R * D / 4; q += bd)
     reinterpret_cast<float4*>(xcat + nbo * D)[q] = reinterpret_cast<const float4*>(Y)[q];
-  for (int i = tid; i < nx; i += bd) fr.x_in[nbo * H0 + i] = lds[o.x + i];
+  for (int i = tid; i < nx; i += bd) fr.x_in[nbo * H0 + i] = lds[o.t.x + i];
   for (int k = tid; k < ne; k += bd) {
-    fr.ew_in[ebo + k] = lds[o.ew + k];
+    fr.ew_in[ebo + k] = lds[o.t.ew + k];
     if (copy) fr.e[eb64 + k] = lds[o.fe + k];
     const int32_t s = (int32_t)nb + ssrc[k], d = (int32_t)nb + sdst[k];
     const int32_t tp = eb + stperm[k], sp = eb + ssperm[k];
@@ -722,10 +659,7 @@ k_sgcn_stack_bwd(int R, int Emax, int H0, int L, const float* __restrict__ x_in,
     return;
   }
   SF_PROBE(9);
-  const int32_t* ssrc = reinterpret_cast<const int32_t*>(sf_lds + o.src);
-  const int32_t* sdst = reinterpret_cast<const int32_t*>(sf_lds + o.dst);
-  const int32_t* ssptr = reinterpret_cast<const int32_t*>(sf_lds + o.sptr);
-  const int32_t* ssperm = reinterpret_cast<const int32_t*>(sf_lds + o.sperm);
+  const int32_t* ssptr = lds_i32(sf_lds, o.t.sptr);
 #pragma unroll
   for (int j = 0; j < 2; ++j)
     if (tid + j * SF_TB < R * D / 4) reinterpret_cast<float4*>(sf_lds + o.dycat)[tid + j * SF_TB] = dyv[j];
@@ -742,12 +676,12 @@ k_sgcn_stack_bwd(int R, int Emax, int H0, int L, const float* __restrict__ x_in,
   float* Ycat = sf_lds + o.ycat;
   for (int l = 0; l < L; ++l) {
     const float* wl = sf_lds + o.wallT + l * (F * (F > H0 ? F : H0) + F);
-    sf_layer<F>(sf_lds, o, R, l == 0 ? H0 : F, l == 0 ? sf_lds + o.x : Ycat + (l - 1) * F, l == 0 ? H0 : D,
+    sf_layer<F>(sf_lds, o, R, l == 0 ? H0 : F, l == 0 ? sf_lds + o.t.x : Ycat + (l - 1) * F, l == 0 ? H0 : D,
                 sf_lds + o.act + l * R * F, Ycat + l * F, D, wl, wl + F * (l == 0 ? H0 : F));
   }
   SF_PROBE(10);
-  for (int k = tid; k < ne; k += SF_TB) sf_lds[o.dwhat + k] = 0.f;
-  for (int i = tid; i < R; i += SF_TB) sf_lds[o.dwloop + i] = 0.f;
+  for (int k = tid; k < ne; k += SF_TB) sf_lds[o.n.dwhat + k] = 0.f;
+  for (int i = tid; i < R; i += SF_TB) sf_lds[o.n.dwloop + i] = 0.f;
   float* G = sf_lds + o.g;
   float* dH = sf_lds + o.dh;
   float* dX = sf_lds + o.dx;
@@ -764,7 +698,7 @@ k_sgcn_stack_bwd(int R, int Emax, int H0, int L, const float* __restrict__ x_in,
     const int fin = l == 0 ? H0 : F;
     const float* H = sf_lds + o.act + l * R * F;
     const float* Y = Ycat + l * F;                     // row stride D
-    const float* xin = l == 0 ? sf_lds + o.x : Ycat + (l - 1) * F;
+    const float* xin = l == 0 ? sf_lds + o.t.x : Ycat + (l - 1) * F;
     const int ldx = l == 0 ? H0 : D;
     if (pend_off >= 0)                                 // dW of the layer above
       for (int e = tid; e < pend_n; e += SF_TB) {
@@ -790,64 +724,17 @@ k_sgcn_stack_bwd(int R, int Emax, int H0, int L, const float* __restrict__ x_in,
     const float* Wl = sf_lds + o.wall + l * (F * (F > H0 ? F : H0) + F);            // W_l [fo][fi] for dX = dH W
     __syncthreads();
     // dH = A_hat^T G (by-source lists, four entries per step); coefficient gradients accumulate over the layers
-    {
-      const int32_t* sbdst = reinterpret_cast<const int32_t*>(sf_lds + o.bdst);
-      for (int e = tid; e < R * FQ; e += SF_TB) {
-        const int sn = e / FQ, q = e - sn * FQ;
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-        const int p1 = ssptr[sn + 1];
-        for (int p = ssptr[sn]; p < p1; p += 4) {
-          int tj[4];
-          float wj[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            tj[j] = sbdst[p + j];
-            wj[j] = sf_lds[o.bwhat + p + j];
-          }
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (p + j < p1) {
-              const float4 g4 = *reinterpret_cast<const float4*>(G + tj[j] * F + q * 4);
-              acc.x += wj[j] * g4.x; acc.y += wj[j] * g4.y; acc.z += wj[j] * g4.z; acc.w += wj[j] * g4.w;
-            }
-        }
-        const float wl = sf_lds[o.wloop + sn];
-        const float4 gs = *reinterpret_cast<const float4*>(G + sn * F + q * 4);
-        acc.x += wl * gs.x; acc.y += wl * gs.y; acc.z += wl * gs.z; acc.w += wl * gs.w;
-        *reinterpret_cast<float4*>(dH + sn * F + q * 4) = acc;
-      }
+    for (int e = tid; e < R * FQ; e += SF_TB) {
+      const int sn = e / FQ, q = e - sn * FQ;
+      float4 acc = gcn_walk4(lds_i32(sf_lds, o.n.bdst), sf_lds + o.n.bwhat, ssptr[sn], ssptr[sn + 1], G, F, q);
+      const float wl = sf_lds[o.n.wloop + sn];
+      const float4 gs = *reinterpret_cast<const float4*>(G + sn * F + q * 4);
+      acc.x += wl * gs.x; acc.y += wl * gs.y; acc.z += wl * gs.z; acc.w += wl * gs.w;
+      *reinterpret_cast<float4*>(dH + sn * F + q * 4) = acc;
     }
-    for (int k = tid; k < ne + R; k += SF_TB) {          // per edge: G[dst] . H[src]; then per node: G[i] . H[i]
-      int sn, tn;
-      float* dstp;
-      if (k < ne) {
-        sn = ssrc[k];
-        tn = sdst[k];
-        if (sn == tn) continue;
-        dstp = sf_lds + o.dwhat + k;
-      } else {
-        sn = tn = k - ne;
-        dstp = sf_lds + o.dwloop + sn;
-      }
-      float acc = 0.f;
-#pragma unroll
-      for (int c = 0; c < FQ; ++c) {
-        const float4 g4 = *reinterpret_cast<const float4*>(G + tn * F + c * 4);
-        const float4 h4 = *reinterpret_cast<const float4*>(H + sn * F + c * 4);
-        acc += g4.x * h4.x;
-        acc += g4.y * h4.y;
-        acc += g4.z * h4.z;
-        acc += g4.w * h4.w;
-      }
-      *dstp += acc;
-    }
+    gcn_coef_grads(sf_lds, o.t, o.n, R, ne, G, H, F, FQ, SF_TB);
     constexpr int DB_PARTS = SF_TB / F < 16 ? SF_TB / F : 16;
-    if (tid < DB_PARTS * F) {                          // bias gradient: 16 thread groups share the node range
-      const int fo = tid % F, part = tid / F;
-      float acc = 0.f;
-      for (int i = part; i < R; i += DB_PARTS) acc += G[i * F + fo];
-      red_db[tid] = acc;
-    }
+    gcn_bias_partials(G, R, F, DB_PARTS, red_db);      // bias gradient: 16 thread groups share the node range
     __syncthreads();
     if (tid < F) {
       float acc = 0.f;
@@ -937,42 +824,9 @@ k_sgcn_stack_bwd(int R, int Emax, int H0, int L, const float* __restrict__ x_in,
   }
   SF_PROBE(13);
   // ---- gcn_norm backward (k_gcn_norm_bwd_deg / _edge of sgcn.hip, per graph)
-  const int32_t* stptr = reinterpret_cast<const int32_t*>(sf_lds + o.tptr);
-  const int32_t* stperm = reinterpret_cast<const int32_t*>(sf_lds + o.tperm);
-  // the two sums of a node — over the edges it sends (by-source list) and over those it receives (by-target list) —
-  // as products per list POSITION first (360 + 360 independent threads), then short sums of consecutive words per
-  // node: the node-per-thread form chased permutation -> edge -> endpoint through ~8 dependent LDS reads on 90 threads
-  float* v1 = sf_lds + o.v1;                            // [ne] by-source order
-  float* v2 = sf_lds + o.v2;                            // [ne] by-target order
-  const int32_t* sbdst2 = reinterpret_cast<const int32_t*>(sf_lds + o.bdst);
-  const int32_t* stsrc2 = reinterpret_cast<const int32_t*>(sf_lds + o.tsrc);
-  for (int p = tid; p < ne; p += SF_TB) {
-    const int k1 = ssperm[p], t = sbdst2[p];
-    v1[p] = t != ssrc[k1] ? sf_lds[o.dwhat + k1] * sf_lds[o.ew + k1] * sf_lds[o.dis + t] : 0.f;
-    const int k2 = stperm[p], sn = stsrc2[p];
-    v2[p] = sn != sdst[k2] ? sf_lds[o.dwhat + k2] * sf_lds[o.ew + k2] * sf_lds[o.dis + sn] : 0.f;
-  }
+  gcn_norm_bwd_products(sf_lds, o.t, o.n, ne, SF_TB);
   __syncthreads();
-  for (int i = tid; i < R; i += SF_TB) {
-    float dd = 0.f;
-    for (int p = ssptr[i]; p < ssptr[i + 1]; ++p) dd += v1[p];       // list order; stored loops add an exact 0
-    for (int p = stptr[i]; p < stptr[i + 1]; ++p) dd += v2[p];
-    const float di = sf_lds[o.dis + i];
-    dd += 2.f * sf_lds[o.dwloop + i] * sf_lds[o.wl + i] * di;
-    sf_lds[o.ddeg + i] = -0.5f * di * di * di * dd;
-  }
-  __syncthreads();
-  for (int k = tid; k < ne; k += SF_TB) {
-    const int s = ssrc[k], t = sdst[k];
-    float g;
-    if (s != t) {
-      g = sf_lds[o.dis + s] * sf_lds[o.dis + t] * sf_lds[o.dwhat + k] + sf_lds[o.ddeg + t];
-    } else {
-      g = (reinterpret_cast<const int32_t*>(sf_lds + o.loop)[s] == eb + k) ? sf_lds[o.ddeg + s] + sf_lds[o.dis + s] * sf_lds[o.dis + s] * sf_lds[o.dwloop + s]
-                                        : 0.f;
-    }
-    dew_in[eb + k] = g;
-  }
+  gcn_norm_bwd_edges(sf_lds, o.t, o.n, R, ne, eb, dew_in, SF_TB);
   for (int e = tid; e < R * H0; e += SF_TB) dx_in[nb * H0 + e] = dX[e];
   for (int e = tid; e < P; e += SF_TB) dpar_partial[(int64_t)blockIdx.x * P + e] = prow[e];
   SF_PROBE(14);

@@ -1,7 +1,8 @@
 // SGCN_Ori's graph stack (kernel/sgcn.py:111-138), LDS-resident: gcn_norm once, h1 = relu(GCNConv1(x)) [R, F1],
 // acts = GCNConv3(h1) [R, F3] WITHOUT ReLU (the Grad-CAM tap, final_conv_acts), h3 = relu(acts), and the head's input
 // row z = [h1 node-major | h3 node-major] written in place — ONE kernel per direction, one 512-thread workgroup per graph,
-// the phase structure of csrc/sgcn_fused.hip (whose thread count was measured there) with two layers of DIFFERENT width.
+// the phase structure of the uniform stack (csrc/sgcn_fused.hip, whose thread count was measured there) with two layers
+// of DIFFERENT width.  The staged graph, gcn_norm and the list walks of a layer are csrc/gcn_lds.h, shared with it.
 //
 // What differs from igcn_sgcn_stack_*: the two widths (3 -> 32 -> 5 by default) are independent and need not sit on
 // the 4 / 8 / 16 / 32 grid — inside LDS each is rounded up to a multiple of 4 (P1, P3: every access moves 16 bytes;
@@ -12,6 +13,7 @@
 // Same preconditions as the uniform stack: block-diagonal batch of uniform graphs on the per-graph plan; sums run in
 // the plan's stable by-target / by-source order, no atomics, deterministic.
 #include "common.h"
+#include "gcn_lds.h"
 
 #define SO_T 512
 #define SO_MAXH0 8
@@ -19,10 +21,11 @@
 #define SO_DB_PARTS 8         // thread groups that share the node range of a bias gradient
 
 struct SoLayout {
-  int x, dis, wl, wloop, ew, src, dst, tptr, tperm, tsrc, twhat, loop;      // the staged graph and its coefficients
+  GraphLds t;                                                               // the staged graph
+  GcnNormLds n;                                                             // gcn_norm: coefficients, lists, backward
   int w1t, b1, w3t, b3;                                                     // W1^T [H0][P1] | b1 [P1] | W3^T [P1][P3] | b3
   int h1, y1, h3, a;                                                        // transforms and layer outputs
-  int sptr, sperm, bdst, bwhat, w3, dy1, dy3, dh, dx0, dwhat, dwloop, ddeg, v1, v2, redb, redw, prow;   // backward
+  int w3, dy1, dy3, dh, dx0, redb, redw, prow;                              // backward
   int total;
 };
 
@@ -36,18 +39,8 @@ __host__ __device__ inline SoLayout so_layout(int R, int Emax, int H0, int F1, i
   int p = 0;
   auto take = [&](int n) { int q = p; p += (n + 3) & ~3; return q; };
   const int P1 = so_pad(F1), P3 = so_pad(F3), PM = P1 > P3 ? P1 : P3;
-  o.x = take(R * H0);
-  o.dis = take(R);
-  o.wl = take(R);
-  o.wloop = take(R);
-  o.ew = take(Emax);
-  o.src = take(Emax);
-  o.dst = take(Emax);
-  o.tptr = take(R + 1);
-  o.tperm = take(Emax);
-  o.tsrc = take(Emax + 4);                         // by-TARGET order (+4: the 4-wide list walk reads past the end)
-  o.twhat = take(Emax + 4);
-  o.loop = take(R);
+  graph_lds_layout(o.t, R, Emax, H0, take);
+  gcn_norm_layout(o.n, R, Emax, take);
   o.w1t = take(H0 * P1);
   o.b1 = take(P1);
   o.w3t = take(P1 * P3);
@@ -57,28 +50,20 @@ __host__ __device__ inline SoLayout so_layout(int R, int Emax, int H0, int F1, i
   o.h3 = backward ? take(R * P3) : o.h1;
   o.y1 = take(R * P1);
   o.a = take(R * P3);
-  o.sptr = o.sperm = o.bdst = o.bwhat = o.w3 = o.dy1 = o.dy3 = o.dh = o.dx0 = o.dwhat = o.dwloop = 0;
-  o.ddeg = o.v1 = o.v2 = o.redb = o.redw = o.prow = 0;
+  o.w3 = o.dy1 = o.dy3 = o.dh = o.dx0 = o.redb = o.redw = o.prow = 0;
   if (backward) {
-    o.sptr = take(R + 1);
-    o.sperm = take(Emax);
-    o.bdst = take(Emax + 4);                       // by-SOURCE order
-    o.bwhat = take(Emax + 4);
+    graph_lds_layout_bwd(o.t, R, Emax, take);
     o.w3 = take(P3 * P1);                          // W3 [fo][fi] as stored (padded): dX1 = dH3 W3
     o.dy1 = take(R * P1);                          // d z's h1 block, then G1 in place, then v1
     o.dy3 = take(R * P3);                          // d z's h3 block, then G3 = the gradient at the tap in place
     o.dh = take(R * PM);
     o.dx0 = take(R * H0);
-    o.dwhat = take(Emax);
-    o.dwloop = take(R);
-    o.ddeg = take(R);
-    // gcn_norm backward: per-position products (by-source / by-target order) — in G1 / the first transform, dead by
-    // then, when they fit
-    o.v1 = Emax <= R * P1 ? o.dy1 : take(Emax);
-    o.v2 = Emax <= R * P1 ? o.h1 : take(Emax);
     o.redb = take(SO_DB_PARTS * SO_MAXF);
     o.redw = take(2 * SO_T);                       // dW partials: parts * outputs <= 2 * SO_T (so_dw_parts)
     o.prow = take(so_param_floats(H0, F1, F3));
+    // gcn_norm backward's per-position products go into G1 / the first transform, dead by then, when they fit
+    const bool fits = Emax <= R * P1;
+    gcn_norm_layout_bwd(o.n, R, Emax, fits ? o.dy1 : -1, fits ? o.h1 : -1, take);
   }
   o.total = p;
   return o;
@@ -98,38 +83,17 @@ struct SoArgs {
   int32_t* status;
 };
 
-// Stage the graph and the weights, then gcn_norm and the by-target (backward: also by-source) lists — the arithmetic,
-// in the order, of sf_stage / sf_lists (csrc/sgcn_fused.hip).  Returns the edge count or -1 (status bit 1) when the
-// graph has more than Emax edges.  Ends WITHOUT a barrier behind the last list phase.
+// Stage the graph (graph_lds_load) and the weights, then gcn_norm and the by-target (backward: also by-source) lists
+// (gcn_lists).  Returns the edge count or -1 (status bit 1) for a refused graph.  Ends WITHOUT a barrier behind the
+// last list phase.
 template <bool BWD>
-__device__ __forceinline__ int so_stage(float* lds, const SoLayout& o, const SoArgs& a, int64_t nb, int32_t& eb_out) {
+__device__ __forceinline__ int so_stage(float* lds, const SoLayout& o, const SoArgs& a, int64_t nb, int32_t& eb) {
   const int tid = threadIdx.x, R = a.R, H0 = a.H0, F1 = a.F1, F3 = a.F3;
   const int P1 = so_pad(F1), P3 = so_pad(F3);
-  const int32_t eb = a.tgt_ptr[nb];
-  const int ne = a.tgt_ptr[nb + R] - eb;
-  eb_out = eb;
-  if (ne > a.Emax || ne < 0) {
-    if (tid == 0 && a.status) atomicOr(a.status, 2);
-    return -1;
-  }
-  int32_t* ssrc = reinterpret_cast<int32_t*>(lds + o.src);
-  int32_t* sdst = reinterpret_cast<int32_t*>(lds + o.dst);
-  int32_t* stptr = reinterpret_cast<int32_t*>(lds + o.tptr);
-  int32_t* stperm = reinterpret_cast<int32_t*>(lds + o.tperm);
-  int32_t* sloop = reinterpret_cast<int32_t*>(lds + o.loop);
-  for (int i = tid; i < R * H0; i += SO_T) lds[o.x + i] = a.x_in[nb * H0 + i];
-  for (int i = tid; i < R; i += SO_T) sloop[i] = a.loop_edge[nb + i];
-  for (int i = tid; i <= R; i += SO_T) {
-    stptr[i] = a.tgt_ptr[nb + i] - eb;
-    if (BWD) reinterpret_cast<int32_t*>(lds + o.sptr)[i] = a.src_ptr[nb + i] - eb;
-  }
-  for (int k = tid; k < ne; k += SO_T) {
-    ssrc[k] = a.src32[eb + k] - (int32_t)nb;
-    sdst[k] = a.dst32[eb + k] - (int32_t)nb;
-    lds[o.ew + k] = a.ew_in[eb + k];
-    stperm[k] = a.tgt_perm[eb + k] - eb;
-    if (BWD) reinterpret_cast<int32_t*>(lds + o.sperm)[k] = a.src_perm[eb + k] - eb;
-  }
+  const int ne = graph_lds_load<BWD>(lds, o.t, R, a.Emax, H0, nb, a.x_in, a.ew_in, a.src32, a.dst32, a.tgt_ptr,
+                                     a.tgt_perm, a.src_ptr, a.src_perm, a.status, eb, SO_T);
+  if (ne < 0) return -1;
+  for (int i = tid; i < R; i += SO_T) lds_i32(lds, o.n.loop)[i] = a.loop_edge[nb + i];
   // weights, transposed and padded: W1t[fi][fo] (fo < P1), W3t[fi][fo] (fi < P1, fo < P3); padding = 0
   for (int j = tid; j < H0 * P1; j += SO_T) {
     const int fi = j / P1, fo = j - fi * P1;
@@ -144,40 +108,7 @@ __device__ __forceinline__ int so_stage(float* lds, const SoLayout& o, const SoA
   }
   for (int j = tid; j < P3; j += SO_T) lds[o.b3 + j] = j < F3 ? a.b3[j] : 0.f;
   __syncthreads();
-  // gcn_norm (PyG: stored loops dropped, one loop per node added whose weight is the LAST stored loop's or 1)
-  int32_t* stsrc = reinterpret_cast<int32_t*>(lds + o.tsrc);
-  for (int p = tid; p < ne; p += SO_T) {
-    const int k = stperm[p];
-    const int sk = ssrc[k];
-    stsrc[p] = sk;
-    lds[o.twhat + p] = sk != sdst[k] ? lds[o.ew + k] : 0.f;
-  }
-  __syncthreads();
-  for (int i = tid; i < R; i += SO_T) {
-    float deg = 0.f;
-    for (int p = stptr[i]; p < stptr[i + 1]; ++p) deg += lds[o.twhat + p];     // list order (loops add an exact 0)
-    const int32_t le = sloop[i];
-    const float lw = le >= 0 ? lds[o.ew + (le - eb)] : 1.f;
-    deg += lw;
-    float d = 1.0f / sqrtf(deg);
-    if (deg == 0.f) d = 0.f;
-    lds[o.dis + i] = d;
-    lds[o.wl + i] = lw;
-    lds[o.wloop + i] = d * lw * d;
-  }
-  __syncthreads();
-  for (int p = tid; p < ne; p += SO_T)
-    lds[o.twhat + p] = lds[o.dis + stsrc[p]] * lds[o.twhat + p] * lds[o.dis + sdst[stperm[p]]];
-  if (BWD) {
-    const int32_t* ssperm = reinterpret_cast<const int32_t*>(lds + o.sperm);
-    int32_t* sbdst = reinterpret_cast<int32_t*>(lds + o.bdst);
-    for (int p = tid; p < ne; p += SO_T) {
-      const int k = ssperm[p];
-      const int i = ssrc[k], t = sdst[k];
-      sbdst[p] = t;
-      lds[o.bwhat + p] = t != i ? lds[o.dis + i] * lds[o.ew + k] * lds[o.dis + t] : 0.f;
-    }
-  }
+  gcn_lists<BWD>(lds, o.t, o.n, R, ne, eb, SO_T);
   return ne;
 }
 
@@ -218,34 +149,13 @@ __device__ __forceinline__ void so_transform(int R, int fin, const float* X, int
 template <bool RELU>
 __device__ __forceinline__ void so_aggregate(const float* lds, const SoLayout& o, int R, int P, const float* H,
                                              const float* bt, float* Y) {
-  const int32_t* stptr = reinterpret_cast<const int32_t*>(lds + o.tptr);
-  const int32_t* stsrc = reinterpret_cast<const int32_t*>(lds + o.tsrc);
+  const int32_t* stptr = lds_i32(lds, o.t.tptr);
+  const int32_t* stsrc = lds_i32(lds, o.n.tsrc);
   const int PQ = P >> 2;
   for (int e = threadIdx.x; e < R * PQ; e += SO_T) {
     const int i = e / PQ, q = e - i * PQ;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    const int p1 = stptr[i + 1];
-    for (int p = stptr[i]; p < p1; p += 4) {
-      const int s0 = stsrc[p], s1 = stsrc[p + 1], s2 = stsrc[p + 2], s3 = stsrc[p + 3];
-      const float c0 = lds[o.twhat + p], c1 = lds[o.twhat + p + 1], c2 = lds[o.twhat + p + 2], c3 = lds[o.twhat + p + 3];
-      {
-        const float4 h4 = *reinterpret_cast<const float4*>(H + s0 * P + q * 4);
-        acc.x += c0 * h4.x; acc.y += c0 * h4.y; acc.z += c0 * h4.z; acc.w += c0 * h4.w;
-      }
-      if (p + 1 < p1) {
-        const float4 h4 = *reinterpret_cast<const float4*>(H + s1 * P + q * 4);
-        acc.x += c1 * h4.x; acc.y += c1 * h4.y; acc.z += c1 * h4.z; acc.w += c1 * h4.w;
-      }
-      if (p + 2 < p1) {
-        const float4 h4 = *reinterpret_cast<const float4*>(H + s2 * P + q * 4);
-        acc.x += c2 * h4.x; acc.y += c2 * h4.y; acc.z += c2 * h4.z; acc.w += c2 * h4.w;
-      }
-      if (p + 3 < p1) {
-        const float4 h4 = *reinterpret_cast<const float4*>(H + s3 * P + q * 4);
-        acc.x += c3 * h4.x; acc.y += c3 * h4.y; acc.z += c3 * h4.z; acc.w += c3 * h4.w;
-      }
-    }
-    const float wl = lds[o.wloop + i];
+    float4 acc = gcn_walk4(stsrc, lds + o.n.twhat, stptr[i], stptr[i + 1], H, P, q);
+    const float wl = lds[o.n.wloop + i];
     const float4 hs = *reinterpret_cast<const float4*>(H + i * P + q * 4);
     const float4 b4 = *reinterpret_cast<const float4*>(bt + q * 4);
     acc.x = acc.x + wl * hs.x + b4.x; acc.y = acc.y + wl * hs.y + b4.y;
@@ -259,7 +169,7 @@ __device__ __forceinline__ void so_aggregate(const float* lds, const SoLayout& o
 
 // both layers out of LDS into LDS; ends behind a barrier
 __device__ __forceinline__ void so_forward(float* lds, const SoLayout& o, int R, int H0, int P1, int P3) {
-  so_transform<false>(R, H0, lds + o.x, H0, lds + o.w1t, P1, lds + o.h1);
+  so_transform<false>(R, H0, lds + o.t.x, H0, lds + o.w1t, P1, lds + o.h1);
   __syncthreads();                                 // (also orders the lists of so_stage before their first use)
   so_aggregate<true>(lds, o, R, P1, lds + o.h1, lds + o.b1, lds + o.y1);
   __syncthreads();
@@ -301,74 +211,22 @@ __device__ __forceinline__ int so_dw_parts(int nitems, int nout) {
   return parts > 16 ? 16 : (parts < 1 ? 1 : parts);
 }
 
-// One layer's walk of the transposed lists: dH = A_hat^T G (by-source order), the coefficient gradients
-// dwhat[k] += G[dst] . H[src], dwloop[i] += G[i] . H[i], and the bias-gradient partials.  No barrier inside.
+// One layer's walk of the transposed lists: dH = A_hat^T G (by-source order), the coefficient gradients and the
+// bias-gradient partials.  No barrier inside.
 __device__ __forceinline__ void so_layer_bwd_lists(float* lds, const SoLayout& o, int R, int ne, int P, const float* G,
                                                    const float* H, float* dH) {
-  const int tid = threadIdx.x;
-  const int32_t* ssrc = reinterpret_cast<const int32_t*>(lds + o.src);
-  const int32_t* sdst = reinterpret_cast<const int32_t*>(lds + o.dst);
-  const int32_t* ssptr = reinterpret_cast<const int32_t*>(lds + o.sptr);
-  const int32_t* sbdst = reinterpret_cast<const int32_t*>(lds + o.bdst);
+  const int32_t* ssptr = lds_i32(lds, o.t.sptr);
   const int PQ = P >> 2;
-  for (int e = tid; e < R * PQ; e += SO_T) {
+  for (int e = threadIdx.x; e < R * PQ; e += SO_T) {
     const int sn = e / PQ, q = e - sn * PQ;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    const int p1 = ssptr[sn + 1];
-    for (int p = ssptr[sn]; p < p1; p += 4) {
-      const int t0 = sbdst[p], t1 = sbdst[p + 1], t2 = sbdst[p + 2], t3 = sbdst[p + 3];
-      const float c0 = lds[o.bwhat + p], c1 = lds[o.bwhat + p + 1], c2 = lds[o.bwhat + p + 2], c3 = lds[o.bwhat + p + 3];
-      {
-        const float4 g4 = *reinterpret_cast<const float4*>(G + t0 * P + q * 4);
-        acc.x += c0 * g4.x; acc.y += c0 * g4.y; acc.z += c0 * g4.z; acc.w += c0 * g4.w;
-      }
-      if (p + 1 < p1) {
-        const float4 g4 = *reinterpret_cast<const float4*>(G + t1 * P + q * 4);
-        acc.x += c1 * g4.x; acc.y += c1 * g4.y; acc.z += c1 * g4.z; acc.w += c1 * g4.w;
-      }
-      if (p + 2 < p1) {
-        const float4 g4 = *reinterpret_cast<const float4*>(G + t2 * P + q * 4);
-        acc.x += c2 * g4.x; acc.y += c2 * g4.y; acc.z += c2 * g4.z; acc.w += c2 * g4.w;
-      }
-      if (p + 3 < p1) {
-        const float4 g4 = *reinterpret_cast<const float4*>(G + t3 * P + q * 4);
-        acc.x += c3 * g4.x; acc.y += c3 * g4.y; acc.z += c3 * g4.z; acc.w += c3 * g4.w;
-      }
-    }
-    const float wl = lds[o.wloop + sn];
+    float4 acc = gcn_walk4(lds_i32(lds, o.n.bdst), lds + o.n.bwhat, ssptr[sn], ssptr[sn + 1], G, P, q);
+    const float wl = lds[o.n.wloop + sn];
     const float4 gs = *reinterpret_cast<const float4*>(G + sn * P + q * 4);
     acc.x += wl * gs.x; acc.y += wl * gs.y; acc.z += wl * gs.z; acc.w += wl * gs.w;
     *reinterpret_cast<float4*>(dH + sn * P + q * 4) = acc;
   }
-  for (int k = tid; k < ne + R; k += SO_T) {          // per edge: G[dst] . H[src]; then per node: G[i] . H[i]
-    int sn, tn;
-    float* dstp;
-    if (k < ne) {
-      sn = ssrc[k];
-      tn = sdst[k];
-      if (sn == tn) continue;
-      dstp = lds + o.dwhat + k;
-    } else {
-      sn = tn = k - ne;
-      dstp = lds + o.dwloop + sn;
-    }
-    float acc = 0.f;
-    for (int c = 0; c < PQ; ++c) {
-      const float4 g4 = *reinterpret_cast<const float4*>(G + tn * P + c * 4);
-      const float4 h4 = *reinterpret_cast<const float4*>(H + sn * P + c * 4);
-      acc += g4.x * h4.x;
-      acc += g4.y * h4.y;
-      acc += g4.z * h4.z;
-      acc += g4.w * h4.w;
-    }
-    *dstp += acc;
-  }
-  if (tid < SO_DB_PARTS * P) {                       // (P <= 32: SO_DB_PARTS * P <= SO_T)
-    const int fo = tid % P, part = tid / P;
-    float acc = 0.f;
-    for (int i = part; i < R; i += SO_DB_PARTS) acc += G[i * P + fo];
-    lds[o.redb + tid] = acc;
-  }
+  gcn_coef_grads(lds, o.t, o.n, R, ne, G, H, P, PQ, SO_T);
+  gcn_bias_partials(G, R, P, SO_DB_PARTS, lds + o.redb);      // (P <= 32: SO_DB_PARTS * P <= SO_T)
 }
 
 __global__ void __launch_bounds__(SO_T)
@@ -400,8 +258,8 @@ k_sgcn_ori_bwd(const SoArgs a, const float* __restrict__ dz, const float* __rest
     const int i = e / P3, f = e - i * P3;
     lds[o.dy3 + e] = f < F3 ? dzrow[R * F1 + i * F3 + f] : 0.f;
   }
-  for (int k = tid; k < ne; k += SO_T) lds[o.dwhat + k] = 0.f;
-  for (int i = tid; i < R; i += SO_T) lds[o.dwloop + i] = 0.f;
+  for (int k = tid; k < ne; k += SO_T) lds[o.n.dwhat + k] = 0.f;
+  for (int i = tid; i < R; i += SO_T) lds[o.n.dwloop + i] = 0.f;
   so_forward(lds, o, R, H0, P1, P3);                   // both transforms kept (h1, h3), outputs in y1 / a
   float* prow = lds + o.prow;
   const int off_b1 = F1 * H0, off_w3 = off_b1 + F1, off_b3 = off_w3 + F3 * F1;
@@ -475,7 +333,7 @@ k_sgcn_ori_bwd(const SoArgs a, const float* __restrict__ dz, const float* __rest
       const int e = idx % n1, part = idx / n1;
       const int fo = e / H0, fi = e - fo * H0;
       float acc = 0.f;
-      for (int i = part; i < R; i += parts1) acc += dH[i * P1 + fo] * lds[o.x + i * H0 + fi];
+      for (int i = part; i < R; i += parts1) acc += dH[i * P1 + fo] * lds[o.t.x + i * H0 + fi];
       lds[o.redw + idx] = acc;
     }
     for (int e = tid; e < R * H0; e += SO_T) {        // d x_in[i, fi] = sum_fo dH1[i, fo] W1[fo, fi]
@@ -485,48 +343,15 @@ k_sgcn_ori_bwd(const SoArgs a, const float* __restrict__ dz, const float* __rest
       lds[o.dx0 + e] = acc;
     }
   }
-  // ---- gcn_norm backward (per list position first, then short sums per node: csrc/sgcn_fused.hip)
-  const int32_t* ssrc = reinterpret_cast<const int32_t*>(lds + o.src);
-  const int32_t* sdst = reinterpret_cast<const int32_t*>(lds + o.dst);
-  const int32_t* ssptr = reinterpret_cast<const int32_t*>(lds + o.sptr);
-  const int32_t* ssperm = reinterpret_cast<const int32_t*>(lds + o.sperm);
-  const int32_t* stptr = reinterpret_cast<const int32_t*>(lds + o.tptr);
-  const int32_t* stperm = reinterpret_cast<const int32_t*>(lds + o.tperm);
-  const int32_t* sbdst = reinterpret_cast<const int32_t*>(lds + o.bdst);
-  const int32_t* stsrc = reinterpret_cast<const int32_t*>(lds + o.tsrc);
-  for (int p = tid; p < ne; p += SO_T) {
-    const int k1 = ssperm[p], t = sbdst[p];
-    lds[o.v1 + p] = t != ssrc[k1] ? lds[o.dwhat + k1] * lds[o.ew + k1] * lds[o.dis + t] : 0.f;
-    const int k2 = stperm[p], sn = stsrc[p];
-    lds[o.v2 + p] = sn != sdst[k2] ? lds[o.dwhat + k2] * lds[o.ew + k2] * lds[o.dis + sn] : 0.f;
-  }
+  // ---- gcn_norm backward; dW1's partials meet between its two halves
+  gcn_norm_bwd_products(lds, o.t, o.n, ne, SO_T);
   __syncthreads();
   for (int e = tid; e < F1 * H0; e += SO_T) {          // dW1: rows fo < F1 of the padded partials
     float acc = 0.f;
     for (int p2 = 0; p2 < parts1; ++p2) acc += lds[o.redw + p2 * n1 + e];
     prow[e] = acc;
   }
-  for (int i = tid; i < R; i += SO_T) {
-    float dd = 0.f;
-    for (int p = ssptr[i]; p < ssptr[i + 1]; ++p) dd += lds[o.v1 + p];     // list order; stored loops add an exact 0
-    for (int p = stptr[i]; p < stptr[i + 1]; ++p) dd += lds[o.v2 + p];
-    const float di = lds[o.dis + i];
-    dd += 2.f * lds[o.dwloop + i] * lds[o.wl + i] * di;
-    lds[o.ddeg + i] = -0.5f * di * di * di * dd;
-  }
-  __syncthreads();
-  for (int k = tid; k < ne; k += SO_T) {
-    const int s = ssrc[k], t = sdst[k];
-    float g;
-    if (s != t) {
-      g = lds[o.dis + s] * lds[o.dis + t] * lds[o.dwhat + k] + lds[o.ddeg + t];
-    } else {
-      g = (reinterpret_cast<const int32_t*>(lds + o.loop)[s] == eb + k)
-              ? lds[o.ddeg + s] + lds[o.dis + s] * lds[o.dis + s] * lds[o.dwloop + s]
-              : 0.f;
-    }
-    dew_in[eb + k] = g;
-  }
+  gcn_norm_bwd_edges(lds, o.t, o.n, R, ne, eb, dew_in, SO_T);
   for (int e = tid; e < R * H0; e += SO_T) dx_in[nb * H0 + e] = lds[o.dx0 + e];
   for (int e = tid; e < NP; e += SO_T) dpar_partial[(int64_t)blockIdx.x * NP + e] = prow[e];
 }

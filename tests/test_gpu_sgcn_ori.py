@@ -233,6 +233,34 @@ def test_launches_are_deterministic_and_write_everything(widths, kind):
     assert torch.equal(a["z"], c["z"]) and torch.equal(a["dacts"], c["tap"].grads)
 
 
+@pytest.mark.parametrize("kind", ["r7", "r90x3"])
+@pytest.mark.parametrize("f1", [4, 8, 16, 32])
+def test_first_layer_equals_the_uniform_stack_bit_for_bit(f1, kind):
+    """Both stacks run gcn_norm and the by-target walk of csrc/gcn_lds.h and the same first transform, one workgroup per
+    graph, sums in list order: the h1 block of SgcnOriStack's z IS SgcnStack's output with L = 1, F = F1 on the same x,
+    edge weights, W1, b1 — equal bits, not a bound (measured equal on the commit that still had the two copies)."""
+    from igcn_amd import ops
+    from igcn_amd.data import Batch
+    h0, f3 = 3, 5
+    graphs, rois = _graph_set(kind, h0, seed=40 + f1)
+    batch = Batch.from_data_list(graphs).to("cuda")
+    plan = ops.plan_for(batch)
+    plan.check()
+    assert ops.sgcn_ori_supported(plan, rois, h0, f1, f3) and ops.sgcn_stack_supported(plan, rois, h0, f1, 1)
+    rng = np.random.default_rng(f1)
+    w1 = torch.from_numpy(rng.standard_normal((f1, h0)) / np.sqrt(h0)).float().cuda()
+    b1 = torch.from_numpy(0.3 * rng.standard_normal(f1)).float().cuda()
+    w3 = torch.from_numpy(rng.standard_normal((f3, f1)) / np.sqrt(f1)).float().cuda()
+    b3 = torch.from_numpy(0.3 * rng.standard_normal(f3)).float().cuda()
+    with torch.no_grad():
+        z, _ = ops.SgcnOriStack.apply(batch.x, batch.edge_attr, plan, rois, None, w1, b1, w3, b3)
+        y = ops.SgcnStack.apply(batch.x, batch.edge_attr, plan, rois, w1, b1)
+    plan.check()
+    h1 = z[:, :rois * f1].reshape(len(graphs) * rois, f1)
+    assert y.shape == h1.shape and int((h1 > 0).sum()) > 0 and int((h1 == 0).sum()) > 0
+    assert torch.equal(h1, y)
+
+
 def test_too_many_edges_sets_status_bit_1():
     from igcn_amd._lib import call, ptr, stream_ptr
     c = _stack_case((3, 5, 10), "r7")

@@ -166,6 +166,9 @@ def test_lds_sizes_and_param_floats():
     assert lib.igcn_sgcn_ori_lds_bytes(90, 270, 3, 32, 9, 1) > lib.igcn_sgcn_ori_lds_bytes(90, 270, 3, 32, 8, 1)
     assert lib.igcn_sgcn_ori_lds_bytes(90, 270, 3, 32, 5, 1) < lib.igcn_sgcn_ori_lds_bytes(90, 270, 3, 32, 32, 1) - 30000
     assert lib.igcn_sgcn_ori_param_floats(3, 32, 5) == 32 * 3 + 32 + 5 * 32 + 5
+    # its LDS sizes as they were before the staged-graph / gcn_norm layout moved to csrc/gcn_lds.h
+    assert [lib.igcn_sgcn_ori_lds_bytes(90, 270, 3, 32, 5, b) for b in (0, 1)] == [36976, 79680]
+    assert [lib.igcn_sgcn_ori_lds_bytes(7, 40, 3, 5, 10, b) for b in (0, 1)] == [2704, 10512]
     # the uniform stack keeps its LDS sizes (the values its build gave before this kernel existed)
     assert lib.igcn_sgcn_stack_lds_bytes(90, 270, 3, 16, 2, 0) == 30032
     assert lib.igcn_sgcn_stack_lds_bytes(90, 270, 3, 16, 2, 1) == 78528
