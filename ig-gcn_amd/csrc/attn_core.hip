@@ -2,7 +2,7 @@
 //   q  [B, Lq, H*HD]        = query projection          kv [B, Lk, 2, H*HD] = key|value projection (one GEMM)
 //   o  [B, Lq, H*HD]        = softmax(q k^T / sqrt(HD)) v  per head, heads concatenated (input of out_proj)
 // kernel/sgcn_img_snp.py:240 (nn.MultiheadAttention core).  This file is the C-ABI entry and the shape dispatch; the
-// kernels are in attn_mfma.hip (matrix cores, any head_dim <= 32): one workgroup per (sample, head) with K, V (and, in
+// kernels are in attn_mfma.hip (matrix cores, any head_dim <= 96): one workgroup per (sample, head) with K, V (and, in
 // the backward, Q and dO) of the head in LDS, or — when those do not fit — chunked variants that stream the other side
 // of the attention through LDS.  [Round 1's VALU kernels, reachable only through an A/B switch since the matrix-core
 // path covered every shape they did, are removed.]
@@ -46,9 +46,9 @@ static bool use_resident(int D, int H, int Lq, int Lk) {
   return H > 0 && Lq > 0 && Lk > 0 && igcn_attn_mfma_lds_bytes(D, H, Lq, Lk, 1) != 0;
 }
 
-// ... or do not: the chunked kernels stream them (head_dim <= 32)
+// ... or do not: the chunked kernels stream them (head_dim <= 96)
 static bool use_chunked(int D, int H, int Lq, int Lk) {
-  return H > 0 && D > 0 && D % H == 0 && D / H <= 32 && Lq > 0 && Lk > 0 && !use_resident(D, H, Lq, Lk) &&
+  return H > 0 && D > 0 && D % H == 0 && D / H <= 96 && Lq > 0 && Lk > 0 && !use_resident(D, H, Lq, Lk) &&
          igcn_attn_mfma_lds_bytes(D, H, 16, 16, 1) != 0;
 }
 
@@ -56,7 +56,7 @@ extern "C" size_t igcn_attn_core_bwd_scratch_floats(int B, int H, int Lq) {
   return igcn_attn_mfma_chunked_scratch_floats(B, H, Lq);
 }
 
-// dynamic LDS bytes needed, or 0 when the shape is not covered (head_dim > 32)
+// dynamic LDS bytes needed, or 0 when the shape is not covered (head_dim > 96)
 extern "C" size_t igcn_attn_core_lds_bytes(int D, int H, int Lq, int Lk, int backward) {
   if (use_resident(D, H, Lq, Lk)) return igcn_attn_mfma_lds_bytes(D, H, Lq, Lk, backward);
   if (use_chunked(D, H, Lq, Lk)) return 96 * 1024;               // streamed in ~96 KB chunks
@@ -69,7 +69,7 @@ extern "C" int igcn_attn_core_fwd(int B, int D, int H, int Lq, int Lk, const flo
   if (use_resident(D, H, Lq, Lk)) return igcn_attn_mfma_fwd(B, D, H, Lq, Lk, q, kv, o, lse, (hipStream_t)stream);
   if (use_chunked(D, H, Lq, Lk))
     return igcn_attn_mfma_fwd_chunked(B, D, H, Lq, Lk, q, kv, o, lse, (hipStream_t)stream);
-  igcn_set_error("attn_core_fwd: unsupported shape D=%d H=%d Lq=%d Lk=%d (head_dim <= 32)", D, H, Lq, Lk);
+  igcn_set_error("attn_core_fwd: unsupported shape D=%d H=%d Lq=%d Lk=%d (head_dim <= 96)", D, H, Lq, Lk);
   return IGCN_ERR_UNSUPPORTED;
 }
 
@@ -85,6 +85,6 @@ extern "C" int igcn_attn_core_bwd(int B, int D, int H, int Lq, int Lk, const flo
     IGCN_REQUIRE(scratch != nullptr, "attn_core_bwd: this shape needs igcn_attn_core_bwd_scratch_floats() of scratch");
     return igcn_attn_mfma_bwd_chunked(B, D, H, Lq, Lk, q, kv, o, lse, dout, dq, dkv, scratch, (hipStream_t)stream);
   }
-  igcn_set_error("attn_core_bwd: unsupported shape D=%d H=%d Lq=%d Lk=%d (head_dim <= 32)", D, H, Lq, Lk);
+  igcn_set_error("attn_core_bwd: unsupported shape D=%d H=%d Lq=%d Lk=%d (head_dim <= 96)", D, H, Lq, Lk);
   return IGCN_ERR_UNSUPPORTED;
 }

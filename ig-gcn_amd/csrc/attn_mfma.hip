@@ -1,8 +1,9 @@
 // Cross-attention core on the CDNA4 matrix cores (exact-fp32 v_mfma_f32_16x16x4_f32), in place on the projection
 // outputs like attn_core.hip:   q [B,Lq,H*hd]   kv [B,Lk,2,H*hd]   o [B,Lq,H*hd]
 // (kernel/sgcn_img_snp.py:240, the nn.MultiheadAttention core; softmax(q k^T / sqrt(hd)) v per head).
-// Any head_dim up to 32: the head's columns are zero-padded in LDS to HDP = the next multiple of 4 (template
-// parameter; 10 -> 12, 15 -> 16, 24 -> 24 ...), the output / gradient tiles to multiples of 16 rows.
+// Any head_dim up to 96: the head's columns are zero-padded in LDS to HDP (template parameter) = the next multiple of 4
+// up to 32 (10 -> 12, 15 -> 16, 24 -> 24 ...) and the next multiple of 16 above (33 -> 48, 64 -> 64, 80 -> 80, 96: four
+// widths per kernel instead of sixteen), the output / gradient tiles to multiples of 16 rows.
 //
 // Layout trick (no cross-lane transposes, no LDS round trip for the probabilities): a 16x16 score tile is computed
 // TRANSPOSED, S^T = K_tile Q_tile^T, so that in the MFMA accumulator layout lane (g = l>>4, n = l&15) holds
@@ -17,6 +18,12 @@
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #define AM_MAX_WAVES 16
+// Backward kernels of the wide heads (HDP 48..96: NO = HDP / 16 accumulator tiles for each of dK and dV next to 2 * HDP / 4
+// operand registers) do not fit the 128 registers a 16-wave workgroup leaves a lane.  Their launches never ask for more
+// than AM_BWD_MAX_WAVES = 8 waves (the clamps at the launch sites use the same constant), so they declare 8: a
+// 256-register budget, zero scratch.  HDP <= 32 keeps the 16-wave bound it had.
+#define AM_BWD_MAX_WAVES 8
+#define AM_BWD_THREADS(HDP) (64 * ((HDP) > 32 ? AM_BWD_MAX_WAVES : AM_MAX_WAVES))
 
 __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
@@ -31,7 +38,7 @@ __device__ __forceinline__ void am_stage(const float* __restrict__ src, int64_t 
   for (int t = threadIdx.x; t < rows_pad * NQ; t += blockDim.x) {
     const int j = t / NQ, c = (t % NQ) * 4;
     float v[4] = {0.f, 0.f, 0.f, 0.f};
-    if (j < rows_valid) {
+    if (j < rows_valid && (HDP <= 32 || c < hd)) {              // (HDP > 32: see am_stage_pair)
       const float* p = src + (int64_t)j * row_stride + c;
       if (vec) {
         const float4 t4 = *reinterpret_cast<const float4*>(p);
@@ -67,7 +74,9 @@ __device__ __forceinline__ void am_stage_pair(const float* __restrict__ src_a, c
       const int t = t0 + u * step, j = t / NQ, c = (t % NQ) * 4;
 #pragma unroll
       for (int e = 0; e < 4; ++e) va[u][e] = vb[u][e] = 0.f;
-      if (t < total && j < rows_valid) {
+      // HDP > 32 pads to 16 columns, so a vec head (head_dim % 4 == 0) can end before HDP: the 16-byte slots past it
+      // belong to the next head (or the next row) and stay zero.  Up to 32, vec means head_dim == HDP.
+      if (t < total && j < rows_valid && (HDP <= 32 || c < hd)) {
         const float* pa = src_a + (int64_t)j * row_stride + c;
         const float* pb = src_b + (int64_t)j * row_stride + c;
         if (vec) {
@@ -260,7 +269,7 @@ k_attn_mfma_fwd(int H, int hd_rt, int vec_rt, int Lq, int Lk, const float* __res
 
 // backward: dq [B,Lq,D], dkv [B,Lk,2,D]
 template <int HDP, bool EXACT>
-__global__ void __launch_bounds__(64 * AM_MAX_WAVES)
+__global__ void __launch_bounds__(AM_BWD_THREADS(HDP))
 k_attn_mfma_bwd(int H, int hd_rt, int vec_rt, int Lq, int Lk, const float* __restrict__ q,
                 const float* __restrict__ kv, const float* __restrict__ o, const float* __restrict__ lse,
                 const float* __restrict__ dout, float* __restrict__ dq, float* __restrict__ dkv, int items) {
@@ -282,7 +291,7 @@ k_attn_mfma_bwd(int H, int hd_rt, int vec_rt, int Lq, int Lk, const float* __res
   const float* qbase = q + (int64_t)b * Lq * D + h * hd;
   const float* dobase = dout + (int64_t)b * Lq * D + h * hd;
   // delta = rowsum(o * do) and lse: thread r's row, requested ahead of the staging passes (same reason as there)
-  {
+  if constexpr (HDP <= 32) {
     const int r = threadIdx.x;
     float orow[HDP], drow[HDP], lv = INFINITY;
     const bool mine = r < Lqp, live = r < Lq;
@@ -326,6 +335,30 @@ k_attn_mfma_bwd(int H, int hd_rt, int vec_rt, int Lq, int Lk, const float* __res
       }
       dl[r2] = d;
       ls[r2] = l2;
+    }
+  } else {
+    // wide heads: two whole rows (2 * HDP registers) cannot wait in a lane across the staging; the rows are summed
+    // four columns at a time behind it instead (o from global, dO from lines the staging has just pulled into L2)
+    am_stage_pair<HDP>(kbase, kbase + D, 2 * D, hd, vec, Lk, Lkp, Ks, Vs);
+    am_stage_pair<HDP>(qbase, dobase, D, hd, vec, Lq, Lqp, Qs, dOs);
+    for (int r = threadIdx.x; r < Lqp; r += blockDim.x) {
+      float d = 0.f, lv = INFINITY;
+      if (r < Lq) {
+        const float* op = o + (int64_t)(b * Lq + r) * D + h * hd;
+        const float* dp = dobase + (int64_t)r * D;
+        if (vec) {                                              // head_dim % 4 == 0, 16-byte aligned rows
+#pragma unroll 4
+          for (int c = 0; c < hd; c += 4) {
+            const float4 a = *reinterpret_cast<const float4*>(op + c), d4 = *reinterpret_cast<const float4*>(dp + c);
+            d += a.x * d4.x + a.y * d4.y + a.z * d4.z + a.w * d4.w;
+          }
+        } else {
+          for (int c = 0; c < hd; ++c) d += op[c] * dp[c];
+        }
+        lv = lse[((int64_t)b * H + h) * Lq + r];
+      }
+      dl[r] = d;
+      ls[r] = lv;
     }
   }
   if (threadIdx.x == 0) *next_task = 0;
@@ -584,7 +617,7 @@ k_attn_mfma_bwd_shared(int H, int Lq, int Lk, const float* __restrict__ q, const
   }
 }
 
-static int am_hdp(int hd) { return (hd + 3) & ~3; }
+static int am_hdp(int hd) { return hd <= 32 ? (hd + 3) & ~3 : (hd + 15) & ~15; }
 
 static size_t am_lds_bytes(int hd, int Lq, int Lk, int backward) {
   const size_t Lkp = (size_t)((Lk + 15) & ~15), Lqp = (size_t)((Lq + 15) & ~15);
@@ -594,11 +627,11 @@ static size_t am_lds_bytes(int hd, int Lq, int Lk, int backward) {
   return fl * sizeof(float);
 }
 
-// 0 when the MFMA path does not cover the shape (head_dim 1..32; K, V (+ Q, dO) of one head must fit LDS)
+// 0 when the MFMA path does not cover the shape (head_dim 1..96; K, V (+ Q, dO) of one head must fit LDS)
 size_t igcn_attn_mfma_lds_bytes(int D, int H, int Lq, int Lk, int backward) {
   if (H <= 0 || D <= 0 || D % H || Lq <= 0 || Lk <= 0) return 0;
   const int hd = D / H;
-  if (hd > 32) return 0;
+  if (hd > 96) return 0;
   const size_t bytes = am_lds_bytes(hd, Lq, Lk, backward);
   return bytes <= 150 * 1024 ? bytes : 0;
 }
@@ -611,7 +644,8 @@ static int am_vec(int D, int hd, const void* a, const void* b, const void* c, co
 #define AM_DISPATCH(hdp, CALL)                                                                    \
   switch (hdp) {                                                                                   \
     case 4: CALL(4); break;   case 8: CALL(8); break;   case 12: CALL(12); break; case 16: CALL(16); break; \
-    case 20: CALL(20); break; case 24: CALL(24); break; case 28: CALL(28); break; default: CALL(32); break; \
+    case 20: CALL(20); break; case 24: CALL(24); break; case 28: CALL(28); break; case 48: CALL(48); break; \
+    case 64: CALL(64); break; case 80: CALL(80); break; case 96: CALL(96); break; default: CALL(32); break; \
   }
 
 int igcn_attn_mfma_fwd(int B, int D, int H, int Lq, int Lk, const float* q, const float* kv, float* o, float* lse,
@@ -643,9 +677,10 @@ int igcn_attn_mfma_bwd(int B, int D, int H, int Lq, int Lk, const float* q, cons
                        const float* lse, const float* dout, float* dq, float* dkv, hipStream_t st) {
   const int hd = D / H;
   const size_t lds = am_lds_bytes(hd, Lq, Lk, 1);
-  const int vec = am_vec(D, hd, q, kv, dout, dq) && (uintptr_t)dkv % 16 == 0;
+  // (o too: the kernel reads its rows 16 bytes at a time for delta)
+  const int vec = am_vec(D, hd, q, kv, dout, dq) && (uintptr_t)dkv % 16 == 0 && (uintptr_t)o % 16 == 0;
   const int tasks = (Lq + 15) / 16 + (Lk + 15) / 16;
-  const int waves = tasks < 8 ? (tasks < 4 ? 4 : tasks) : 8;
+  const int waves = tasks < AM_BWD_MAX_WAVES ? (tasks < 4 ? 4 : tasks) : AM_BWD_MAX_WAVES;
   {
     // shared score tiles: head_dim 16 with 16-byte rows, <= 8 query tiles, >= 8 key tiles, partials fit over K | V
     const int nqt = (Lq + 15) / 16, nkt = (Lk + 15) / 16;
@@ -756,7 +791,7 @@ k_attn_mfma_fwd_chunked(int H, int hd, int vec, int Lq, int Lk, int CH, const fl
 }
 
 template <int HDP>
-__global__ void __launch_bounds__(64 * AM_MAX_WAVES)
+__global__ void __launch_bounds__(AM_BWD_THREADS(HDP))
 k_attn_mfma_bwd_dq_chunked(int H, int hd, int vec, int Lq, int Lk, int CH, const float* __restrict__ q,
                            const float* __restrict__ kv, const float* __restrict__ o, const float* __restrict__ lse,
                            const float* __restrict__ dout, float* __restrict__ dq, float* __restrict__ delta) {
@@ -824,7 +859,7 @@ k_attn_mfma_bwd_dq_chunked(int H, int hd, int vec, int Lq, int Lk, int CH, const
 }
 
 template <int HDP>
-__global__ void __launch_bounds__(64 * AM_MAX_WAVES)
+__global__ void __launch_bounds__(AM_BWD_THREADS(HDP))
 k_attn_mfma_bwd_dkv_chunked(int H, int hd, int vec, int Lq, int Lk, int CH, const float* __restrict__ q,
                             const float* __restrict__ kv, const float* __restrict__ lse,
                             const float* __restrict__ dout, const float* __restrict__ delta,
@@ -946,7 +981,8 @@ int igcn_attn_mfma_bwd_chunked(int B, int D, int H, int Lq, int Lk, const float*
   const size_t lds_q = (size_t)2 * chk * ld * sizeof(float);
   const size_t lds_k = ((size_t)2 * chq * ld + 2 * chq) * sizeof(float);
   const int nqt = (Lq + 15) / 16, nkt = (Lk + 15) / 16;
-  const int nwq = nqt < 8 ? (nqt < 4 ? 4 : nqt) : 8, nwk = nkt < 8 ? (nkt < 4 ? 4 : nkt) : 8;
+  const int nwq = nqt < AM_BWD_MAX_WAVES ? (nqt < 4 ? 4 : nqt) : AM_BWD_MAX_WAVES;
+  const int nwk = nkt < AM_BWD_MAX_WAVES ? (nkt < 4 ? 4 : nkt) : AM_BWD_MAX_WAVES;
   dim3 gq(B * H, (nqt + nwq - 1) / nwq), gk(B * H, (nkt + nwk - 1) / nwk);
 #define CALL(HDPV)                                                                                               \
   {                                                                                                              \

@@ -307,8 +307,9 @@ class SGCN_GCN_IMGSNP(torch.nn.Module):
     def _cross_attention(self, query, memory, relu_owed=False, defer_out_proj=False):
         """relu(nn.MultiheadAttention(D, 2, batch_first=True)(query, memory, memory)[0]) (:240-241) with the
         parameters of ``self.multihead_attn``: MFMA-GEMM projections (key and value as one GEMM) around the attention
-        core igcn_attn_core_*, which works on the projection outputs in place (head_dim 16: matrix cores); shapes the
-        core does not cover use a batched GEMM + softmax composite."""
+        core igcn_attn_core_*, which works on the projection outputs in place (matrix cores, head_dim <= 96: the
+        attention of every row of the reference's sweeps — the hidden-32 rows stop earlier, in the GO read-out: DESIGN.md
+        section 8); wider heads use a batched GEMM + softmax composite."""
         mha = self.multihead_attn
         d, h = mha.embed_dim, mha.num_heads
         b, lq, lk = query.shape[0], query.shape[1], memory.shape[1]
@@ -319,7 +320,7 @@ class SGCN_GCN_IMGSNP(torch.nn.Module):
             # deferrable partial sums), key / value bias gradients in closed form
             o = ops.ProjectedAttention.apply(query, memory, w, bias, h, bf)
         else:
-            # head_dim > 32 (outside the core's coverage): plain batched-GEMM + softmax composite.  Deliberately not
+            # head_dim > 96 (outside the core's coverage): plain batched-GEMM + softmax composite.  Deliberately not
             # the library's fused SDPA kernels (known issues)
             q, kv = ops.InProj.apply(query, memory, w, bias, bf)             # [B, Lq, D], [B, Lk, 2D] = key | value
             hd = d // h

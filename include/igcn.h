@@ -762,11 +762,11 @@ int igcn_gram_loss_fwd_rbf_unit(int B, int RD, int groups, const float* G, const
  *   o [B,Lq,D] = per head softmax(q k^T / sqrt(head_dim)) v, heads concatenated; lse [B,H,Lq] saved for the backward
  * One workgroup per (sample, head); no head transposes or contiguous copies on either side.  The backward returns
  * dq [B,Lq,D] and dkv [B,Lk,2,D] in the layouts the projection-gradient GEMMs read.
- * head_dim <= 32 runs on the matrix cores (exact-fp32 MFMA, any Lq, head columns zero-padded to a multiple of 4 in
- * LDS); when K, V — and Q, dO in the backward — of one head fit LDS one workgroup per (sample, head) keeps them
- * resident, otherwise the other side of the attention is streamed through LDS in chunks (512 queries x 1300 keys of
- * the 512-ROI configuration).  A VALU kernel (head_dim in {4,..,24} step 4, Lq <= 256) remains for A/B runs.
- * igcn_attn_core_lds_bytes: dynamic LDS needed, 0 = shape not covered.
+ * head_dim <= 96 runs on the matrix cores (exact-fp32 MFMA, any Lq; head columns zero-padded in LDS to a multiple of 4
+ * up to 32 and to 48 / 64 / 80 / 96 above); when K, V — and Q, dO in the backward — of one head fit LDS one workgroup
+ * per (sample, head) keeps them resident, otherwise the other side of the attention is streamed through LDS in chunks
+ * (512 queries x 1300 keys of the 512-ROI configuration; every head wider than 32 at the model's 90 x 400).
+ * igcn_attn_core_lds_bytes: dynamic LDS needed (96 KB = the streamed form), 0 = shape not covered (head_dim > 96).
  */
 size_t igcn_attn_core_lds_bytes(int D, int H, int Lq, int Lk, int backward);
 size_t igcn_attn_core_bwd_scratch_floats(int B, int H, int Lq);
