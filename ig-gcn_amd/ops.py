@@ -2796,6 +2796,8 @@ class HeadLoss(torch.autograd.Function):
             raise _lib.IgcnError("head loss: inconsistent shapes")
         dev = lin_f.device
         lib = _lib.load()
+        if not lib.igcn_head_loss_supported(k, c, nr):
+            raise _lib.IgcnError(f"head loss: K/4 a power of two <= 64 and C, NR <= 4 (K={k} C={c} NR={nr})")
         f32 = dict(dtype=torch.float32, device=dev)
         nblk = int(lib.igcn_head_loss_blocks(b, k))
         out8 = torch.empty(8, **f32)
@@ -2846,13 +2848,15 @@ class HeadLoss(torch.autograd.Function):
         dwb = _keep(torch.empty(wcols, dtype=torch.float32, device=dev))
         _keep(wpart)
         o1, o2 = c * k + c, nr * k + nr
-        with _immediate(ctx.w_final[0]):
-            call("igcn_reduce_rows_final", ptr(wpart), nblk, wcols, o1, ptr(dwb), stream_ptr())
-        with _immediate(ctx.w_final[1]):
-            call("igcn_reduce_rows_final", wpart.data_ptr() + 4 * o1, nblk, wcols, o2, ptr(dwb[o1:]), stream_ptr())
         gout = _f32(gout).reshape(1)
+        unit = gout.data_ptr() in UNIT_GRAD_PTRS
+        # (another upstream gradient scales the sums below: they are then needed here, not at the flush)
+        with _immediate(ctx.w_final[0] and unit):
+            call("igcn_reduce_rows_final", ptr(wpart), nblk, wcols, o1, ptr(dwb), stream_ptr())
+        with _immediate(ctx.w_final[1] and unit):
+            call("igcn_reduce_rows_final", wpart.data_ptr() + 4 * o1, nblk, wcols, o2, ptr(dwb[o1:]), stream_ptr())
         UNIT_DGRAM.clear()
-        if gout.data_ptr() in UNIT_GRAD_PTRS:
+        if unit:
             UNIT_DGRAM[dgram.data_ptr()] = unit_dgram(lam)
         else:                                        # every gradient is linear in the upstream one
             dx1, dx2, dxhat, dgram, dprob, dwb = (t * gout for t in (dx1, dx2, dxhat, dgram, dprob, dwb))

@@ -55,16 +55,19 @@ def _loader(graphs, bsz=8):
 ROWS = ("logp", "pred", "y", "reg", "clini_score", "out_lin", "linear_outf", "sbjID")
 
 
-def test_evaluate_matches_the_eager_eval_functions_and_the_oracle():
-    """20 graphs at batch 8: two full batches and a ragged tail (two batch shapes, the full one captured)."""
+@pytest.mark.parametrize("classes,regr", [(3, 3), (2, 4)])
+def test_evaluate_matches_the_eager_eval_functions_and_the_oracle(classes, regr):
+    """20 graphs at batch 8: two full batches and a ragged tail (two batch shapes, the full one captured) — with three
+    classes and three regression targets, and with the trainer's heads (two classes, four targets)."""
     from igcn_amd import synth
     from igcn_amd.data import Batch
     from igcn_amd.train import eval_acc, eval_loss, eval_outputs, evaluate
     from oracle import go_network as OG, sgcn_img_snp as OS
-    model, (go_snps, adj) = _model()
-    graphs = _graphs()
+    model, (go_snps, adj) = _model(classes, regr)
+    graphs = _graphs(num_classes=classes, num_regr=regr)
     loader = _loader(graphs)
-    got = evaluate(model, loader, LAM, device="cuda")
+    got = evaluate(model, loader, LAM, device="cuda", num_classes=classes, num_regr=regr)
+    assert got["logp"].shape == (20, classes) and got["reg"].shape == (20, regr)
     loss = eval_loss(model, loader, LAM, device="cuda")
     acc = eval_acc(model, loader, device="cuda")
     outs = eval_outputs(model, loader, device="cuda")

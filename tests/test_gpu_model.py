@@ -298,10 +298,13 @@ def test_full_model_vs_oracle_larger(bsz, pool, explain):
 
 def train_mode_vs_oracle(monkeypatch, rois, pool, bsz, dense=False, bf16=False, maps=("sparse", "default"),
                          graph_seed=78, go_seed=1, tol=1e-4, gtol=1e-3, max_flips=40, band=2e-5, formulations=(True, False),
-                         layers=2, hidden=16, h0=3, dropout=False, controls=False):
+                         layers=2, hidden=16, h0=3, dropout=False, controls=False, num_classes=3, num_regr=3, lam=None):
     """TRAINING mode (batch statistics in every BatchNorm) of the HIP model against the fp64 oracle: the seven loss
     terms of train() at ``tol`` and every gradient at ``gtol``, for the step formulations ``formulations`` (True: both
     passes as one 2B-sample sweep; False: two forward() calls).  Returns the number of imposed ReLU decisions.
+    ``num_classes`` / ``num_regr``: the heads of the model and of the synthetic labels / targets; ``lam``: lambda_loss
+    (default [1, 1, 0.5, 1.5e-6, 0.1, 0.2]).  A parameter the oracle's loss does not depend on (with lam[0] = 0 the
+    classifier branch, :540-542) must come back from the HIP step without a gradient or with one that is exactly zero.
 
     ``dropout=False``: every dropout switched off.  ``dropout=True``: as the model trains — the mask generator's stream
     counter is set to dropout_cases.COUNTER, what ``ops.dropout_masks`` returned is recorded, required equal bit for bit
@@ -327,17 +330,18 @@ def train_mode_vs_oracle(monkeypatch, rois, pool, bsz, dense=False, bf16=False, 
     from igcn_amd.sgcn_img_snp import SGCN_GCN_IMGSNP
     from igcn_amd.train import losses
     from oracle import dropout as OD, go_network as OG, sgcn_img_snp as OS
-    lam = [1.0, 1.0, 0.5, 1.5e-6, 0.1, 0.2]
+    lam = [1.0, 1.0, 0.5, 1.5e-6, 0.1, 0.2] if lam is None else lam
     go_snps, adj, pool_dim = synth.go_hierarchy(pool, seed=go_seed)
     a_g, a = synth.go_sparse_inputs(go_snps, adj, "cuda")
-    model = SGCN_GCN_IMGSNP(layers, hidden, a_g, a, pool_dim, 32, "cuda", rois=rois, H_0=h0, num_classes=3,
-                            isSoftSimilarity=True, rbf_gamma=0.01, isCrossAtten=True, num_regr=3,
+    model = SGCN_GCN_IMGSNP(layers, hidden, a_g, a, pool_dim, 32, "cuda", rois=rois, H_0=h0, num_classes=num_classes,
+                            isSoftSimilarity=True, rbf_gamma=0.01, isCrossAtten=True, num_regr=num_regr,
                             isuseProb4Regr=True, isImageOnly=False, isSNPsOnly=False, bf16_transforms=bf16).cuda().train()
     sd = seeded_state({k: v.shape for k, v in model.state_dict().items()}, 5)
     model.load_state_dict(sd)
     for m in (model, model.go_network):
         m._dropout_enabled = bool(dropout)
-    graphs = synth.brain_graph_list(bsz, seed=graph_seed, rois=rois, h0=h0, tsne_dim=16, dense=dense)
+    graphs = synth.brain_graph_list(bsz, seed=graph_seed, rois=rois, h0=h0, tsne_dim=16, dense=dense,
+                                    num_classes=num_classes, num_regr=num_regr)
     # oracle, fp64, training mode
     a_g_c, a_c = synth.go_sparse_inputs(go_snps, adj)
     idx = OG.go_index_sets(a_g_c, a_c, list(pool), 2)
@@ -485,6 +489,9 @@ def train_mode_vs_oracle(monkeypatch, rois, pool, bsz, dense=False, bf16=False, 
             for k, w in want.items():
                 assert_matches(got[k], w.numpy(), gtol, f"grad {k} (maps={mp_}, batched={batched}, "
                                                         f"{rf.flips} imposed decisions)", floor=1e-6)
+            for k in OS.trainable_keys(st):          # the oracle's loss does not depend on it: no gradient, or exactly zero
+                if k not in want:
+                    assert k not in got or float(got[k].abs().max()) == 0.0, (k, batched, float(got[k].abs().max()))
             if controls and dropout and batched:
                 sites, arrays = masks[0]
                 own = (loss, terms)
@@ -533,6 +540,42 @@ def test_train_mode_with_dropout_vs_oracle_under_the_steps_own_masks(monkeypatch
     train_mode_vs_oracle(monkeypatch, c["rois"], pool, c["bsz"], maps=("default",), graph_seed=c["graph_seed"],
                          go_seed=c["go_seed"], formulations=(batched,), layers=c["layers"], hidden=c["hidden"], h0=c["h0"],
                          dropout=True, controls=(pool == DC.SMALL_POOL and batched))
+
+
+L_MAIN, L_TRAINER = [0, 1, 0.5, 1.5e-6, 0.1, 0], [1, 1, 1, 2.5e-6, 0.2, 0.2]      # main.py:73-78; the trainer's own :55-62
+
+
+@pytest.mark.parametrize("case", ["trainer", "trainer_chain", "trainer_dropout", "main"])
+def test_train_mode_at_the_trainers_heads_vs_oracle(monkeypatch, case):
+    """The heads the trainer builds — two classes (main.py:196-199), four regression targets
+    (kernel/train_eval_sgcn_img_snps.py:55-62) — at the headline dims on the 500-node GO DAG, B = 8, against the fp64
+    oracle with the bounds of the (3, 3) tests: the seven terms at 1e-4, every gradient at 1e-3.
+    ``trainer``: C = 2, NR = 4, the trainer's lambda_loss, dropout off, both formulations; ``trainer_chain``: the stacked
+    sweep again with the output layers and the loss head as small_linear_pair + LossHead (IGCN_NO_HEAD_LOSS_FUSED=1; the
+    two-forward form never takes the fused launch); ``trainer_dropout``: dropout on, stacked sweep — the heads' keep
+    factors at a binary head; ``main``: C = 2, NR = 3 under main.py's default lambda_loss, whose lam[0] = lam[5] = 0
+    switches the class terms and the orthogonality term off: the classifier branch then has no gradient in the oracle and
+    none, or exact zeros, here.  The recorded calls show which launch closed the stacked sweep."""
+    from calltrace import record_calls
+    c = DC.HEADLINE
+    kw = dict(maps=("default",), graph_seed=c["graph_seed"], go_seed=c["go_seed"], layers=c["layers"], hidden=c["hidden"],
+              h0=c["h0"], num_classes=2)
+    seen = record_calls(monkeypatch)
+    if case == "trainer":
+        train_mode_vs_oracle(monkeypatch, c["rois"], DC.SMALL_POOL, c["bsz"], num_regr=4, lam=L_TRAINER, **kw)
+    elif case == "trainer_chain":
+        monkeypatch.setenv("IGCN_NO_HEAD_LOSS_FUSED", "1")
+        train_mode_vs_oracle(monkeypatch, c["rois"], DC.SMALL_POOL, c["bsz"], num_regr=4, lam=L_TRAINER,
+                             formulations=(True,), **kw)
+    elif case == "trainer_dropout":
+        train_mode_vs_oracle(monkeypatch, c["rois"], DC.SMALL_POOL, c["bsz"], num_regr=4, lam=L_TRAINER,
+                             formulations=(True,), dropout=True, **kw)
+    else:
+        train_mode_vs_oracle(monkeypatch, c["rois"], DC.SMALL_POOL, c["bsz"], num_regr=3, lam=L_MAIN, **kw)
+    called = {n[0] for n in seen}
+    fused = bool(called & {"igcn_head_loss_fwd", "igcn_head_loss_gram_fwd"})
+    assert fused == (case != "trainer_chain"), sorted(n for n in called if "loss" in n)
+    assert ("igcn_loss_head_fwd_grads" in called) == (case == "trainer_chain"), sorted(n for n in called if "loss" in n)
 
 
 def test_captured_step_replays_the_masks_of_its_counter_vs_oracle(monkeypatch):
@@ -772,10 +815,12 @@ def test_full_model_dense_graphs_vs_oracle(rois, bsz):
             assert_matches(params[k].grad, sdo[k].grad.numpy(), 5e-3, "grad " + k, floor=1e-6)
 
 
-@pytest.mark.parametrize("rois,dense", [(90, False), (72, True)])
-def test_graphed_train_step_matches_eager(rois, dense):
+@pytest.mark.parametrize("rois,dense,heads,lam", [(90, False, (3, 3), None), (72, True, (3, 3), None),
+                                                  (90, False, (2, 4), "trainer")],
+                         ids=["90-False", "72-True", "90-False-trainer_heads"])
+def test_graphed_train_step_matches_eager(rois, dense, heads, lam):
     """GraphedTrainStep (whole step replayed from one hipGraph) against the eager train_step on a twin model, three
-    steps on changing batches.  k=3 graphs take the LDS plan build, dense 72-ROI graphs (5184 edges per graph) the
+    steps on changing batches; once more with the trainer's heads (two classes, four targets) and its lambda_loss.  k=3 graphs take the LDS plan build, dense 72-ROI graphs (5184 edges per graph) the
     tiled counting-sort build — both hand-written and captured inside the step graph.  The warm-up steps of the
     constructor are rolled back, so no state is restored by hand here."""
     import copy
@@ -787,17 +832,18 @@ def test_graphed_train_step_matches_eager(rois, dense):
     go_snps, adj, pool_dim = synth.go_hierarchy(pool, seed=2)
     a_g, a = synth.go_sparse_inputs(go_snps, adj, "cuda")
     torch.manual_seed(3)
-    m1 = SGCN_GCN_IMGSNP(2, 8, a_g, a, pool_dim, 32, "cuda", rois=rois, H_0=3, num_classes=3,
-                         isSoftSimilarity=True, rbf_gamma=0.01, isCrossAtten=True, num_regr=3,
+    classes, regr = heads
+    m1 = SGCN_GCN_IMGSNP(2, 8, a_g, a, pool_dim, 32, "cuda", rois=rois, H_0=3, num_classes=classes,
+                         isSoftSimilarity=True, rbf_gamma=0.01, isCrossAtten=True, num_regr=regr,
                          isuseProb4Regr=True, isImageOnly=False, isSNPsOnly=False).cuda().train()
     for m in (m1, m1.go_network):
         m._dropout_enabled = False
     m2 = copy.deepcopy(m1)
-    batches = [Batch.from_data_list(synth.brain_graph_list(6, seed=50 + i, rois=rois, tsne_dim=16, dense=dense)).to("cuda")
-               for i in range(3)]
-    lam = [1.0, 1.0, 0.5, 1.5e-6, 0.1, 0.2]
+    gkw = dict(rois=rois, tsne_dim=16, dense=dense, num_classes=classes, num_regr=regr)
+    batches = [Batch.from_data_list(synth.brain_graph_list(6, seed=50 + i, **gkw)).to("cuda") for i in range(3)]
+    lam = [1.0, 1.0, 0.5, 1.5e-6, 0.1, 0.2] if lam is None else L_TRAINER
     o1, o2 = FlatAdam(m1.parameters(), lr=1e-3), FlatAdam(m2.parameters(), lr=1e-3)
-    static = Batch.from_data_list(synth.brain_graph_list(6, seed=50, rois=rois, tsne_dim=16, dense=dense)).to("cuda")
+    static = Batch.from_data_list(synth.brain_graph_list(6, seed=50, **gkw)).to("cuda")
     static.x.requires_grad_(True)
     snap = {k: v.detach().clone() for k, v in m1.state_dict().items()}
     step = GraphedTrainStep(m1, o1, static, lam, warmup=2)
