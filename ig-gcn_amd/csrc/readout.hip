@@ -282,10 +282,16 @@ static int ro_quad_chunks(unsigned grid_y, int groups) {
 }
 
 template <int F, int D>
+static void ro_launch_apply_w(dim3 grid, hipStream_t st, int B, int N, int groups, const float* x, const float* W,
+                              const float* gamma, const float* beta, const float* mean, const float* rstd, float* out);
+
+template <int F, int D>
 static void ro_launch_apply(dim3 grid, hipStream_t st, int B, int N, int groups, const float* x, const float* W,
                             const float* gamma, const float* beta, const float* mean, const float* rstd,
                             const float* keep, float* out) {
-  if constexpr (D % 4 == 0 && D <= 64 && D >= 16 && 64 % (D / 4) == 0 && F <= D / 4) {
+  if constexpr (D % 16 == 0 && D > 64) {                   // wide rows: k_nlbn_apply_w, defined with its backward below
+    ro_launch_apply_w<F, D>(grid, st, B, N, groups, x, W, gamma, beta, mean, rstd, out);
+  } else if constexpr (D % 4 == 0 && D <= 64 && D >= 16 && 64 % (D / 4) == 0 && F <= D / 4) {
     // 64/(D/4) nodes per wave give 8x the workgroups of the thread-per-node grid: fewer, longer sample chunks
     dim3 gq((unsigned)igcn_cdiv(N, 64 / (D / 4)), ro_quad_chunks(grid.y, groups) * groups);
     hipLaunchKernelGGL((k_nlbn_apply_q<F, D>), gq, dim3(RO_T), 0, st, B, N, groups, x, W, gamma, beta, mean, rstd, out);
@@ -642,8 +648,269 @@ static constexpr bool ro_quad_ok() {
   return D % 4 == 0 && D >= 16 && D <= 64 && 64 % (D / 4) == 0 && F <= D / 4;
 }
 
-#define RO_DISPATCH(F, D, CALL)                                    \
+// ---- wide rows (D % 16 == 0, 64 < D <= 160): lane = (node, quad of a 32-column strip) ------------------------------
+// Past D = 64 a row has more quads than a wave can give one lane each, and the thread-per-node forms would keep D (forward)
+// or 2 D (backward) values per thread and touch 64 different lines per access.  Here eight lanes share a node and a lane owns
+// quad q of EVERY 32-column strip: an access instruction of the wave covers 128 contiguous bytes of each of its eight
+// consecutive rows (a short last strip, D % 32 == 16, has its upper four lanes idle), and over its ceil(D/32) strips the wave
+// reads or writes the 8 D contiguous floats of those rows exactly once.  Forward and backward statistics keep W in
+// registers (20 floats per strip); the backward apply pass needs its registers for the weight gradient (20 per strip) and
+// reads W from LDS instead (3.2 KB at D = 160, eight distinct addresses per wave).  As in the `_q` kernels the weight
+// gradient leaves the workgroup as one [D, F] partial row and nothing shaped [B, N, D] is written but `out`.
+#define RO_WN 8        // nodes per wave
+template <int F, int D>
+static constexpr bool ro_wide_ok() {
+  return D % 16 == 0 && D > 64 && D <= 160 && F <= 8;
+}
+template <int D>
+struct RoWide {
+  static constexpr int S = (D + 31) / 32;          // strips
+  static constexpr int TAIL = (D % 32) / 4;        // quads of a short last strip (0: the last strip is full)
+  static __device__ __forceinline__ bool has(int s, int q) { return s + 1 < S || TAIL == 0 || q < TAIL; }
+  // first column of lane q's quad in strip s; a lane without one is pointed at column 0 (its loads stay in the row)
+  static __device__ __forceinline__ int col(int s, int q) { return has(s, q) ? s * 32 + q * 4 : 0; }
+};
+
+// A pre-activation and its BatchNorm output, written as explicit fused multiply-adds: the forward and both backward passes
+// evaluate the SAME instruction sequence on the same values, so the backward's ReLU decision is the forward's bit for bit
+// (left to the compiler's contraction, two kernels decided one element of 1.8 M within rounding of zero differently: a
+// weight gradient from one decision and a dgamma from the other).
+template <int F>
+__device__ __forceinline__ float ro_w_pre(const float* w, const float (&x)[F]) {
+  float t = w[0] * x[0];
+#pragma unroll
+  for (int c = 1; c < F; ++c) t = fmaf(w[c], x[c], t);
+  return t;
+}
+__device__ __forceinline__ float ro_w_y(float pre, float sc, float sh) { return fmaf(pre, sc, sh); }
+
+template <int F, int D>
+__global__ void __launch_bounds__(RO_T)
+k_nlbn_apply_w(int B, int N, int groups, const float* __restrict__ x, const float* __restrict__ W,
+               const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ mean,
+               const float* __restrict__ rstd, float* __restrict__ out) {
+  using RW = RoWide<D>;
+  constexpr int S = RW::S;
+  const int lane = threadIdx.x & 63, sg = threadIdx.x >> 6;
+  const int q = lane & 7, nw = lane >> 3;
+  const int n = blockIdx.x * RO_WN + nw;
+  const bool live = n < N;
+  const int nc = live ? n : N - 1;
+  const RoChunk ch = ro_chunk(B, groups, RO_BLK_OF_LAUNCH);
+  float w[S][4][F];
+#pragma unroll
+  for (int s = 0; s < S; ++s)
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int c = 0; c < F; ++c) w[s][r][c] = W[(RW::col(s, q) + r) * F + c];
+  const float sc = rstd[(int64_t)ch.g * N + nc] * gamma[nc], sh = fmaf(-mean[(int64_t)ch.g * N + nc], sc, beta[nc]);
+  for (int b = ch.b0 + sg; b < ch.b1; b += RO_SG) {
+    float xv[F];
+#pragma unroll
+    for (int c = 0; c < F; ++c) xv[c] = x[((int64_t)b * F + c) * N + nc];       // one address per node: broadcast
+    float* o = out + ((int64_t)b * N + nc) * D;
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+      float4 v;
+      float* vv = reinterpret_cast<float*>(&v);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        vv[r] = fmaxf(ro_w_y(ro_w_pre<F>(w[s][r], xv), sc, sh), 0.f);
+      }
+      if (live && RW::has(s, q)) *reinterpret_cast<float4*>(o + RW::col(s, q)) = v;
+    }
+  }
+}
+
+template <int F, int D>
+__global__ void __launch_bounds__(RO_T)
+k_nlbn_bwd_stats_w(int B, int N, int groups, const float* __restrict__ x, const float* __restrict__ W,
+                   const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ mean,
+                   const float* __restrict__ rstd, const float* __restrict__ dout, float* __restrict__ partial) {
+  using RW = RoWide<D>;
+  constexpr int S = RW::S;
+  __shared__ float s1[RO_SG][RO_WN], s2[RO_SG][RO_WN];
+  const int lane = threadIdx.x & 63, sg = threadIdx.x >> 6;
+  const int q = lane & 7, nw = lane >> 3;
+  const int n = blockIdx.x * RO_WN + nw;
+  const bool live = n < N;
+  const int nc = live ? n : N - 1;
+  const RoChunk ch = ro_chunk(B, groups, RO_BLK_OF_LAUNCH);
+  float w[S][4][F];
+#pragma unroll
+  for (int s = 0; s < S; ++s)
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int c = 0; c < F; ++c) w[s][r][c] = W[(RW::col(s, q) + r) * F + c];
+  const float mu = mean[(int64_t)ch.g * N + nc], rs = rstd[(int64_t)ch.g * N + nc], ga = gamma[nc], be = beta[nc];
+  const float sc = rs * ga, sh = fmaf(-mu, sc, be);          // as the forward forms them
+  float a1 = 0.f, a2 = 0.f;
+  for (int b = ch.b0 + sg; b < ch.b1; b += RO_SG) {
+    float xv[F];
+    float4 g4[S];
+    const float* gr = dout + ((int64_t)b * N + nc) * D;
+#pragma unroll
+    for (int c = 0; c < F; ++c) xv[c] = x[((int64_t)b * F + c) * N + nc];
+#pragma unroll
+    for (int s = 0; s < S; ++s) g4[s] = *reinterpret_cast<const float4*>(gr + RW::col(s, q));   // all strips in flight
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+      const float g[4] = {g4[s].x, g4[s].y, g4[s].z, g4[s].w};
+      const bool has = RW::has(s, q);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float pre = ro_w_pre<F>(w[s][r], xv);
+        const float xh = (pre - mu) * rs;
+        const float dy = (has && ro_w_y(pre, sc, sh) > 0.f) ? g[r] : 0.f;
+        a1 += dy * xh;
+        a2 += dy;
+      }
+    }
+  }
+  a1 = ro_group_sum_dpp<8>(a1);
+  a2 = ro_group_sum_dpp<8>(a2);
+  if (q == 0) {
+    s1[sg][nw] = a1;
+    s2[sg][nw] = a2;
+  }
+  __syncthreads();
+  if (sg == 0 && q == 0 && live) {
+    float* p = partial + (int64_t)(ch.ck * groups + ch.g) * 2 * N;      // [chunk][group][2][N]
+    p[n] = (s1[0][nw] + s1[1][nw]) + (s1[2][nw] + s1[3][nw]);
+    p[N + n] = (s2[0][nw] + s2[1][nw]) + (s2[2][nw] + s2[3][nw]);
+  }
+}
+
+template <int F, int D>
+__global__ void __launch_bounds__(RO_T)
+k_nlbn_bwd_apply_w(int B, int N, int groups, int training, const float* __restrict__ x, const float* __restrict__ W,
+                   const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ mean,
+                   const float* __restrict__ rstd, const float* __restrict__ dout,
+                   const float* __restrict__ partial, int nchunks, float* __restrict__ dx,
+                   float* __restrict__ wpartial) {
+  using RW = RoWide<D>;
+  constexpr int S = RW::S;
+  static_assert(F <= 8, "k_nlbn_bwd_apply_w: a node's eight lanes hand out its F input gradients");
+  __shared__ __attribute__((aligned(16))) float sw[D * F];
+  __shared__ float red[RO_T / 64][D * F];
+  const int lane = threadIdx.x & 63, sg = threadIdx.x >> 6;
+  const int q = lane & 7, nw = lane >> 3;
+  const int n = blockIdx.x * RO_WN + nw;
+  const bool live = n < N;
+  const int nc = live ? n : N - 1;
+  const RoChunk ch = ro_chunk(B, groups, RO_BLK_OF_LAUNCH);
+  for (int j = threadIdx.x; j < D * F; j += RO_T) sw[j] = W[j];
+  float gw[S][4][F];
+#pragma unroll
+  for (int s = 0; s < S; ++s)
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int c = 0; c < F; ++c) gw[s][r][c] = 0.f;
+  const float mu = mean[(int64_t)ch.g * N + nc], rs = rstd[(int64_t)ch.g * N + nc], ga = gamma[nc], be = beta[nc];
+  const float sc = rs * ga, sh = fmaf(-mu, sc, be);          // as the forward forms them
+  const float cnt = (float)(B / groups) * D;
+  float t1 = 0.f, t2 = 0.f;                                  // this group's (sum dy*xhat, sum dy): chunk partials of
+  if (training)                                              // pass 1, summed here in chunk order
+    for (int c = 0; c < nchunks; ++c) {
+      const float* p = partial + (int64_t)(c * groups + ch.g) * 2 * N;
+      t2 += p[nc];
+      t1 += p[N + nc];
+    }
+  const float m1 = t1 / cnt;                                 // mean(dy)
+  const float m2 = t2 / cnt;                                 // mean(dy*xhat)
+  __syncthreads();
+  for (int b = ch.b0 + sg; b < ch.b1; b += RO_SG) {
+    float xv[F], dxv[F];
+    float4 g4[S];
+    const float* gr = dout + ((int64_t)b * N + nc) * D;
+#pragma unroll
+    for (int c = 0; c < F; ++c) {
+      xv[c] = x[((int64_t)b * F + c) * N + nc];
+      dxv[c] = 0.f;
+    }
+#pragma unroll
+    for (int s = 0; s < S; ++s) g4[s] = *reinterpret_cast<const float4*>(gr + RW::col(s, q));
+    int z = 0;                                                // opaque zero: the weights are re-read from LDS per sample
+#pragma unroll                                                // and strip (hoisted, they cost 20 registers per strip)
+    for (int s = 0; s < S; ++s) {
+      asm volatile("" : "+v"(z), "+v"(dxv[0]));               // (tied to the strip before through the running dx sum)
+      const float g[4] = {g4[s].x, g4[s].y, g4[s].z, g4[s].w};
+      const bool has = RW::has(s, q);
+      float wl[4 * F];                                        // the strip's 4 x F weights: 4 F contiguous floats of W
+      const float4* wp = reinterpret_cast<const float4*>(sw + RW::col(s, q) * F + z);
+#pragma unroll
+      for (int j = 0; j < F; ++j) {
+        const float4 t = wp[j];
+        wl[4 * j] = t.x; wl[4 * j + 1] = t.y; wl[4 * j + 2] = t.z; wl[4 * j + 3] = t.w;
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float wr[F];
+#pragma unroll
+        for (int c = 0; c < F; ++c) wr[c] = wl[r * F + c];
+        const float pre = ro_w_pre<F>(wr, xv);
+        const float xh = (pre - mu) * rs;
+        const float dy = (ro_w_y(pre, sc, sh) > 0.f) ? g[r] : 0.f;
+        const float t = (live && has) ? ga * rs * (dy - m1 - xh * m2) : 0.f;   // shadow lanes add nothing to dW, dx
+#pragma unroll
+        for (int c = 0; c < F; ++c) {
+          gw[s][r][c] += t * xv[c];
+          dxv[c] += wl[r * F + c] * t;
+        }
+      }
+    }
+    float mydx = 0.f;                                       // lane q < F ends up with channel q of dx
+#pragma unroll
+    for (int c = 0; c < F; ++c) {
+      const float t = ro_group_sum_dpp<8>(dxv[c]);
+      if (q == c) mydx = t;
+    }
+    if (live && q < F) dx[((int64_t)b * F + q) * N + n] = mydx;
+  }
+  // dW partial of the workgroup: sum over the wave's nodes (lanes with equal q), then over the four waves
+#pragma unroll
+  for (int s = 0; s < S; ++s)
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int c = 0; c < F; ++c) {
+        float t = gw[s][r][c];
+#pragma unroll
+        for (int o = 8; o < 64; o <<= 1) t += __shfl_xor(t, o, 64);
+        if (nw == 0 && RW::has(s, q)) red[sg][(s * 32 + q * 4 + r) * F + c] = t;
+      }
+  __syncthreads();
+  float* prow = wpartial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * (D * F);
+  for (int j = threadIdx.x; j < D * F; j += RO_T) prow[j] = (red[0][j] + red[1][j]) + (red[2][j] + red[3][j]);
+}
+
+template <int F, int D>
+static void ro_launch_apply_w(dim3 grid, hipStream_t st, int B, int N, int groups, const float* x, const float* W,
+                              const float* gamma, const float* beta, const float* mean, const float* rstd, float* out) {
+  static_assert(ro_wide_ok<F, D>(), "k_nlbn_apply_w: unsupported shape");
+  dim3 gw((unsigned)igcn_cdiv(N, RO_WN), ro_quad_chunks(grid.y, groups) * groups);
+  hipLaunchKernelGGL((k_nlbn_apply_w<F, D>), gw, dim3(RO_T), 0, st, B, N, groups, x, W, gamma, beta, mean, rstd, out);
+}
+
+#define RO_SUPPORTED_TEXT                                                                                        \
+  "supported: F=5 with D in {1,2,3,4,5,6,8,10,12,16,20,24,30,32,48} or a multiple of 16 from 64 to 160; F=2 with D=1"
+#define RO_DISPATCH(F, D, CALL)                                                                                  \
+  RO_DISPATCH_ELSE(F, D, CALL, {                                                                                 \
+    igcn_set_error("node_linear_bn: unsupported (F=%d, D=%d); " RO_SUPPORTED_TEXT, F, D);                        \
+    return IGCN_ERR_UNSUPPORTED;                                                                                 \
+  })
+#define RO_DISPATCH_ELSE(F, D, CALL, ELSE)                         \
   if (F == 5 && D == 32) { CALL(5, 32); }                          \
+  else if (F == 5 && D == 64) { CALL(5, 64); }                     \
+  else if (F == 5 && D == 80) { CALL(5, 80); }                     \
+  else if (F == 5 && D == 96) { CALL(5, 96); }                     \
+  else if (F == 5 && D == 112) { CALL(5, 112); }                   \
+  else if (F == 5 && D == 128) { CALL(5, 128); }                   \
+  else if (F == 5 && D == 144) { CALL(5, 144); }                   \
+  else if (F == 5 && D == 160) { CALL(5, 160); }                   \
   else if (F == 5 && D == 48) { CALL(5, 48); }                     \
   else if (F == 5 && D == 30) { CALL(5, 30); }                     \
   else if (F == 5 && D == 20) { CALL(5, 20); }                     \
@@ -659,10 +926,14 @@ static constexpr bool ro_quad_ok() {
   else if (F == 5 && D == 5) { CALL(5, 5); }                       \
   else if (F == 5 && D == 1) { CALL(5, 1); }                       \
   else if (F == 2 && D == 1) { CALL(2, 1); }                       \
-  else {                                                           \
-    igcn_set_error("node_linear_bn: unsupported (F=%d, D=%d)", F, D); \
-    return IGCN_ERR_UNSUPPORTED;                                   \
-  }
+  else ELSE
+
+// host only: 1 for exactly the (F, D) that RO_DISPATCH accepts
+extern "C" int igcn_node_linear_bn_supported(int F, int D) {
+#define CALL(FV, DV) return 1
+  RO_DISPATCH_ELSE(F, D, CALL, { return 0; })
+#undef CALL
+}
 
 static int ro_cpg(int B, int groups) {
   // sample chunks per group: up to 32 (enough workgroups for small N), but never fewer than RO_SG samples per chunk — a
@@ -710,6 +981,9 @@ extern "C" size_t igcn_node_linear_bn_bwd_scratch_floats(int B, int F, int N, in
   const size_t stats = (size_t)groups * cpg * 2 * N + (size_t)groups * 2 * N;
   const size_t blocks = (size_t)igcn_cdiv(N, RO_NL) * groups * cpg;
   if (D * F <= 16) return stats + blocks * D * F + 68;
+  // wide rows (k_nlbn_bwd_apply_w): one [D, F] partial per workgroup of RO_WN nodes and (at most 8) chunks per group
+  if (D % 16 == 0 && D > 64)
+    return stats + (size_t)igcn_cdiv(N, RO_WN) * groups * (cpg > 8 ? 8 : cpg) * D * F + 68;
   // dpre rows + batched-GEMM slabs, or (row-coalesced path) one [D, F] partial per workgroup of 64/(D/4) nodes
   const size_t gemm_path = (size_t)B * N * D + (size_t)16 * B * D * F;
   const size_t quad_path = D % 4 == 0 ? (size_t)igcn_cdiv(N, 64 / (D / 4 > 64 ? 64 : D / 4)) * groups * cpg * D * F : 0;
@@ -733,6 +1007,16 @@ static int ro_bwd(dim3 grid, int cpg, hipStream_t st, int B, int N, int groups, 
     // dgamma | dbeta = the chunk partials [chunk][group][2N] summed over chunks AND groups: rows of 2N
     if ((rc = igcn_launch_reduce_rows_final(stats, (int64_t)cq * groups, 2 * (int64_t)N, 2 * N, dgb, st))) return rc;
     return igcn_launch_reduce_rows_final(aux, (int64_t)gq.x * gq.y, D * F, D * F, dW, st);
+  } else if constexpr (ro_wide_ok<F, D>()) {
+    const int cq = ro_quad_chunks(grid.y, groups);
+    dim3 gw((unsigned)igcn_cdiv(N, RO_WN), cq * groups);
+    hipLaunchKernelGGL((k_nlbn_bwd_stats_w<F, D>), gw, dim3(RO_T), 0, st, B, N, groups, x, W, gamma, beta, save_mean,
+                       save_rstd, dout, stats);
+    hipLaunchKernelGGL((k_nlbn_bwd_apply_w<F, D>), gw, dim3(RO_T), 0, st, B, N, groups, training, x, W, gamma, beta,
+                       save_mean, save_rstd, dout, stats, cq, dx, aux);
+    IGCN_CHECK_LAUNCH("node_linear_bn_bwd(w)");
+    if ((rc = igcn_launch_reduce_rows_final(stats, (int64_t)cq * groups, 2 * (int64_t)N, 2 * N, dgb, st))) return rc;
+    return igcn_launch_reduce_rows_final(aux, (int64_t)gw.x * gw.y, D * F, D * F, dW, st);
   } else {
     hipLaunchKernelGGL((k_nlbn_bwd_stats<F, D>), grid, dim3(RO_T), 0, st, B, N, groups, x, W, gamma, beta, save_mean,
                        save_rstd, dout, keep, stats);

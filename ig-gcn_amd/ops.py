@@ -2281,6 +2281,12 @@ class NodeLinearBN(torch.autograd.Function):
         return dx, dw, dgb[0], dgb[1], None, None, None, None, None, None, None
 
 
+def node_linear_bn_supported(f, d):
+    """True for the (inputs per node, outputs per node) the read-out kernels are built for (igcn_node_linear_bn_supported):
+    exactly the shapes ``NodeLinearBN`` accepts."""
+    return bool(_lib.load().igcn_node_linear_bn_supported(int(f), int(d)))
+
+
 class NodeLinearBNPair(torch.autograd.Function):
     """Two NodeLinearBN read-outs of the SAME input (go_model.py:254-255: conc_for_attention -> [B,N,D1] and conc ->
     [B,N,1] with its dropout) as one op: paired launches (igcn_node_linear_bn_pair_*), three forward and three

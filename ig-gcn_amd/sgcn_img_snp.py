@@ -308,8 +308,9 @@ class SGCN_GCN_IMGSNP(torch.nn.Module):
         """relu(nn.MultiheadAttention(D, 2, batch_first=True)(query, memory, memory)[0]) (:240-241) with the
         parameters of ``self.multihead_attn``: MFMA-GEMM projections (key and value as one GEMM) around the attention
         core igcn_attn_core_*, which works on the projection outputs in place (matrix cores, head_dim <= 96: the
-        attention of every row of the reference's sweeps — the hidden-32 rows stop earlier, in the GO read-out: DESIGN.md
-        section 8); wider heads use a batched GEMM + softmax composite."""
+        attention of every row of the reference's sweeps, the hidden-32 rows included — their memory comes from the wide
+        GO read-out kernels, attention width 64..160: DESIGN.md section 8); wider heads use a batched GEMM + softmax
+        composite."""
         mha = self.multihead_attn
         d, h = mha.embed_dim, mha.num_heads
         b, lq, lk = query.shape[0], query.shape[1], memory.shape[1]

@@ -31,7 +31,7 @@ extern "C" {
 /* ABI revision: bumped whenever a prototype below changes (argument added, removed or re-ordered).  igcn_version()
  * returns the revision the library was built from; a binding written against a different one must refuse to call
  * (igcn_amd/_lib.py does). */
-#define IGCN_ABI_VERSION 428
+#define IGCN_ABI_VERSION 429
 int igcn_version(void);
 const char* igcn_last_error(void);
 /* A/B switches, set ONCE by the binding when it loads the library (from the IGCN_* environment variables): bit 0 no tiled
@@ -620,6 +620,10 @@ int igcn_stream_pending(void* stream);
  * scratch: igcn_node_linear_bn_scratch_floats(B,N).
  */
 size_t igcn_node_linear_bn_scratch_floats(int B, int N, int groups);
+/* Host only: 1 for the (F, D) the read-out kernels are built for, else 0 — F = 5 with D in {1,2,3,4,5,6,8,10,12,16,20,24,
+ * 30,32,48} or a multiple of 16 from 64 to 160 (row-coalesced kernels from D = 16), and (F, D) = (2, 1).  Exactly what
+ * igcn_node_linear_bn_{fwd,bwd} accept; any other shape is refused there with IGCN_ERR_UNSUPPORTED. */
+int igcn_node_linear_bn_supported(int F, int D);
 int igcn_node_linear_bn_fwd(int B, int F, int N, int D, int groups, const float* x, const float* W,
                             const float* gamma, const float* beta, float* running_mean, float* running_var,
                             int training, float momentum, float eps,
@@ -627,7 +631,8 @@ int igcn_node_linear_bn_fwd(int B, int F, int N, int D, int groups, const float*
                             float* out, float* save_mean /*[groups,N]*/, float* save_rstd /*[groups,N]*/,
                             float* scratch, void* stream);
 /* Outputs dx [B,F,N], dW [D,F], dgb [2,N] = (dgamma, dbeta).  dW = sum_{b,n} dpre[b,n,:] (x) x[b,:,n] is formed in
- * registers when D*F <= 16, else on the MFMA batched-sum GEMM.
+ * registers when D*F <= 16 or the rows are 16-byte quads handled by the row-coalesced kernels (D = 16, 32, 64..160: one
+ * [D,F] partial per workgroup, summed in order), else on the MFMA batched-sum GEMM.
  * scratch: igcn_node_linear_bn_bwd_scratch_floats(B,F,N,D,groups). */
 size_t igcn_node_linear_bn_bwd_scratch_floats(int B, int F, int N, int D, int groups);
 int igcn_node_linear_bn_bwd(int B, int F, int N, int D, int groups, int training, const float* x, const float* W,
