@@ -1032,7 +1032,7 @@ extern "C" int igcn_snps_mask_bwd(int B, int S, const float* snps, const float* 
 // it is one VALU kernel forward and one (+ a short reduction of block partials) backward.
 // Thread = (row, quad of K): KQ = K/4 lanes per row, 256/KQ rows per workgroup pass.
 // =================================================================================================
-#define SL_MAXC 4
+#include "narrow_head.h"
 // (blockIdx.y selects one of up to two layers over the same [R, K] input shape: igcn_small_linear_pair_*)
 struct SmallLinPtrs {
   const float* x[2]; const float* keep[2]; const float* W[2]; const float* b[2]; float* y[2];
@@ -1040,113 +1040,58 @@ struct SmallLinPtrs {
 };
 __global__ void __launch_bounds__(256)
 k_small_linear_fwd(int64_t R, int K, SmallLinPtrs pp) {
-  const float* __restrict__ x = pp.x[blockIdx.y];
-  const float* __restrict__ keep = pp.keep[blockIdx.y];
-  const float* __restrict__ W = pp.W[blockIdx.y];
-  const float* __restrict__ b = pp.b[blockIdx.y];
   float* __restrict__ y = pp.y[blockIdx.y];
   const int C = pp.C[blockIdx.y];
-  const int kq = K / 4, q = threadIdx.x % kq, rl = threadIdx.x / kq, rpb = 256 / kq;
-  const int64_t r = (int64_t)blockIdx.x * rpb + rl;
-  float acc[SL_MAXC];
+  const NhGeom g = nh_geom(K, blockIdx.x);
+  const int64_t r = g.row;
+  if (r >= R) return;
+  float4 xv, kv, w[NH_MAXC];
+  float s[NH_MAXC];
+  nh_load(pp.x[blockIdx.y], pp.keep[blockIdx.y], pp.W[blockIdx.y], r, K, g.q, C, xv, kv, w);
+  nh_keep(xv, kv);
+  nh_scores<true, false>(xv, w, pp.b[blockIdx.y], C, g.kq, s);
+  if (g.q == 0) {
 #pragma unroll
-  for (int c = 0; c < SL_MAXC; ++c) acc[c] = 0.f;
-  if (rl < rpb && r < R) {
-    float4 xv = *reinterpret_cast<const float4*>(x + r * K + 4 * q);
-    if (keep) {                                          // dropout of the input, fused: x * keep
-      const float4 kv = *reinterpret_cast<const float4*>(keep + r * K + 4 * q);
-      xv.x *= kv.x; xv.y *= kv.y; xv.z *= kv.z; xv.w *= kv.w;
-    }
-#pragma unroll
-    for (int c = 0; c < SL_MAXC; ++c)
-      if (c < C) {
-        const float4 w = *reinterpret_cast<const float4*>(W + c * K + 4 * q);
-        acc[c] = (xv.x * w.x + xv.y * w.y) + (xv.z * w.z + xv.w * w.w);
-      }
-  }
-  // sum over the kq lanes of a row (kq is a power of two <= 64, rows do not straddle waves)
-#pragma unroll
-  for (int c = 0; c < SL_MAXC; ++c)
-    for (int o = 1; o < kq; o <<= 1) acc[c] += __shfl_xor(acc[c], o, 64);
-  if (q == 0 && rl < rpb && r < R) {
-#pragma unroll
-    for (int c = 0; c < SL_MAXC; ++c)
-      if (c < C) y[r * C + c] = acc[c] + (b ? b[c] : 0.f);
+    for (int c = 0; c < NH_MAXC; ++c)
+      if (c < C) y[r * C + c] = s[c];
   }
 }
 
 // dx[r, k] = sum_c dy[r, c] W[c, k];  partial[blk][c*K + k] = sum_{r in blk} dy[r, c] x[r, k];
-// partial[blk][C*K + c] = sum_{r in blk} dy[r, c].  Rows of a workgroup: rows_per_block, walked 256/KQ at a time.
+// partial[blk][C*K + c] = sum_{r in blk} dy[r, c].  Rows of a workgroup: rows_per_block, walked 256/KQ at a time, each
+// thread accumulating its row slot's share; nh_wpart sums the slots.
 __global__ void __launch_bounds__(256)
 k_small_linear_bwd(int64_t R, int K, int rows_per_block, SmallLinPtrs pp) {
   const float* __restrict__ x = pp.x[blockIdx.y];
   const float* __restrict__ keep = pp.keep[blockIdx.y];
-  const float* __restrict__ W = pp.W[blockIdx.y];
   const float* __restrict__ dy = pp.dy[blockIdx.y];
   float* __restrict__ dx = pp.dx[blockIdx.y];
-  float* __restrict__ partial = pp.partial[blockIdx.y];
   const int C = pp.C[blockIdx.y];
-  __shared__ float red[256 * 4 * SL_MAXC + 256 * SL_MAXC];
-  const int kq = K / 4, q = threadIdx.x % kq, rl = threadIdx.x / kq, rpb = 256 / kq;
+  __shared__ float red[NH_RED_FLOATS];
+  const NhGeom g = nh_geom(K, blockIdx.x);
+  const int q = g.q;
   const int64_t r0 = (int64_t)blockIdx.x * rows_per_block, r1 = r0 + rows_per_block < R ? r0 + rows_per_block : R;
-  float4 w[SL_MAXC], gw[SL_MAXC];
-  float gb[SL_MAXC];
-#pragma unroll
-  for (int c = 0; c < SL_MAXC; ++c) {
-    w[c] = (c < C) ? *reinterpret_cast<const float4*>(W + c * K + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
-    gw[c] = make_float4(0.f, 0.f, 0.f, 0.f);
-    gb[c] = 0.f;
-  }
-  if (rl < rpb) {
+  float4 w[NH_MAXC], gw[NH_MAXC];
+  float gb[NH_MAXC];
+  nh_load_w(pp.W[blockIdx.y], K, q, C, w);
+  nh_zero(gw, gb);
 #pragma unroll 4
-    for (int64_t r = r0 + rl; r < r1; r += rpb) {
-      float4 xv = *reinterpret_cast<const float4*>(x + r * K + 4 * q);
-      float4 kv = make_float4(1.f, 1.f, 1.f, 1.f);
-      if (keep) {
-        kv = *reinterpret_cast<const float4*>(keep + r * K + 4 * q);
-        xv.x *= kv.x; xv.y *= kv.y; xv.z *= kv.z; xv.w *= kv.w;
+  for (int64_t r = r0 + g.rl; r < r1; r += g.rpb) {
+    float4 xv, kv;
+    nh_load_x(x, keep, r, K, q, xv, kv);
+    nh_keep(xv, kv);
+    float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int c = 0; c < NH_MAXC; ++c)
+      if (c < C) {
+        const float gc = dy[r * C + c];
+        d.x += gc * w[c].x; d.y += gc * w[c].y; d.z += gc * w[c].z; d.w += gc * w[c].w;
+        gw[c].x += gc * xv.x; gw[c].y += gc * xv.y; gw[c].z += gc * xv.z; gw[c].w += gc * xv.w;
+        gb[c] += gc;
       }
-      float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-      for (int c = 0; c < SL_MAXC; ++c)
-        if (c < C) {
-          const float g = dy[r * C + c];
-          d.x += g * w[c].x; d.y += g * w[c].y; d.z += g * w[c].z; d.w += g * w[c].w;
-          gw[c].x += g * xv.x; gw[c].y += g * xv.y; gw[c].z += g * xv.z; gw[c].w += g * xv.w;
-          gb[c] += g;
-        }
-      if (dx) *reinterpret_cast<float4*>(dx + r * K + 4 * q) = make_float4(d.x * kv.x, d.y * kv.y, d.z * kv.z, d.w * kv.w);
-    }
+    if (dx) *reinterpret_cast<float4*>(dx + r * K + 4 * q) = make_float4(d.x * kv.x, d.y * kv.y, d.z * kv.z, d.w * kv.w);
   }
-  // row lanes summed in order through LDS: every channel's partials staged at once (one barrier pair instead of four
-  // per channel), one thread per (channel, column) / per channel
-  float* prow = partial + (int64_t)blockIdx.x * (C * K + C);
-  float* redb = red + 256 * 4 * SL_MAXC;               // [SL_MAXC][256] bias partials
-#pragma unroll
-  for (int c = 0; c < SL_MAXC; ++c)
-    if (c < C) {
-      float* rc = red + c * 1024;
-      rc[threadIdx.x * 4 + 0] = gw[c].x; rc[threadIdx.x * 4 + 1] = gw[c].y;
-      rc[threadIdx.x * 4 + 2] = gw[c].z; rc[threadIdx.x * 4 + 3] = gw[c].w;
-      redb[c * 256 + threadIdx.x] = (q == 0 && rl < rpb) ? gb[c] : 0.f;
-    }
-  __syncthreads();
-  for (int idx = threadIdx.x; idx < C * K; idx += 256) {
-    const int c = idx / K, k = idx - c * K, qq = k / 4, j = k % 4;
-    float t = 0.f;
-    for (int l = 0; l < rpb; ++l) t += red[c * 1024 + (l * kq + qq) * 4 + j];
-    prow[c * K + k] = t;
-  }
-  if (threadIdx.x < C) {
-    float t = 0.f;
-    for (int l = 0; l < rpb; ++l) t += redb[threadIdx.x * 256 + l * kq];
-    prow[C * K + threadIdx.x] = t;
-  }
-}
-
-static bool small_linear_ok(int K, int C) {
-  const int kq = K / 4;
-  return K % 4 == 0 && kq >= 1 && kq <= 64 && (kq & (kq - 1)) == 0 && C >= 1 && C <= SL_MAXC;
+  nh_wpart(g, C, K, gw, gb, red, pp.partial[blockIdx.y] + (int64_t)blockIdx.x * (C * K + C));
 }
 
 // rows per workgroup: 64, or 16 while that leaves fewer than a few hundred workgroups (512 rows: 8 workgroups were the
@@ -1158,12 +1103,11 @@ extern "C" size_t igcn_small_linear_bwd_scratch_floats(int64_t R, int K, int C) 
 
 static int small_linear_fwd_launch(int64_t R, int K, int n, const SmallLinPtrs& pp, hipStream_t st) {
   for (int i = 0; i < n; ++i) {
-    IGCN_REQUIRE(R > 0 && small_linear_ok(K, pp.C[i]), "small_linear: K/4 a power of two <= 64, 1 <= C <= 4 (K=%d C=%d)",
-                 K, pp.C[i]);
+    IGCN_REQUIRE(R > 0 && narrow_head_ok(K, pp.C[i]), "small_linear: " NH_OK_TEXT " (K=%d C=%d)", K, pp.C[i]);
     IGCN_REQUIRE((((uintptr_t)pp.x[i] | (uintptr_t)pp.W[i] | (uintptr_t)pp.keep[i]) & 15) == 0,
                  "small_linear: x, keep and W must be 16-byte aligned");
   }
-  const int rpb = 256 / (K / 4);
+  const int rpb = narrow_head_rows_per_pass(K);
   hipLaunchKernelGGL(k_small_linear_fwd, dim3((unsigned)igcn_cdiv(R, rpb), (unsigned)n), dim3(256), 0, st, R, K, pp);
   IGCN_CHECK_LAUNCH("small_linear_fwd");
   return IGCN_OK;
@@ -1190,8 +1134,7 @@ extern "C" int igcn_small_linear_pair_fwd(int64_t R, int K, int C0, const float*
 
 static int small_linear_bwd_launch(int64_t R, int K, int n, const SmallLinPtrs& pp, float* const* dwb, hipStream_t st) {
   for (int i = 0; i < n; ++i) {
-    IGCN_REQUIRE(R > 0 && small_linear_ok(K, pp.C[i]), "small_linear: K/4 a power of two <= 64, 1 <= C <= 4 (K=%d C=%d)",
-                 K, pp.C[i]);
+    IGCN_REQUIRE(R > 0 && narrow_head_ok(K, pp.C[i]), "small_linear: " NH_OK_TEXT " (K=%d C=%d)", K, pp.C[i]);
     IGCN_REQUIRE((((uintptr_t)pp.x[i] | (uintptr_t)pp.W[i] | (uintptr_t)pp.dx[i] | (uintptr_t)pp.keep[i]) & 15) == 0,
                  "small_linear: 16-byte aligned tensors");
   }

@@ -1705,7 +1705,7 @@ def small_linear_pair(x1, w1, b1, keep1, x2, w2, b2, keep2):
 
 def _small_linear_ok(x2, weight, relu):
     k, c = x2.shape[1], weight.shape[0]
-    kq = k // 4
+    kq = k // 4                                      # (mirrors narrow_head_ok of csrc/narrow_head.h)
     return (not relu and x2.is_cuda and c <= 4 and k % 4 == 0 and 1 <= kq <= 64 and (kq & (kq - 1)) == 0
             and x2.shape[0] > 0)
 
@@ -2765,6 +2765,53 @@ def _loss_weights(lam, hp_ce, hp_mi, b, nr, dev):
     return t
 
 
+def _head_loss_buffers(what, f1, w_a, f2, w_b, labels, x_hat, snps, prob, supported, blocks, n_sums):
+    """The front that HeadLoss.forward and ClusterHeadLoss.forward share: the shape checks of the stacked sweep (features
+    [2B, K] twice, layers [C_a | C_b, K], int64 ``labels`` [B] each, x_hat [2B, S], snps [B, S]), the library's word on
+    (K, C_a, C_b), and the launch's buffers.  Returns ((b, k, c_a, c_b, s, nblk), out8, (out_a [2B, C_a], out_b [2B, C_b]),
+    (dx1, dx2, dxhat), parts [nblk, n_sums], wpart [nblk, C_a K + C_a + C_b K + C_b])."""
+    rows, k = f1.shape
+    b, c_a, c_b, s = rows // 2, w_a.shape[0], w_b.shape[0], snps.shape[1]
+    if any(t.dtype != torch.int64 or t.numel() != b for t in labels) or rows != 2 * b or f2.shape != f1.shape \
+            or x_hat.shape != (2 * b, s) or prob.numel() == 0 or snps.shape[0] != b or w_a.shape[1] != k \
+            or w_b.shape[1] != k:
+        raise _lib.IgcnError(f"{what}: inconsistent shapes")
+    if not supported(k, c_a, c_b):
+        raise _lib.IgcnError(f"{what}: K/4 a power of two <= 64 and 1..4 outputs per layer (K={k}, {c_a} | {c_b} outputs)")
+    f32 = dict(dtype=torch.float32, device=f1.device)
+    nblk = int(blocks(b, k))
+    outs = torch.empty(2 * b, c_a, **f32), torch.empty(2 * b, c_b, **f32)
+    unit = torch.empty_like(f1), torch.empty_like(f2), torch.empty_like(x_hat)
+    return ((b, k, c_a, c_b, s, nblk), torch.empty(8, **f32), outs, unit, torch.empty(nblk, n_sums, **f32),
+            torch.empty(nblk, c_a * k + c_a + c_b * k + c_b, **f32))
+
+
+def _head_loss_backward(unit_grads, wpart, nblk, k, cs, w_final, gout):
+    """The tail that HeadLoss.backward and ClusterHeadLoss.backward share: the two layers' dW | db from the forward's
+    block partials ``wpart``, and the gradients the forward left for an upstream gradient of one (``unit_grads``) scaled
+    by another upstream one.  Returns (upstream is the unit?, the input gradients, (dW_a, db_a, dW_b, db_b))."""
+    c_a, c_b = cs
+    o1, o2 = c_a * k + c_a, c_b * k + c_b
+    wcols = o1 + o2
+    # kept until the flush: the sums below are QUEUED, and a backward sweep that does not ask for the heads' gradients
+    # (the second sweep of train.backward_two_buckets visits this node again) drops dwb on return — its memory would be
+    # handed to a later tensor of the sweep and the flush would write the sums into it
+    dwb = _keep(torch.empty(wcols, dtype=torch.float32, device=wpart.device))
+    _keep(wpart)
+    gout = _f32(gout).reshape(1)
+    unit = gout.data_ptr() in UNIT_GRAD_PTRS
+    # (another upstream gradient scales the sums below: they are then needed here, not at the flush)
+    with _immediate(w_final[0] and unit):
+        call("igcn_reduce_rows_final", ptr(wpart), nblk, wcols, o1, ptr(dwb), stream_ptr())
+    with _immediate(w_final[1] and unit):
+        call("igcn_reduce_rows_final", wpart.data_ptr() + 4 * o1, nblk, wcols, o2, ptr(dwb[o1:]), stream_ptr())
+    if not unit:                                     # every gradient is linear in the upstream one
+        unit_grads = tuple(t * gout for t in unit_grads)
+        dwb = dwb * gout
+    return unit, unit_grads, (dwb[:c_a * k].view(c_a, k), dwb[c_a * k:o1], dwb[o1:o1 + c_b * k].view(c_b, k),
+                              dwb[o1 + c_b * k:])
+
+
 def head_loss_supported(lin_f, w2, reg_f, w2r, keep1, keep2):
     """The fused output-heads + loss launch (igcn_head_loss_fwd) covers these layers, and a unit upstream gradient is what
     the backward will bring (train._unit_grad has registered its scalar)."""
@@ -2795,24 +2842,14 @@ class HeadLoss(torch.autograd.Function):
         lin_f, keep1, w2, b2, reg_f, keep2, w2r, b2r, clin, x_hat, snps, gram, prob = (
             f(t) for t in (lin_f, keep1, w2, b2, reg_f, keep2, w2r, b2r, clin, x_hat, snps, gram, prob))
         y = y.contiguous()
-        rows, k = lin_f.shape
-        b, c, nr, s = rows // 2, w2.shape[0], w2r.shape[0], snps.shape[1]
-        if y.dtype != torch.int64 or y.numel() != b or clin.numel() != b * nr or x_hat.shape != (2 * b, s) \
-                or gram.numel() % 4 != 0 or gram.numel() == 0 or prob.numel() == 0 or snps.shape[0] != b:
+        lib = _lib.load()
+        (b, k, c, nr, s, nblk), out8, (logp, our_reg), (dx1, dx2, dxhat), parts, wpart = _head_loss_buffers(
+            "head loss", lin_f, w2, reg_f, w2r, (y,), x_hat, snps, prob, lib.igcn_head_loss_supported,
+            lib.igcn_head_loss_blocks, 4)
+        if clin.numel() != b * nr or gram.numel() % 4 != 0 or gram.numel() == 0:
             raise _lib.IgcnError("head loss: inconsistent shapes")
         dev = lin_f.device
-        lib = _lib.load()
-        if not lib.igcn_head_loss_supported(k, c, nr):
-            raise _lib.IgcnError(f"head loss: K/4 a power of two <= 64 and C, NR <= 4 (K={k} C={c} NR={nr})")
-        f32 = dict(dtype=torch.float32, device=dev)
-        nblk = int(lib.igcn_head_loss_blocks(b, k))
-        out8 = torch.empty(8, **f32)
-        logp, our_reg = torch.empty(2 * b, c, **f32), torch.empty(2 * b, nr, **f32)
-        dx1, dx2, dxhat = torch.empty_like(lin_f), torch.empty_like(reg_f), torch.empty_like(x_hat)
-        parts = torch.empty(nblk, 4, **f32)
-        wcols = c * k + c + nr * k + nr
-        wpart = torch.empty(nblk, wcols, **f32)
-        dgram, dprob = torch.empty(4, **f32), torch.empty(1, **f32)
+        dgram, dprob = torch.empty(4, dtype=torch.float32, device=dev), torch.empty(1, dtype=torch.float32, device=dev)
         lam6 = (ctypes.c_float * 6)(*[float(v) for v in lam])
         head = (b, k, c, nr, s, ptr(lin_f), ptr(keep1), ptr(w2), ptr(b2), ptr(reg_f), ptr(keep2), ptr(w2r), ptr(b2r), ptr(y),
                 ptr(clin), ptr(x_hat), ptr(snps), lam6, float(hp_ce), float(hp_mi), ptr(logp), ptr(our_reg), ptr(dx1), ptr(dx2),
@@ -2846,31 +2883,14 @@ class HeadLoss(torch.autograd.Function):
             call("igcn_loss_final", ptr(parts), nblk, ptr(gram), gram.numel() // 4, ptr(prob), prob.numel(), ptr(wts),
                  ptr(out8), stream_ptr())
             _keep(parts)
-        dev = dx1.device
-        wcols = c * k + c + nr * k + nr
-        # kept until the flush: the sums below are QUEUED, and a backward sweep that does not ask for the heads' gradients
-        # (the second sweep of train.backward_two_buckets visits this node again) drops dwb on return — its memory would be
-        # handed to a later tensor of the sweep and the flush would write the sums into it
-        dwb = _keep(torch.empty(wcols, dtype=torch.float32, device=dev))
-        _keep(wpart)
-        o1, o2 = c * k + c, nr * k + nr
-        gout = _f32(gout).reshape(1)
-        unit = gout.data_ptr() in UNIT_GRAD_PTRS
-        # (another upstream gradient scales the sums below: they are then needed here, not at the flush)
-        with _immediate(ctx.w_final[0] and unit):
-            call("igcn_reduce_rows_final", ptr(wpart), nblk, wcols, o1, ptr(dwb), stream_ptr())
-        with _immediate(ctx.w_final[1] and unit):
-            call("igcn_reduce_rows_final", wpart.data_ptr() + 4 * o1, nblk, wcols, o2, ptr(dwb[o1:]), stream_ptr())
+        unit, (dx1, dx2, dxhat, dgram, dprob), (dw2, db2, dw2r, db2r) = _head_loss_backward(
+            (dx1, dx2, dxhat, dgram, dprob), wpart, nblk, k, (c, nr), ctx.w_final, gout)
         UNIT_DGRAM.clear()
         if unit:
             UNIT_DGRAM[dgram.data_ptr()] = unit_dgram(lam)
-        else:                                        # every gradient is linear in the upstream one
-            dx1, dx2, dxhat, dgram, dprob, dwb = (t * gout for t in (dx1, dx2, dxhat, dgram, dprob, dwb))
         gs, ps = ctx.gram_shape, ctx.prob_shape
         dgram = dgram.view(2, 2) if gs == (2, 2) else dgram.view(1, 4).expand(gs[0], 4)
         dprob = dprob.view(()) if ps == () else dprob.expand(ps)
-        dw2, db2 = dwb[:c * k].view(c, k), dwb[c * k:o1]
-        dw2r, db2r = dwb[o1:o1 + nr * k].view(nr, k), dwb[o1 + nr * k:]
         return (dx1, None, dw2, db2 if has_b2 else None, dx2, None, dw2r, db2r if has_b2r else None, None, None, dxhat, None,
                 dgram, dprob, None, None, None, None, None)
 
@@ -2917,29 +2937,15 @@ class ClusterHeadLoss(torch.autograd.Function):
         f1, keep1, w1, b1, f2, keep2, w2, b2, x_hat, snps, prob = (
             f(t) for t in (f1, keep1, w1, b1, f2, keep2, w2, b2, x_hat, snps, prob))
         y, clust_y = y.contiguous(), clust_y.contiguous()
-        rows, k = f1.shape
-        b, c1, c2, s = rows // 2, w1.shape[0], w2.shape[0], snps.shape[1]
-        if y.dtype != torch.int64 or clust_y.dtype != torch.int64 or y.numel() != b or clust_y.numel() != b \
-                or rows != 2 * b or f2.shape != f1.shape or x_hat.shape != (2 * b, s) or prob.numel() == 0 \
-                or snps.shape[0] != b or w1.shape[1] != k or w2.shape[1] != k:
-            raise _lib.IgcnError("cluster head loss: inconsistent shapes")
-        dev = f1.device
         lib = _lib.load()
-        if not lib.igcn_cluster_head_loss_supported(k, c1, c2):
-            raise _lib.IgcnError(f"cluster head loss: K/4 a power of two <= 64 and C1, C2 <= 4 (K={k} C1={c1} C2={c2})")
-        wts = _cluster_loss_weights(hp_ce, hp_mi, lambda0, b, predict_cluster, dev)
+        (b, k, c1, c2, s, nblk), out8, (logp1, logp2), (dx1, dx2, dxhat), parts, wpart = _head_loss_buffers(
+            "cluster head loss", f1, w1, f2, w2, (y, clust_y), x_hat, snps, prob, lib.igcn_cluster_head_loss_supported,
+            lib.igcn_cluster_head_loss_blocks, 5)
+        wts = _cluster_loss_weights(hp_ce, hp_mi, lambda0, b, predict_cluster, f1.device)
         if wts is None:
             raise _lib.IgcnError("cluster head loss: the loss weights must be uploaded outside a capture "
                                  "(ops._cluster_loss_weights)")
-        f32 = dict(dtype=torch.float32, device=dev)
-        nblk = int(lib.igcn_cluster_head_loss_blocks(b, k))
-        out8 = torch.empty(8, **f32)
-        logp1, logp2 = torch.empty(2 * b, c1, **f32), torch.empty(2 * b, c2, **f32)
-        dx1, dx2, dxhat = torch.empty_like(f1), torch.empty_like(f2), torch.empty_like(x_hat)
-        parts = torch.empty(nblk, 5, **f32)
-        wcols = c1 * k + c1 + c2 * k + c2
-        wpart = torch.empty(nblk, wcols, **f32)
-        dprob = torch.empty(1, **f32)
+        dprob = torch.empty(1, dtype=torch.float32, device=f1.device)
         call("igcn_cluster_head_loss_fwd", b, k, c1, c2, s, ptr(f1), ptr(keep1), ptr(w1), ptr(b1), ptr(f2), ptr(keep2),
              ptr(w2), ptr(b2), ptr(y), ptr(clust_y), ptr(x_hat), ptr(snps), float(hp_ce), float(hp_mi), float(lambda0),
              1 if predict_cluster else 0, ptr(logp1), ptr(logp2), ptr(dx1), ptr(dx2), ptr(dxhat), ptr(parts), ptr(wpart),
@@ -2964,23 +2970,10 @@ class ClusterHeadLoss(torch.autograd.Function):
             parts, prob, wts, out8 = ctx.final
             call("igcn_cluster_loss_final", ptr(parts), nblk, ptr(prob), prob.numel(), ptr(wts), ptr(out8), stream_ptr())
             _keep(parts)
-        wcols = c1 * k + c1 + c2 * k + c2
-        dwb = _keep(torch.empty(wcols, dtype=torch.float32, device=dx1.device))       # (kept until the flush: HeadLoss)
-        _keep(wpart)
-        o1, o2 = c1 * k + c1, c2 * k + c2
-        gout = _f32(gout).reshape(1)
-        unit = gout.data_ptr() in UNIT_GRAD_PTRS
-        # (another upstream gradient scales the sums below: they are then needed here, not at the flush)
-        with _immediate(ctx.w_final[0] and unit):
-            call("igcn_reduce_rows_final", ptr(wpart), nblk, wcols, o1, ptr(dwb), stream_ptr())
-        with _immediate(ctx.w_final[1] and unit):
-            call("igcn_reduce_rows_final", wpart.data_ptr() + 4 * o1, nblk, wcols, o2, ptr(dwb[o1:]), stream_ptr())
-        if not unit:                                 # every gradient is linear in the upstream one
-            dx1, dx2, dxhat, dprob, dwb = (t * gout for t in (dx1, dx2, dxhat, dprob, dwb))
+        _, (dx1, dx2, dxhat, dprob), (dw1, db1, dw2, db2) = _head_loss_backward(
+            (dx1, dx2, dxhat, dprob), wpart, nblk, k, (c1, c2), ctx.w_final, gout)
         ps = ctx.prob_shape
         dprob = dprob.view(()) if ps == () else dprob.expand(ps)
-        dw1, db1 = dwb[:c1 * k].view(c1, k), dwb[c1 * k:o1]
-        dw2, db2 = dwb[o1:o1 + c2 * k].view(c2, k), dwb[o1 + c2 * k:]
         return (dx1, None, dw1, db1 if has_b1 else None, dx2, None, dw2, db2 if has_b2 else None, None, None, dxhat, None,
                 dprob, None, None, None, None, None)
 

@@ -9,7 +9,9 @@ synthetic 3000-node GO DAG (bench.POOL), dropout on, lambda0 = 1e-5.  Three part
      (ops.small_linear_pair + log_softmax + nll_loss + the torch reconstruction sum) and of the headline
      SGCN_GCN_IMGSNP step of bench.py on the same batch, the three taking turns block by block;
   2. ``launches`` — us per launch, hot (a hipGraph of 50 launches between two events), of igcn_cluster_head_loss_fwd and
-     of igcn_mask_reg3_fwd / _bwd at the step's shapes;
+     of igcn_mask_reg3_fwd / _bwd at the step's shapes, and of the headline's narrow-layer launches at theirs
+     (igcn_head_loss_gram_fwd, igcn_head_loss_fwd, igcn_small_linear_pair_fwd / _bwd); ``--launches-only`` runs this part alone (an A/B of
+     two builds of the library: one run per build, taking turns);
   3. ``--trace fused|unfused`` runs 40 eager train steps of one route and nothing else — the program to put behind
      ``rocprofv3 --kernel-trace --stats --output-format csv -d DIR --``, once per route, in runs of their own;
      ``--summarise DIR_FUSED DIR_UNFUSED`` then lists every kernel whose launches per step differ between the two routes
@@ -143,10 +145,61 @@ def launch_us(dev):
     out = {"shape": {"B": b, "K": k, "C1": c1, "C2": c2, "S": s, "head_loss_blocks": nblk, "n_edge": n_edge,
                      "mask_reg_blocks": int(lib.igcn_mask_reg_blocks(90 + n_edge + 54))},
            "timing": f"hot: a hipGraph of {ITERS} launches between two events, best of 3, per launch"}
-    for name, fn in (("cluster_head_loss_fwd_us", head), ("mask_reg3_fwd_us", reg_fwd), ("mask_reg3_bwd_us", reg_bwd)):
+    launches = [("cluster_head_loss_fwd_us", head), ("mask_reg3_fwd_us", reg_fwd), ("mask_reg3_bwd_us", reg_bwd)]
+    for name, fn in launches + headline_launches(dev, out["shape"]):
         out[name] = round(bench._time_graph(fn) / ITERS, 2)
         print(f"{name}: {out[name]:.2f} us", flush=True)
     return out
+
+
+def headline_launches(dev, shape):
+    """The headline trainer's narrow-layer launches at its step's shapes: B = 256, K = 64, (C, NR) = (2, 4), S = 54, the
+    Gram role on out_z [2B, 40] with tsne [B, 90]; the unfused pair forward / backward on the same 2B rows."""
+    import ctypes
+    from igcn_amd._lib import call, ptr, stream_ptr
+    lib = _lib.load()
+    b, k, c, nr, s, rd, groups, t_dim = bench.GRAPHS_PER_GPU, 64, 2, 4, 54, 40, 2, 90
+    shape["headline"] = {"B": b, "K": k, "C": c, "NR": nr, "S": s, "RD": rd, "groups": groups, "T": t_dim}
+    r = lambda *sh: torch.randn(*sh, device=dev)                             # noqa: E731
+    e = lambda *sh: torch.empty(*sh, device=dev)                             # noqa: E731
+    x1, x2, w1, b1, w2, b2 = r(2 * b, k).relu(), r(2 * b, k).relu(), r(c, k), r(c), r(nr, k), r(nr)
+    keep1, keep2 = ((torch.rand(2 * b, k, device=dev) > 0.5).float() * 2 for _ in range(2))
+    y, clin, x_hat, snps = torch.randint(0, c, (b,), device=dev), r(b, nr), r(2 * b, s), torch.rand(b, s, device=dev)
+    nblk = int(lib.igcn_head_loss_blocks(b, k))
+    o = [e(2 * b, c), e(2 * b, nr), e(2 * b, k), e(2 * b, k), e(2 * b, s), e(nblk, 4), e(nblk, c * k + c + nr * k + nr),
+         e(4), e(1)]
+    z = r(groups, b, rd)
+    gram, tsne = (z @ z.transpose(1, 2)).contiguous(), r(b, t_dim)
+    lap, gscr, sym = e(b, b), e(b, 2 * groups), e(groups, b, b)
+    lam6, gout = (ctypes.c_float * 6)(1.0, 1.0, 1.0, 1e-5, 0.1, 0.1), (ctypes.c_float * (2 * groups))(*[0.1] * (2 * groups))
+
+    def head_gram():
+        for _ in range(ITERS):
+            call("igcn_head_loss_gram_fwd", b, k, c, nr, s, ptr(x1), ptr(keep1), ptr(w1), ptr(b1), ptr(x2), ptr(keep2),
+                 ptr(w2), ptr(b2), ptr(y), ptr(clin), ptr(x_hat), ptr(snps), lam6, 1.0, 1.0, *[ptr(t) for t in o], b, rd,
+                 groups, ptr(gram), ptr(tsne), t_dim, 0.05, ptr(lap), ptr(gscr), gout, ptr(sym), stream_ptr())
+
+    def head_alone():                                # (the head role without the Gram rows: igcn_head_loss_fwd)
+        for _ in range(ITERS):
+            call("igcn_head_loss_fwd", b, k, c, nr, s, ptr(x1), ptr(keep1), ptr(w1), ptr(b1), ptr(x2), ptr(keep2), ptr(w2),
+                 ptr(b2), ptr(y), ptr(clin), ptr(x_hat), ptr(snps), lam6, 1.0, 1.0, *[ptr(t) for t in o], stream_ptr())
+    rows = 2 * b
+    y1, y2, dy1, dy2, dx1, dx2 = e(rows, c), e(rows, nr), r(rows, c), r(rows, nr), e(rows, k), e(rows, k)
+    dwb1, dwb2 = e(c * k + c), e(nr * k + nr)
+    s1 = e(int(lib.igcn_small_linear_bwd_scratch_floats(rows, k, c)))
+    s2 = e(int(lib.igcn_small_linear_bwd_scratch_floats(rows, k, nr)))
+
+    def pair_fwd():
+        for _ in range(ITERS):
+            call("igcn_small_linear_pair_fwd", rows, k, c, ptr(x1), ptr(keep1), ptr(w1), ptr(b1), ptr(y1), nr, ptr(x2),
+                 ptr(keep2), ptr(w2), ptr(b2), ptr(y2), stream_ptr())
+
+    def pair_bwd():                                  # (the kernel and its two short reductions of block partials)
+        for _ in range(ITERS):
+            call("igcn_small_linear_pair_bwd", rows, k, c, ptr(x1), ptr(keep1), ptr(w1), ptr(dy1), ptr(dx1), ptr(dwb1),
+                 ptr(s1), nr, ptr(x2), ptr(keep2), ptr(w2), ptr(dy2), ptr(dx2), ptr(dwb2), ptr(s2), stream_ptr())
+    return [("head_loss_gram_fwd_us", head_gram), ("head_loss_fwd_us", head_alone), ("small_linear_pair_fwd_us", pair_fwd),
+            ("small_linear_pair_bwd_us", pair_bwd)]
 
 
 def trace_workload(dev, route):
@@ -196,6 +249,7 @@ def main():
     ap.add_argument("--blocks", type=int, default=5)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--trace", choices=["fused", "unfused"], default=None)
+    ap.add_argument("--launches-only", action="store_true", help="part 2 alone")
     ap.add_argument("--summarise", nargs=2, metavar=("DIR_FUSED", "DIR_UNFUSED"), default=None)
     args = ap.parse_args()
     res = {}
@@ -208,7 +262,8 @@ def main():
         _lib.load()
         if args.trace:
             return trace_workload(dev, args.trace)
-        res["step"] = step_ms(dev, args.blocks, args.steps)
+        if not args.launches_only:
+            res["step"] = step_ms(dev, args.blocks, args.steps)
         res["launches"] = launch_us(dev)
         res["device"] = torch.cuda.get_device_name(0)
     print(json.dumps(res))
