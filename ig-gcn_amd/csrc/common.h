@@ -64,6 +64,8 @@ static inline bool igcn_first_on_device(IgcnPerDevice& f) {
 
 static inline int64_t igcn_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+
 // ---- wave / block reductions (deterministic: fixed tree) ---------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

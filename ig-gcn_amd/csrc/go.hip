@@ -6,6 +6,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "nodes_ln.h"
 #include <algorithm>
 #include <vector>
 
@@ -1050,8 +1051,6 @@ __device__ __forceinline__ void go_butterfly(float (&acc)[F], int lane) {
   }
 }
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-
 // ---- LayerNorm-over-nodes backward folded into its consumer's copy-in -------------------------------------------
 // The gradient a GO layer's backward receives is the LayerNorm's input gradient (go_model.py:246-251: y = layer(x),
 // x' = dropout(relu(LN(y)))).  The LDS-resident backward kernels hold ONE sample — all FOUT rows of its N nodes — so
@@ -1059,9 +1058,9 @@ __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast
 // LayerNorm's own dX launch (one workgroup per (sample, channel) row: 12.8 us x 4 in the default step), the 15 MB it
 // writes and the 15 MB read back disappear, and since a workgroup sees all channels of a sample it also leaves the
 // affine gradients summed over them — part [B][2][N - pool] (d gamma | d beta rows of the kept nodes), reduced over samples by the deferred
-// final reduction instead of k_nodes_ln_bwd_affine_multi's second pass over y and dz.  Arithmetic per element as
-// k_nodes_ln_bwd_dy_v / ln_bwd_affine_v_body.  Preconditions (igcn_go_ln_fused_ok): N, pool multiples of 4, N / 4 <= T,
-// 16-byte aligned tensors.
+// final reduction instead of k_nodes_ln_bwd_affine_multi's second pass over y and dz.  Arithmetic per element:
+// nodes_ln.h's float4 functions under the ReLU policy.  Preconditions (igcn_go_ln_fused_ok): N, pool multiples of 4,
+// N / 4 <= T, 16-byte aligned tensors.
 struct LnFuse {
   const float *y, *dz, *gamma, *beta, *keep, *mean, *rstd;
   float* part;
@@ -1149,24 +1148,20 @@ __device__ __forceinline__ void ln_bwd_into_lds(const LnFuse& L, int b, int N, f
   }
   float s[2 * FOUT];
   float4 dg = zero4, db = zero4;
+  const LnRelu relu(nullptr);
 #pragma unroll
   for (int c = 0; c < FOUT; ++c) {
     float4 xh = zero4, dx = zero4;
-    if (live) xh = make_float4((yv[c].x - mu[c]) * rs[c], (yv[c].y - mu[c]) * rs[c], (yv[c].z - mu[c]) * rs[c],
-                               (yv[c].w - mu[c]) * rs[c]);
+    if (live) xh = ln_xhat(yv[c], mu[c], rs[c]);
     if (act) {
       float4 u = up[c];
-      u.x *= kp.x; u.y *= kp.y; u.z *= kp.z; u.w *= kp.w;
-      u.x = xh.x * g.x + be.x > 0.f ? u.x : 0.f;
-      u.y = xh.y * g.y + be.y > 0.f ? u.y : 0.f;
-      u.z = xh.z * g.z + be.z > 0.f ? u.z : 0.f;
-      u.w = xh.w * g.w + be.w > 0.f ? u.w : 0.f;
-      dx = make_float4(u.x * g.x, u.y * g.y, u.z * g.z, u.w * g.w);
-      dg.x += u.x * xh.x; dg.y += u.y * xh.y; dg.z += u.z * xh.z; dg.w += u.w * xh.w;
-      db.x += u.x; db.y += u.y; db.z += u.z; db.w += u.w;
+      ln_keep(u, kp);
+      u = ln_up(relu, ln_u(xh, g, be), u);
+      dx = ln_dxhat(u, g);
+      ln_affine_acc<true>(u, xh, dg, db);
     }
-    s[c] = (dx.x + dx.y) + (dx.z + dx.w);
-    s[FOUT + c] = (dx.x * xh.x + dx.y * xh.y) + (dx.z * xh.z + dx.w * xh.w);
+    s[c] = ln_sum4(dx);
+    s[FOUT + c] = ln_dot4(dx, xh);
     yv[c] = xh;                                         // the registers now hold xhat and the masked, scaled upstream
     up[c] = dx;
   }
@@ -1184,15 +1179,8 @@ __device__ __forceinline__ void ln_bwd_into_lds(const LnFuse& L, int b, int N, f
   go_block_sums<2 * FOUT, T>(s, red, [fN](float t, int) { return t / fN; });
   if (live) {
 #pragma unroll
-    for (int c = 0; c < FOUT; ++c) {
-      const float s1 = s[c], s2 = s[FOUT + c];
-      float4 o;
-      o.x = rs[c] * (up[c].x - s1 - yv[c].x * s2);
-      o.y = rs[c] * (up[c].y - s1 - yv[c].y * s2);
-      o.z = rs[c] * (up[c].z - s1 - yv[c].z * s2);
-      o.w = rs[c] * (up[c].w - s1 - yv[c].w * s2);
-      *reinterpret_cast<float4*>(dys + c * N + n) = o;
-    }
+    for (int c = 0; c < FOUT; ++c)
+      *reinterpret_cast<float4*>(dys + c * N + n) = ln_dy<true>(rs[c], up[c], yv[c], s[c], s[FOUT + c]);
   }
 }
 
@@ -1693,440 +1681,6 @@ extern "C" int igcn_go_attn_ln_bwd(int B, int N, int fin, int fout, const int32_
   if (pool == 0) return igcn_launch_reduce_rows_final(part, B, 2 * (int64_t)M, 2 * M, dgb, (hipStream_t)stream);
   if ((rc = igcn_launch_reduce_rows_final(part, B, 2 * (int64_t)M, M, dgb + pool, (hipStream_t)stream))) return rc;
   return igcn_launch_reduce_rows_final(part + M, B, 2 * (int64_t)M, M, dgb + N + pool, (hipStream_t)stream);
-}
-
-// =================================================================================================
-// LayerNorm over nodes + ReLU + node dropout + pooling
-// =================================================================================================
-__global__ void __launch_bounds__(GO_T)
-k_nodes_ln_fwd(int f, int N, int pool, float eps, const float* __restrict__ y, const float* __restrict__ gamma,
-               const float* __restrict__ beta, const float* __restrict__ keep, float* __restrict__ z,
-               float* __restrict__ mean_out, float* __restrict__ rstd_out) {
-  __shared__ float red[16];
-  const int row = blockIdx.x;  // b*f + c
-  const int b = row / f;
-  const float* yr = y + (int64_t)row * N;
-  float s = 0.f;
-  for (int n = threadIdx.x; n < N; n += GO_T) s += yr[n];
-  const float mean = block_sum_all(s, red) / (float)N;
-  float v = 0.f;
-  for (int n = threadIdx.x; n < N; n += GO_T) {
-    const float d = yr[n] - mean;
-    v += d * d;
-  }
-  const float var = block_sum_all(v, red) / (float)N;
-  const float rstd = 1.0f / sqrtf(var + eps);
-  if (threadIdx.x == 0) {
-    mean_out[row] = mean;
-    rstd_out[row] = rstd;
-  }
-  const int M = N - pool;
-  float* zr = z + (int64_t)row * M;
-  for (int n = pool + threadIdx.x; n < N; n += GO_T) {
-    float t = (yr[n] - mean) * rstd * gamma[n] + beta[n];
-    t = fmaxf(t, 0.f);
-    if (keep) t *= keep[(int64_t)b * N + n];
-    zr[n - pool] = t;
-  }
-}
-
-// Register-resident form: the row (N <= 4096 floats, N and pool multiples of 4) is read ONCE with 16-byte loads and
-// kept in registers for the mean, the variance and the normalisation (the generic kernel makes three passes).
-#define LN_VPT 4
-#define LN_TMAX 1024
-
-// Which (sample, channel) row a workgroup takes: XCD c the rows [c R/8, (c+1) R/8) in order, so that the f channel rows
-// of a sample — which all read the sample's dropout factors keep[b, :] — meet in one L2 (blockIdx.x taken as it comes
-// puts them on f different XCDs).
-__device__ __forceinline__ int ln_row() {
-  const int n = (int)gridDim.x, x = (int)blockIdx.x;
-  return (n & 7) ? x : (x & 7) * (n >> 3) + (x >> 3);
-}
-
-// (256 threads for rows up to 4096 nodes, 1024 threads up to 16384: the 10 000-node hierarchy of configs[4])
-__global__ void __launch_bounds__(LN_TMAX)
-k_nodes_ln_fwd_v(int f, int N, int pool, float eps, const float* __restrict__ y, const float* __restrict__ gamma,
-                 const float* __restrict__ beta, const float* __restrict__ keep, float* __restrict__ z,
-                 float* __restrict__ mean_out, float* __restrict__ rstd_out) {
-  __shared__ float red[16];
-  const int row = ln_row(), b = row / f, nv = N / 4;
-  const float* yr = y + (int64_t)row * N;
-  float4 v[LN_VPT];
-  // the affine parameters and the dropout factors of the thread's slots are requested with the row, in front of the two
-  // block sums (asked for behind them, their round trip was the tail of every workgroup of a 2560-workgroup latency chain)
-  float4 g4[LN_VPT], be4[LN_VPT], k4[LN_VPT];
-#pragma unroll
-  for (int i = 0; i < LN_VPT; ++i) {
-    const int q = threadIdx.x + i * (int)blockDim.x, n = 4 * q;
-    v[i] = q < nv ? ld4(yr + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
-    g4[i] = be4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    k4[i] = make_float4(1.f, 1.f, 1.f, 1.f);
-    if (q < nv && n >= pool) {
-      g4[i] = ld4(gamma + n);
-      be4[i] = ld4(beta + n);
-      if (keep) k4[i] = ld4(keep + (int64_t)b * N + n);
-    }
-  }
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < LN_VPT; ++i) s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-  const float mean = block_sum_all(s, red) / (float)N;
-  float var = 0.f;
-#pragma unroll
-  for (int i = 0; i < LN_VPT; ++i) {
-    if (threadIdx.x + i * (int)blockDim.x < nv) {
-      const float a = v[i].x - mean, bb = v[i].y - mean, c = v[i].z - mean, d = v[i].w - mean;
-      var += (a * a + bb * bb) + (c * c + d * d);
-    }
-  }
-  var = block_sum_all(var, red) / (float)N;
-  const float rstd = 1.0f / sqrtf(var + eps);
-  if (threadIdx.x == 0) {
-    mean_out[row] = mean;
-    rstd_out[row] = rstd;
-  }
-  float* zr = z + (int64_t)row * (N - pool);
-#pragma unroll
-  for (int i = 0; i < LN_VPT; ++i) {
-    const int q = threadIdx.x + i * (int)blockDim.x, n = 4 * q;
-    if (q < nv && n >= pool) {
-      const float4 g = g4[i], be = be4[i];
-      float4 o;
-      o.x = fmaxf((v[i].x - mean) * rstd * g.x + be.x, 0.f);
-      o.y = fmaxf((v[i].y - mean) * rstd * g.y + be.y, 0.f);
-      o.z = fmaxf((v[i].z - mean) * rstd * g.z + be.z, 0.f);
-      o.w = fmaxf((v[i].w - mean) * rstd * g.w + be.w, 0.f);
-      if (keep) {
-        const float4 k = k4[i];
-        o.x *= k.x; o.y *= k.y; o.z *= k.z; o.w *= k.w;
-      }
-      *reinterpret_cast<float4*>(zr + (n - pool)) = o;
-    }
-  }
-}
-
-__global__ void __launch_bounds__(LN_TMAX)
-k_nodes_ln_bwd_dy_v(int f, int N, int pool, const float* __restrict__ y, const float* __restrict__ gamma,
-                    const float* __restrict__ beta, const float* __restrict__ keep, const float* __restrict__ mean,
-                    const float* __restrict__ rstd, const float* __restrict__ dz, float* __restrict__ dy) {
-  __shared__ float red[16];
-  const int row = ln_row(), b = row / f, nv = N / 4;
-  const float mu = mean[row], rs = rstd[row];
-  const float* yr = y + (int64_t)row * N;
-  const float* dzr = dz + (int64_t)row * (N - pool);
-  float4 xh[LN_VPT], dx[LN_VPT];
-  float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-  for (int i = 0; i < LN_VPT; ++i) {
-    const int q = threadIdx.x + i * (int)blockDim.x, n = 4 * q;
-    xh[i] = dx[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (q < nv) {
-      const float4 yv = ld4(yr + n), g = ld4(gamma + n);
-      xh[i] = make_float4((yv.x - mu) * rs, (yv.y - mu) * rs, (yv.z - mu) * rs, (yv.w - mu) * rs);
-      if (n >= pool) {
-        const float4 be = ld4(beta + n);
-        float4 up = ld4(dzr + (n - pool));
-        if (keep) {
-          const float4 k = ld4(keep + (int64_t)b * N + n);
-          up.x *= k.x; up.y *= k.y; up.z *= k.z; up.w *= k.w;
-        }
-        dx[i].x = xh[i].x * g.x + be.x > 0.f ? up.x * g.x : 0.f;
-        dx[i].y = xh[i].y * g.y + be.y > 0.f ? up.y * g.y : 0.f;
-        dx[i].z = xh[i].z * g.z + be.z > 0.f ? up.z * g.z : 0.f;
-        dx[i].w = xh[i].w * g.w + be.w > 0.f ? up.w * g.w : 0.f;
-      }
-      s1 += (dx[i].x + dx[i].y) + (dx[i].z + dx[i].w);
-      s2 += (dx[i].x * xh[i].x + dx[i].y * xh[i].y) + (dx[i].z * xh[i].z + dx[i].w * xh[i].w);
-    }
-  }
-  s1 = block_sum_all(s1, red) / (float)N;
-  s2 = block_sum_all(s2, red) / (float)N;
-  float* dyr = dy + (int64_t)row * N;
-#pragma unroll
-  for (int i = 0; i < LN_VPT; ++i) {
-    const int q = threadIdx.x + i * (int)blockDim.x;
-    if (q < nv) {
-      float4 o;
-      o.x = rs * (dx[i].x - s1 - xh[i].x * s2);
-      o.y = rs * (dx[i].y - s1 - xh[i].y * s2);
-      o.z = rs * (dx[i].z - s1 - xh[i].z * s2);
-      o.w = rs * (dx[i].w - s1 - xh[i].w * s2);
-      *reinterpret_cast<float4*>(dyr + 4 * q) = o;
-    }
-  }
-}
-
-static int ln_threads(int N) { return N <= GO_T * 4 * LN_VPT ? GO_T : LN_TMAX; }
-static bool ln_vec_ok(int N, int pool, const void* a, const void* b, const void* c, const void* d, const void* e,
-                      const void* k) {
-  auto al = [](const void* p) { return p == nullptr || ((uintptr_t)p % 16) == 0; };
-  return N % 4 == 0 && pool % 4 == 0 && N <= LN_TMAX * 4 * LN_VPT && al(a) && al(b) && al(c) && al(d) && al(e) && al(k);
-}
-
-extern "C" int igcn_nodes_ln_fwd(int B, int f, int N, int pool, float eps, const float* y, const float* gamma,
-                                 const float* beta, const float* keep, float* z, float* mean, float* rstd,
-                                 void* stream) {
-  IGCN_REQUIRE(B > 0 && f > 0 && N > 0 && pool >= 0 && pool < N, "nodes_ln_fwd: bad sizes");
-  if (ln_vec_ok(N, pool, y, gamma, beta, z, nullptr, keep)) {
-    hipLaunchKernelGGL(k_nodes_ln_fwd_v, dim3(B * f), dim3(ln_threads(N)), 0, (hipStream_t)stream, f, N, pool, eps, y, gamma,
-                       beta, keep, z, mean, rstd);
-    IGCN_CHECK_LAUNCH("nodes_ln_fwd_v");
-    return IGCN_OK;
-  }
-  hipLaunchKernelGGL(k_nodes_ln_fwd, dim3(B * f), dim3(GO_T), 0, (hipStream_t)stream, f, N, pool, eps, y, gamma,
-                     beta, keep, z, mean, rstd);
-  IGCN_CHECK_LAUNCH("nodes_ln_fwd");
-  return IGCN_OK;
-}
-
-__global__ void __launch_bounds__(GO_T)
-k_nodes_ln_bwd_dy(int f, int N, int pool, const float* __restrict__ y, const float* __restrict__ gamma,
-                  const float* __restrict__ beta, const float* __restrict__ keep, const float* __restrict__ mean,
-                  const float* __restrict__ rstd, const float* __restrict__ dz, float* __restrict__ dy) {
-  __shared__ float red[16];
-  const int row = blockIdx.x;
-  const int b = row / f;
-  const float mu = mean[row], rs = rstd[row];
-  const float* yr = y + (int64_t)row * N;
-  const int M = N - pool;
-  const float* dzr = dz + (int64_t)row * M;
-  float s1 = 0.f, s2 = 0.f;
-  for (int n = threadIdx.x; n < N; n += GO_T) {
-    const float xh = (yr[n] - mu) * rs;
-    float up = 0.f;
-    if (n >= pool && xh * gamma[n] + beta[n] > 0.f) {
-      up = dzr[n - pool];
-      if (keep) up *= keep[(int64_t)b * N + n];
-    }
-    const float dxh = up * gamma[n];
-    s1 += dxh;
-    s2 += dxh * xh;
-  }
-  s1 = block_sum_all(s1, red) / (float)N;
-  s2 = block_sum_all(s2, red) / (float)N;
-  float* dyr = dy + (int64_t)row * N;
-  for (int n = threadIdx.x; n < N; n += GO_T) {
-    const float xh = (yr[n] - mu) * rs;
-    float up = 0.f;
-    if (n >= pool && xh * gamma[n] + beta[n] > 0.f) {
-      up = dzr[n - pool];
-      if (keep) up *= keep[(int64_t)b * N + n];
-    }
-    dyr[n] = rs * (up * gamma[n] - s1 - xh * s2);
-  }
-}
-
-// dgamma[n] = sum_rows up*xhat ; dbeta[n] = sum_rows up.  Block = 64 node lanes x 4 row groups over a
-// chunk of LN_RC rows; partial[chunk][2][N] is summed over chunks (in order) by k_reduce_rows.
-#define LN_RC 64
-__global__ void __launch_bounds__(256)
-k_nodes_ln_bwd_affine(int rows, int f, int N, int pool, const float* __restrict__ y,
-                      const float* __restrict__ gamma, const float* __restrict__ beta,
-                      const float* __restrict__ keep, const float* __restrict__ mean,
-                      const float* __restrict__ rstd, const float* __restrict__ dz,
-                      float* __restrict__ partial) {
-  __shared__ float sg[4][64], sb[4][64];
-  const int nl = threadIdx.x & 63, rg = threadIdx.x >> 6;
-  const int n = blockIdx.x * 64 + nl;
-  const int r0 = blockIdx.y * LN_RC, r1 = min(rows, r0 + LN_RC);
-  float dg = 0.f, db = 0.f;
-  if (n < N && n >= pool) {
-    const float ga = gamma[n], be = beta[n];
-    const int M = N - pool;
-#pragma unroll 4
-    for (int row = r0 + rg; row < r1; row += 4) {      // unconditional, independent loads: several rows in flight
-      const float yv = y[(int64_t)row * N + n];
-      float up = dz[(int64_t)row * M + (n - pool)];
-      if (keep) up *= keep[(int64_t)(row / f) * N + n];
-      const float xh = (yv - mean[row]) * rstd[row];
-      up = (xh * ga + be > 0.f) ? up : 0.f;
-      dg += up * xh;
-      db += up;
-    }
-  }
-  sg[rg][nl] = dg;
-  sb[rg][nl] = db;
-  __syncthreads();
-  if (rg == 0 && n < N) {
-    float* prow = partial + (int64_t)blockIdx.y * 2 * N;
-    prow[n] = (sg[0][nl] + sg[1][nl]) + (sg[2][nl] + sg[3][nl]);
-    prow[N + n] = (sb[0][nl] + sb[1][nl]) + (sb[2][nl] + sb[3][nl]);
-  }
-}
-
-// 16-bytes-per-lane form (N, pool multiples of 4, aligned rows): thread = (quad of nodes, row lane); one float4 of y,
-// dz and keep per row instead of four scalar loads each.  Same chunk layout of the partials.
-__device__ __forceinline__ void
-ln_bwd_affine_v_body(const int bx, const int by, int rows, int f, int N, int pool, const float* __restrict__ y,
-                     const float* __restrict__ gamma, const float* __restrict__ beta,
-                     const float* __restrict__ keep, const float* __restrict__ mean,
-                     const float* __restrict__ rstd, const float* __restrict__ dz,
-                     float* __restrict__ partial) {
-  __shared__ float4 sg[16][16], sb[16][16];
-  const int nq = threadIdx.x & 15, rg = threadIdx.x >> 4;
-  const int n = (bx * 16 + nq) * 4;
-  const int r0 = by * LN_RC, r1 = min(rows, r0 + LN_RC);
-  float4 dg = make_float4(0.f, 0.f, 0.f, 0.f), db = dg;
-  if (n < N && n >= pool) {
-    const float4 ga = ld4(gamma + n), be = ld4(beta + n);
-    const int M = N - pool;
-#pragma unroll 4
-    for (int row = r0 + rg; row < r1; row += 16) {
-      const float4 yv = ld4(y + (int64_t)row * N + n);
-      float4 up = ld4(dz + (int64_t)row * M + (n - pool));
-      if (keep) {
-        const float4 k = ld4(keep + (int64_t)(row / f) * N + n);
-        up.x *= k.x; up.y *= k.y; up.z *= k.z; up.w *= k.w;
-      }
-      const float mu = mean[row], rs = rstd[row];
-      const float x0 = (yv.x - mu) * rs, x1 = (yv.y - mu) * rs, x2 = (yv.z - mu) * rs, x3 = (yv.w - mu) * rs;
-      up.x = (x0 * ga.x + be.x > 0.f) ? up.x : 0.f;
-      up.y = (x1 * ga.y + be.y > 0.f) ? up.y : 0.f;
-      up.z = (x2 * ga.z + be.z > 0.f) ? up.z : 0.f;
-      up.w = (x3 * ga.w + be.w > 0.f) ? up.w : 0.f;
-      dg.x += up.x * x0; dg.y += up.y * x1; dg.z += up.z * x2; dg.w += up.w * x3;
-      db.x += up.x; db.y += up.y; db.z += up.z; db.w += up.w;
-    }
-  }
-  sg[rg][nq] = dg;
-  sb[rg][nq] = db;
-  __syncthreads();
-  if (rg == 0 && n < N) {
-    float4 tg = make_float4(0.f, 0.f, 0.f, 0.f), tb = tg;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {                     // row lanes summed in order
-      const float4 a = sg[r][nq], c = sb[r][nq];
-      tg.x += a.x; tg.y += a.y; tg.z += a.z; tg.w += a.w;
-      tb.x += c.x; tb.y += c.y; tb.z += c.z; tb.w += c.w;
-    }
-    float* prow = partial + (int64_t)by * 2 * N;
-    *reinterpret_cast<float4*>(prow + n) = tg;
-    *reinterpret_cast<float4*>(prow + N + n) = tb;
-  }
-}
-
-__global__ void __launch_bounds__(256)
-k_nodes_ln_bwd_affine_v(int rows, int f, int N, int pool, const float* __restrict__ y,
-                        const float* __restrict__ gamma, const float* __restrict__ beta,
-                        const float* __restrict__ keep, const float* __restrict__ mean,
-                        const float* __restrict__ rstd, const float* __restrict__ dz,
-                        float* __restrict__ partial) {
-  ln_bwd_affine_v_body((int)blockIdx.x, (int)blockIdx.y, rows, f, N, pool, y, gamma, beta, keep, mean, rstd, dz, partial);
-}
-
-// The affine-gradient passes of SEVERAL LayerNorm layers in one flat grid: d gamma / d beta are parameter gradients —
-// nothing in the backward reads them — so the passes of a whole backward can wait for its end and share one launch
-// (four grids of 150-750 workgroups each, which otherwise run one after the other between the layers' dX kernels).
-#define LN_AFF_MAX 4
-struct LnAffProb {
-  int rows, f, N, pool, gx, wg0;
-  const float *y, *gamma, *beta, *keep, *mean, *rstd, *dz;
-  float* partial;
-};
-struct LnAffGroup { int n; LnAffProb p[LN_AFF_MAX]; };
-__global__ void __launch_bounds__(256) k_nodes_ln_bwd_affine_multi(const LnAffGroup G) {
-  int pi = 0;
-#pragma unroll
-  for (int i = 1; i < LN_AFF_MAX; ++i)
-    if (i < G.n && (int)blockIdx.x >= G.p[i].wg0) pi = i;
-  const LnAffProb& p = G.p[pi];
-  const int l = (int)blockIdx.x - p.wg0;
-  ln_bwd_affine_v_body(l % p.gx, l / p.gx, p.rows, p.f, p.N, p.pool, p.y, p.gamma, p.beta, p.keep, p.mean, p.rstd, p.dz,
-                       p.partial);
-}
-
-extern "C" size_t igcn_nodes_ln_bwd_scratch_floats(int B, int f, int N) {
-  return (size_t)(igcn_cdiv((int64_t)B * f, LN_RC) * 2 * N + 64);
-}
-
-extern "C" int igcn_nodes_ln_bwd(int B, int f, int N, int pool, const float* y, const float* gamma,
-                                 const float* beta, const float* keep, const float* mean, const float* rstd,
-                                 const float* dz, float* dy, float* dgb /*[2,N]: dgamma then dbeta*/,
-                                 float* scratch, void* stream) {
-  IGCN_REQUIRE(B > 0 && f > 0 && N > 0 && pool >= 0 && pool < N, "nodes_ln_bwd: bad sizes");
-  hipStream_t st = (hipStream_t)stream;
-  if (ln_vec_ok(N, pool, y, gamma, beta, dz, dy, keep)) {
-    hipLaunchKernelGGL(k_nodes_ln_bwd_dy_v, dim3(B * f), dim3(ln_threads(N)), 0, st, f, N, pool, y, gamma, beta, keep, mean,
-                       rstd, dz, dy);
-  } else {
-    hipLaunchKernelGGL(k_nodes_ln_bwd_dy, dim3(B * f), dim3(GO_T), 0, st, f, N, pool, y, gamma, beta, keep, mean, rstd,
-                       dz, dy);
-  }
-  const int64_t chunks = igcn_cdiv((int64_t)B * f, LN_RC);
-  if (ln_vec_ok(N, pool, y, gamma, beta, dz, scratch, keep)) {
-    hipLaunchKernelGGL(k_nodes_ln_bwd_affine_v, dim3((unsigned)igcn_cdiv(N, 64), (unsigned)chunks), dim3(256), 0, st,
-                       B * f, f, N, pool, y, gamma, beta, keep, mean, rstd, dz, scratch);
-  } else {
-    hipLaunchKernelGGL(k_nodes_ln_bwd_affine, dim3((unsigned)igcn_cdiv(N, 64), (unsigned)chunks), dim3(256), 0, st,
-                       B * f, f, N, pool, y, gamma, beta, keep, mean, rstd, dz, scratch);
-  }
-  IGCN_CHECK_LAUNCH("nodes_ln_bwd");
-  return igcn_launch_reduce_rows_final(scratch, chunks, 2 * (int64_t)N, 2 * N, dgb, st);
-}
-
-// The backward in two calls: igcn_nodes_ln_bwd_dy now, and the affine gradients of up to LN_AFF_MAX layers later in one
-// launch (igcn_nodes_ln_bwd_affine_multi) — see k_nodes_ln_bwd_affine_multi.
-extern "C" int igcn_nodes_ln_bwd_dy(int B, int f, int N, int pool, const float* y, const float* gamma,
-                                    const float* beta, const float* keep, const float* mean, const float* rstd,
-                                    const float* dz, float* dy, void* stream) {
-  IGCN_REQUIRE(B > 0 && f > 0 && N > 0 && pool >= 0 && pool < N, "nodes_ln_bwd_dy: bad sizes");
-  hipStream_t st = (hipStream_t)stream;
-  if (ln_vec_ok(N, pool, y, gamma, beta, dz, dy, keep)) {
-    hipLaunchKernelGGL(k_nodes_ln_bwd_dy_v, dim3(B * f), dim3(ln_threads(N)), 0, st, f, N, pool, y, gamma, beta, keep, mean,
-                       rstd, dz, dy);
-  } else {
-    hipLaunchKernelGGL(k_nodes_ln_bwd_dy, dim3(B * f), dim3(GO_T), 0, st, f, N, pool, y, gamma, beta, keep, mean, rstd,
-                       dz, dy);
-  }
-  IGCN_CHECK_LAUNCH("nodes_ln_bwd_dy");
-  return IGCN_OK;
-}
-
-// table [n][13] int64 = {B, f, N, pool, y, gamma, beta, keep, mean, rstd, dz, scratch, dgb} per layer (pointers as
-// integers; scratch of igcn_nodes_ln_bwd_scratch_floats, dgb [2,N]).  Layers whose tensors do not allow 16-byte
-// accesses get their own launch of the scalar kernel.
-extern "C" int igcn_nodes_ln_bwd_affine_multi(int n, const int64_t* table, void* stream) {
-  IGCN_REQUIRE(n >= 1 && n <= LN_AFF_MAX && table != nullptr, "nodes_ln_bwd_affine_multi: 1..%d layers", LN_AFF_MAX);
-  hipStream_t st = (hipStream_t)stream;
-  LnAffGroup G = {};
-  int wgs = 0;
-  int64_t chunks_of[LN_AFF_MAX];
-  bool grouped[LN_AFF_MAX];
-  for (int i = 0; i < n; ++i) {
-    const int64_t* t = table + 13 * i;
-    const int B = (int)t[0], f = (int)t[1], N = (int)t[2], pool = (int)t[3];
-    const float *y = (const float*)t[4], *gamma = (const float*)t[5], *beta = (const float*)t[6], *keep = (const float*)t[7];
-    const float *mean = (const float*)t[8], *rstd = (const float*)t[9], *dz = (const float*)t[10];
-    float* scratch = (float*)t[11];
-    IGCN_REQUIRE(B > 0 && f > 0 && N > 0 && pool >= 0 && pool < N && scratch != nullptr,
-                 "nodes_ln_bwd_affine_multi: bad layer %d", i);
-    const int64_t chunks = igcn_cdiv((int64_t)B * f, LN_RC);
-    chunks_of[i] = chunks;
-    grouped[i] = ln_vec_ok(N, pool, y, gamma, beta, dz, scratch, keep);
-    if (!grouped[i]) {
-      hipLaunchKernelGGL(k_nodes_ln_bwd_affine, dim3((unsigned)igcn_cdiv(N, 64), (unsigned)chunks), dim3(256), 0, st,
-                         B * f, f, N, pool, y, gamma, beta, keep, mean, rstd, dz, scratch);
-      continue;
-    }
-    LnAffProb& p = G.p[G.n++];
-    p.rows = B * f; p.f = f; p.N = N; p.pool = pool;
-    p.y = y; p.gamma = gamma; p.beta = beta; p.keep = keep; p.mean = mean; p.rstd = rstd; p.dz = dz; p.partial = scratch;
-    p.gx = (int)igcn_cdiv(N, 64);
-    p.wg0 = wgs;
-    wgs += p.gx * (int)chunks;
-  }
-  if (G.n > 0) {
-    for (int i = G.n; i < LN_AFF_MAX; ++i) G.p[i] = G.p[0];
-    hipLaunchKernelGGL(k_nodes_ln_bwd_affine_multi, dim3((unsigned)wgs), dim3(256), 0, st, G);
-  }
-  IGCN_CHECK_LAUNCH("nodes_ln_bwd_affine_multi");
-  for (int i = 0; i < n; ++i) {
-    const int64_t* t = table + 13 * i;
-    const int N = (int)t[2];
-    const int rc = igcn_launch_reduce_rows_final((float*)t[11], chunks_of[i], 2 * (int64_t)N, 2 * N, (float*)t[12], st);
-    if (rc) return rc;
-  }
-  return IGCN_OK;
 }
 
 // =================================================================================================

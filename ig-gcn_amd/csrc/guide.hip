@@ -1,5 +1,6 @@
-// GUIDE_IMGSNP (kernel/guide_img_snp.py + kernel/guide_go_model.py): the PReLU forms of the GO network's
-// normalisation blocks, and the image gate + encoder_i_N in one launch per direction.
+// GUIDE_IMGSNP (kernel/guide_img_snp.py + kernel/guide_go_model.py): the BatchNorm + PReLU blocks of the GO network's
+// GUIDE form, and the image gate + encoder_i_N in one launch per direction.  (Its LayerNorm-over-nodes + PReLU block is
+// csrc/nodes_ln.hip's kernels under the LnPrelu policy.)
 //
 // nn.PReLU() has ONE slope a (shape [1]): y = u > 0 ? u : a u; du = u > 0 ? dy : a dy; da = sum (u > 0 ? 0 : u dy), dy
 // carrying the dropout factor behind the activation.  The slope is read from device memory (a captured step follows
@@ -11,150 +12,6 @@
 #define GD_T 256
 
 __device__ __forceinline__ float gd_prelu(float u, float a) { return u > 0.f ? u : a * u; }
-
-// =================================================================================================
-// LayerNorm over nodes + PReLU + node dropout + pooling (guide_go_model.py:246-251, 273-275 with w_act / w_act_out)
-// =================================================================================================
-__global__ void __launch_bounds__(GD_T)
-k_nodes_ln_prelu_fwd(int f, int N, int pool, float eps, const float* __restrict__ y, const float* __restrict__ gamma,
-                     const float* __restrict__ beta, const float* __restrict__ keep, const float* __restrict__ slope,
-                     float* __restrict__ z, float* __restrict__ mean_out, float* __restrict__ rstd_out) {
-  __shared__ float red[16];
-  const int row = blockIdx.x, b = row / f;
-  const float* yr = y + (int64_t)row * N;
-  float s = 0.f;
-  for (int n = threadIdx.x; n < N; n += GD_T) s += yr[n];
-  const float mean = block_sum_all(s, red) / (float)N;
-  float v = 0.f;
-  for (int n = threadIdx.x; n < N; n += GD_T) {
-    const float d = yr[n] - mean;
-    v += d * d;
-  }
-  const float var = block_sum_all(v, red) / (float)N;
-  const float rstd = 1.0f / sqrtf(var + eps);
-  if (threadIdx.x == 0) {
-    mean_out[row] = mean;
-    rstd_out[row] = rstd;
-  }
-  const float a = slope[0];
-  const int M = N - pool;
-  float* zr = z + (int64_t)row * M;
-  for (int n = pool + threadIdx.x; n < N; n += GD_T) {
-    float t = gd_prelu((yr[n] - mean) * rstd * gamma[n] + beta[n], a);
-    if (keep) t *= keep[(int64_t)b * N + n];
-    zr[n - pool] = t;
-  }
-}
-
-// dy of one (sample, channel) row and that row's share of d a
-__global__ void __launch_bounds__(GD_T)
-k_nodes_ln_prelu_bwd_dy(int f, int N, int pool, const float* __restrict__ y, const float* __restrict__ gamma,
-                        const float* __restrict__ beta, const float* __restrict__ keep, const float* __restrict__ slope,
-                        const float* __restrict__ mean, const float* __restrict__ rstd, const float* __restrict__ dz,
-                        float* __restrict__ dy, float* __restrict__ da_part) {
-  __shared__ float red[16];
-  const int row = blockIdx.x, b = row / f, M = N - pool;
-  const float mu = mean[row], rs = rstd[row], a = slope[0];
-  const float* yr = y + (int64_t)row * N;
-  const float* dzr = dz + (int64_t)row * M;
-  float s1 = 0.f, s2 = 0.f, sa = 0.f;
-  for (int n = threadIdx.x; n < N; n += GD_T) {
-    const float xh = (yr[n] - mu) * rs;
-    float e = 0.f;
-    if (n >= pool) {
-      float up = dzr[n - pool];
-      if (keep) up *= keep[(int64_t)b * N + n];
-      const float u = xh * gamma[n] + beta[n];
-      e = u > 0.f ? up : a * up;
-      sa += u > 0.f ? 0.f : u * up;
-    }
-    const float dxh = e * gamma[n];
-    s1 += dxh;
-    s2 += dxh * xh;
-  }
-  s1 = block_sum_all(s1, red) / (float)N;
-  s2 = block_sum_all(s2, red) / (float)N;
-  sa = block_sum_all(sa, red);
-  if (threadIdx.x == 0) da_part[row] = sa;
-  float* dyr = dy + (int64_t)row * N;
-  for (int n = threadIdx.x; n < N; n += GD_T) {
-    const float xh = (yr[n] - mu) * rs;
-    float e = 0.f;
-    if (n >= pool) {
-      float up = dzr[n - pool];
-      if (keep) up *= keep[(int64_t)b * N + n];
-      e = xh * gamma[n] + beta[n] > 0.f ? up : a * up;
-    }
-    dyr[n] = rs * (e * gamma[n] - s1 - xh * s2);
-  }
-}
-
-// d gamma[n] = sum_rows e xhat, d beta[n] = sum_rows e over a chunk of GD_RC rows: partial [chunk][2][N]
-#define GD_RC 64
-__global__ void __launch_bounds__(256)
-k_nodes_ln_prelu_bwd_affine(int rows, int f, int N, int pool, const float* __restrict__ y,
-                            const float* __restrict__ gamma, const float* __restrict__ beta,
-                            const float* __restrict__ keep, const float* __restrict__ slope,
-                            const float* __restrict__ mean, const float* __restrict__ rstd,
-                            const float* __restrict__ dz, float* __restrict__ partial) {
-  __shared__ float sg[4][64], sb[4][64];
-  const int nl = threadIdx.x & 63, rg = threadIdx.x >> 6;
-  const int n = blockIdx.x * 64 + nl;
-  const int r0 = blockIdx.y * GD_RC, r1 = min(rows, r0 + GD_RC);
-  float dg = 0.f, db = 0.f;
-  if (n < N && n >= pool) {
-    const float ga = gamma[n], be = beta[n], a = slope[0];
-    const int M = N - pool;
-    for (int row = r0 + rg; row < r1; row += 4) {
-      float up = dz[(int64_t)row * M + (n - pool)];
-      if (keep) up *= keep[(int64_t)(row / f) * N + n];
-      const float xh = (y[(int64_t)row * N + n] - mean[row]) * rstd[row];
-      const float e = xh * ga + be > 0.f ? up : a * up;
-      dg += e * xh;
-      db += e;
-    }
-  }
-  sg[rg][nl] = dg;
-  sb[rg][nl] = db;
-  __syncthreads();
-  if (rg == 0 && n < N) {
-    float* prow = partial + (int64_t)blockIdx.y * 2 * N;
-    prow[n] = (sg[0][nl] + sg[1][nl]) + (sg[2][nl] + sg[3][nl]);
-    prow[N + n] = (sb[0][nl] + sb[1][nl]) + (sb[2][nl] + sb[3][nl]);
-  }
-}
-
-extern "C" int igcn_nodes_ln_prelu_fwd(int B, int f, int N, int pool, float eps, const float* y, const float* gamma,
-                                       const float* beta, const float* keep, const float* slope, float* z, float* mean,
-                                       float* rstd, void* stream) {
-  IGCN_REQUIRE(B > 0 && f > 0 && N > 0 && pool >= 0 && pool < N && slope, "nodes_ln_prelu_fwd: bad sizes");
-  hipLaunchKernelGGL(k_nodes_ln_prelu_fwd, dim3(B * f), dim3(GD_T), 0, (hipStream_t)stream, f, N, pool, eps, y, gamma,
-                     beta, keep, slope, z, mean, rstd);
-  IGCN_CHECK_LAUNCH("nodes_ln_prelu_fwd");
-  return IGCN_OK;
-}
-
-extern "C" size_t igcn_nodes_ln_prelu_bwd_scratch_floats(int B, int f, int N) {
-  return (size_t)(igcn_cdiv((int64_t)B * f, GD_RC) * 2 * N + (int64_t)B * f + 64);
-}
-
-extern "C" int igcn_nodes_ln_prelu_bwd(int B, int f, int N, int pool, const float* y, const float* gamma,
-                                       const float* beta, const float* keep, const float* slope, const float* mean,
-                                       const float* rstd, const float* dz, float* dy, float* dgb, float* dslope,
-                                       float* scratch, void* stream) {
-  IGCN_REQUIRE(B > 0 && f > 0 && N > 0 && pool >= 0 && pool < N && slope && dslope, "nodes_ln_prelu_bwd: bad sizes");
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t rows = (int64_t)B * f, chunks = igcn_cdiv(rows, GD_RC);
-  float* da_part = scratch + chunks * 2 * N;
-  hipLaunchKernelGGL(k_nodes_ln_prelu_bwd_dy, dim3((unsigned)rows), dim3(GD_T), 0, st, f, N, pool, y, gamma, beta, keep,
-                     slope, mean, rstd, dz, dy, da_part);
-  hipLaunchKernelGGL(k_nodes_ln_prelu_bwd_affine, dim3((unsigned)igcn_cdiv(N, 64), (unsigned)chunks), dim3(256), 0, st,
-                     (int)rows, f, N, pool, y, gamma, beta, keep, slope, mean, rstd, dz, scratch);
-  IGCN_CHECK_LAUNCH("nodes_ln_prelu_bwd");
-  const int rc = igcn_launch_reduce_rows_final(scratch, chunks, 2 * (int64_t)N, 2 * N, dgb, st);
-  if (rc) return rc;
-  return igcn_launch_reduce_rows_final(da_part, rows, 1, 1, dslope, st);
-}
 
 // =================================================================================================
 // BatchNorm1d(C) + PReLU (+ dropout) on [B, C], optionally behind a per-node linear (guide_go_model.py:117-136 conc /

@@ -1985,12 +1985,37 @@ def _go_attn_backward(x, w_inc, w_s, a_in, a_s, csr, final, dy):
     return dx, dpar
 
 
-def _nodes_ln_backward(y, gamma, beta, keep, mean, rstd, pool, final, dz):
-    """(dy, dgb [2, N]) of NodesLayerNorm: the dX pass now, the affine pass with the other layers' when deferred."""
+def _nodes_ln_forward(y, gamma, beta, keep, pool, eps, slope=None):
+    """(z [B, f, N - pool], mean [B f], rstd [B f]) of the LayerNorm block behind y [B, f, N] (csrc/nodes_ln.hip): ReLU,
+    or PReLU with ``slope``."""
+    b, f, n = y.shape
+    z = torch.empty(b, f, n - pool, dtype=torch.float32, device=y.device)
+    mean = torch.empty(b * f, dtype=torch.float32, device=y.device)
+    rstd = torch.empty_like(mean)
+    if slope is None:
+        call("igcn_nodes_ln_fwd", b, f, n, pool, float(eps), ptr(y), ptr(gamma), ptr(beta), ptr(keep), ptr(z),
+             ptr(mean), ptr(rstd), stream_ptr())
+    else:
+        call("igcn_nodes_ln_prelu_fwd", b, f, n, pool, float(eps), ptr(y), ptr(gamma), ptr(beta), ptr(keep), ptr(slope),
+             ptr(z), ptr(mean), ptr(rstd), stream_ptr())
+    return z, mean, rstd
+
+
+def _nodes_ln_backward(y, gamma, beta, keep, mean, rstd, pool, final, dz, slope=None):
+    """(dy, dgb [2, N], da) of the LayerNorm block: the dX pass now, the affine pass with the other layers' when
+    deferred.  With ``slope`` (PReLU) one immediate call, and da [1] is the slope's gradient; None otherwise."""
     b, f, n = y.shape
     dy = torch.empty_like(y)
     dgb = torch.empty(2, n, dtype=torch.float32, device=y.device)
     lib = _lib.load()
+    if slope is not None:
+        da = torch.empty(1, dtype=torch.float32, device=y.device)
+        scratch = _keep(torch.empty(int(lib.igcn_nodes_ln_prelu_bwd_scratch_floats(b, f, n)), dtype=torch.float32,
+                                    device=y.device))
+        with _immediate(final):
+            call("igcn_nodes_ln_prelu_bwd", b, f, n, pool, ptr(y), ptr(gamma), ptr(beta), ptr(keep), ptr(slope),
+                 ptr(mean), ptr(rstd), ptr(dz), ptr(dy), ptr(dgb), ptr(da), ptr(scratch), stream_ptr())
+        return dy, dgb, da
     scratch = _keep(torch.empty(int(lib.igcn_nodes_ln_bwd_scratch_floats(b, f, n)), dtype=torch.float32,
                                 device=y.device))
     if _DEFER["on"] and final and not switches.on("IGCN_LN_AFFINE_NOW"):
@@ -2003,7 +2028,7 @@ def _nodes_ln_backward(y, gamma, beta, keep, mean, rstd, pool, final, dz):
         with _immediate(final):
             call("igcn_nodes_ln_bwd", b, f, n, pool, ptr(y), ptr(gamma), ptr(beta), ptr(keep), ptr(mean),
                  ptr(rstd), ptr(dz), ptr(dy), ptr(dgb), ptr(scratch), stream_ptr())
-    return dy, dgb
+    return dy, dgb, None
 
 
 def _go_decode_backward(x, w_out, w_sout, csr, final, dy):
@@ -2053,12 +2078,7 @@ class NodesLayerNorm(torch.autograd.Function):
     def forward(ctx, y, gamma, beta, keep, pool, eps):
         y, gamma, beta = _f32(y), _f32(gamma), _f32(beta)
         keep = _f32(keep) if keep is not None else None
-        b, f, n = y.shape
-        z = torch.empty(b, f, n - pool, dtype=torch.float32, device=y.device)
-        mean = torch.empty(b * f, dtype=torch.float32, device=y.device)
-        rstd = torch.empty_like(mean)
-        call("igcn_nodes_ln_fwd", b, f, n, pool, float(eps), ptr(y), ptr(gamma), ptr(beta), ptr(keep), ptr(z),
-             ptr(mean), ptr(rstd), stream_ptr())
+        z, mean, rstd = _nodes_ln_forward(y, gamma, beta, keep, pool, eps)
         ctx.save_for_backward(y, gamma, beta, keep, mean, rstd)
         ctx.pool = pool
         ctx.final = _leaves(gamma, beta)
@@ -2067,8 +2087,28 @@ class NodesLayerNorm(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dz):
         y, gamma, beta, keep, mean, rstd = ctx.saved_tensors
-        dy, dgb = _nodes_ln_backward(y, gamma, beta, keep, mean, rstd, ctx.pool, ctx.final, _f32(dz))
+        dy, dgb, _ = _nodes_ln_backward(y, gamma, beta, keep, mean, rstd, ctx.pool, ctx.final, _f32(dz))
         return dy, dgb[0], dgb[1], None, None, None
+
+
+class NodesLayerNormPReLU(torch.autograd.Function):
+    """LayerNorm over nodes + PReLU(slope) + node dropout + level pooling (guide_go_model.py:246-251, :273-275)."""
+
+    @staticmethod
+    def forward(ctx, y, gamma, beta, slope, keep, pool, eps):
+        y, gamma, beta, slope = _f32(y), _f32(gamma), _f32(beta), _f32(slope)
+        keep = _f32(keep) if keep is not None else None
+        z, mean, rstd = _nodes_ln_forward(y, gamma, beta, keep, pool, eps, slope)
+        ctx.save_for_backward(y, gamma, beta, slope, keep, mean, rstd)
+        ctx.pool = pool
+        ctx.final = _leaves(gamma, beta, slope)
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        y, gamma, beta, slope, keep, mean, rstd = ctx.saved_tensors
+        dy, dgb, da = _nodes_ln_backward(y, gamma, beta, keep, mean, rstd, ctx.pool, ctx.final, _f32(dz), slope)
+        return dy, dgb[0], dgb[1], da.view_as(slope), None, None, None
 
 
 def _al16(*ts):
@@ -2095,11 +2135,7 @@ class GoAttentionLN(torch.autograd.Function):
         y = torch.empty(b, fout, n, dtype=torch.float32, device=x.device)
         call("igcn_go_attn_fwd", b, n, fin, fout, ptr(csr.row_ptr), ptr(csr.col), ptr(x), ptr(w_inc), ptr(w_s),
              ptr(a_in), ptr(a_s), ptr(y), stream_ptr())
-        z = torch.empty(b, fout, n - pool, dtype=torch.float32, device=x.device)
-        mean = torch.empty(b * fout, dtype=torch.float32, device=x.device)
-        rstd = torch.empty_like(mean)
-        call("igcn_nodes_ln_fwd", b, fout, n, pool, float(eps), ptr(y), ptr(gamma), ptr(beta), ptr(keep), ptr(z),
-             ptr(mean), ptr(rstd), stream_ptr())
+        z, mean, rstd = _nodes_ln_forward(y, gamma, beta, keep, pool, eps)
         ctx.save_for_backward(x, w_inc, w_s, a_in, a_s, y, gamma, beta, keep, mean, rstd)
         ctx.csr, ctx.pool, ctx.fan = csr, pool, fan
         ctx.final_attn, ctx.final_ln = _leaves(w_inc, w_s, a_in, a_s), _leaves(gamma, beta)
@@ -2149,7 +2185,7 @@ class GoAttentionLN(torch.autograd.Function):
                      pool, ptr(y), ptr(gamma), ptr(beta), ptr(keep), ptr(mean), ptr(rstd), ptr(dz), ptr(dz2), ptr(dz3),
                      ptr(dx), ptr(dpar), ptr(dgb), ptr(scratch), ptr(part), stream_ptr())
         else:
-            dy, dgb = _nodes_ln_backward(y, gamma, beta, keep, mean, rstd, pool, ctx.final_ln, dz)
+            dy, dgb, _ = _nodes_ln_backward(y, gamma, beta, keep, mean, rstd, pool, ctx.final_ln, dz)
             dx, dpar = _go_attn_backward(x, w_inc, w_s, a_in, a_s, csr, ctx.final_attn, dy)
         return (dx, dpar[:k].view(fout, fin), dpar[k:2 * k].view(fout, fin),
                 dpar[2 * k:2 * k + 2 * fout].view_as(a_in), dpar[2 * k + 2 * fout:].view_as(a_s), None,
@@ -2168,13 +2204,9 @@ class GoDecodeLN(torch.autograd.Function):
         fout, nout = w_out.shape[0], csr.n_rows
         assert csr.n_cols == nin
         y = torch.empty(b, fout, nout, dtype=torch.float32, device=x.device)
-        z = torch.empty_like(y)
-        mean = torch.empty(b * fout, dtype=torch.float32, device=x.device)
-        rstd = torch.empty_like(mean)
         call("igcn_go_decode_fwd", b, nin, nout, fin, fout, ptr(csr.row_ptr), ptr(csr.col), ptr(x), ptr(w_out),
              ptr(w_sout), ptr(y), stream_ptr())
-        call("igcn_nodes_ln_fwd", b, fout, nout, 0, float(eps), ptr(y), ptr(gamma), ptr(beta), ptr(keep), ptr(z),
-             ptr(mean), ptr(rstd), stream_ptr())
+        z, mean, rstd = _nodes_ln_forward(y, gamma, beta, keep, 0, eps)
         ctx.save_for_backward(x, w_out, w_sout, y, gamma, beta, keep, mean, rstd)
         ctx.csr = csr
         ctx.final_dec, ctx.final_ln = _leaves(w_out, w_sout), _leaves(gamma, beta)
@@ -2202,7 +2234,7 @@ class GoDecodeLN(torch.autograd.Function):
                      ptr(x), ptr(w_out), ptr(w_sout), ptr(y), ptr(gamma), ptr(beta), ptr(keep), ptr(mean), ptr(rstd),
                      ptr(dz), ptr(dx), ptr(dpar), ptr(dgb), ptr(scratch), ptr(part), stream_ptr())
         else:
-            dy, dgb = _nodes_ln_backward(y, gamma, beta, keep, mean, rstd, 0, ctx.final_ln, dz)
+            dy, dgb, _ = _nodes_ln_backward(y, gamma, beta, keep, mean, rstd, 0, ctx.final_ln, dz)
             dx, dpar = _go_decode_backward(x, w_out, w_sout, csr, ctx.final_dec, dy)
         return dx, dpar[:k].view(fout, fin), dpar[k:].view(fout, fin), None, dgb[0], dgb[1], None, None
 
@@ -3024,41 +3056,8 @@ class AttentionCore(torch.autograd.Function):
 
 
 # =================================================================================================
-# GUIDE_IMGSNP: PReLU forms of the GO normalisation blocks, the image gate + encoder (csrc/guide.hip)
+# GUIDE_IMGSNP: BatchNorm + PReLU blocks, the image gate + encoder (csrc/guide.hip); NodesLayerNormPReLU: by NodesLayerNorm
 # =================================================================================================
-class NodesLayerNormPReLU(torch.autograd.Function):
-    """LayerNorm over nodes + PReLU(slope) + node dropout + level pooling (guide_go_model.py:246-251, :273-275)."""
-
-    @staticmethod
-    def forward(ctx, y, gamma, beta, slope, keep, pool, eps):
-        y, gamma, beta, slope = _f32(y), _f32(gamma), _f32(beta), _f32(slope)
-        keep = _f32(keep) if keep is not None else None
-        b, f, n = y.shape
-        z = torch.empty(b, f, n - pool, dtype=torch.float32, device=y.device)
-        mean = torch.empty(b * f, dtype=torch.float32, device=y.device)
-        rstd = torch.empty_like(mean)
-        call("igcn_nodes_ln_prelu_fwd", b, f, n, pool, float(eps), ptr(y), ptr(gamma), ptr(beta), ptr(keep), ptr(slope),
-             ptr(z), ptr(mean), ptr(rstd), stream_ptr())
-        ctx.save_for_backward(y, gamma, beta, slope, keep, mean, rstd)
-        ctx.pool = pool
-        ctx.final = _leaves(gamma, beta, slope)
-        return z
-
-    @staticmethod
-    def backward(ctx, dz):
-        y, gamma, beta, slope, keep, mean, rstd = ctx.saved_tensors
-        b, f, n = y.shape
-        dy = torch.empty_like(y)
-        dgb = torch.empty(2, n, dtype=torch.float32, device=y.device)
-        da = torch.empty(1, dtype=torch.float32, device=y.device)
-        scratch = _keep(torch.empty(int(_lib.load().igcn_nodes_ln_prelu_bwd_scratch_floats(b, f, n)),
-                                    dtype=torch.float32, device=y.device))
-        with _immediate(ctx.final):
-            call("igcn_nodes_ln_prelu_bwd", b, f, n, ctx.pool, ptr(y), ptr(gamma), ptr(beta), ptr(keep), ptr(slope),
-                 ptr(mean), ptr(rstd), ptr(_f32(dz)), ptr(dy), ptr(dgb), ptr(da), ptr(scratch), stream_ptr())
-        return dy, dgb[0], dgb[1], da.view_as(slope), None, None, None
-
-
 def bn_prelu_forward(x, weight, bn, slope, training, keep=None):
     """y = dropout(PReLU(BatchNorm1d_C(pre))) without autograd (igcn_bn_prelu_fwd): ``weight`` None -> pre = x [B,C];
     else x [B,F,C] channel-major and pre[b,c,:] = weight x[b,:,c].  Returns (y [B,C,D], save_mean, save_rstd)."""

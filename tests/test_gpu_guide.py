@@ -1,4 +1,4 @@
-"""GPU checks of GUIDE_IMGSNP and its kernels (csrc/guide.hip):
+"""GPU checks of GUIDE_IMGSNP and its kernels (csrc/guide.hip; the LayerNorm form: csrc/nodes_ln.hip):
   * the PReLU forms (LayerNorm over nodes, BatchNorm1d on [B, C], per-node linear + BatchNorm) against float64 torch,
     dropout on, slopes 0.25 / negative / above 1, and bit-identical d slope from two identical calls;
   * the gate + encoder_i_N kernel against a float64 restatement (tests/guide_ref.py) with imposed noise, and eval;
@@ -379,8 +379,8 @@ def _ln_u(y, gamma):
     return lambda beta: xh * gamma + beta
 
 
-# (b, f, N, pool): rows b f = 1 / 64 / 65 / 1280, N around the 64-node tiles and GD_T = 256 threads, the bench's 1200 /
-# 3000-node layers (20 chunks of GD_RC = 64 rows), pool 0 and pool = N - 1
+# (b, f, N, pool): rows b f = 1 / 64 / 65 / 1280, N around the 64-node tiles and LN_T = 256 threads, the bench's 1200 /
+# 3000-node layers (20 chunks of LN_RC = 64 rows), pool 0 and pool = N - 1
 LN_SHAPES = [(1, 1, 63, 0), (8, 8, 64, 63), (13, 5, 65, 7), (4, 16, 256, 0), (5, 13, 257, 256), (256, 5, 1200, 800),
              (256, 5, 3000, 1800), (2, 3, 4100, 100), (1, 1, 4100, 4099)]
 
