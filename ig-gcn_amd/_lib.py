@@ -14,7 +14,7 @@ from . import switches
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libigcn.so")
 
-ABI_VERSION = 429        # include/igcn.h IGCN_ABI_VERSION this table was written against (tests/test_abi.py compares)
+ABI_VERSION = 430        # include/igcn.h IGCN_ABI_VERSION this table was written against (tests/test_abi.py compares)
 
 P, I, L, F, Z = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
 
@@ -209,6 +209,10 @@ SIGNATURES = {
     "igcn_cluster_head_loss_blocks": (I, [I, I]),
     "igcn_cluster_head_loss_fwd": (I, [I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, F, F, F, I, P, P, P, P, P, P, P, P, P]),
     "igcn_cluster_loss_final": (I, [P, I, P, I, P, P, P]),
+    "igcn_snps_head_supported": (I, [I, I, I, I]),
+    "igcn_snps_head_workspace_bytes": (Z, [I, I, I, I]),
+    "igcn_snps_head_loss_fwd": (I, [I, I, I, I, P, P, P, P, P, P, F, F, I, P, P, P, P, P, P, P, F, P, P, P, P]),
+    "igcn_snps_head_loss_bwd": (I, [I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, F, P, P, P, P, P, P, P, P, P, P]),
     "igcn_reduce_flush": (I, [P]),
     "igcn_reduce_flush_tick": (I, [P, P]),
     "igcn_comm_unique_id_bytes": (I, []),

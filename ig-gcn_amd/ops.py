@@ -3010,6 +3010,86 @@ class ClusterHeadLoss(torch.autograd.Function):
                 dprob, None, None, None, None, None)
 
 
+def snps_head_supported(latent, snps, w1):
+    """The fused head + loss launches of the genetics-only trainer (igcn_snps_head_loss_*) cover this shape."""
+    return (latent.is_cuda and latent.dim() == 2 and snps.dim() == 2 and latent.dtype == snps.dtype == torch.float32
+            and latent.shape[0] == snps.shape[0] and w1.dim() == 2 and w1.shape[1] == latent.shape[1] + snps.shape[1]
+            and bool(_lib.load().igcn_snps_head_supported(latent.shape[0], latent.shape[1], snps.shape[1], w1.shape[0])))
+
+
+def snps_head_predict(latent, snps, bn, w1, w2, b2):
+    """Eval-mode ``y_hat`` [B] of the genetics-only head from the forward launch alone (igcn_snps_head_loss_fwd without
+    labels: a grid over the rows, any B).  ``bn``: the head's BatchNorm1d module.  Not differentiable."""
+    latent, snps, w1, w2, b2 = (_f32(t.detach()) for t in (latent, snps, w1, w2, b2))
+    b, l = latent.shape
+    s, h = snps.shape[1], w1.shape[0]
+    y_hat = torch.empty(b, dtype=torch.float32, device=latent.device)
+    call("igcn_snps_head_loss_fwd", b, l, s, h, ptr(latent), ptr(snps), ptr(_f32(bn.weight.detach())),
+         ptr(_f32(bn.bias.detach())), ptr(bn.running_mean), ptr(bn.running_var), 0.0, float(bn.eps), 0, None, None, ptr(w1),
+         ptr(w2), ptr(b2), None, None, 0.0, ptr(y_hat), None, None, stream_ptr())
+    return y_hat
+
+
+class SnpsHeadLoss(torch.autograd.Function):
+    """The ``classification`` head of the GO network on cat(latent, snps) — BatchNorm1d over the batch, ReLU, dropout,
+    Linear(-> 16), ReLU, dropout, Linear(16 -> 1), sigmoid — with ``sum BCELoss(y_hat, label) + lambda0 sum (x_hat -
+    snps)^2`` of kernel/train_eval_snps.py:314-320, as ONE launch per direction (igcn_snps_head_loss_fwd / _bwd,
+    csrc/snps_head.hip).  In training mode the forward updates ``running_mean`` / ``running_var`` in place.
+    Returns (loss, terms [2] = {class, recon}, y_hat [B]); the last two are not differentiable.
+
+    ``lazy``: accepted for the protocol of HeadLoss / ClusterHeadLoss — the forward launch is one workgroup and writes the
+    loss value itself, so there is no last step to defer.  An upstream gradient that is the cached unit scalar of
+    train._unit_grad is passed as "one" (NULL: the kernel neither loads nor multiplies by it); any other is read from the
+    device by the backward launch, so nothing here synchronises."""
+
+    @staticmethod
+    def forward(ctx, latent, snps, x_hat, label, gamma, beta, running_mean, running_var, momentum, eps, training, keep1,
+                keep2, w1, w2, b2, lambda0, lazy=False):
+        f = lambda t: _f32(t) if t is not None else None               # noqa: E731
+        latent, snps, x_hat, label, gamma, beta, keep1, keep2, w1, w2, b2 = (
+            f(t) for t in (latent, snps, x_hat, label, gamma, beta, keep1, keep2, w1, w2, b2))
+        b, l = latent.shape
+        s, h = snps.shape[1], w1.shape[0]
+        k1 = l + s
+        if (snps.shape[0] != b or x_hat.shape != (b, s) or label.numel() != b or gamma.numel() != k1 or w1.shape[1] != k1
+                or w2.shape != (1, h) or b2.numel() != 1 or (keep1 is not None and keep1.shape != (b, k1))
+                or (keep2 is not None and keep2.shape != (b, h))):
+            raise _lib.IgcnError("snps head loss: inconsistent shapes")
+        if training and b == 1:
+            raise ValueError("snps head loss: training mode needs more than one sample per batch (BatchNorm1d)")
+        if not training:
+            keep1 = keep2 = None
+        lib = _lib.load()
+        dev = latent.device
+        ws = torch.empty((int(lib.igcn_snps_head_workspace_bytes(b, l, s, h)) + 3) // 4, dtype=torch.float32, device=dev)
+        y_hat = torch.empty(b, dtype=torch.float32, device=dev)
+        out = torch.empty(3, dtype=torch.float32, device=dev)
+        call("igcn_snps_head_loss_fwd", b, l, s, h, ptr(latent), ptr(snps), ptr(gamma), ptr(beta), ptr(running_mean),
+             ptr(running_var), float(momentum), float(eps), int(bool(training)), ptr(keep1), ptr(keep2), ptr(w1), ptr(w2),
+             ptr(b2), ptr(label), ptr(x_hat), float(lambda0), ptr(y_hat), ptr(out), ptr(ws), stream_ptr())
+        ctx.save_for_backward(latent, snps, x_hat, label, gamma, beta, keep1, keep2, w1, w2, y_hat, ws)
+        ctx.cfg = (b, l, s, h, bool(training), float(lambda0))
+        loss, terms = out[0], out[1:]
+        ctx.mark_non_differentiable(terms, y_hat)
+        ctx.set_materialize_grads(False)
+        return loss, terms, y_hat
+
+    @staticmethod
+    def backward(ctx, gout, _gt=None, _gy=None):
+        latent, snps, x_hat, label, gamma, beta, keep1, keep2, w1, w2, y_hat, ws = ctx.saved_tensors
+        b, l, s, h, training, lambda0 = ctx.cfg
+        gout = _f32(gout).reshape(1)
+        up = None if gout.data_ptr() in UNIT_GRAD_PTRS else gout
+        dlatent, dxhat = torch.empty_like(latent), torch.empty_like(x_hat)
+        dgamma, dbeta, dw1 = torch.empty_like(gamma), torch.empty_like(beta), torch.empty_like(w1)
+        dw2b = torch.empty(h + 4, dtype=torch.float32, device=latent.device)
+        call("igcn_snps_head_loss_bwd", b, l, s, h, int(training), ptr(latent), ptr(snps), ptr(gamma), ptr(beta), ptr(keep1),
+             ptr(keep2), ptr(w1), ptr(w2), ptr(label), ptr(y_hat), ptr(x_hat), lambda0, ptr(up), ptr(ws), ptr(dlatent),
+             ptr(dxhat), ptr(dgamma), ptr(dbeta), ptr(dw1), ptr(dw2b), dw2b.data_ptr() + 4 * h, stream_ptr())
+        return (dlatent, None, dxhat, None, dgamma, dbeta, None, None, None, None, None, None, None, dw1,
+                dw2b[:h].view(1, h), dw2b[h:h + 1], None, None)
+
+
 # =================================================================================================
 # Cross-attention: projections + attention core
 # =================================================================================================

@@ -31,7 +31,7 @@ extern "C" {
 /* ABI revision: bumped whenever a prototype below changes (argument added, removed or re-ordered).  igcn_version()
  * returns the revision the library was built from; a binding written against a different one must refuse to call
  * (igcn_amd/_lib.py does). */
-#define IGCN_ABI_VERSION 429
+#define IGCN_ABI_VERSION 430
 int igcn_version(void);
 const char* igcn_last_error(void);
 /* A/B switches, set ONCE by the binding when it loads the library (from the IGCN_* environment variables): bit 0 no tiled
@@ -1090,6 +1090,41 @@ int igcn_cluster_head_loss_fwd(int B, int K, int C1, int C2, int S, const float*
                                float* dx2, float* dxhat, float* parts, float* wpart, float* dprob, void* stream);
 int igcn_cluster_loss_final(const float* parts, int nparts, const float* prob, int prob_rows, const float* wts, float* out,
                             void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The genetics-only trainer's head and loss (csrc/snps_head.hip; kernel/train_eval_snps.py:314-320 on the
+ * ``classification`` module of kernel/go_model.py:148-157), one launch per direction:
+ *   x = cat(latent [B, L], snps [B, S]) (two pointers, never materialised; K1 = L + S), a = relu(BatchNorm1d(K1)(x)) keep1,
+ *   h = relu(a W1^T) keep2 (W1 [H, K1], no bias), y_hat = sigmoid(h W2^T + b2) (W2 [1, H]),
+ *   class = sum BCELoss(y_hat, label), recon = lambda0 sum (x_hat - snps)^2, out [3] = {class + recon, class, recon}.
+ * BCELoss is torch's on the probability: -(y max(log p, -100) + (1 - y) max(log(1 - p), -100)), gradient
+ * (p - y) / max(p (1 - p), 1e-12) p (1 - p); label [B] floats in [0, 1].  lambda0 == 0: recon and dx_hat are exact zeros.
+ * keep1 [B, K1] / keep2 [B, H]: {0, 1/(1-p)} factors of igcn_dropout_masks or NULL; training mode only.
+ * Training mode normalises with the batch statistics (biased variance, from centred values) and updates running_mean /
+ * running_var with momentum m: (1 - m) running + m batch, the variance unbiased (B / (B - 1)); eval mode normalises with
+ * the running statistics.
+ * Supported (igcn_snps_head_supported; IGCN_ERR_UNSUPPORTED otherwise, nothing written): H == 16, L, S >= 1, L + S <= 96,
+ * 1 <= B <= 1024; training mode needs B >= 2.  Both directions are ONE workgroup that loops over passes of 64 rows (the
+ * batch statistics, the loss sums and the parameter gradients couple the rows); every sum runs in a fixed order, no
+ * atomics.  label == NULL (eval mode only): y_hat alone for any 1 <= B <= 2^24 on a grid over the rows; x_hat, out, ws may be
+ * NULL.
+ * ws: caller-owned, igcn_snps_head_workspace_bytes, 16-byte aligned (as keep2 and W2): the statistics the forward
+ * normalised with and the hidden activations, read by the backward.
+ * igcn_snps_head_loss_bwd: the backward for the upstream gradient upstream[0] (a DEVICE scalar; NULL: one), from the same
+ * inputs plus the forward's y_hat and ws.  Writes dlatent [B, L] (the SNP columns are data: no gradient), dx_hat [B, S] =
+ * 2 lambda0 (x_hat - snps) upstream, dgamma / dbeta [K1], dW1 [H, K1], dW2 [H], db2 [1]. */
+int igcn_snps_head_supported(int B, int L, int S, int H);
+size_t igcn_snps_head_workspace_bytes(int B, int L, int S, int H);
+int igcn_snps_head_loss_fwd(int B, int L, int S, int H, const float* latent, const float* snps, const float* bn_weight,
+                            const float* bn_bias, float* running_mean, float* running_var, float momentum, float eps,
+                            int training, const float* keep1, const float* keep2, const float* W1, const float* W2,
+                            const float* b2, const float* label, const float* x_hat, float lambda0, float* y_hat,
+                            float* out, void* ws, void* stream);
+int igcn_snps_head_loss_bwd(int B, int L, int S, int H, int training, const float* latent, const float* snps,
+                            const float* bn_weight, const float* bn_bias, const float* keep1, const float* keep2,
+                            const float* W1, const float* W2, const float* label, const float* y_hat, const float* x_hat,
+                            float lambda0, const float* upstream, const void* ws, float* dlatent, float* dx_hat,
+                            float* dgamma, float* dbeta, float* dW1, float* dW2, float* db2, void* stream);
 /* igcn_loss_head_fwd that also writes the gradients igcn_loss_head_bwd would return for gout = 1 (each element's gradient
  * is known where its forward term is computed): a train step, whose d loss / d loss is one, then has no backward launch
  * for the loss head.  dlogp [2B,C] (of the raw scores when from_logits), dreg [2B,NR], dxhat [2B,S], dgram [4], dprob [1]. */
