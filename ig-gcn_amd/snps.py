@@ -30,6 +30,7 @@ import torch.nn.functional as F
 
 from . import _lib, ops, switches
 from . import train as T
+from .capture import GradTable, ShapeCache, _capture, kept_trainer, rolled_back
 
 SNPS_LAMBDA0 = 1e-5                      # kernel/train_eval_snps.py:169
 SNPS_TERMS = ("class", "recon")
@@ -123,9 +124,8 @@ def _fwd_bwd(model, optimizer, data, label, lambda0, temperature=None):
     """zero_grad, forward, loss, backward (:307-324).  Returns the device vector [loss, class, recon]."""
     optimizer.zero_grad()
     if data.is_cuda:
-        T.forget_riders()
+        T.forget_riders(model)
         T.ensure_unit_grad(data.device)
-    model._predrawn = None
     loss, terms, _ = losses_snps(model, data, label, lambda0, temperature, lazy_value=True)
     # (no deferred reductions: train._single_use_parameters keeps the deferral to the models whose batched sweep was
     # built for it, and the bare GO network — whose attention read-out feeds nothing here — is not one of them)
@@ -144,15 +144,14 @@ def train_step_snps(model, optimizer, data, label, lambda0=SNPS_LAMBDA0, tempera
 
 
 class GraphedSnpsStep:
-    """The whole genetics-only step — forward, loss, backward, Adam — captured ONCE into a hipGraph and replayed per step
-    (the counterpart of ``train.GraphedTrainStep`` for a batch that is a pair of tensors).  ``load(data, label)`` copies
-    a batch of the captured shape into the static inputs, ``step()`` replays and returns the loss (a device scalar that
-    the next replay overwrites; ``terms`` = the device vector [loss, class, recon]).
+    """The whole genetics-only step — forward, loss, backward, Adam — captured ONCE into a hipGraph and replayed per step:
+    the protocol of ``capture.py`` for a batch that is a pair of tensors.  ``load(data, label)`` copies a batch of the
+    captured shape into the static inputs, ``step()`` replays and returns the loss (a device scalar that the next replay
+    overwrites; ``terms`` = the device vector [loss, class, recon]).
 
-    Construction runs ``warmup`` eager steps on the construction batch; the optimiser state (parameters, Adam moments,
-    step count), every module buffer (BatchNorm running statistics, ``num_batches_tracked``) and the dropout generator's
-    counter are snapshotted before and restored after them, as ``GraphedTrainStep`` documents: N replays equal N eager
-    steps.  Single process only (no gradient exchange)."""
+    Construction runs ``warmup`` eager steps on the construction batch and rolls them back (``capture.rolled_back``:
+    optimiser state, module buffers, the dropout generator's counter): N replays equal N eager steps.  Single process
+    only (no gradient exchange)."""
 
     def __init__(self, model, optimizer, data, label, lambda0=SNPS_LAMBDA0, warmup=3, temperature=None):
         _check_optimizer(optimizer)
@@ -160,43 +159,17 @@ class GraphedSnpsStep:
             raise ValueError("GraphedSnpsStep: needs device tensors and a table-mode train.FlatAdam")
         self.model, self.opt, self.lambda0, self.temperature = model, optimizer, float(lambda0), temperature
         self.data, self.label = data.detach().clone().contiguous(), label.detach().clone().contiguous()
-        opt = optimizer
-        saved = [t.clone() for t in (opt.flat, opt.exp_avg, opt.exp_avg_sq, opt.step_count)]
-        saved_buf = [(b, b.clone()) for b in model.buffers()]
-        saved_has = list(opt._has_state)
-        drop = getattr(model, "_drop_state", None)
-        saved_drop = drop.state.clone() if drop is not None else None
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
+        with rolled_back(model, optimizer):
             for _ in range(int(warmup)):
                 self._fwd_bwd()
-                opt.step()
-        torch.cuda.current_stream().wait_stream(side)
-        with torch.no_grad():
-            for dst, src in zip((opt.flat, opt.exp_avg, opt.exp_avg_sq, opt.step_count), saved):
-                dst.copy_(src)
-            for b, v in saved_buf:
-                b.copy_(v)
-            if saved_drop is not None and getattr(model, "_drop_state", None) is drop:
-                drop.state.copy_(saved_drop)
-        T.forget_riders()
-        model._predrawn = None
-        opt._has_state = saved_has
-        torch.cuda.synchronize()
+                optimizer.step()
         self.graph = torch.cuda.CUDAGraph()
-        self._table = torch.zeros_like(opt.table)      # this graph's own gradient-pointer table (GraphedTrainStep)
-        with T._capture(self.graph):
+        self._table = GradTable(optimizer)
+        with _capture(self.graph):
             self.terms = self._fwd_bwd()
-            opt.step(refresh=False, table=self._table)
+            optimizer.step(refresh=False, table=self._table.table)
         self.loss = self.terms[0]
-        for p in opt.params:
-            if p.grad is not None and not p.grad.is_contiguous():
-                raise _lib.IgcnError(f"graphed step: a parameter gradient is not contiguous (shape {tuple(p.shape)})")
-        opt.refresh_table(table=self._table)
-        self._table_live = list(opt._table_live)
-        self._grads = [p.grad for p in opt.params]
-        self._hyper_version = opt._hyper_version
+        self._table.seal()
         torch.cuda.synchronize()
 
     def _fwd_bwd(self):
@@ -211,56 +184,37 @@ class GraphedSnpsStep:
             _lib.copy_multi([(self.data, data), (self.label, label.reshape(self.label.shape))])
 
     def step(self):
-        opt = self.opt
-        if opt._hyper_version != self._hyper_version:
-            raise RuntimeError("graphed step: betas / eps of the optimiser changed after the capture — rebuild the step")
-        if getattr(opt, "_ticked", False):
-            raise RuntimeError("graphed step: an eager backward advanced the step counter and no optimizer.step() "
-                               "followed it")
-        if opt._table_owner is not self:                 # (host book-keeping only: the device table is this graph's own)
-            opt._table_owner = self
-            opt._table_live = list(self._table_live)
-            for p, g in zip(opt.params, self._grads):
-                p.grad = g
+        self._table.claim(self)
         self.graph.replay()
-        opt.mark_stepped()
+        self.opt.mark_stepped()
         return self.loss
 
     __call__ = step
 
 
-class SnpsEpochTrainer:
+class SnpsEpochTrainer(ShapeCache):
     """train() kernel/train_eval_snps.py:298-335 over a whole loader: one captured step per batch SHAPE (the full batches
     and the ragged tail of a loader without ``drop_last``) once the shape has been seen ``capture_after`` times, the eager
-    ``train_step_snps`` until then — the scheme of ``train.EpochTrainer``."""
+    ``train_step_snps`` until then (``capture.ShapeCache``)."""
 
     def __init__(self, model, optimizer, lambda0=SNPS_LAMBDA0, temperature=None, capture_after=1, max_graphs=4, warmup=2):
         _check_optimizer(optimizer)
         self.model, self.opt, self.lambda0, self.temperature = model, optimizer, float(lambda0), temperature
-        self.capture_after, self.max_graphs, self.warmup = int(capture_after), int(max_graphs), int(warmup)
-        self.steps, self.seen = {}, {}
-        self.counts = {"replayed": 0, "eager": 0, "captured": 0}
+        self.warmup = int(warmup)
+        super().__init__(capture_after, max_graphs)
 
     def step(self, data, label):
         """One optimisation step; returns the device vector [loss, class, recon] (valid until the next step of the
         same shape)."""
-        sig = (tuple(data.shape), int(label.numel()))
-        g = self.steps.get(sig)
+        graphable = data.is_cuda and isinstance(self.opt, T.FlatAdam) and not self.opt.flat_grads
+        g = self.lookup((tuple(data.shape), int(label.numel())), graphable,
+                        lambda: GraphedSnpsStep(self.model, self.opt, data, label, self.lambda0, self.warmup,
+                                                self.temperature),
+                        lambda g: g.load(data, label))
         if g is None:
-            n = self.seen.get(sig, 0)
-            self.seen[sig] = n + 1
-            graphable = data.is_cuda and isinstance(self.opt, T.FlatAdam) and not self.opt.flat_grads
-            if graphable and n >= self.capture_after and len(self.steps) < self.max_graphs:
-                g = self.steps[sig] = GraphedSnpsStep(self.model, self.opt, data, label, self.lambda0, self.warmup,
-                                                      self.temperature)
-                self.counts["captured"] += 1
-        if g is None:
-            self.counts["eager"] += 1
             vec = _fwd_bwd(self.model, self.opt, data, label, self.lambda0, self.temperature)
             self.opt.step()
             return vec
-        g.load(data, label)
-        self.counts["replayed"] += 1
         g.step()
         return g.terms
 
@@ -292,15 +246,9 @@ def fit_epoch_snps(model, optimizer, loader, device=None, lambda0=SNPS_LAMBDA0, 
     this once per epoch re-uses them.  The learning rate is the caller's: ``optimizer.param_groups[0]['lr'] *= factor``
     (the reference's StepLR(50, 0.7) and its own decay are both such multiplications) is read by the captured steps from
     device memory."""
-    import weakref
-    cache = optimizer.__dict__.setdefault("_igcn_snps_trainers", {})
     key = (id(model), float(lambda0), temperature.data_ptr() if torch.is_tensor(temperature) else temperature)
-    tr = cache.get(key)
-    if tr is not None and tr._model_ref() is not model:
-        tr = None
-    if tr is None:
-        tr = cache[key] = SnpsEpochTrainer(model, optimizer, lambda0, temperature)
-        tr._model_ref = weakref.ref(model)
+    tr = kept_trainer(optimizer, "_igcn_snps_trainers", key,
+                      lambda: SnpsEpochTrainer(model, optimizer, lambda0, temperature), model)
     return tr.fit_epoch(loader, device)
 
 

@@ -13,6 +13,7 @@ import torch.nn.functional as F
 from . import _lib
 from . import switches
 from ._lib import call, ptr, stream_ptr
+from .capture import GradTable, ShapeCache, _capture, kept_trainer, rolled_back
 
 # sgcn_hyperparameters.py:18-23
 HP = SimpleNamespace(lamda_x_l1=0.1, lamda_e_l1=0.1, lamda_x_ent=0.1, lamda_e_ent=0.1, lamda_mi=1, lamda_ce=1)
@@ -223,14 +224,17 @@ class FlatAdam:
     def step(self, grad_scale=1.0, refresh=True, from_flat=None, table=None):
         """``from_flat``: read gradients from the flat bucket (after an all-reduce); default = flat mode only.
         When the backward's flush has advanced ``step_count`` already (``backward_to_grads(tick=True)`` with deferred
-        reductions sets ``_ticked``), the one-thread counter launch in front is skipped."""
+        reductions sets ``_ticked``), the one-thread counter launch in front is skipped.  Under a stream capture nothing
+        executes, so ``_has_state`` is left alone: whoever replays the graph keeps that book (``mark_stepped``)."""
         hyper = (ptr(self.lr_dev), float(self.betas[0]), float(self.betas[1]), float(self.eps), float(grad_scale))
         sfx = "_ticked" if getattr(self, "_ticked", False) else ""
         self._ticked = False
+        ran = not (self.flat.is_cuda and torch.cuda.is_current_stream_capturing())
         if self.flat_grads or from_flat:
             call("igcn_adam_step" + sfx, self.flat.numel(), ptr(self.flat), ptr(self.grad), ptr(self.exp_avg),
                  ptr(self.exp_avg_sq), ptr(self.step_count), *hyper, stream_ptr())
-            self._has_state = [True] * len(self.params)
+            if ran:
+                self._has_state = [True] * len(self.params)
             return
         if refresh:
             self.refresh_table(table=table)
@@ -241,7 +245,8 @@ class FlatAdam:
         else:
             call("igcn_adam_step_multi" + sfx, len(self.params), ptr(tab), ptr(self.numel), ptr(self.step_count), *hyper,
                  stream_ptr())
-        self.mark_stepped()
+        if ran:
+            self.mark_stepped()
 
     def mark_stepped(self):
         """Book-keeping of a table-mode step (also called per replay of a captured one): the parameters the table holds
@@ -674,12 +679,14 @@ def _single_use_parameters(model):
 
 def forget_riders(model=None):
     """Drop every rider still waiting on the current stream WITHOUT launching it (igcn_rider_cancel) together with the
-    dropout masks a model drew ahead for a forward that never came (go_network._predrawn): the start of every step, and
-    the error path of one that raised half way."""
+    dropout masks a model drew ahead for a forward that never came (``_predrawn`` of the model's GO network, or of the
+    model itself where it IS the GO network): the start of every step, and the error path of one that raised half way."""
     call("igcn_rider_cancel", stream_ptr())
     go = getattr(model, "go_network", None)
     if go is not None:
         go._predrawn = None
+    if hasattr(model, "_predrawn"):
+        model._predrawn = None
 
 
 def stream_pending():
@@ -810,30 +817,47 @@ def train_step(model, optimizer, data, lambda_loss=DEFAULT_LAMBDA, hp=HP, temper
     return loss.detach()
 
 
-class _capture:
-    """``torch.cuda.graph`` with the cyclic garbage collector held off while the capture is open.  torch collects once on
-    entry; a collection that starts DURING the capture — any allocation of the step, on this thread or on the autograd
-    engine's — may finalise an object whose destructor the runtime refuses inside a capture (another captured step's
-    hipGraph: every GraphedTrainStep sits in a reference cycle with its optimiser's pointer table, so it dies whenever the
-    collector gets to it) and the process aborts."""
-
-    def __init__(self, graph, **kw):
-        self.ctx = torch.cuda.graph(graph, **kw)
-
-    def __enter__(self):
-        import gc
-        self.was = gc.isenabled()
-        self.ctx.__enter__()            # (synchronises, collects once, empties the allocator cache, begins the capture)
-        gc.disable()
-        return self
-
-    def __exit__(self, *exc):
-        import gc
-        try:
-            return self.ctx.__exit__(*exc)
-        finally:
-            if self.was:
-                gc.enable()
+def load_batch(plan, data, batch):
+    """Copy a new batch (same graph count / node count / edge count) into ``data``, the static input tensors of a capture
+    with the plan ``plan`` — including the per-graph node and edge offsets the segmented plan build reads (a batch with
+    the same total edge count but different per-graph counts would otherwise be grouped on the wrong segments); a batch
+    the capture was not sized for is refused (ValueError).  ``batch is data``: a producer wrote the static inputs in
+    place (loader.DeviceFeeder(into=step.data)) — nothing to copy."""
+    if batch is data:
+        return
+    if plan.segmented:
+        node_ptr, edge_ptr, _, _ = plan._seg
+        bp, be = getattr(batch, "ptr", None), getattr(batch, "edge_ptr", None)
+        if bp is None or be is None or bp.shape != node_ptr.shape or be.shape != edge_ptr.shape:
+            raise ValueError("graphed step (segmented plan): the new batch must carry ptr / edge_ptr of the "
+                             "same graph count")
+        mn, me = getattr(batch, "_max_nodes", None), getattr(batch, "_max_edges", None)
+        # LDS build: the kernel's own limits; tiled build: the tile count the workspace was sized for
+        e_lim = plan._seg[3] if plan._tiled else plan.SEG_MAX_EDGES
+        n_lim = plan._seg[2] if plan._tiled else plan.SEG_MAX_NODES
+        if mn is None or me is None or mn > n_lim or me > e_lim:
+            raise ValueError("graphed step (per-graph plan): the new batch exceeds the per-graph sizes the "
+                             f"captured build was sized for ({n_lim} nodes / {e_lim} edges)")
+        if plan._stack_dims is not None and me > plan._stack_dims[1]:
+            # the captured LDS-resident SGCN stack was launched (and its LDS sized) for the construction batch's
+            # largest graph; a graph beyond that would be skipped by its workgroup (and flagged in plan.status)
+            raise ValueError("graphed step: a graph of the new batch has more edges "
+                             f"({me}) than the captured SGCN stack was sized for ({plan._stack_dims[1]}); "
+                             "build the step on a batch that contains the largest graph, or pass max_edges")
+        if plan.nodes_per_graph and int(mn) * (int(bp.numel()) - 1) != plan.n_nodes:
+            raise ValueError("graphed step: the captured kernels assume uniform graphs of "
+                             f"{plan.nodes_per_graph} nodes")
+        pairs = [(node_ptr, bp), (edge_ptr, be)]
+    else:
+        pairs = []
+    for k in ("x", "edge_index", "edge_attr", "snps_feat", "y", "clini_score", "tsne_fdim", "clust_y"):
+        dst, src = getattr(data, k, None), getattr(batch, k, None)
+        if dst is not None and src is not None:
+            if dst.shape != src.shape:
+                raise ValueError(f"graphed step needs fixed shapes; {k}: {tuple(src.shape)} vs {tuple(dst.shape)}")
+            pairs.append((dst, src))
+    with torch.no_grad():
+        _lib.copy_multi(pairs)                      # one launch for the whole hand-over (igcn_copy_multi)
 
 
 class GraphedTrainStep:
@@ -848,9 +872,9 @@ class GraphedTrainStep:
     The graph plan of the batch is rebuilt every step, inside the graph: all three builders (LDS per graph, tiled
     counting sort per graph, general LSD radix sort) are hand-written kernels with caller-owned workspace.
 
-    Construction runs ``warmup`` eager steps (allocator / library warm-up) on the construction batch; the optimiser
-    state (parameters, Adam moments, step count) and every module buffer (BatchNorm running statistics,
-    ``num_batches_tracked``) are snapshotted before and restored after them, so N replays equal N reference steps.
+    Construction runs ``warmup`` eager steps (allocator / library warm-up) on the construction batch and rolls them back
+    (``capture.rolled_back``: optimiser state, module buffers, the mask generators' counters), so N replays equal N
+    reference steps.  The host-side protocol around the captures — roll-back, pointer table, shape cache — is capture.py's.
     """
 
     def __init__(self, model, optimizer, data, lambda_loss=DEFAULT_LAMBDA, hp=HP, world_size=1, warmup=3,
@@ -890,147 +914,123 @@ class GraphedTrainStep:
             self.plan._copies = {}
         # every plan builder is hand-written and capturable: the build is part of the captured step
         self.plan_in_graph = True
-        opt = self.opt
-        saved = [t.clone() for t in (opt.flat, opt.exp_avg, opt.exp_avg_sq, opt.step_count)]
-        saved_buf = [(b, b.clone()) for b in model.buffers()]
-        saved_has = list(opt._has_state)
-        # the dropout generator's stream counter is not a registered buffer: saved / restored like them, so that a shape
-        # captured in the middle of an epoch does not shift the masks of every later step against an eager run
-        drop = getattr(getattr(model, "go_network", None), "_drop_state", None)
-        saved_drop = drop.state.clone() if drop is not None else None
-        gate = getattr(model, "_gate_state", None)                 # (GUIDE_IMGSNP's Gumbel-noise counter: likewise)
-        saved_gate = gate.state.clone() if gate is not None else None
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):                     # eager steps: allocator + library warm-up
-                if self.two is not None:
-                    def between_eager():
-                        self.two.pack_early()
-                        self.two.start_early()
-                    self._fwd_bwd(between=between_eager)
-                    self.two.pack_rest()
-                    self.two.finish()
-                    self.opt.step(grad_scale=1.0 / world_size, from_flat=True)
-                    continue
-                self._fwd_bwd()
-                if dist:
-                    self.opt.pack_grads()
-                    self._reduce()
-                    self.opt.step(grad_scale=1.0 / world_size, from_flat=True)
-                else:
-                    self.opt.step()
-        torch.cuda.current_stream().wait_stream(side)
-        with torch.no_grad():                           # undo the warm-up steps (capture itself executes nothing)
-            for dst, src in zip((opt.flat, opt.exp_avg, opt.exp_avg_sq, opt.step_count), saved):
-                dst.copy_(src)
-            for b, v in saved_buf:
-                b.copy_(v)
-            drop_now = getattr(getattr(model, "go_network", None), "_drop_state", None)
-            if saved_drop is not None and drop_now is drop:
-                drop.state.copy_(saved_drop)
-            if saved_gate is not None and getattr(model, "_gate_state", None) is gate:
-                gate.state.copy_(saved_gate)
-        forget_riders(model)
-        opt._has_state = saved_has
-        torch.cuda.synchronize()
-        self.g_main = torch.cuda.CUDAGraph()
-        # this graph's OWN gradient-pointer table: the captured Adam / pack kernels read it, so captured steps of one
-        # optimiser (the shapes of an epoch, two alternating input sets) never re-upload anything when they take turns
-        self._table = torch.zeros_like(opt.table)
-        if not self.plan_in_graph:
-            self.plan.rebuild(self.data.edge_index)
+        with rolled_back(model, optimizer):
+            for _ in range(warmup):
+                self._warmup_step()
+        self._table = GradTable(optimizer)
         # with a process group alive, its watchdog / progress threads may touch the runtime while this thread
         # captures: flag only this thread's unsafe calls (the launches of the autograd thread still land in the
         # capturing stream and are captured)
-        mode = "thread_local" if dist else "global"
+        self._mode = "thread_local" if dist else "global"
+        self.g_main = torch.cuda.CUDAGraph()
+        self.g_rest = self.g_opt = None
         if dist and comm is not None and comm_in_graph is not False:
-            # one graph for the whole distributed step: RCCL's all-reduce is captured between pack and Adam
-            try:
-                with _capture(self.g_main, capture_error_mode=mode):
-                    self.loss = self._fwd_bwd(rebuild=self.plan_in_graph)
-                    self.opt.pack_grads(refresh=False, table=self._table)
-                    comm.all_reduce_(self.opt.grad)
-                    self.opt.step(grad_scale=1.0 / world_size, from_flat=True)
-                self.comm_in_graph = True
-            except Exception as exc:                     # noqa: BLE001 — capture refused: two graphs instead
-                if comm_in_graph:
-                    raise
-                import sys
-                print(f"[igcn] all-reduce capture refused ({type(exc).__name__}: {exc}); using two graphs around it",
-                      file=sys.stderr)
-                torch.cuda.synchronize()
-                self.g_main = torch.cuda.CUDAGraph()
-            if comm_in_graph is None and world_size > 1 and torch.distributed.is_initialized():
-                # every rank must replay the same form: one rank inside a captured collective and another outside
-                # would hang.  A rank that captured but must step down re-captures below.
-                flag = torch.tensor([1 if self.comm_in_graph else 0], device=self.opt.flat.device, dtype=torch.int32)
-                torch.distributed.all_reduce(flag, op=torch.distributed.ReduceOp.MIN)
-                if self.comm_in_graph and int(flag.item()) == 0:
-                    self.comm_in_graph = False
-                    self.g_main = torch.cuda.CUDAGraph()
-        self.g_rest = None
+            self._capture_with_collective(comm_in_graph)
         if self.two is not None:
-            # two captures around ONE backward: the first ends (and the second begins) between its two sweeps, on the same
-            # capture stream and without leaving it (torch.cuda.graph's own entry — synchronise, collect, empty the
-            # allocator's cache — must not run in the middle of a backward whose tensors live in the first graph's pool)
-            import gc
-            self.g_rest = torch.cuda.CUDAGraph()
-            cap_stream = torch.cuda.Stream()
-            torch.cuda.synchronize()
-            gc.collect()
-            torch.cuda.empty_cache()
-            was = gc.isenabled()
-            gc.disable()
-            cap_stream.wait_stream(torch.cuda.current_stream())
-            open_graph = [None]
-            try:
-                with torch.cuda.stream(cap_stream):
-                    self.g_main.capture_begin(capture_error_mode=mode)
-                    open_graph[0] = self.g_main
-
-                    def between():
-                        self.two.pack_early(table=self._table, refresh=False)
-                        self.g_main.capture_end()
-                        open_graph[0] = None
-                        self.g_rest.capture_begin(pool=self.g_main.pool(), capture_error_mode=mode)
-                        open_graph[0] = self.g_rest
-                    try:
-                        self.loss = self._fwd_bwd(rebuild=self.plan_in_graph, between=between)
-                        self.two.pack_rest(table=self._table, refresh=False)
-                    finally:
-                        if open_graph[0] is not None:
-                            open_graph[0].capture_end()
-                torch.cuda.current_stream().wait_stream(cap_stream)
-            finally:
-                if was:
-                    gc.enable()
+            self._capture_two_buckets()
         elif not self.comm_in_graph:
-            with _capture(self.g_main, capture_error_mode=mode):
-                self.loss = self._fwd_bwd(rebuild=self.plan_in_graph)
-                if not dist:
-                    self.opt.step(refresh=False, table=self._table)   # reads the pointer table at replay time
-                else:
-                    self.opt.pack_grads(refresh=False, table=self._table)
-        # the captured gradient tensors keep their addresses — which only helps if the table can point AT them: a
-        # non-contiguous gradient would be copied by refresh_table, and the replays would never update the copy
-        for p in self.opt.params:
-            if p.grad is not None and not p.grad.is_contiguous():
-                raise _lib.IgcnError("graphed step: a parameter gradient is not contiguous "
-                                     f"(shape {tuple(p.shape)}, strides {p.grad.stride()})")
-        self.opt.refresh_table(table=self._table)
-        # the parameters' ``.grad`` belong to whoever stepped last: an eager ``train_step`` (the ragged last batch of an
-        # epoch) or another captured step re-points them, and __call__ puts this graph's own back before it replays
-        self._table_live = list(self.opt._table_live)
-        self._grads = [p.grad for p in self.opt.params]
+            self._capture_single()
+        self._table.seal()
         self._x_grad = self.data.x.grad
-        self._hyper_version = self.opt._hyper_version
-        self.g_opt = None
         if dist and not self.comm_in_graph:
-            self.g_opt = torch.cuda.CUDAGraph()
-            with _capture(self.g_opt, pool=self.g_main.pool(), capture_error_mode=mode):
-                self.opt.step(grad_scale=1.0 / world_size, from_flat=True)
+            self._capture_adam()
         torch.cuda.synchronize()
+
+    def _warmup_step(self):
+        # one eager step of the form that will be captured
+        if self.two is not None:
+            def between_eager():
+                self.two.pack_early()
+                self.two.start_early()
+            self._fwd_bwd(between=between_eager)
+            self.two.pack_rest()
+            self.two.finish()
+            self.opt.step(grad_scale=1.0 / self.world, from_flat=True)
+            return
+        self._fwd_bwd()
+        if self.dist:
+            self.opt.pack_grads()
+            self._reduce()
+            self.opt.step(grad_scale=1.0 / self.world, from_flat=True)
+        else:
+            self.opt.step()
+
+    def _capture_with_collective(self, comm_in_graph):
+        # one graph for the whole distributed step: RCCL's all-reduce is captured between pack and Adam (``comm_in_graph``
+        # says whether every rank did; otherwise ``g_main`` is left empty for the two-graph form)
+        try:
+            with _capture(self.g_main, capture_error_mode=self._mode):
+                self.loss = self._fwd_bwd(rebuild=self.plan_in_graph)
+                self.opt.pack_grads(refresh=False, table=self._table.table)
+                self.comm.all_reduce_(self.opt.grad)
+                self.opt.step(grad_scale=1.0 / self.world, from_flat=True)
+            self.comm_in_graph = True
+        except Exception as exc:                     # noqa: BLE001 — capture refused: two graphs instead
+            if comm_in_graph:
+                raise
+            print(f"[igcn] all-reduce capture refused ({type(exc).__name__}: {exc}); using two graphs around it",
+                  file=sys.stderr)
+            torch.cuda.synchronize()
+            self.g_main = torch.cuda.CUDAGraph()
+        if comm_in_graph is None and self.world > 1 and torch.distributed.is_initialized():
+            # every rank must replay the same form: one rank inside a captured collective and another outside
+            # would hang.  A rank that captured but must step down re-captures below.
+            flag = torch.tensor([1 if self.comm_in_graph else 0], device=self.opt.flat.device, dtype=torch.int32)
+            torch.distributed.all_reduce(flag, op=torch.distributed.ReduceOp.MIN)
+            if self.comm_in_graph and int(flag.item()) == 0:
+                self.comm_in_graph = False
+                self.g_main = torch.cuda.CUDAGraph()
+
+    def _capture_two_buckets(self):
+        # two captures around ONE backward: the first ends (and the second begins) between its two sweeps, on the same
+        # capture stream and without leaving it (torch.cuda.graph's own entry — synchronise, collect, empty the
+        # allocator's cache — must not run in the middle of a backward whose tensors live in the first graph's pool)
+        import gc
+        self.g_rest = torch.cuda.CUDAGraph()
+        cap_stream = torch.cuda.Stream()
+        torch.cuda.synchronize()
+        gc.collect()
+        torch.cuda.empty_cache()
+        was = gc.isenabled()
+        gc.disable()
+        cap_stream.wait_stream(torch.cuda.current_stream())
+        open_graph = [None]
+        try:
+            with torch.cuda.stream(cap_stream):
+                self.g_main.capture_begin(capture_error_mode=self._mode)
+                open_graph[0] = self.g_main
+
+                def between():
+                    self.two.pack_early(table=self._table.table, refresh=False)
+                    self.g_main.capture_end()
+                    open_graph[0] = None
+                    self.g_rest.capture_begin(pool=self.g_main.pool(), capture_error_mode=self._mode)
+                    open_graph[0] = self.g_rest
+                try:
+                    self.loss = self._fwd_bwd(rebuild=self.plan_in_graph, between=between)
+                    self.two.pack_rest(table=self._table.table, refresh=False)
+                finally:
+                    if open_graph[0] is not None:
+                        open_graph[0].capture_end()
+            torch.cuda.current_stream().wait_stream(cap_stream)
+        finally:
+            if was:
+                gc.enable()
+
+    def _capture_single(self):
+        # the default form, one graph: with the Adam step where no gradient exchange follows, up to the pack where one does
+        with _capture(self.g_main, capture_error_mode=self._mode):
+            self.loss = self._fwd_bwd(rebuild=self.plan_in_graph)
+            if not self.dist:
+                self.opt.step(refresh=False, table=self._table.table)   # reads the pointer table at replay time
+            else:
+                self.opt.pack_grads(refresh=False, table=self._table.table)
+
+    def _capture_adam(self):
+        # the Adam step behind a gradient exchange that stays outside the graphs: a graph of its own
+        self.g_opt = torch.cuda.CUDAGraph()
+        with _capture(self.g_opt, pool=self.g_main.pool(), capture_error_mode=self._mode):
+            self.opt.step(grad_scale=1.0 / self.world, from_flat=True)
 
     def _fwd_bwd(self, rebuild=True, between=None):
         """``between`` (two-bucket form): called between the two sweeps of the backward, when the heads' gradients are
@@ -1083,77 +1083,25 @@ class GraphedTrainStep:
             torch.distributed.all_reduce(self.opt.grad)
 
     def load(self, batch):
-        """Copy a new batch (same graph count / node count / edge count) into the static input tensors — including
-        the per-graph node and edge offsets the segmented plan build reads (a batch with the same total edge count
-        but different per-graph counts would otherwise be grouped on the wrong segments).  ``batch is self.data``: a
-        producer wrote the static inputs in place (loader.DeviceFeeder(into=step.data)) — nothing to copy."""
-        if batch is self.data:
-            return
-        if self.plan.segmented:
-            node_ptr, edge_ptr, _, _ = self.plan._seg
-            bp, be = getattr(batch, "ptr", None), getattr(batch, "edge_ptr", None)
-            if bp is None or be is None or bp.shape != node_ptr.shape or be.shape != edge_ptr.shape:
-                raise ValueError("graphed step (segmented plan): the new batch must carry ptr / edge_ptr of the "
-                                 "same graph count")
-            mn, me = getattr(batch, "_max_nodes", None), getattr(batch, "_max_edges", None)
-            # LDS build: the kernel's own limits; tiled build: the tile count the workspace was sized for
-            e_lim = self.plan._seg[3] if self.plan._tiled else self.plan.SEG_MAX_EDGES
-            n_lim = self.plan._seg[2] if self.plan._tiled else self.plan.SEG_MAX_NODES
-            if mn is None or me is None or mn > n_lim or me > e_lim:
-                raise ValueError("graphed step (per-graph plan): the new batch exceeds the per-graph sizes the "
-                                 f"captured build was sized for ({n_lim} nodes / {e_lim} edges)")
-            if self.plan._stack_dims is not None and me > self.plan._stack_dims[1]:
-                # the captured LDS-resident SGCN stack was launched (and its LDS sized) for the construction batch's
-                # largest graph; a graph beyond that would be skipped by its workgroup (and flagged in plan.status)
-                raise ValueError("graphed step: a graph of the new batch has more edges "
-                                 f"({me}) than the captured SGCN stack was sized for ({self.plan._stack_dims[1]}); "
-                                 "build the step on a batch that contains the largest graph, or pass max_edges")
-            if self.plan.nodes_per_graph and int(mn) * (int(bp.numel()) - 1) != self.plan.n_nodes:
-                raise ValueError("graphed step: the captured kernels assume uniform graphs of "
-                                 f"{self.plan.nodes_per_graph} nodes")
-            pairs = [(node_ptr, bp), (edge_ptr, be)]
-        else:
-            pairs = []
-        for k in ("x", "edge_index", "edge_attr", "snps_feat", "y", "clini_score", "tsne_fdim", "clust_y"):
-            dst, src = getattr(self.data, k, None), getattr(batch, k, None)
-            if dst is not None and src is not None:
-                if dst.shape != src.shape:
-                    raise ValueError(f"graphed step needs fixed shapes; {k}: {tuple(src.shape)} vs {tuple(dst.shape)}")
-                pairs.append((dst, src))
-        with torch.no_grad():
-            _lib.copy_multi(pairs)                      # one launch for the whole hand-over (igcn_copy_multi)
+        """``load_batch`` into the static inputs ``self.data``."""
+        load_batch(self.plan, self.data, batch)
 
     def _own_the_table(self):
-        opt = self.opt
-        if opt._hyper_version != self._hyper_version:
-            raise RuntimeError("graphed step: betas / eps of the optimiser changed after the capture (they are by-value "
-                               "launch arguments; only the learning rate is read from device memory) — rebuild the step")
-        if getattr(opt, "_ticked", False):
-            raise RuntimeError("graphed step: an eager backward advanced the step counter and no optimizer.step() "
-                               "followed it")
-        if opt._table_owner is not self:                # (host book-keeping only: the device table is this graph's own)
-            opt._table_owner = self
-            opt._table_live = list(self._table_live)
-            for p, g in zip(opt.params, self._grads):
-                p.grad = g
+        if self._table.claim(self):
             self.data.x.grad = self._x_grad
 
     def __call__(self):
         self._own_the_table()
-        if not self.plan_in_graph:
-            self.plan.rebuild(self.data.edge_index)
         self.g_main.replay()
         if self.two is not None:
             self.two.start_early()                      # the heads' all-reduce: side stream, beside the second graph
             self.g_rest.replay()
             self.two.finish()                           # the remainder's, then the join
             self.g_opt.replay()
-            self.opt._has_state = [True] * len(self.opt.params)
         elif self.g_opt is not None:
             self._reduce()
             self.g_opt.replay()
-            self.opt._has_state = [True] * len(self.opt.params)
-        elif self.dist:
+        if self.dist:                                   # (every form of the distributed step runs Adam from the flat bucket)
             self.opt._has_state = [True] * len(self.opt.params)
         else:
             self.opt.mark_stepped()
@@ -1183,7 +1131,7 @@ def _clone_batch(data):
     return out
 
 
-class EpochTrainer:
+class EpochTrainer(ShapeCache):
     """``train()`` of kernel/train_eval_sgcn_img_snps.py:511-548 over a whole loader, on the fast path.
 
     The reference's loader is ``DataLoader(train_dataset, batch_size, shuffle=True)`` (:96-97: no ``drop_last``), so an
@@ -1203,33 +1151,22 @@ class EpochTrainer:
     def __init__(self, model, optimizer, lambda_loss=DEFAULT_LAMBDA, hp=HP, world_size=1, comm=None, capture_after=1,
                  max_graphs=4, warmup=2, temperature=None):
         self.model, self.opt, self.lam, self.hp = model, optimizer, lambda_loss, hp
-        self.temperature = temperature
+        self.temperature, self.warmup = temperature, int(warmup)
         self.world, self.comm = world_size, comm
-        self.capture_after, self.max_graphs, self.warmup = int(capture_after), int(max_graphs), int(warmup)
-        self.steps = {}                              # signature -> GraphedTrainStep
-        self.seen = {}                               # signature -> times met
-        self.counts = {"replayed": 0, "eager": 0, "captured": 0}
+        super().__init__(capture_after, max_graphs)  # ``steps``: signature -> GraphedTrainStep
 
     def step(self, data):
         """One optimisation step on ``data`` (a device batch).  Returns the loss as a device scalar that stays valid
         until the next step of the same shape."""
-        sig = _batch_signature(data)
-        g = self.steps.get(sig)
+        graphable = data.x.is_cuda and isinstance(self.opt, FlatAdam) and not self.opt.flat_grads
+        g = self.lookup(_batch_signature(data), graphable,
+                        lambda: GraphedTrainStep(self.model, self.opt, _clone_batch(data), self.lam, self.hp,
+                                                 world_size=self.world, comm=self.comm, warmup=self.warmup,
+                                                 temperature=self.temperature),
+                        lambda g: g.load(data))
         if g is None:
-            n = self.seen.get(sig, 0)
-            self.seen[sig] = n + 1
-            graphable = data.x.is_cuda and isinstance(self.opt, FlatAdam) and not self.opt.flat_grads
-            if graphable and n >= self.capture_after and len(self.steps) < self.max_graphs:
-                g = self.steps[sig] = GraphedTrainStep(self.model, self.opt, _clone_batch(data), self.lam, self.hp,
-                                                       world_size=self.world, comm=self.comm, warmup=self.warmup,
-                                                       temperature=self.temperature)
-                self.counts["captured"] += 1
-        if g is None:
-            self.counts["eager"] += 1
             return train_step(self.model, self.opt, data, self.lam, self.hp, self.temperature, world_size=self.world,
                               comm=self.comm)
-        g.load(data)
-        self.counts["replayed"] += 1
         return g()
 
     def fit_epoch(self, loader, device=None):
@@ -1256,7 +1193,6 @@ def fit_epoch(model, optimizer, loader, temperature=None, lambda_loss=DEFAULT_LA
     # (``temperature`` is read by GUIDE_IMGSNP's gate only; the other models, like the reference's GO network, ignore it.)
     # The captured steps bake the regulariser weights of ``hp`` in as launch arguments: they are part of the key; the
     # model and the communicator are held by weak reference, so an id() recycled after garbage collection cannot alias
-    import weakref
     hp_key = tuple(float(getattr(hp, k)) for k in ("lamda_x_l1", "lamda_e_l1", "lamda_x_ent", "lamda_e_ent", "lamda_mi",
                                                     "lamda_ce"))
     if getattr(model, "clusterlabel", False):       # (the cluster trainer's ``lambda0``: one number)
@@ -1268,15 +1204,9 @@ def fit_epoch(model, optimizer, loader, temperature=None, lambda_loss=DEFAULT_LA
         # library's default lambda stands for GUIDE's own default (losses_guide)
         key += (("tensor", temperature.data_ptr()) if torch.is_tensor(temperature) else temperature,
                 lambda_loss is DEFAULT_LAMBDA)
-    cache = optimizer.__dict__.setdefault("_igcn_epoch_trainers", {})
-    tr = cache.get(key)
-    if tr is not None and (tr._model_ref() is not model or (comm is not None and tr._comm_ref() is not comm)):
-        tr = None                                             # the id belonged to an object that is gone
-    if tr is None:
-        tr = cache[key] = EpochTrainer(model, optimizer, lambda_loss, hp, world_size=world_size, comm=comm,
-                                       temperature=temperature)
-        tr._model_ref = weakref.ref(model)
-        tr._comm_ref = weakref.ref(comm) if comm is not None else (lambda: None)
+    tr = kept_trainer(optimizer, "_igcn_epoch_trainers", key,
+                      lambda: EpochTrainer(model, optimizer, lambda_loss, hp, world_size=world_size, comm=comm,
+                                           temperature=temperature), model, comm)
     return tr.fit_epoch(loader, device)
 
 
@@ -1358,7 +1288,7 @@ _EVALUATORS = weakref.WeakKeyDictionary()      # model -> {(lambda_loss, hp): Ev
 
 class _EvalGraph:
     """One captured evaluation batch: the batched sweep under ``torch.no_grad()`` in eval mode, then igcn_eval_collect.
-    ``plan`` / ``data`` are what ``GraphedTrainStep.load`` reads: its checks and its one-launch hand-over are reused."""
+    ``load``: the checks and the one-launch hand-over of ``load_batch``, then the subject ids; False = refused."""
 
     def __init__(self, ev, data):
         from . import ops
@@ -1371,11 +1301,14 @@ class _EvalGraph:
         torch.cuda.synchronize()
 
     def load(self, batch):
-        GraphedTrainStep.load(self, batch)
+        try:
+            load_batch(self.plan, self.data, batch)
+        except ValueError:                           # beyond the per-graph sizes the capture was made for
+            return False
         self.data.sbjID.copy_(batch.sbjID.reshape(self.data.sbjID.shape), non_blocking=True)
 
 
-class Evaluator:
+class Evaluator(ShapeCache):
     """``eval_loss``, ``eval_acc`` and ``eval_scores`` of kernel/train_eval_sgcn_img_snps.py:551-671 in ONE sweep per batch,
     with the metrics computed on the device.
 
@@ -1415,23 +1348,25 @@ class Evaluator:
         if self.fixed and int(capacity) < 1:
             raise ValueError("Evaluator: capacity must be at least one row")
         self.capacity = int(capacity) if capacity is not None else 0
-        self.max_graphs = int(max_graphs)
+        super().__init__(1, max_graphs)              # (the first sighting of a shape is its warm-up)
         self.graphed = _batched(model)
-        self.graphs, self.seen = {}, {}
         self.storage = None                          # where the model's tensors were when ``graphs`` were captured
-        self.counts = {"eager": 0, "replayed": 0, "captured": 0}
         self.rows = None
 
     @property
     def model(self):
         return self._model()
 
+    @property
+    def graphs(self):
+        return self.steps                            # signature -> _EvalGraph
+
     def _reserve(self, need, dev):
         """Epoch buffers of ``max(need, capacity)`` rows (``capacity`` only when fixed)."""
         cap = self.capacity if self.fixed else max(int(need), self.capacity)
         if self.rows is not None and cap == self.capacity:
             return
-        self.graphs, self.seen = {}, {}              # the captured collects point at the old buffers
+        self.steps, self.seen = {}, {}               # the captured collects point at the old buffers
         self.capacity = cap
         self.rows = {k: torch.zeros((cap,) if w is None else (cap, getattr(self, w)), dtype=dt, device=dev)
                      for k, (dt, w) in _EVAL_ROWS.items()}
@@ -1473,25 +1408,12 @@ class Evaluator:
         assert_nothing_pending("Evaluator")
 
     def _batch(self, data):
-        sig = _batch_signature(data)
-        g = self.graphs.get(sig)
-        if g is None and self.graphed and data.x.is_cuda:
-            n = self.seen.get(sig, 0)
-            self.seen[sig] = n + 1
-            if n >= 1 and len(self.graphs) < self.max_graphs:
-                g = self.graphs[sig] = _EvalGraph(self, _clone_batch(data))
-                self.counts["captured"] += 1
-        if g is not None:
-            try:
-                g.load(data)
-            except ValueError:                       # beyond the per-graph sizes the capture was made for
-                g = None
+        g = self.lookup(_batch_signature(data), self.graphed and data.x.is_cuda,
+                        lambda: _EvalGraph(self, _clone_batch(data)), lambda g: g.load(data))
         if g is None:
-            self.counts["eager"] += 1
             self._sweep(data)
-            return
-        g.g.replay()
-        self.counts["replayed"] += 1
+        else:
+            g.g.replay()
 
     def evaluate(self, loader, device=None):
         """One pass over ``loader``; returns the metrics and the per-row tensors (see ``evaluate``)."""
@@ -1503,7 +1425,7 @@ class Evaluator:
         self._reserve(need, dev)
         storage = tuple(t.data_ptr() for t in (*model.parameters(), *model.buffers()))
         if storage != self.storage:
-            self.graphs, self.seen = {}, {}          # the captured launches would read the old storage
+            self.steps, self.seen = {}, {}           # the captured launches would read the old storage
             self.storage = storage
         was = model.training
         model.eval()

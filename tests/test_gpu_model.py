@@ -864,6 +864,29 @@ def test_graphed_train_step_matches_eager(rois, dense, heads, lam):
         assert bool((d <= tol).all()), (k, float(d.max()))
 
 
+def test_graphed_train_step_construction_leaves_no_trace_with_dropout_on():
+    """tests/rollback_state.py's case at the model of test_graphed_train_step_matches_eager: with every dropout ON and
+    after one eager step, constructing the step (two warm-up steps) leaves the parameters, both moments, the step count,
+    every buffer, the mask generator's counter and ``_has_state`` bit for bit what they were, before any replay."""
+    from rollback_state import graphed_train_step_case
+    graphed_train_step_case(two_graphs=False)
+
+
+def test_two_graph_train_step_construction_leaves_no_trace_with_dropout_on():
+    """The same for ``distributed=True, world_size=1``: the single-rank rehearsal of [graph] -> all-reduce -> [Adam
+    graph], whose warm-up packs, reduces and steps from the flat gradient and whose construction captures a second
+    graph.  It needs a process group: in a child process, so that the group does not outlive the test."""
+    import os
+    import subprocess
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    code = (f"import sys; sys.path[:0] = [{os.path.dirname(here)!r}, {here!r}]\n"
+            "from rollback_state import graphed_train_step_case\ngraphed_train_step_case(two_graphs=True)\n"
+            "print('ROLLBACK-OK')")
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "ROLLBACK-OK" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
+
+
 _DIST_SCRIPT = r"""
 import copy, os, sys, torch
 sys.path.insert(0, os.environ["IGCN_ROOT"])

@@ -389,6 +389,24 @@ def test_graphed_step_equals_eager_steps(golden):
         step.load(*_samples(6, 1))
 
 
+def test_graphed_step_construction_leaves_no_trace_with_dropout_on(golden):
+    """The 32-sample shape with every dropout ON, after one eager step (non-zero Adam moments, a live mask generator on
+    the GO network, which here is the model itself): the constructor's two warm-up steps are rolled back — parameters,
+    both moments, the step count, every buffer, the generator's counter and ``_has_state`` bit for bit, before any
+    replay."""
+    from igcn_amd import snps
+    from igcn_amd.train import FlatAdam
+    from rollback_state import assert_rolled_back, rollback_state
+    model, _ = _model(golden("snps_only"), "b32", dropout=True)
+    model.train()
+    opt = FlatAdam(model.parameters(), lr=1e-3)
+    snps.train_step_snps(model, opt, *_samples(32, 299))
+    before = rollback_state(model, opt)
+    assert "generator _drop_state" in before[0] and bool(before[0]["exp_avg"].any()) and any(before[1])
+    snps.GraphedSnpsStep(model, opt, *_samples(32, 300), warmup=2)
+    assert_rolled_back(model, opt, before)
+
+
 def test_fit_epoch_equals_the_eager_loop(golden):
     """70 samples at batch 32 — two full batches and a ragged tail of 6 — over two epochs: the three returned sums and the
     final parameters against train_step_snps by hand (each shape is captured the second time it is met)."""

@@ -24,7 +24,7 @@ for tag, two in [("default", False), ("two", True)] + [(k, True) for k in VARIAN
     step = GraphedTrainStep(model, opt, data, W.LAM, world_size=1, distributed=True, two_buckets=two)
     step()
     torch.cuda.synchronize()
-    out[tag] = {k: (g.detach().cpu().clone() if g is not None else None) for k, g in zip(names, step._grads)}
+    out[tag] = {k: (g.detach().cpu().clone() if g is not None else None) for k, g in zip(names, step._table.grads)}
     print(tag, "two" if step.two is not None else "plain")
 for a, b in [("default", "two")] + [("default", k) for k in VARIANTS]:
     bad = {}
