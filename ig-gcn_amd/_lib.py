@@ -14,7 +14,7 @@ from . import switches
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libigcn.so")
 
-ABI_VERSION = 430        # include/igcn.h IGCN_ABI_VERSION this table was written against (tests/test_abi.py compares)
+ABI_VERSION = 431        # include/igcn.h IGCN_ABI_VERSION this table was written against (tests/test_abi.py compares)
 
 P, I, L, F, Z = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
 
@@ -154,6 +154,10 @@ SIGNATURES = {
     "igcn_attn_core_split_fwd": (I, [I, I, I, I, I, P, P, P, P, P]),
     "igcn_attn_core_split_bwd_supported": (I, [I, I, I, I]),
     "igcn_attn_core_split_bwd": (I, [I, I, I, I, I, P, P, P, P, P, P, P, P, P]),
+    "igcn_attn_weights_supported": (I, [I, I, I, I]),
+    "igcn_attn_weights_chunk_rows": (I, [I, I, I, I]),
+    "igcn_attn_weights": (I, [I, I, I, I, I, P, P, P, P]),
+    "igcn_attn_map_accumulate": (I, [I, I, I, I, P, P, P, P, P, P]),
     "igcn_spmm_fwd": (I, [I, I, I, I, L, P, P, P, P, P, P]),
     "igcn_spmm_bwd_scratch_floats": (Z, [I, I, I, I, L]),
     "igcn_spmm_bwd": (I, [I, I, I, I, L, P, P, P, P, P, P, P, P, P, P, P, P, P]),

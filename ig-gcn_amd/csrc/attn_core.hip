@@ -23,6 +23,12 @@ int igcn_attn_mfma_fwd_chunked(int B, int D, int H, int Lq, int Lk, const float*
 int igcn_attn_mfma_bwd_chunked(int B, int D, int H, int Lq, int Lk, const float* q, const float* kv, const float* o,
                                const float* lse, const float* dout, float* dq, float* dkv, float* delta,
                                hipStream_t st);
+int igcn_attn_mfma_weights_supported(int D, int H, int Lq, int Lk);
+int igcn_attn_mfma_weights_chunk_rows(int D, int H, int Lq, int Lk);
+int igcn_attn_mfma_weights(int B, int D, int H, int Lq, int Lk, const float* q, const float* kv, float* w,
+                           hipStream_t st);
+int igcn_attn_mfma_map_accumulate(int B, int Lq, int Lk, int C, const float* w, const int64_t* y, double* sums,
+                                  int64_t* counts, int64_t* state, hipStream_t st);
 
 // attn_split.hip: head_dim 16 on split bf16 operands (fp32-grade results, bf16 matrix rate) — the default for that width;
 // IGCN_ATTN_EXACT_FP32=1 keeps the exact-fp32 kernels
@@ -87,4 +93,35 @@ extern "C" int igcn_attn_core_bwd(int B, int D, int H, int Lq, int Lk, const flo
   }
   igcn_set_error("attn_core_bwd: unsupported shape D=%d H=%d Lq=%d Lk=%d (head_dim <= 96)", D, H, Lq, Lk);
   return IGCN_ERR_UNSUPPORTED;
+}
+
+// ---- attention weights (the head-averaged softmax nn.MultiheadAttention returns next to its output) ----------------
+extern "C" int igcn_attn_weights_supported(int D, int H, int Lq, int Lk) {
+  return igcn_attn_mfma_weights_supported(D, H, Lq, Lk);
+}
+
+extern "C" int igcn_attn_weights_chunk_rows(int D, int H, int Lq, int Lk) {
+  return igcn_attn_mfma_weights_chunk_rows(D, H, Lq, Lk);
+}
+
+extern "C" int igcn_attn_weights(int B, int D, int H, int Lq, int Lk, const float* q, const float* kv, float* w,
+                                 void* stream) {
+  if (!igcn_attn_mfma_weights_supported(D, H, Lq, Lk)) {
+    igcn_set_error("attn_weights: unsupported shape D=%d H=%d Lq=%d Lk=%d (head_dim <= 96, 16 keys of all heads in LDS)",
+                   D, H, Lq, Lk);
+    return IGCN_ERR_UNSUPPORTED;
+  }
+  IGCN_REQUIRE(B >= 0 && (int64_t)B * ((Lq + 15) / 16) < (int64_t)1 << 31, "attn_weights: B=%d Lq=%d out of range", B, Lq);
+  IGCN_REQUIRE(q != nullptr && kv != nullptr && w != nullptr, "attn_weights: null pointer");
+  if (B == 0) return IGCN_OK;
+  return igcn_attn_mfma_weights(B, D, H, Lq, Lk, q, kv, w, (hipStream_t)stream);
+}
+
+extern "C" int igcn_attn_map_accumulate(int B, int Lq, int Lk, int C, const float* w, const int64_t* y, double* sums,
+                                        int64_t* counts, int64_t* state, void* stream) {
+  IGCN_REQUIRE(B >= 0 && Lq > 0 && Lk > 0 && C > 0, "attn_map_accumulate: B=%d Lq=%d Lk=%d C=%d", B, Lq, Lk, C);
+  IGCN_REQUIRE(w != nullptr && y != nullptr && sums != nullptr && counts != nullptr && state != nullptr,
+               "attn_map_accumulate: null pointer");
+  if (B == 0) return IGCN_OK;
+  return igcn_attn_mfma_map_accumulate(B, Lq, Lk, C, w, y, sums, counts, state, (hipStream_t)stream);
 }

@@ -998,3 +998,252 @@ int igcn_attn_mfma_bwd_chunked(int B, int D, int H, int Lq, int Lk, const float*
   IGCN_CHECK_LAUNCH("attn_mfma_bwd_chunked");
   return IGCN_OK;
 }
+
+// =================================================================================================
+// Attention WEIGHTS (the second output of nn.MultiheadAttention, kernel/sgcn_img_snp.py:240):
+//   w[b, i, j] = (1 / H) sum_h softmax_j(q_h[b, i] . k_h[b, j] / sqrt(hd))                      [B, Lq, Lk]
+// a reported quantity, not a step of the training path: exact-fp32 operands, own row maximum and row sum (the forward's
+// lse is not read, so rows sum to 1 whichever core ran the forward).
+//   workgroup = (sample, block of nw 16-query tiles), wave = one query tile; the keys of ALL heads of a chunk of CH
+//   key rows sit in LDS ([H][CH][HDP + 1]; the whole key side when it fits, otherwise streamed twice):
+//   pass 0: per head the running (max, sum) of every query over all keys — per lane over its own keys, the four lane
+//           groups and the chunks meet in a per-wave LDS table [H][max | sum][16];
+//   pass 1: the same transposed score tiles again, AW_GT key tiles at a time; every lane adds exp2(s - max_h) / (H sum_h)
+//           over the heads in registers and stores four consecutive keys of its query.
+// The head average never leaves the lane that writes the element: one writer per element, no atomics, a fixed order.
+// =================================================================================================
+#define AW_MAX_WAVES 8
+#define AW_LDS_BUDGET (72 * 1024)          /* two workgroups per CU */
+#define AW_SU 8                            /* 16-byte loads a thread has in flight while staging */
+#define AW_GT 8                            /* key tiles per group of pass 1 (4 accumulator registers each) */
+
+// Key rows [0, kn) of ALL heads of a chunk -> Ks [H][CH][HDP + 1]; columns hd..HDP-1 and rows kn..knp-1 zero.  src: the
+// chunk's first kv row (the key half of a row is D contiguous floats: the heads side by side).  vec (head_dim % 4 == 0,
+// 16-byte aligned rows): whole rows in 16-byte slots, every thread issuing AW_SU loads before it stores any — a chunk
+// is one or two memory round trips, not one per slot (see am_stage_pair); otherwise head by head through am_stage.
+template <int HDP>
+__device__ __forceinline__ void aw_stage_keys(const float* __restrict__ src, int D, int H, int hd, int vec, int kn,
+                                              int knp, int CH, float* __restrict__ Ks) {
+  constexpr int LD = HDP + 1;
+  if (!vec) {
+    for (int h = 0; h < H; ++h) am_stage<HDP>(src + h * hd, 2 * D, hd, 0, kn, knp, Ks + (size_t)h * CH * LD);
+    return;
+  }
+  const int nq = D >> 2, total = kn * nq, step = (int)blockDim.x;
+  for (int t0 = threadIdx.x; t0 < total; t0 += step * AW_SU) {
+    float4 v[AW_SU];
+#pragma unroll
+    for (int u = 0; u < AW_SU; ++u) {
+      const int t = t0 + u * step;
+      v[u] = (t < total) ? ld4(src + (int64_t)(t / nq) * 2 * D + (t % nq) * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int u = 0; u < AW_SU; ++u) {
+      const int t = t0 + u * step;
+      if (t < total) {
+        const int j = t / nq, c = (t % nq) * 4, h = c / hd;      // a slot lies inside one head (head_dim % 4 == 0)
+        float* d = Ks + ((size_t)h * CH + j) * LD + (c - h * hd);
+        d[0] = v[u].x; d[1] = v[u].y; d[2] = v[u].z; d[3] = v[u].w;
+      }
+    }
+  }
+  const int padc = HDP - hd, padr = knp - kn;                    // (padc > 0 only above 32 columns)
+  for (int t = threadIdx.x; t < H * kn * padc; t += step) {
+    const int r = t / padc;                                      // = h * kn + j
+    Ks[((size_t)(r / kn) * CH + r % kn) * LD + hd + t % padc] = 0.f;
+  }
+  for (int t = threadIdx.x; t < H * padr * HDP; t += step) {
+    const int r = t / HDP;                                       // = h * padr + (j - kn)
+    Ks[((size_t)(r / padr) * CH + kn + r % padr) * LD + t % HDP] = 0.f;
+  }
+}
+
+template <int HDP>
+__global__ void __launch_bounds__(64 * AW_MAX_WAVES)
+k_attn_weights(int H, int hd, int vec, int wvec, int Lq, int Lk, int CH, int nqb, const float* __restrict__ q,
+               const float* __restrict__ kv, float* __restrict__ wout) {
+  constexpr int LD = HDP + 1, NC = HDP / 4;
+  extern __shared__ float smem[];
+  const int b = blockIdx.x / nqb, D = H * hd;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6, n = lane & 15, g = lane >> 4;
+  float* Ks = smem;                                              // [H][CH][LD]
+  float* St = Ks + (size_t)H * CH * LD + (size_t)w * H * 32;     // this wave's [H][max | sum][16] (log2 domain)
+  const int qt = (blockIdx.x % nqb) * nw + w, qi = qt * 16 + n;
+  const bool active = qt * 16 < Lq;                              // wave-uniform (a wave past Lq only keeps the barriers)
+  const bool resident = CH >= Lk;
+  const float scale = rsqrtf((float)hd) * 1.44269504088896341f, inv_h = 1.f / (float)H;
+  const float* qrow = q + (int64_t)(b * (int64_t)Lq + (qi < Lq ? qi : 0)) * D;
+  float* wrow = wout + ((int64_t)b * Lq + qi) * Lk;
+  for (int i = lane; i < H * 32; i += 64) St[i] = (i & 16) ? 0.f : -INFINITY;
+  for (int pass = 0; pass < 2; ++pass) {
+    for (int k0 = 0; k0 < Lk; k0 += CH) {
+      const int kn = min(CH, Lk - k0), knp = (kn + 15) & ~15, nkt = knp >> 4;
+      if (pass == 0 || !resident) {
+        __syncthreads();                                         // the previous chunk is consumed
+        aw_stage_keys<HDP>(kv + ((int64_t)b * Lk + k0) * 2 * D, D, H, hd, vec, kn, knp, CH, Ks);
+      }
+      __syncthreads();                                           // (also: pass 0's table is complete before pass 1 reads it)
+      if (!active) continue;
+      if (pass == 0) {
+        for (int h = 0; h < H; ++h) {
+          float qb[NC];
+#pragma unroll
+          for (int c = 0; c < NC; ++c) qb[c] = (qi < Lq && 4 * c + g < hd) ? qrow[h * hd + 4 * c + g] * scale : 0.f;
+          const float* kh = Ks + (size_t)h * CH * LD;
+          float m = -INFINITY, l = 0.f;                          // over this lane's keys {16 kt + 4 g + r}
+          for (int kt = 0; kt < nkt; ++kt) {
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            const float* kr = kh + (kt * 16 + n) * LD + g;
+#pragma unroll
+            for (int c = 0; c < NC; ++c) acc = mfma4(kr[4 * c], qb[c], acc);
+            const int nv = kn - (kt * 16 + 4 * g);               // this lane's valid keys of the tile (>= 4: all)
+            float tmax = -INFINITY;
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              if (r < nv) tmax = fmaxf(tmax, acc[r]);
+            if (tmax > m) {
+              l *= __builtin_amdgcn_exp2f(m - tmax);             // 2^(-inf) = 0 on the first tile (l = 0)
+              m = tmax;
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              if (r < nv) l += __builtin_amdgcn_exp2f(acc[r] - m);
+          }
+          float M = fmaxf(m, __shfl_xor(m, 16, 64));
+          M = fmaxf(M, __shfl_xor(M, 32, 64));                   // finite: a chunk holds at least one key
+          float ls = (m == -INFINITY) ? 0.f : l * __builtin_amdgcn_exp2f(m - M);
+          ls += __shfl_xor(ls, 16, 64);
+          ls += __shfl_xor(ls, 32, 64);
+          const float mo = St[h * 32 + n], lo = St[h * 32 + 16 + n];
+          const float mn = fmaxf(mo, M);
+          const float ln = lo * __builtin_amdgcn_exp2f(mo - mn) + ls * __builtin_amdgcn_exp2f(M - mn);
+          if (g == 0) {                                          // (the wave's reads above were issued before these writes)
+            St[h * 32 + n] = mn;
+            St[h * 32 + 16 + n] = ln;
+          }
+        }
+      } else {
+        for (int kt0 = 0; kt0 < nkt; kt0 += AW_GT) {
+          f32x4 out[AW_GT];
+#pragma unroll
+          for (int u = 0; u < AW_GT; ++u) out[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
+          for (int h = 0; h < H; ++h) {
+            float qb[NC];
+#pragma unroll
+            for (int c = 0; c < NC; ++c) qb[c] = (qi < Lq && 4 * c + g < hd) ? qrow[h * hd + 4 * c + g] * scale : 0.f;
+            const float* kh = Ks + (size_t)h * CH * LD;
+            const float mh = St[h * 32 + n], ih = inv_h / St[h * 32 + 16 + n];
+#pragma unroll
+            for (int u = 0; u < AW_GT; ++u) {
+              if (kt0 + u < nkt) {                               // wave-uniform
+                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+                const float* kr = kh + ((kt0 + u) * 16 + n) * LD + g;
+#pragma unroll
+                for (int c = 0; c < NC; ++c) acc = mfma4(kr[4 * c], qb[c], acc);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) out[u][r] += __builtin_amdgcn_exp2f(acc[r] - mh) * ih;   // (padding keys: never stored)
+              }
+            }
+          }
+          if (qi < Lq) {
+#pragma unroll
+            for (int u = 0; u < AW_GT; ++u) {
+              const int key = k0 + (kt0 + u) * 16 + 4 * g;       // four consecutive keys of query qi
+              if (kt0 + u < nkt && key < k0 + kn) {
+                if (wvec) {                                      // Lk % 4 == 0 and a 16-byte aligned base: key + 3 < Lk
+                  *reinterpret_cast<float4*>(wrow + key) = make_float4(out[u][0], out[u][1], out[u][2], out[u][3]);
+                } else {
+#pragma unroll
+                  for (int r = 0; r < 4; ++r)
+                    if (key + r < k0 + kn) wrow[key + r] = out[u][r];
+                }
+              }
+            }
+          }
+        }
+      }
+    }
+  }
+}
+
+// keys per LDS chunk of the weights kernel (a multiple of 16), 0 when 16 keys of all heads and the waves' tables do not
+// fit the budget (then the shape is not covered)
+static int aw_chunk(int D, int H) {
+  const int hd = D / H;
+  const size_t table = (size_t)AW_MAX_WAVES * H * 32 * sizeof(float);
+  const size_t row = (size_t)H * (am_hdp(hd) + 1) * sizeof(float);
+  if (table + 16 * row > AW_LDS_BUDGET) return 0;
+  return (int)((AW_LDS_BUDGET - table) / row) & ~15;             // (>= 16 by the test above)
+}
+
+int igcn_attn_mfma_weights_supported(int D, int H, int Lq, int Lk) {
+  if (H <= 0 || D <= 0 || D % H || Lq <= 0 || Lk <= 0 || D / H > 96) return 0;
+  return aw_chunk(D, H) != 0;
+}
+
+// 0 = every key resident (or shape not covered), else the keys per chunk
+int igcn_attn_mfma_weights_chunk_rows(int D, int H, int Lq, int Lk) {
+  if (!igcn_attn_mfma_weights_supported(D, H, Lq, Lk)) return 0;
+  const int ch = aw_chunk(D, H);
+  return ch >= Lk ? 0 : ch;
+}
+
+int igcn_attn_mfma_weights(int B, int D, int H, int Lq, int Lk, const float* q, const float* kv, float* w,
+                           hipStream_t st) {
+  const int hd = D / H, vec = am_vec(D, hd, q, kv, kv, kv);
+  const int wvec = (Lk % 4 == 0 && (uintptr_t)w % 16 == 0) ? 1 : 0;
+  int ch = aw_chunk(D, H);
+  if (ch > ((Lk + 15) & ~15)) ch = (Lk + 15) & ~15;
+  const int nqt = (Lq + 15) / 16, nw = nqt < AW_MAX_WAVES ? (nqt < 4 ? 4 : nqt) : AW_MAX_WAVES;
+  const int nqb = (nqt + nw - 1) / nw;
+  const size_t lds = ((size_t)H * ch * (am_hdp(hd) + 1) + (size_t)nw * H * 32) * sizeof(float);
+#define CALL(HDPV)                                                                                               \
+  {                                                                                                              \
+    IGCN_ALLOW_BIG_LDS((k_attn_weights<HDPV>));                                                                  \
+    hipLaunchKernelGGL((k_attn_weights<HDPV>), dim3((unsigned)((int64_t)B * nqb)), dim3(64 * nw), lds, st, H, hd, vec, \
+                       wvec, Lq, Lk, ch, nqb, q, kv, w);                                                         \
+  }
+  AM_DISPATCH(am_hdp(hd), CALL)
+#undef CALL
+  IGCN_CHECK_LAUNCH("attn_weights");
+  return IGCN_OK;
+}
+
+// Per-class sums of a batch of maps: thread = one map element, the B samples walked in order (fp64 accumulators, a
+// fixed order, no atomics); thread 0 counts the samples per class and the labels outside [0, C).
+__global__ void __launch_bounds__(256)
+k_attn_map_accumulate(int B, int64_t E, int C, const float* __restrict__ w, const int64_t* __restrict__ y,
+                      double* __restrict__ sums, int64_t* __restrict__ counts, int64_t* __restrict__ state) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= E) return;
+  int64_t cur = -1;
+  double acc = 0.0;
+  for (int b = 0; b < B; ++b) {
+    const int64_t c = y[b];
+    if (c < 0 || c >= C) continue;
+    if (c != cur) {                                              // the accumulator follows the label: one read, one write per run
+      if (cur >= 0) sums[cur * E + e] = acc;
+      cur = c;
+      acc = sums[c * E + e];
+    }
+    acc += (double)w[(int64_t)b * E + e];
+  }
+  if (cur >= 0) sums[cur * E + e] = acc;
+  if (e == 0) {
+    int64_t bad = 0;
+    for (int b = 0; b < B; ++b) {
+      const int64_t c = y[b];
+      if (c < 0 || c >= C) ++bad; else counts[c] += 1;
+    }
+    state[0] += bad;
+  }
+}
+
+int igcn_attn_mfma_map_accumulate(int B, int Lq, int Lk, int C, const float* w, const int64_t* y, double* sums,
+                                  int64_t* counts, int64_t* state, hipStream_t st) {
+  const int64_t E = (int64_t)Lq * Lk;
+  hipLaunchKernelGGL(k_attn_map_accumulate, dim3((unsigned)igcn_cdiv(E, 256)), dim3(256), 0, st, B, E, C, w, y, sums,
+                     counts, state);
+  IGCN_CHECK_LAUNCH("attn_map_accumulate");
+  return IGCN_OK;
+}

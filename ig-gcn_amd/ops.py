@@ -3135,6 +3135,45 @@ class AttentionCore(torch.autograd.Function):
         return dq, dkv, None, None
 
 
+def attention_weights(q, kv, heads):
+    """The weights nn.MultiheadAttention returns next to its output (kernel/sgcn_img_snp.py:240, head-averaged):
+    mean_h softmax(q_h k_h^T / sqrt(hd)) -> [B, Lq, Lk] from the projection outputs q [B, Lq, D] and kv [B, Lk, 2D]
+    (fp32, contiguous; only the key half of kv is read).  No autograd.  One launch of the exact-fp32 kernel
+    (igcn_attn_weights) where it covers the shape (igcn_attn_weights_supported); heads wider than 96 take the
+    batched-GEMM + softmax composite ``_cross_attention`` uses for them."""
+    if q.dtype != torch.float32 or kv.dtype != torch.float32:
+        raise TypeError("attention_weights: q and kv must be float32")
+    q, kv = q.detach(), kv.detach()
+    b, lq, d = q.shape
+    lk = kv.shape[1]
+    if d % heads or kv.numel() != b * lk * 2 * d:
+        raise ValueError(f"attention_weights: q {tuple(q.shape)} and kv {tuple(kv.shape)} do not fit {heads} heads")
+    if _lib.load().igcn_attn_weights_supported(d, heads, lq, lk):
+        w = torch.empty(b, lq, lk, dtype=torch.float32, device=q.device)
+        call("igcn_attn_weights", b, d, heads, lq, lk, ptr(q), ptr(kv), ptr(w), stream_ptr())
+        return w
+    hd = d // heads
+    qh = q.view(b, lq, heads, hd).transpose(1, 2)
+    kh = kv.view(b, lk, 2, heads, hd)[:, :, 0]
+    att = torch.softmax((qh @ kh.permute(0, 2, 3, 1)) * hd ** -0.5, dim=-1)
+    return att.mean(dim=1)
+
+
+def attention_map_accumulate(w, y, sums, counts, state):
+    """sums[y[b]] += w[b] and counts[y[b]] += 1 over a batch of attention maps w [B, Lq, Lk] (igcn_attn_map_accumulate:
+    fp64 sums [C, Lq, Lk], int64 counts [C]; labels outside [0, C) are skipped and counted in state[0]).  One launch,
+    a fixed summation order."""
+    b, lq, lk = w.shape
+    c = counts.numel()
+    if (w.dtype != torch.float32 or y.dtype != torch.int64 or sums.dtype != torch.float64 or counts.dtype != torch.int64
+            or state.dtype != torch.int64):
+        raise TypeError("attention_map_accumulate: w float32, y / counts / state int64, sums float64")
+    if y.numel() != b or tuple(sums.shape) != (c, lq, lk) or state.numel() < 1:
+        raise ValueError(f"attention_map_accumulate: w {tuple(w.shape)}, y {tuple(y.shape)}, sums {tuple(sums.shape)}, "
+                         f"counts {tuple(counts.shape)} do not fit")
+    call("igcn_attn_map_accumulate", b, lq, lk, c, ptr(w), ptr(y), ptr(sums), ptr(counts), ptr(state), stream_ptr())
+
+
 # =================================================================================================
 # GUIDE_IMGSNP: BatchNorm + PReLU blocks, the image gate + encoder (csrc/guide.hip); NodesLayerNormPReLU: by NodesLayerNorm
 # =================================================================================================

@@ -349,6 +349,41 @@ class SGCN_GCN_IMGSNP(torch.nn.Module):
         produce every parameter gradient once instead of adding two per-pass contributions."""
         return self._forward_grouped(data, temperature, device, (False, True))
 
+    def _check_config(self, masked):
+        """Raises for a configuration a subclass's forward cannot run (SGCN_GCN_CLUSTERLABEL); nothing to refuse here."""
+
+    def attention_weights(self, data, temperature=None, device=None, isExplain=False):
+        """The second output of ``self.multihead_attn(batch_x, atten_out, atten_out)`` (:240), which the reference's
+        forward discards: the head-averaged cross-attention weights [B, rois, Ntop] (fp32) — how strongly every brain
+        region attends to every top-level GO term.  The image branch and the GO network run as in ``forward`` — in eval
+        mode under ``torch.no_grad()``: BatchNorm on its running statistics, no dropout — up to the packed input
+        projection (at the forward's projection precision); ops.attention_weights then forms the probabilities the
+        attention cores never do.  The model is left as it was: ``training``, parameters, buffers, random state; the
+        hand-over to ``loss_probability`` and ``last_edge_prob`` are reset as after an evaluation sweep."""
+        if not self.isCrossAtten or self.isImageOnly or self.isSNPsOnly:
+            raise ValueError("attention_weights: the model has no cross-attention (needs isCrossAtten=True, "
+                             "isImageOnly=False, isSNPsOnly=False)")
+        flags = (bool(isExplain),)
+        self._check_config(any(flags))
+        x = data.x
+        if x.shape[0] % self.rois:
+            raise ValueError(f"every graph must have exactly rois={self.rois} nodes (got {x.shape[0]} nodes)")
+        was = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                plan = ops.plan_for(data, keep_pending=True)
+                route, fan = self._image_route(data, plan, flags)
+                img = route(data, plan, flags, fan)
+                batch_x = img.xcat.view(x.shape[0] // self.rois, self.rois, -1)
+                atten_out = self.go_network(img.snps_in, temperature, device, groups=1, extra_dropout=[])[3]
+                mha = self.multihead_attn
+                q, kv = ops.InProj.apply(batch_x, atten_out, mha.in_proj_weight, mha.in_proj_bias, self.bf16_transforms)
+                return ops.attention_weights(q.contiguous(), kv.contiguous(), mha.num_heads)
+        finally:
+            self.last_edge_prob, self._handoff = None, _Handoff()     # no later loss_probability is served from this batch
+            self.train(was)
+
     def predraw_dropout(self, data, groups=2):
         """The dropout masks of the next training sweep over ``data`` (``groups`` passes batched: the train step's plain |
         masked pair), drawn as a RIDER of the launch that follows on this stream — a captured step queues them in front

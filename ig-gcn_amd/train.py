@@ -1506,6 +1506,44 @@ def eval_scores_of(r):
             r["specificity"], r["out_lin"].cpu(), r["sbjID"].cpu(), r["linear_outf"].cpu(), regression)
 
 
+def attention_maps(model, loader, temperature=None, device=None, isExplain=False, num_classes=None, top_k=10):
+    """The ROI x GO-term attention table of a cohort: ``model.attention_weights`` (the weights
+    ``self.multihead_attn`` returns at kernel/sgcn_img_snp.py:240, which the reference discards) of every batch of
+    ``loader``, summed per class of ``data.y`` on the device (igcn_attn_map_accumulate: fp64, sample order) and read
+    once at the end.  Returns a dict: ``mean`` [C, rois, Ntop] (fp32; zeros for a class without subjects), ``count`` [C]
+    (int64), ``overall`` [rois, Ntop] (the count-weighted mean over the classes), ``go_rows`` [Ntop] (int64: the GO node
+    behind every key row — the encoder drops the two deepest levels, which lead the builder's node order, so the rows
+    are nodes N - Ntop .. N - 1), ``top_terms`` [rois, top_k] (int64: the GO nodes of the ``top_k`` largest entries
+    of every row of ``overall``) and ``n`` (subjects).  A label outside [0, C) raises IgcnError after the pass."""
+    from . import ops
+    head = model.lin2_classify if getattr(model, "clusterlabel", False) else model.lin2
+    c = int(num_classes) if num_classes is not None else int(head.weight.shape[0])
+    if c <= 0:
+        raise ValueError(f"attention_maps: num_classes={c}")
+    sums = counts = state = None
+    n = 0
+    for data in _batches(loader, device):
+        w = model.attention_weights(data, temperature, device, isExplain)
+        if sums is None:
+            sums = torch.zeros(c, w.shape[1], w.shape[2], dtype=torch.float64, device=w.device)
+            counts = torch.zeros(c, dtype=torch.int64, device=w.device)
+            state = torch.zeros(1, dtype=torch.int64, device=w.device)
+        y = data.y.view(-1).to(device=w.device, dtype=torch.int64).contiguous()
+        ops.attention_map_accumulate(w, y, sums, counts, state)
+        n += int(data.num_graphs)
+    if n == 0:
+        raise ValueError("attention_maps: the loader is empty")
+    skipped = int(state.item())                                  # the pass's one synchronisation
+    if skipped:
+        raise _lib.IgcnError(f"attention_maps: {skipped} of {n} labels lie outside [0, {c})")
+    mean = (sums / counts.clamp(min=1).view(c, 1, 1).double()).float()
+    overall = (sums.sum(0) / float(n)).float()
+    n_top, n_nodes = overall.shape[1], int(model.go_network.n_nodes)
+    go_rows = torch.arange(n_nodes - n_top, n_nodes, dtype=torch.int64, device=overall.device)
+    top = torch.topk(overall, min(int(top_k), n_top), dim=1).indices
+    return {"mean": mean, "count": counts, "overall": overall, "go_rows": go_rows, "top_terms": go_rows[top], "n": n}
+
+
 def output_importance(model):
     """The arrays util/output.py:20-32 writes per fold: node / SNP importance and the edge-mask weights."""
     out = {"node_importance": model.prob.detach().cpu().numpy(),

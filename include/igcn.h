@@ -31,7 +31,7 @@ extern "C" {
 /* ABI revision: bumped whenever a prototype below changes (argument added, removed or re-ordered).  igcn_version()
  * returns the revision the library was built from; a binding written against a different one must refuse to call
  * (igcn_amd/_lib.py does). */
-#define IGCN_ABI_VERSION 430
+#define IGCN_ABI_VERSION 431
 int igcn_version(void);
 const char* igcn_last_error(void);
 /* A/B switches, set ONCE by the binding when it loads the library (from the IGCN_* environment variables): bit 0 no tiled
@@ -803,6 +803,24 @@ int igcn_attn_core_split_fwd(int B, int D, int H, int Lq, int Lk, const float* q
 int igcn_attn_core_split_bwd_supported(int D, int H, int Lq, int Lk);
 int igcn_attn_core_split_bwd(int B, int D, int H, int Lq, int Lk, const float* q, const float* kv, const float* o,
                              const float* lse, const float* dout, float* dq, float* dkv, float* scratch, void* stream);
+
+/* The attention WEIGHTS nn.MultiheadAttention returns next to its output (kernel/sgcn_img_snp.py:240,
+ * ``attn_output, attn_output_weights = self.multihead_attn(...)``): the head-averaged softmax
+ *   w[b,i,j] = (1/H) sum_h softmax_j(q_h[b,i] . k_h[b,j] / sqrt(head_dim))        w [B,Lq,Lk]
+ * on the projection outputs in place (q [B,Lq,D], kv [B,Lk,2,D]: only the key half is read).  Exact fp32 operands on
+ * v_mfma_f32_16x16x4_f32; the kernel takes its own row maximum and row sum (it does not read the forward's lse), keeps
+ * the head average inside the lane that stores the element — one writer per element, no atomics, bit-reproducible —
+ * and streams the keys through LDS in chunks when all heads' keys do not fit (igcn_attn_weights_chunk_rows: keys per
+ * chunk, 0 = resident).  Covered: head_dim <= 96 with 16 keys of all H heads in the kernel's 72 KB of LDS (D up to
+ * ~1000), any Lq, any Lk; anything else: IGCN_ERR_UNSUPPORTED. */
+int igcn_attn_weights_supported(int D, int H, int Lq, int Lk);
+int igcn_attn_weights_chunk_rows(int D, int H, int Lq, int Lk);
+int igcn_attn_weights(int B, int D, int H, int Lq, int Lk, const float* q, const float* kv, float* w, void* stream);
+/* Per-class sums of a batch of such maps (kernel/sgcn_img_snp.py:240; the ROI x GO-term table of a cohort):
+ * sums[y[b]] += w[b] in sample order with fp64 accumulators (one thread per map element, no atomics), counts[y[b]] += 1;
+ * labels outside [0, C) are skipped and counted in state[0].  sums [C,Lq,Lk] double, counts [C] and state [1] int64. */
+int igcn_attn_map_accumulate(int B, int Lq, int Lk, int C, const float* w, const int64_t* y, double* sums,
+                             int64_t* counts, int64_t* state, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Sparse SNP<->GO maps with learnable non-zeros — gene encoding go_model.py:208-215 (C=2 channels,
