@@ -597,6 +597,11 @@ extern "C" int igcn_spmm_bwd_dval_multi(int n, const int64_t* table, void* strea
 __device__ __forceinline__ float go_exp(float z) { return __expf(z); }
 __device__ __forceinline__ float go_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 __device__ __forceinline__ float go_tanh(float z) { return 1.f - 2.f * go_rcp(1.f + __expf(2.f * z)); }
+// the two attention coefficients of an encoder layer (go_model.py:226-244), spelled ONCE for the forward and for
+// igcn_go_attn_coeffs: s_e = exp(tanh(a1 . x_in[row] + a2 . x_in[col])) of an edge (p, q: the two dot products) and
+// beta_r = sigmoid(a_s . x_s[r]) of a node's self loop (z: the dot product)
+__device__ __forceinline__ float go_edge_score(float p, float q) { return go_exp(go_tanh(p + q)); }
+__device__ __forceinline__ float go_self_gate(float z) { return go_rcp(1.f + go_exp(-z)); }
 
 template <int FIN, int FOUT>
 struct AttnW {
@@ -699,8 +704,8 @@ k_go_attn_fwd(int N, const int32_t* __restrict__ row_ptr, const int32_t* __restr
     load_node<FIN>(xb, N, m1, xm1);
     transform<FIN, FOUT>(W.wi, xm0, xi0);
     transform<FIN, FOUT>(W.wi, xm1, xi1);
-    const float s0 = go_exp(go_tanh(p + dot<FOUT>(W.a2, xi0)));
-    const float s1 = two ? go_exp(go_tanh(p + dot<FOUT>(W.a2, xi1))) : 0.f;
+    const float s0 = go_edge_score(p, dot<FOUT>(W.a2, xi0));
+    const float s1 = two ? go_edge_score(p, dot<FOUT>(W.a2, xi1)) : 0.f;
     Z += s0;
 #pragma unroll
     for (int c = 0; c < FOUT; ++c) agg[c] += s0 * xi0[c];
@@ -711,7 +716,7 @@ k_go_attn_fwd(int N, const int32_t* __restrict__ row_ptr, const int32_t* __restr
     }
   }
   const float zinv = p1 > p0 ? go_rcp(Z) : 0.f;
-  const float g = go_rcp(1.f + go_exp(-dot<FOUT>(W.as, xs)));
+  const float g = go_self_gate(dot<FOUT>(W.as, xs));
   float* yb = y + (int64_t)b * FOUT * N;
 #pragma unroll
   for (int c = 0; c < FOUT; ++c) yb[c * N + n] = agg[c] * zinv + xs[c] * g;
@@ -738,6 +743,90 @@ extern "C" int igcn_go_attn_fwd(int B, int N, int fin, int fout, const int32_t* 
   GO_DISPATCH(fin, fout, CALL)
 #undef CALL
   IGCN_CHECK_LAUNCH("go_attn_fwd");
+  return IGCN_OK;
+}
+
+// ---- the layer's attention coefficients as an output (attention roll-out) -----------------------
+// alpha [B, nnz] (CSR order; nnz = row_ptr[N]) = s_e / Z_row and beta [B, N] = the self-loop gate, from the operands
+// k_go_attn_fwd forms them from and throws away: same thread -> node map, same transform-then-dot per neighbour, same
+// go_edge_score / go_self_gate, the row sum Z in list order and alpha_e = s_e * rcp(Z) as the forward applies it to the
+// aggregate.  A thread writes s_e into its row's slots and scales them after the walk: one writer per element.  A row
+// longer than GO_COEF_HEAVY entries (no GO term has that many parents; a synthetic hub does) is left to the whole
+// wave behind the per-thread walks: lanes stride the list, Z is a fixed-tree wave sum (so it differs from the
+// forward's in-order sum by rounding for those rows only), every lane scales the slots it wrote.
+#define GO_COEF_HEAVY 64
+template <int FIN, int FOUT>
+__global__ void __launch_bounds__(GO_T)
+k_go_attn_coeffs(int N, const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
+                 const float* __restrict__ x, const float* __restrict__ w_inc, const float* __restrict__ w_s,
+                 const float* __restrict__ a_in, const float* __restrict__ a_s, float* __restrict__ alpha,
+                 float* __restrict__ beta) {
+  AttnW<FIN, FOUT> W;
+  W.load(w_inc, w_s, a_in, a_s);
+  int bx, b;
+  go_block(bx, b);
+  const int n = bx * GO_T + threadIdx.x, lane = threadIdx.x & 63;
+  const bool live = n < N;                                   // (no early return: the wave walks below are collective)
+  const float* xb = x + (int64_t)b * FIN * N;
+  float* ab = alpha + (int64_t)b * row_ptr[N];
+  float p = 0.f;
+  int32_t p0 = 0, p1 = 0;
+  if (live) {
+    float xr[FIN], xin[FOUT], xs[FOUT];
+    load_node<FIN>(xb, N, n, xr);
+    transform<FIN, FOUT>(W.wi, xr, xin);
+    transform<FIN, FOUT>(W.ws, xr, xs);
+    p = dot<FOUT>(W.a1, xin);
+    beta[(int64_t)b * N + n] = go_self_gate(dot<FOUT>(W.as, xs));
+    p0 = row_ptr[n];
+    p1 = row_ptr[n + 1];
+  }
+  const bool heavy = p1 - p0 > GO_COEF_HEAVY;
+  if (!heavy && p1 > p0) {
+    float Z = 0.f;
+    for (int32_t e = p0; e < p1; ++e) {
+      float xm[FIN], xi[FOUT];
+      load_node<FIN>(xb, N, col[e], xm);
+      transform<FIN, FOUT>(W.wi, xm, xi);
+      const float s = go_edge_score(p, dot<FOUT>(W.a2, xi));
+      Z += s;
+      ab[e] = s;
+    }
+    const float zinv = go_rcp(Z);
+    for (int32_t e = p0; e < p1; ++e) ab[e] *= zinv;
+  }
+  unsigned long long hv = __ballot(heavy);
+  while (hv) {
+    const int src = __ffsll((long long)hv) - 1;
+    hv &= hv - 1;
+    const float ph = __shfl(p, src, 64);
+    const int32_t q0 = __shfl(p0, src, 64), q1 = __shfl(p1, src, 64);
+    float z = 0.f;
+    for (int32_t e = q0 + lane; e < q1; e += 64) {
+      float xm[FIN], xi[FOUT];
+      load_node<FIN>(xb, N, col[e], xm);
+      transform<FIN, FOUT>(W.wi, xm, xi);
+      const float s = go_edge_score(ph, dot<FOUT>(W.a2, xi));
+      z += s;
+      ab[e] = s;
+    }
+    const float zinv = go_rcp(wave_sum_all(z));
+    for (int32_t e = q0 + lane; e < q1; e += 64) ab[e] *= zinv;
+  }
+}
+
+extern "C" int igcn_go_attn_coeffs(int B, int N, int fin, int fout, const int32_t* row_ptr, const int32_t* col,
+                                   const float* x, const float* w_inc, const float* w_s, const float* a_in,
+                                   const float* a_s, float* alpha, float* beta, void* stream) {
+  IGCN_REQUIRE(B > 0 && N > 0, "go_attn_coeffs: bad sizes");
+  hipStream_t st = (hipStream_t)stream;
+  dim3 grid((unsigned)igcn_cdiv(N, GO_T), B);
+#define CALL(FI, FO)                                                                                              \
+  hipLaunchKernelGGL((k_go_attn_coeffs<FI, FO>), grid, dim3(GO_T), 0, st, N, row_ptr, col, x, w_inc, w_s, a_in, a_s, \
+                     alpha, beta)
+  GO_DISPATCH(fin, fout, CALL)
+#undef CALL
+  IGCN_CHECK_LAUNCH("go_attn_coeffs");
   return IGCN_OK;
 }
 

@@ -238,3 +238,47 @@ class Gene_ontology_network(nn.Module):
         if zeros3 is None or zeros3.device != dev:
             zeros3 = self._zeros3 = torch.zeros(3, device=dev)
         return latent, x_d, [zeros3], atten_out
+
+    def encoding_relevance(self):
+        """R_0 [54, N] (channel-major: SNPs x GO nodes), shared by all samples: how much of node n's gene encoding
+        (:208-215) comes from SNP s — E[n, s] = sum_c |t_c[k]| at the non-zeros k = (n, s), every node's row scaled to
+        sum 1 (a node without SNPs stays 0).  A few tensor operations, once per roll-out."""
+        csr = self.gene_csr
+        mag = torch.stack([t.detach().abs() for t in self.t]).sum(0).float()
+        e = torch.zeros(csr.n_rows * csr.n_cols, dtype=torch.float32, device=mag.device)
+        if csr.nnz:
+            e[csr.flat_pos.to(mag.device)] = mag
+        e = e.view(csr.n_rows, csr.n_cols)
+        tot = e.sum(1, keepdim=True)
+        return (e / torch.where(tot > 0, tot, torch.ones_like(tot))).t().contiguous()
+
+    def attention_rollout(self, data, T=None, device=None, return_coeffs=False):
+        """Attention roll-out (Abnar & Zuidema) from the top-level GO terms down to the SNPs, per sample: R_top
+        [B, Ntop, 54] (fp32, non-negative, rows summing to at most 1) for the SNP features ``data`` [B, 54].  The gene
+        encoding and the encoder layers (:208-251) run as in ``forward`` — in eval mode under ``torch.no_grad()``: no
+        dropout, no random numbers drawn — and every layer's input also goes through igcn_go_attn_coeffs (its alpha per
+        edge and beta per node, by the forward's arithmetic) and igcn_go_rollout_layer, which mixes the relevance
+        R_l [B, 54, N_l] of the layer's nodes as the layer mixes their features and keeps the pooled nodes; R_0 is
+        ``encoding_relevance()``.  LayerNorm, ReLU and the feature transforms are not part of the roll-out.
+        ``return_coeffs``: also [(alpha_l, beta_l)] per layer.  The network is left as it was (``training``, parameters,
+        buffers, dropout and random state)."""
+        was = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                r = self.encoding_relevance()
+                x = ops.SparseMap.apply(data, self.gene_csr, *self.t)
+                coeffs = []
+                for j in range(self.n_l):
+                    csr = self.enc_csr[j]
+                    par = (self.w_inc[j].weight, self.w_s_loop[j].weight, self.w_att_in[j].weight, self.w_att_s[j].weight)
+                    alpha, beta = ops.go_attention_coeffs(x, *par, csr)
+                    r = ops.go_rollout_layer(r, alpha, beta, csr, self.pool[j])
+                    coeffs.append((alpha, beta))
+                    if j + 1 < self.n_l:
+                        x = ops.GoAttentionLN.apply(x, *par, csr, self.G_B[j].weight, self.G_B[j].bias, None, self.pool[j],
+                                                    self.G_B[j].eps, 1)
+                r_top = r.transpose(1, 2)
+                return (r_top, coeffs) if return_coeffs else r_top
+        finally:
+            self.train(was)

@@ -46,6 +46,10 @@ class Gene_ontology_network(go_model.Gene_ontology_network):
     def predraw_dropout(self, *a, **kw):
         raise NotImplementedError("the GUIDE GO network draws its masks in its forward")
 
+    def attention_rollout(self, *a, **kw):
+        raise NotImplementedError("attention_rollout runs the encoder of go_model.py (LayerNorm + ReLU blocks); the GUIDE "
+                                  "GO network's PReLU blocks are not covered")
+
     def forward(self, data, T=None, device=None, extra_dropout=()):
         """``extra_dropout`` [(shape, p), ...]: dropout sites of the caller drawn by the same launch; their factors are
         left in ``self.extra_masks``."""

@@ -3174,6 +3174,70 @@ def attention_map_accumulate(w, y, sums, counts, state):
     call("igcn_attn_map_accumulate", b, lq, lk, c, ptr(w), ptr(y), ptr(sums), ptr(counts), ptr(state), stream_ptr())
 
 
+def go_attention_coeffs(x, w_inc, w_s, a_in, a_s, csr):
+    """The attention coefficients of one GO encoder layer (go_model.py:226-244), which GoAttention forms and discards:
+    (alpha [B, nnz] in the CSR order of ``csr``, every row's entries summing to 1; beta [B, N], the self-loop gate) from
+    the layer's input x [B, fin, N] and its four parameters (igcn_go_attn_coeffs: the forward's arithmetic).  No autograd."""
+    x, w_inc, w_s, a_in, a_s = (_f32(t.detach()) for t in (x, w_inc, w_s, a_in, a_s))
+    if x.dim() != 3 or w_inc.dim() != 2:
+        raise ValueError(f"go_attention_coeffs: x {tuple(x.shape)} must be [B, fin, N], w_inc {tuple(w_inc.shape)} [fout, fin]")
+    b, fin, n = x.shape
+    fout = w_inc.shape[0]
+    if (n != csr.n_rows or n != csr.n_cols or tuple(w_inc.shape) != (fout, fin) or tuple(w_s.shape) != (fout, fin)
+            or a_in.numel() != 2 * fout or a_s.numel() != fout or b < 1):
+        raise ValueError(f"go_attention_coeffs: x {tuple(x.shape)}, w_inc {tuple(w_inc.shape)}, w_s {tuple(w_s.shape)}, "
+                         f"a_in {tuple(a_in.shape)}, a_s {tuple(a_s.shape)} do not fit a {csr.n_rows} x {csr.n_cols} structure")
+    alpha = torch.empty(b, csr.nnz, dtype=torch.float32, device=x.device)
+    beta = torch.empty(b, n, dtype=torch.float32, device=x.device)
+    call("igcn_go_attn_coeffs", b, n, fin, fout, ptr(csr.row_ptr), ptr(csr.col), ptr(x), ptr(w_inc), ptr(w_s), ptr(a_in),
+         ptr(a_s), ptr(alpha), ptr(beta), stream_ptr())
+    return alpha, beta
+
+
+def go_rollout_layer(r_in, alpha, beta, csr, pool):
+    """One roll-out step through an encoder layer (igcn_go_rollout_layer): relevance r_in — [S, N] shared by all samples
+    (the encoding relevance) or [B, S, N] — mixed by the layer's alpha [B, nnz] and beta [B, N] and pooled to the nodes
+    >= ``pool``: [B, S, N - pool], channel-major like the activations."""
+    b, n = beta.shape if beta.dim() == 2 else (0, 0)
+    shared = r_in.dim() == 2
+    s = r_in.shape[-2] if r_in.dim() in (2, 3) else 0
+    pool = int(pool)
+    if any(t.dtype != torch.float32 for t in (r_in, alpha, beta)):
+        raise TypeError("go_rollout_layer: r_in, alpha and beta must be float32")
+    if (b < 1 or s < 1 or n != csr.n_rows or n != csr.n_cols or tuple(alpha.shape) != (b, csr.nnz) or not 0 <= pool < n
+            or tuple(r_in.shape) != ((s, n) if shared else (b, s, n))):
+        raise ValueError(f"go_rollout_layer: r_in {tuple(r_in.shape)}, alpha {tuple(alpha.shape)}, beta {tuple(beta.shape)}, "
+                         f"pool {pool} do not fit a {csr.n_rows} x {csr.n_cols} structure with {csr.nnz} entries")
+    if not _lib.load().igcn_go_rollout_chunk(n):
+        raise ValueError(f"go_rollout_layer: {n} nodes: one relevance column does not fit the kernel's LDS")
+    r_in, alpha, beta = r_in.contiguous(), alpha.contiguous(), beta.contiguous()
+    out = torch.empty(b, s, n - pool, dtype=torch.float32, device=beta.device)
+    call("igcn_go_rollout_layer", b, n, s, pool, ptr(csr.row_ptr), ptr(csr.col), ptr(alpha), ptr(beta), ptr(r_in),
+         0 if shared else s * n, ptr(out), stream_ptr())
+    return out
+
+
+def snp_association(w, r_top):
+    """assoc[b] = w[b] . r_top[b]: the cross-attention weights w [B, rois, Ntop] times the rolled-out relevance r_top
+    [B, Ntop, S] (any strides: the roll-out's channel-major result transposed, as it comes) -> [B, rois, S].  One launch
+    of the library's exact-fp32 batched product (igcn_gemm_f32_batched, K whole: a fixed summation order)."""
+    if w.dtype != torch.float32 or r_top.dtype != torch.float32:
+        raise TypeError("snp_association: w and r_top must be float32")
+    if w.dim() != 3 or r_top.dim() != 3 or w.shape[0] != r_top.shape[0] or w.shape[2] != r_top.shape[1] or not w.numel() \
+            or not r_top.numel():
+        raise ValueError(f"snp_association: w {tuple(w.shape)} [B, rois, Ntop] and r_top {tuple(r_top.shape)} [B, Ntop, S] "
+                         "do not fit")
+    w = w.detach().contiguous()
+    r_top = r_top.detach()
+    b, rois, n_top = w.shape
+    s = r_top.shape[2]
+    rc = r_top.transpose(1, 2).contiguous()                 # [B, S, Ntop]: no copy for the roll-out's own layout
+    out = torch.empty(b, rois, s, dtype=torch.float32, device=w.device)
+    call("igcn_gemm_f32_batched", rois, s, n_top, b, ptr(w), n_top, 1, rois * n_top, ptr(rc), n_top, 1, s * n_top, ptr(out),
+         rois * s, s, 1, None, stream_ptr())
+    return out
+
+
 # =================================================================================================
 # GUIDE_IMGSNP: BatchNorm + PReLU blocks, the image gate + encoder (csrc/guide.hip); NodesLayerNormPReLU: by NodesLayerNorm
 # =================================================================================================

@@ -360,8 +360,30 @@ class SGCN_GCN_IMGSNP(torch.nn.Module):
         projection (at the forward's projection precision); ops.attention_weights then forms the probabilities the
         attention cores never do.  The model is left as it was: ``training``, parameters, buffers, random state; the
         hand-over to ``loss_probability`` and ``last_edge_prob`` are reset as after an evaluation sweep."""
+        return self._attention_pass("attention_weights", data, temperature, device, isExplain, lambda w, snps_in: w)
+
+    def snp_association(self, data, temperature=None, device=None, isExplain=False):
+        """The ROI x SNP association map of every subject, [B, rois, 54] (fp32, non-negative, rows summing to at most
+        1): ``attention_weights`` — region to top-level GO term — times the attention roll-out of the GO encoder from
+        those terms down to the SNPs (``Gene_ontology_network.attention_rollout``: go_model.py:208-251, the per-sample
+        edge attention and self-importance of both encoder layers and the learnable SNP -> GO encoding).  Same pass, same
+        contract as ``attention_weights`` (eval mode, no_grad, the model left as it was); the product is one launch of
+        the library's exact-fp32 batched GEMM (ops.snp_association)."""
+        return self._snp_association(data, temperature, device, isExplain)[0]
+
+    def _snp_association(self, data, temperature=None, device=None, isExplain=False):
+        """(assoc [B, rois, 54], r_top [B, Ntop, 54]) of one batch: ``snp_association`` with the roll-out it used."""
+        def tail(w, snps_in):
+            r_top = self.go_network.attention_rollout(snps_in, temperature, device)
+            return ops.snp_association(w, r_top), r_top
+        return self._attention_pass("snp_association", data, temperature, device, isExplain, tail)
+
+    def _attention_pass(self, name, data, temperature, device, isExplain, tail):
+        """The pass ``attention_weights`` and ``snp_association`` share: refuse a model without cross-attention, run
+        the image branch, the GO network and the in-projection in eval mode under no_grad, form the weights w, return
+        ``tail(w, snps_in)`` (``snps_in``: the SNP features the GO network saw) and restore the model."""
         if not self.isCrossAtten or self.isImageOnly or self.isSNPsOnly:
-            raise ValueError("attention_weights: the model has no cross-attention (needs isCrossAtten=True, "
+            raise ValueError(f"{name}: the model has no cross-attention (needs isCrossAtten=True, "
                              "isImageOnly=False, isSNPsOnly=False)")
         flags = (bool(isExplain),)
         self._check_config(any(flags))
@@ -379,7 +401,7 @@ class SGCN_GCN_IMGSNP(torch.nn.Module):
                 atten_out = self.go_network(img.snps_in, temperature, device, groups=1, extra_dropout=[])[3]
                 mha = self.multihead_attn
                 q, kv = ops.InProj.apply(batch_x, atten_out, mha.in_proj_weight, mha.in_proj_bias, self.bf16_transforms)
-                return ops.attention_weights(q.contiguous(), kv.contiguous(), mha.num_heads)
+                return tail(ops.attention_weights(q.contiguous(), kv.contiguous(), mha.num_heads), img.snps_in)
         finally:
             self.last_edge_prob, self._handoff = None, _Handoff()     # no later loss_probability is served from this batch
             self.train(was)

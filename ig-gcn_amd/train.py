@@ -1544,6 +1544,52 @@ def attention_maps(model, loader, temperature=None, device=None, isExplain=False
     return {"mean": mean, "count": counts, "overall": overall, "go_rows": go_rows, "top_terms": go_rows[top], "n": n}
 
 
+def association_maps(model, loader, temperature=None, device=None, isExplain=False, num_classes=None, top_k=10):
+    """The ROI x SNP association table of a cohort: ``model.snp_association`` — the cross-attention weights of
+    kernel/sgcn_img_snp.py:240 times the attention roll-out of the GO encoder (go_model.py:208-251) down to the 54
+    SNPs — of every batch of ``loader``, summed per class of ``data.y`` on the device (igcn_attn_map_accumulate with
+    Lk = 54: fp64, sample order) and read once at the end.  Returns a dict: ``mean`` [C, rois, 54] (fp32; zeros for a
+    class without subjects), ``count`` [C] (int64), ``overall`` [rois, 54] (the mean over all subjects), ``go_to_snp``
+    [Ntop, 54] (the cohort mean of the roll-out R_top itself), ``go_rows`` [Ntop] (int64: the GO node behind every row
+    of ``go_to_snp``, as in ``attention_maps``), ``top_snps`` [rois, top_k] (int64: the SNP columns of the ``top_k``
+    largest entries of every row of ``overall``) and ``n`` (subjects).  A label outside [0, C) raises IgcnError after
+    the pass."""
+    from . import ops
+    head = model.lin2_classify if getattr(model, "clusterlabel", False) else model.lin2
+    c = int(num_classes) if num_classes is not None else int(head.weight.shape[0])
+    if c <= 0:
+        raise ValueError(f"association_maps: num_classes={c}")
+    sums = counts = state = go_sums = go_counts = zero_y = None
+    n = 0
+    for data in _batches(loader, device):
+        a, r_top = model._snp_association(data, temperature, device, isExplain)
+        if sums is None:
+            dev = a.device
+            sums = torch.zeros(c, a.shape[1], a.shape[2], dtype=torch.float64, device=dev)
+            go_sums = torch.zeros(1, r_top.shape[1], r_top.shape[2], dtype=torch.float64, device=dev)
+            counts, go_counts = (torch.zeros(k, dtype=torch.int64, device=dev) for k in (c, 1))
+            state = torch.zeros(1, dtype=torch.int64, device=dev)
+        y = data.y.view(-1).to(device=a.device, dtype=torch.int64).contiguous()
+        ops.attention_map_accumulate(a, y, sums, counts, state)
+        if zero_y is None or zero_y.numel() != y.numel():
+            zero_y = torch.zeros_like(y)
+        ops.attention_map_accumulate(r_top.contiguous(), zero_y, go_sums, go_counts, state)
+        n += int(data.num_graphs)
+    if n == 0:
+        raise ValueError("association_maps: the loader is empty")
+    skipped = int(state.item())                                  # the pass's one synchronisation
+    if skipped:
+        raise _lib.IgcnError(f"association_maps: {skipped} of {n} labels lie outside [0, {c})")
+    mean = (sums / counts.clamp(min=1).view(c, 1, 1).double()).float()
+    overall = (sums.sum(0) / float(n)).float()
+    go_to_snp = (go_sums[0] / float(n)).float()
+    n_top, n_nodes = go_to_snp.shape[0], int(model.go_network.n_nodes)
+    go_rows = torch.arange(n_nodes - n_top, n_nodes, dtype=torch.int64, device=overall.device)
+    top = torch.topk(overall, min(int(top_k), overall.shape[1]), dim=1).indices
+    return {"mean": mean, "count": counts, "overall": overall, "go_to_snp": go_to_snp, "go_rows": go_rows,
+            "top_snps": top, "n": n}
+
+
 def output_importance(model):
     """The arrays util/output.py:20-32 writes per fold: node / SNP importance and the edge-mask weights."""
     out = {"node_importance": model.prob.detach().cpu().numpy(),

@@ -31,7 +31,7 @@ extern "C" {
 /* ABI revision: bumped whenever a prototype below changes (argument added, removed or re-ordered).  igcn_version()
  * returns the revision the library was built from; a binding written against a different one must refuse to call
  * (igcn_amd/_lib.py does). */
-#define IGCN_ABI_VERSION 431
+#define IGCN_ABI_VERSION 432
 int igcn_version(void);
 const char* igcn_last_error(void);
 /* A/B switches, set ONCE by the binding when it loads the library (from the IGCN_* environment variables): bit 0 no tiled
@@ -866,6 +866,28 @@ int igcn_spmm_bwd_dval_multi(int n, const int64_t* table, void* stream);
 int igcn_go_attn_fwd(int B, int N, int fin, int fout, const int32_t* row_ptr, const int32_t* col,
                      const float* x, const float* w_inc, const float* w_s, const float* a_in, const float* a_s,
                      float* y, void* stream);
+/* The attention coefficients of that layer as an OUTPUT (go_model.py:226-244: attention_adj :173-180 forms them per
+ * sample and the layer consumes them; igcn_go_attn_fwd keeps them in registers):
+ *   alpha[b,e] = s_e / sum_{e' in row(e)} s_e'   [B,nnz], CSR order, nnz = row_ptr[N]
+ *   beta[b,r]  = sigmoid(a_s.x_s[r])             [B,N]
+ * by the forward's own device functions, thread -> node map and order of operations (the row sum in list order, the
+ * quotient as s_e * rcp(sum)); rows longer than 64 entries are walked by a whole wave (their row sum is a fixed-tree
+ * wave sum).  One writer per element, no atomics, bit-reproducible.  Same (fin,fout) as igcn_go_attn_fwd, any N. */
+int igcn_go_attn_coeffs(int B, int N, int fin, int fout, const int32_t* row_ptr, const int32_t* col,
+                        const float* x, const float* w_inc, const float* w_s, const float* a_in, const float* a_s,
+                        float* alpha, float* beta, void* stream);
+/* One step of the attention roll-out through the pooled hierarchy (go_model.py:219-251: the layer mixes a node with its
+ * list and its self loop, :246-251 keeps nodes >= pool), on relevance kept channel-major like the activations:
+ *   r_out[b,s,r-pool] = (sum_{e in row r} alpha[b,e] r_in[b,s,col_e] + beta[b,r] r_in[b,s,r])
+ *                       / (sum_{e in row r} alpha[b,e] + beta[b,r])            for pool <= r < N
+ * and r_out[b,s,r-pool] = r_in[b,s,r] for a row without a list.  r_in [B,S,N] with r_in_batch_stride elements between
+ * samples (0: one [S,N] table shared by all samples — the encoding relevance of go_model.py:208-215), r_out
+ * [B,S,N-pool].  A workgroup keeps igcn_go_rollout_chunk(N) relevance columns of one sample in LDS (8, 4, 2 or 1:
+ * the most that fit 80 KB; 0 = N above 20 480 nodes, IGCN_ERR_UNSUPPORTED).  One writer per element, no atomics. */
+int igcn_go_rollout_chunk(int N);
+int igcn_go_rollout_layer(int B, int N, int S, int pool, const int32_t* row_ptr, const int32_t* col,
+                          const float* alpha, const float* beta, const float* r_in, int64_t r_in_batch_stride,
+                          float* r_out, void* stream);
 /* Backward in O(nnz*f) (the reference's autograd forms a dense N x N product per sample and layer).
  * t_ptr/t_row: the transposed structure (for each column the rows that read it).
  * Outputs: dx [B,fin,N]; dparams float[ 2*fout*fin + 2*fout + fout ] = (dW_inc, dW_s, da_in, da_s).
