@@ -14,7 +14,7 @@ from . import switches
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libigcn.so")
 
-ABI_VERSION = 432        # include/igcn.h IGCN_ABI_VERSION this table was written against (tests/test_abi.py compares)
+ABI_VERSION = 433        # include/igcn.h IGCN_ABI_VERSION this table was written against (tests/test_abi.py compares)
 
 P, I, L, F, Z = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
 
@@ -36,6 +36,8 @@ SIGNATURES = {
     "igcn_edge_mask_fwd_reg": (I, [L, L, I, I, P, P, P, P, P, P, P, P, P, P, P, P, I, F, F, F, F, F, P, P, I, P, P]),
     "igcn_edge_mask_bwd_reg": (I, [L, L, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, F, F, F, F, F, P, P, P, P, P,
                                    P, I, P, P]),
+    "igcn_edge_dense_map_supported": (I, [I, I]),
+    "igcn_edge_dense_map": (I, [L, I, L, P, P, P, P, P, P, P, P, P]),
     "igcn_gcn_norm_fwd": (I, [L, L, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "igcn_gcn_norm_bwd": (I, [L, L, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "igcn_gcn_propagate_fwd": (I, [L, L, I, I, P, L, P, P, P, P, P, L, I, P]),
@@ -52,6 +54,8 @@ SIGNATURES = {
     "igcn_gat_stack_lds_bytes": (Z, [I, I, I, I, I, I]),
     "igcn_gat_stack_param_floats": (I, [I, I, I]),
     "igcn_gat_stack_fwd": (I, [L, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P]),
+    "igcn_gat_stack_alpha_tile": (I, [I, I, I, I, I]),
+    "igcn_gat_stack_alpha": (I, [L, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P]),
     "igcn_gat_stack_bwd": (I, [L, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "igcn_gat_stack_bwd_ew": (I, [L, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "igcn_sgcn_front_lds_bytes": (Z, [I, I, I, I, I]),

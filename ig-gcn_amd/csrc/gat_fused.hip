@@ -17,6 +17,7 @@
 // owns the stored edges k = tid, tid + 256, ... and adds, layer by layer into its own element of dew,
 //   d ea_k = c_l (dpre_l[k] + dpre_l[Emax + dst_k] / cnt_dst)      (the logit term + the mean-valued virtual loop)
 // with cnt_i = the number of kept (src != dst) edges into i; a stored self-loop gets an exact 0.
+// igcn_gat_stack_alpha hands out what the forward drops: every layer's alpha as dense [R][R] maps (k_gat_stack_alpha).
 //
 // Preconditions (host wrappers / per-graph plan builder): uniform graphs of R nodes (graph g = nodes [gR, (g+1)R), its
 // edges contiguous in stored order); sums run in list order; no atomics: deterministic.
@@ -260,6 +261,76 @@ k_gat_stack_fwd(int R, int Emax, int H0, int L, const float* __restrict__ x_in, 
     reinterpret_cast<float4*>(xcat + nb * D)[e] = reinterpret_cast<const float4*>(gt_lds + o.y)[e];
 }
 
+// The attention coefficients of every layer as dense maps, G [graph][l][source row][target column] (igcn_gat_stack_alpha):
+// the forward above — gt_stage and gt_layer_fwd on the forward's own LDS layout, so alpha is what the forward used — and,
+// after each layer and before the next one overwrites alpha, the layer's [R][R] block built in LDS one tile of TC
+// target columns at a time (behind the layout: one [R][TC] block) and stored with consecutive lanes on consecutive
+// columns.  Column c of a tile is walked by NP = 256 / TC threads, thread (c, part) owning the source rows s with
+// s % NP == part: one writer per element, the stored copies of an edge added in list order, the diagonal set to the
+// added loop's alpha by its owner (stored self-loops are skipped: PyG removes them), zeros stored like everything else.
+static int gt_alpha_tile(int R, int Emax, int H0, int F, int L) {
+  const size_t base = (size_t)gt_layout(R, Emax, H0, F, L, 0).total * 4;
+  for (int tc = 64; tc >= 1; tc >>= 1)
+    if (base + (size_t)R * tc * 4 <= 150 * 1024) return tc;
+  return 0;
+}
+
+template <int F>
+__global__ void __launch_bounds__(GT_T)
+k_gat_stack_alpha(int R, int Emax, int H0, int L, int TC, const float* __restrict__ x_in,
+                  const float* __restrict__ ew_in, const int32_t* __restrict__ src32,
+                  const int32_t* __restrict__ dst32, const int32_t* __restrict__ tgt_ptr,
+                  const int32_t* __restrict__ tgt_perm, GtParams prm, float* __restrict__ G,
+                  int32_t* __restrict__ status) {
+  extern __shared__ float gt_lds[];
+  const GtLayout o = gt_layout(R, Emax, H0, F, L, 0);
+  const int tid = threadIdx.x;
+  const int64_t nb = (int64_t)blockIdx.x * R;
+  float* Gb = G + (int64_t)blockIdx.x * L * R * R;
+  if (gt_stage<false>(gt_lds, o, R, Emax, H0, F, L, nb, x_in, ew_in, src32, dst32, tgt_ptr, tgt_perm, nullptr,
+                      nullptr, prm, status) < 0) {
+    for (int64_t e = tid; e < (int64_t)L * R * R; e += GT_T) Gb[e] = 0.f;      // refused graph: defined output
+    return;
+  }
+  const int32_t* src = lds_i32(gt_lds, o.t.src);
+  const int32_t* tptr = lds_i32(gt_lds, o.t.tptr);
+  const int32_t* tperm = lds_i32(gt_lds, o.t.tperm);
+  const float* alpha = gt_lds + o.alpha;
+  float* tile = gt_lds + o.total;                                               // [R][TC]
+  const int NP = GT_T / TC;
+  const int c = tid / NP, part = tid - c * NP;
+  bool bad = false;
+  for (int l = 0; l < L; ++l) {
+    gt_layer_fwd<F>(gt_lds, o, R, Emax, H0, L, l, gt_lds + o.lgs, gt_lds + o.lgd, gt_lds + o.alpha);
+    float* Gl = Gb + (int64_t)l * R * R;
+    for (int j0 = 0; j0 < R; j0 += TC) {
+      const int w = min(TC, R - j0);
+      for (int e = tid; e < R * TC; e += GT_T) tile[e] = 0.f;
+      __syncthreads();
+      if (c < w) {
+        const int j = j0 + c;
+        for (int p = tptr[j]; p < tptr[j + 1]; ++p) {
+          const int k = tperm[p], s = src[k];
+          if (s == j) continue;
+          if (s < 0 || s >= R) {                                                // the edge leaves its graph
+            bad = true;
+            continue;
+          }
+          if (s % NP == part) tile[s * TC + c] += alpha[k];
+        }
+        if (j % NP == part) tile[j * TC + c] = alpha[Emax + j];
+      }
+      __syncthreads();
+      for (int e = tid; e < R * w; e += GT_T) {
+        const int i = e / w, cc = e - i * w;
+        Gl[(int64_t)i * R + j0 + cc] = tile[i * TC + cc];
+      }
+      __syncthreads();                                                          // (the next tile zeroes it again)
+    }
+  }
+  if (bad && status) atomicOr(status, 1);
+}
+
 template <int F, bool EW>
 __global__ void __launch_bounds__(GT_T)
 k_gat_stack_bwd(int R, int Emax, int H0, int L, const float* __restrict__ x_in, const float* __restrict__ ew_in,
@@ -498,6 +569,50 @@ extern "C" int igcn_gat_stack_fwd(int64_t n_graphs, int R, int max_edges, int H0
   }
 #undef GT_FWD
   IGCN_CHECK_LAUNCH("gat_stack_fwd");
+  return IGCN_OK;
+}
+
+extern "C" int igcn_gat_stack_alpha_tile(int R, int max_edges, int H0, int F, int L) {
+  if (R <= 0 || max_edges < 0 || !(F == 4 || F == 8 || F == 16 || F == 32) || H0 < 1 || H0 > GT_MAXH0 || L < 1 ||
+      L > GT_MAXL)
+    return 0;
+  return gt_alpha_tile(R, max_edges, H0, F, L);
+}
+
+extern "C" int igcn_gat_stack_alpha(int64_t n_graphs, int R, int max_edges, int H0, int F, int L, const float* x_in,
+                                    const float* ew_in, const int32_t* src32, const int32_t* dst32,
+                                    const int32_t* tgt_ptr, const int32_t* tgt_perm, const float* const* params,
+                                    float* G, int32_t* status, void* stream) {
+  int rc = gt_check("gat_stack_alpha", n_graphs, R, max_edges, H0, F, L, 0);
+  if (rc) return rc;
+  const int tc = gt_alpha_tile(R, max_edges, H0, F, L);
+  if (tc == 0) {
+    igcn_set_error("gat_stack_alpha: no column of the [R, R] map fits beside the stack in 150 KB of LDS (R=%d, E<=%d, "
+                   "H0=%d, F=%d, L=%d)", R, max_edges, H0, F, L);
+    return IGCN_ERR_UNSUPPORTED;
+  }
+  IGCN_REQUIRE(x_in && ew_in && src32 && dst32 && tgt_ptr && tgt_perm && params && G, "gat_stack_alpha: null argument");
+  GtParams prm = {};
+  for (int j = 0; j < 6 * L; ++j) {
+    IGCN_REQUIRE(params[j], "gat_stack_alpha: null parameter %d", j);
+    prm.p[j] = params[j];
+  }
+  const size_t lds = igcn_gat_stack_lds_bytes(R, max_edges, H0, F, L, 0) + (size_t)R * tc * 4;
+  hipStream_t st = (hipStream_t)stream;
+#define GT_ALPHA(FV)                                                                                               \
+  {                                                                                                                \
+    if (lds > 64 * 1024) IGCN_ALLOW_BIG_LDS((k_gat_stack_alpha<FV>));                                              \
+    hipLaunchKernelGGL((k_gat_stack_alpha<FV>), dim3((unsigned)n_graphs), dim3(GT_T), lds, st, R, max_edges, H0, L, \
+                       tc, x_in, ew_in, src32, dst32, tgt_ptr, tgt_perm, prm, G, status);                          \
+  }
+  switch (F) {
+    case 4: GT_ALPHA(4) break;
+    case 8: GT_ALPHA(8) break;
+    case 16: GT_ALPHA(16) break;
+    default: GT_ALPHA(32) break;
+  }
+#undef GT_ALPHA
+  IGCN_CHECK_LAUNCH("gat_stack_alpha");
   return IGCN_OK;
 }
 

@@ -90,6 +90,24 @@ def gat_stack(convs, x_in, ew_in, plan_g, rois):
     return _unpad(ops.GatStack.apply(x_in, ew_in, plan_g, rois, *params), f, fp)
 
 
+def gat_attention(model, convs, data, isExplain=False):
+    """The attention coefficients of the GATConv list ``convs`` on a batch, as dense maps [B, L, rois, rois] (fp32; source
+    row, target column; ops.gat_stack_alpha): what PyG returns under ``return_attention_weights=True`` and the reference's
+    forwards (kernel/gcn_img_snp.py:217-221, kernel/sgcn.py:235-267) never ask for.  The plain pass reads ``data.x`` and
+    ``data.edge_attr``; ``isExplain``: ``x * prob`` and ``edge_weight * e`` of ``model.cal_probability``, as the masked
+    forward does.  Under ``torch.no_grad()``; reads the parameters and writes nothing of the model."""
+    x = data.x
+    if x.shape[0] % model.rois:
+        raise ValueError(f"every graph must have exactly rois={model.rois} nodes (got {x.shape[0]} nodes)")
+    with torch.no_grad():
+        plan = ops.plan_for(data)
+        plan.flush_pending_check()
+        x_in, ew_in = x, data.edge_attr
+        if isExplain:
+            x_in, ew_in = model.cal_probability(x, data.edge_index, data.edge_attr, plan=plan)[:2]
+        return ops.gat_stack_alpha(x_in, ew_in, plan, model.rois, *gat_padded_params(convs)[2])
+
+
 class GCN_IMGSNP(SGCN_GCN_IMGSNP):
     # one plain pass per step (train.losses dispatches the five-term loss): no batched (plain | masked) sweep
     batched_passes = False
@@ -129,6 +147,18 @@ class GCN_IMGSNP(SGCN_GCN_IMGSNP):
 
     def forward_pair(self, data, temperature=None, device=None):
         raise NotImplementedError("GCN_IMGSNP runs one plain pass per step (no isExplain pass)")
+
+    def edge_importance(self, data, weighted=False, return_count=False):
+        raise ValueError("edge_importance: GCN_IMGSNP trains no masks (prob_bias takes no gradient and nothing in its "
+                         "forward reads it)")
+
+    def gat_attention(self, data, isExplain=False):
+        """``gat_attention`` (this module) of the one plain pass; needs ``ifUseGAT``."""
+        if isExplain:
+            raise ValueError("GCN_IMGSNP has one plain pass (no masked pass)")
+        if not self.ifUseGAT:
+            return super().gat_attention(data)
+        return gat_attention(self, self._gcn_convs, data)
 
     def _image_route(self, data, plan, flags):
         if flags != (False,):

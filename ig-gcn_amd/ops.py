@@ -3174,6 +3174,78 @@ def attention_map_accumulate(w, y, sums, counts, state):
     call("igcn_attn_map_accumulate", b, lq, lk, c, ptr(w), ptr(y), ptr(sums), ptr(counts), ptr(state), stream_ptr())
 
 
+def edge_dense_map(values, plan, rois, want_count=False):
+    """Per-edge ``values`` [E] (fp32, stored-edge order: cal_probability's ``e``, kernel/sgcn_img_snp.py:133-151, or the
+    weight ``edge_weight * e``) of a batch of uniform ``rois``-node graphs as dense maps [B, rois, rois] — source row,
+    target column, the orientation of the reference's ``data.A`` — on the batch's GraphPlan (igcn_edge_dense_map: one
+    launch writes every element once, zeros included; the stored copies of an edge are added in stored order; no
+    atomics, the same bits every run).  ``want_count``: also the number of stored copies of every edge, (map, cnt).
+    An edge that leaves its graph is not written and flagged in ``plan.status`` (``plan.check()`` raises).  No
+    autograd."""
+    rois = int(rois)
+    if not torch.is_tensor(values) or values.dtype != torch.float32 or values.dim() != 1:
+        raise ValueError("edge_dense_map: values must be a float32 vector [E]")
+    if rois < 1 or plan.n_nodes < rois or plan.n_nodes % rois:
+        raise ValueError(f"edge_dense_map: {plan.n_nodes} nodes are no batch of graphs with rois={rois} nodes each")
+    if values.numel() != plan.n_edges:
+        raise ValueError(f"edge_dense_map: {values.numel()} values for a plan of {plan.n_edges} edges")
+    if not values.is_cuda or values.device != plan.src32.device:
+        raise ValueError("edge_dense_map: values must live on the plan's device")
+    if not _lib.load().igcn_edge_dense_map_supported(rois, int(bool(want_count))):
+        raise ValueError(f"edge_dense_map: rois={rois}: one target column does not fit the kernel's LDS")
+    plan.flush_pending_build()
+    if plan.status is None:                                  # (the general build keeps no status word of its own)
+        plan.status = torch.zeros(2, dtype=torch.int32, device=values.device)
+    values = values.detach().contiguous()
+    b = plan.n_nodes // rois
+    out = torch.empty(b, rois, rois, dtype=torch.float32, device=values.device)
+    cnt = torch.empty_like(out) if want_count else None
+    call("igcn_edge_dense_map", b, rois, plan.n_edges, ptr(values), ptr(plan.src32), ptr(plan.dst32), ptr(plan.tgt_ptr),
+         ptr(plan.tgt_perm), ptr(out), ptr(cnt), ptr(plan.status), stream_ptr())
+    return (out, cnt) if want_count else out
+
+
+def gat_stack_alpha(x_in, ew_in, plan, rois, *params):
+    """The attention coefficients of every GATConv layer of ops.GatStack's forward — PyG's
+    ``return_attention_weights=True``, which kernel/gcn_img_snp.py:217-221 and kernel/sgcn.py:235-267 never ask for — as
+    dense maps G [B, L, rois, rois], source row and target column: the summed alpha of the stored copies of an edge, the
+    added self-loop's alpha on the diagonal, 0 at stored self-loops and elsewhere; every target column sums to 1
+    (igcn_gat_stack_alpha: the forward's own staging and layer functions, one launch).  Arguments of ops.GatStack; no
+    autograd.  Shapes outside the stack raise ValueError."""
+    rois = int(rois)
+    if len(params) < 6 or len(params) % 6:
+        raise ValueError(f"gat_stack_alpha: {len(params)} parameter tensors (six per layer: W, bias, att_src, att_dst, "
+                         "lin_edge, att_edge)")
+    if x_in.dim() != 2 or rois < 1 or x_in.shape[0] % rois or x_in.shape[0] != plan.n_nodes:
+        raise ValueError(f"gat_stack_alpha: x_in {tuple(x_in.shape)} does not fit a plan of {plan.n_nodes} nodes in "
+                         f"graphs of rois={rois}")
+    if ew_in.numel() != plan.n_edges:
+        raise ValueError(f"gat_stack_alpha: {ew_in.numel()} edge attributes for a plan of {plan.n_edges} edges")
+    if not x_in.is_cuda:
+        raise ValueError("gat_stack_alpha: the GATConv layers run on the GPU kernels only (igcn_gat_stack_*)")
+    x_in, ew_in = _f32(x_in.detach()), _f32(ew_in.detach().reshape(-1))
+    params = [_f32(t.detach()) for t in params]
+    n, h0 = x_in.shape
+    f, layers = params[0].shape[0], len(params) // 6
+    for l in range(layers):
+        fin = h0 if l == 0 else f
+        if tuple(params[6 * l].shape) != (f, fin) or any(t.numel() != f for t in params[6 * l + 1:6 * l + 6]):
+            raise ValueError(f"gat_stack_alpha: layer {l}'s parameters do not fit W [{f}, {fin}] and five vectors [{f}]")
+    seg = getattr(plan, "_stack_dims", None)
+    if seg is None or seg[0] != rois:
+        raise ValueError(f"gat_stack_alpha: needs a per-graph plan of uniform graphs with rois={rois} nodes each")
+    if not _lib.load().igcn_gat_stack_alpha_tile(rois, seg[1], h0, f, layers):
+        raise ValueError(f"gat_stack_alpha: needs F in {GAT_WIDTHS}, 1 <= layers <= {GAT_MAX_LAYERS}, 1 <= H0 <= "
+                         f"{GAT_MAX_H0} and a graph that fits {GAT_LDS_BYTES // 1024} KB of LDS beside one map column "
+                         f"(rois={rois}, max edges {seg[1]}, H0={h0}, F={f}, L={layers})")
+    plan.flush_pending_build()
+    g = torch.empty(n // rois, layers, rois, rois, dtype=torch.float32, device=x_in.device)
+    pp = (ctypes.c_void_p * len(params))(*[t.data_ptr() for t in params])
+    call("igcn_gat_stack_alpha", n // rois, rois, seg[1], h0, f, layers, ptr(x_in), ptr(ew_in), ptr(plan.src32),
+         ptr(plan.dst32), ptr(plan.tgt_ptr), ptr(plan.tgt_perm), pp, ptr(g), ptr(plan.status), stream_ptr())
+    return g
+
+
 def go_attention_coeffs(x, w_inc, w_s, a_in, a_s, csr):
     """The attention coefficients of one GO encoder layer (go_model.py:226-244), which GoAttention forms and discards:
     (alpha [B, nnz] in the CSR order of ``csr``, every row's entries summing to 1; beta [B, N], the self-loop gate) from

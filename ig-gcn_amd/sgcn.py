@@ -40,8 +40,8 @@ import torch.nn.functional as F
 from torch.nn import Linear, Parameter, init
 
 from . import ops, switches
-from .gcn_img_snp import ROIS_REF, GATConv, gat_stack
-from .sgcn_img_snp import GCNConv, _grid_width, masked_inputs, sgcn_stack
+from .gcn_img_snp import ROIS_REF, GATConv, gat_attention, gat_stack
+from .sgcn_img_snp import GCNConv, _grid_width, edge_importance, masked_inputs, sgcn_stack
 
 
 class _ImageOnly(torch.nn.Module):
@@ -126,6 +126,13 @@ class _ImageOnly(torch.nn.Module):
         logp = F.log_softmax(ops.linear(f1, self.lin2.weight, self.lin2.bias), dim=-1)
         return [logp[k * bsz:(k + 1) * bsz] for k in range(g)] if g > 1 else [logp]
 
+    def edge_importance(self, data, weighted=False, return_count=False):
+        """``sgcn_img_snp.edge_importance`` of a batch: the dense [B, rois, rois] form of ``cal_probability``'s edge mask."""
+        return edge_importance(self, data, weighted, return_count)
+
+    def gat_attention(self, data, isExplain=False):
+        raise ValueError(f"gat_attention: {self.__class__.__name__} has GCNConv layers (no attention coefficients)")
+
     def _check_stack(self, plan, x, explain_flags):
         pass
 
@@ -157,6 +164,10 @@ class SGCN_GAT(_ImageOnly):
                                    ew_grad=torch.is_grad_enabled() and any(explain_flags))
         if why is not None:
             raise ValueError(f"GAT stack: {why}")
+
+    def gat_attention(self, data, isExplain=False):
+        """``gcn_img_snp.gat_attention`` of the plain or the masked pass: [B, L, rois, rois]."""
+        return gat_attention(self, [self.conv1, *self.convs], data, isExplain)
 
     def _stack(self, x_in, ew_in, plan_g):
         return gat_stack([self.conv1, *self.convs], x_in, ew_in, plan_g, self.rois)

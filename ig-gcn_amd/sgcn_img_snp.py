@@ -119,6 +119,24 @@ def masked_inputs(model, data, plan, flags, stacked, snps_feat=None, aliases=Non
     return x_in, ew_in, snps_in, e
 
 
+def edge_importance(model, data, weighted=False, return_count=False):
+    """The learned connective-importance mask of ``model.cal_probability`` (kernel/sgcn_img_snp.py:133-151; kernel/sgcn.py
+    :198-209,321-332) of every subject as a dense region x region map [B, rois, rois] (fp32) — source row, target column:
+    the orientation of the reference's ``data.A``, so a map overlays it.  ``weighted``: ``edge_weight * e``, the weight the
+    masked pass's convolutions consume, instead of ``e``; ``return_count``: also the number of stored copies of every edge,
+    (map, cnt).  The stored copies of an edge are summed in stored order; 0 where no edge is stored.  Two launches under
+    ``torch.no_grad()`` — the model's own mask launch (igcn_edge_mask_fwd; batches of complete graphs take it too) and
+    ops.edge_dense_map — that read the parameters and write nothing of the model."""
+    x = data.x
+    if x.shape[0] % model.rois:
+        raise ValueError(f"every graph must have exactly rois={model.rois} nodes (got {x.shape[0]} nodes)")
+    with torch.no_grad():
+        plan = ops.plan_for(data)
+        plan.flush_pending_check()
+        _, ewm, _, e = model.cal_probability(x, data.edge_index, data.edge_attr, plan=plan)[:4]
+        return ops.edge_dense_map((ewm if weighted else e).reshape(-1), plan, model.rois, return_count)
+
+
 class _ImageBranch(NamedTuple):
     """What an image route hands the rest of the forward."""
     xcat: torch.Tensor                  # cat_l relu(GCNConv_l(.)) of every pass, [g*n, L*hidden]
@@ -370,6 +388,13 @@ class SGCN_GCN_IMGSNP(torch.nn.Module):
         contract as ``attention_weights`` (eval mode, no_grad, the model left as it was); the product is one launch of
         the library's exact-fp32 batched GEMM (ops.snp_association)."""
         return self._snp_association(data, temperature, device, isExplain)[0]
+
+    def edge_importance(self, data, weighted=False, return_count=False):
+        """``edge_importance`` (this module) of a batch: the dense [B, rois, rois] form of ``cal_probability``'s edge mask."""
+        return edge_importance(self, data, weighted, return_count)
+
+    def gat_attention(self, data, isExplain=False):
+        raise ValueError(f"gat_attention: {self.__class__.__name__} has GCNConv layers (no attention coefficients)")
 
     def _snp_association(self, data, temperature=None, device=None, isExplain=False):
         """(assoc [B, rois, 54], r_top [B, Ntop, 54]) of one batch: ``snp_association`` with the roll-out it used."""

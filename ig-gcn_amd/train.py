@@ -1590,6 +1590,78 @@ def association_maps(model, loader, temperature=None, device=None, isExplain=Fal
             "top_snps": top, "n": n}
 
 
+def connectivity_maps(model, loader, source="mask", weighted=False, isExplain=False, num_classes=None, top_k=10,
+                      symmetric=False, temperature=None, device=None):
+    """The ROI x ROI connectivity table of a cohort — the brain connections the model keeps.  ``source="mask"``:
+    ``model.edge_importance`` (the connective-importance mask of cal_probability, kernel/sgcn_img_snp.py:133-151;
+    ``weighted``: times the edge weight); ``source="gat"``: ``model.gat_attention`` (the per-edge GATConv attention of
+    every layer, kernel/sgcn.py:235-267 / kernel/gcn_img_snp.py:217-221; ``isExplain``: of the masked pass).  Every
+    batch's maps are summed per class of ``data.y`` on the device (igcn_attn_map_accumulate: fp64, sample order; one
+    call per quantity) and read once at the end.  Maps are indexed [source region, target region], like ``data.A``.
+    Returns a dict: ``mean`` [C, R, R] ([C, L, R, R] for "gat"; fp32, zeros for a class without subjects), ``count`` [C]
+    (int64), ``overall`` [R, R] ([L, R, R]: the mean over all subjects), ``strength`` [R] ((row sum + column sum) / 2 of
+    ``overall``; of its layer mean for "gat"), ``top_edges`` [top_k, 2] (int64: the (source, target) pairs of the largest
+    entries of ``overall`` / its layer mean, largest first), ``n`` (subjects) and, for "mask" only, ``present`` [R, R]
+    (the mean number of stored copies of the edge per subject) and ``mean_present`` [R, R] (``overall / present`` where
+    ``present > 0``, else 0: the mean mask over the subjects that store the edge).  ``symmetric``: ``mean``, ``overall``,
+    ``mean_present`` and ``present`` are returned as (M + M^T) / 2 (per layer for "gat"), applied once to the finished
+    tables; ``strength`` and ``top_edges`` are taken from the ``overall`` that is returned.  ``temperature`` is accepted
+    for the signature of the sibling passes (no GO network runs here).  A label outside [0, C) raises IgcnError after the
+    pass."""
+    from . import ops
+    if source not in ("mask", "gat"):
+        raise ValueError(f"connectivity_maps: source={source!r} ('mask' or 'gat')")
+    if num_classes is None:
+        head = (model.lin2_classify if getattr(model, "clusterlabel", False) else
+                model.lin2 if hasattr(model, "lin2") else model.fc3)
+        num_classes = head.weight.shape[0]
+    c = int(num_classes)
+    if c <= 0:
+        raise ValueError(f"connectivity_maps: num_classes={c}")
+    sums = counts = state = cp_sums = cp_counts = zero_y = None
+    n, shape = 0, None
+    for data in _batches(loader, device):
+        if source == "mask":
+            m, cnt = model.edge_importance(data, weighted=weighted, return_count=True)
+        else:
+            m, cnt = model.gat_attention(data, isExplain=isExplain), None
+        if sums is None:
+            dev, shape = m.device, tuple(m.shape[1:])
+            r = shape[-1]
+            sums = torch.zeros(c, m.numel() // (m.shape[0] * r), r, dtype=torch.float64, device=dev)
+            counts = torch.zeros(c, dtype=torch.int64, device=dev)
+            state = torch.zeros(1, dtype=torch.int64, device=dev)
+            if cnt is not None:
+                cp_sums = torch.zeros(1, r, r, dtype=torch.float64, device=dev)
+                cp_counts = torch.zeros(1, dtype=torch.int64, device=dev)
+        y = data.y.view(-1).to(device=m.device, dtype=torch.int64).contiguous()
+        ops.attention_map_accumulate(m.view(m.shape[0], -1, m.shape[-1]), y, sums, counts, state)
+        if cnt is not None:
+            if zero_y is None or zero_y.numel() != y.numel():
+                zero_y = torch.zeros_like(y)
+            ops.attention_map_accumulate(cnt, zero_y, cp_sums, cp_counts, state)
+        n += int(data.num_graphs)
+    if n == 0:
+        raise ValueError("connectivity_maps: the loader is empty")
+    skipped = int(state.item())                                  # the pass's one synchronisation
+    if skipped:
+        raise _lib.IgcnError(f"connectivity_maps: {skipped} of {n} labels lie outside [0, {c})")
+    sym = (lambda t: (t + t.transpose(-1, -2)) / 2) if symmetric else (lambda t: t)
+    mean = sums / counts.clamp(min=1).view(c, 1, 1).double()
+    overall = sums.sum(0) / float(n)
+    out = {"mean": sym(mean.view(c, *shape)).float(), "count": counts, "overall": sym(overall.view(shape)).float(), "n": n}
+    if cp_sums is not None:
+        present = cp_sums[0] / float(n)
+        mean_present = torch.where(present > 0, overall / present.clamp(min=1e-300), torch.zeros_like(overall))
+        out["present"], out["mean_present"] = sym(present).float(), sym(mean_present).float()
+    flat = out["overall"] if len(shape) == 2 else out["overall"].double().mean(0).float()
+    r = flat.shape[-1]
+    out["strength"] = ((flat.double().sum(1) + flat.double().sum(0)) / 2).float()
+    top = torch.topk(flat.reshape(-1), min(int(top_k), r * r)).indices
+    out["top_edges"] = torch.stack((top // r, top % r), dim=1)
+    return out
+
+
 def output_importance(model):
     """The arrays util/output.py:20-32 writes per fold: node / SNP importance and the edge-mask weights."""
     out = {"node_importance": model.prob.detach().cpu().numpy(),

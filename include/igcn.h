@@ -31,7 +31,7 @@ extern "C" {
 /* ABI revision: bumped whenever a prototype below changes (argument added, removed or re-ordered).  igcn_version()
  * returns the revision the library was built from; a binding written against a different one must refuse to call
  * (igcn_amd/_lib.py does). */
-#define IGCN_ABI_VERSION 432
+#define IGCN_ABI_VERSION 433
 int igcn_version(void);
 const char* igcn_last_error(void);
 /* A/B switches, set ONCE by the binding when it loads the library (from the IGCN_* environment variables): bit 0 no tiled
@@ -88,6 +88,21 @@ int igcn_gat_stack_bwd_ew(int64_t n_graphs, int R, int max_edges, int H0, int F,
                           const int32_t* tgt_perm, const int32_t* src_ptr, const int32_t* src_perm,
                           const float* const* params, const float* dxcat, float* dx_in, float* dew, float* dparams,
                           float* scratch, int32_t* status, void* stream);
+/* The coefficients the GATConv layers of that stack form and drop — what PyG hands out under
+ * return_attention_weights=True (kernel/gcn_img_snp.py:217-221 with ifUseGAT, kernel/sgcn.py:235-267 SGCN_GAT.forward)
+ * — as dense region x region maps, source row and target column like the reference's data.A:
+ *   G [n_graphs, L, R, R]: G[g,l,i,j] = the sum over the stored copies of edge (i -> j), i != j, of alpha_l; G[g,l,j,j] =
+ *   alpha_l of target j's added self-loop (stored self-loops contribute exactly 0: PyG removes them; a target without
+ *   incoming edges has 1); 0 elsewhere.  Every target column sums to 1 up to the 1e-16 of the denominator.
+ * Arguments and limits of igcn_gat_stack_fwd, G in place of xcat.  One workgroup per graph runs the forward's own
+ * staging and layer functions on the forward's LDS layout and, after each layer, builds that layer's block one tile
+ * of igcn_gat_stack_alpha_tile(...) target columns at a time in LDS (one [R, tile] block behind the layout, the whole
+ * within 150 KB; 0 = nothing fits: IGCN_ERR_UNSUPPORTED): every element stored exactly once, zeros included, one writer
+ * per element, no atomics, copies added in list order: bit-identical from run to run. */
+int igcn_gat_stack_alpha_tile(int R, int max_edges, int H0, int F, int L);
+int igcn_gat_stack_alpha(int64_t n_graphs, int R, int max_edges, int H0, int F, int L, const float* x_in,
+                         const float* ew_in, const int32_t* src32, const int32_t* dst32, const int32_t* tgt_ptr,
+                         const int32_t* tgt_perm, const float* const* params, float* G, int32_t* status, void* stream);
 int igcn_graph_plan_build(int64_t n_nodes, int64_t n_edges, const int64_t* edge_index /*[2,E]*/,
                           int32_t* src32, int32_t* dst32, int32_t* tgt_ptr, int32_t* tgt_perm,
                           int32_t* src_ptr, int32_t* src_perm, int32_t* loop_edge,
@@ -136,6 +151,23 @@ int igcn_graph_plan_replicate(int64_t n_nodes, int64_t n_edges, int copies,
                               const int32_t* loop_edge,
                               int32_t* o_src32, int32_t* o_dst32, int32_t* o_tgt_ptr, int32_t* o_tgt_perm,
                               int32_t* o_src_ptr, int32_t* o_src_perm, int32_t* o_loop_edge, void* stream);
+
+/* Per-edge values as dense region x region maps — the connective-importance mask e of cal_probability
+ * (kernel/sgcn_img_snp.py:133-151; kernel/sgcn.py:198-209,321-332), or the weight edge_weight * e the convolutions
+ * consume, laid out like the reference's data.A / coo_matrix(A).row, .col (source row, target column) for uniform
+ * graphs of R nodes on the plan arrays (graph g = nodes [gR, (g+1)R)):
+ *   map [n_graphs, R, R]: map[g,i,j] = the sum, in stored order, of values[k] over the stored copies k of edge
+ *   (gR + i -> gR + j); 0 where none is stored.  cnt [n_graphs, R, R] (or NULL): the number of copies, as fp32.
+ * One workgroup per (graph, tile of igcn_edge_dense_map_supported(R, cnt != NULL) target columns) builds the tile in
+ * LDS (<= 64 KB) and stores it once: every element of map / cnt is written exactly once by the launch, zeros included
+ * (no fill in front), one writer per element, no atomics, bit-identical from run to run.  Any per-target degree, ragged
+ * edge counts, graphs without edges.  An edge whose ends lie in different graphs is not written and sets bit 0 of
+ * `status` (device int32, or NULL).  igcn_edge_dense_map_supported = 0 (R above 8192 with counts, 16 384 without):
+ * IGCN_ERR_UNSUPPORTED before anything runs. */
+int igcn_edge_dense_map_supported(int R, int want_count);
+int igcn_edge_dense_map(int64_t n_graphs, int R, int64_t n_edges, const float* values, const int32_t* src32,
+                        const int32_t* dst32, const int32_t* tgt_ptr, const int32_t* tgt_perm, float* map,
+                        float* cnt /*or NULL*/, int32_t* status /*or NULL*/, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Learned regional / connective importance masks — cal_probability, kernel/sgcn_img_snp.py:133-151.
