@@ -14,7 +14,7 @@ from . import switches
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libigcn.so")
 
-ABI_VERSION = 433        # include/igcn.h IGCN_ABI_VERSION this table was written against (tests/test_abi.py compares)
+ABI_VERSION = 434        # include/igcn.h IGCN_ABI_VERSION this table was written against (tests/test_abi.py compares)
 
 P, I, L, F, Z = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
 
@@ -38,6 +38,8 @@ SIGNATURES = {
                                    P, I, P, P]),
     "igcn_edge_dense_map_supported": (I, [I, I]),
     "igcn_edge_dense_map": (I, [L, I, L, P, P, P, P, P, P, P, P, P]),
+    "igcn_saliency_maps": (I, [I, I, I, I, P, P, I, P, I, P, P, P]),
+    "igcn_grad_cam": (I, [I, I, I, P, P, I, P, P, P]),
     "igcn_gcn_norm_fwd": (I, [L, L, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "igcn_gcn_norm_bwd": (I, [L, L, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "igcn_gcn_propagate_fwd": (I, [L, L, I, I, P, L, P, P, P, P, P, L, I, P]),

@@ -1459,23 +1459,29 @@ class SnpsMask(torch.autograd.Function):
             full = out = torch.empty_like(snps)
         call("igcn_snps_mask_fwd", b, s, ptr(snps), ptr(p), ptr(out), ptr(sp), ptr(full[:b]) if stacked else None,
              stream_ptr())
-        ctx.save_for_backward(snps, p)
+        # the SNP batch is data in every train step; only a saliency pass (saliency.py) asks for its gradient
+        ctx.save_for_backward(snps, p, *((sp,) if ctx.needs_input_grad[0] else ()))
         ctx.stacked = stacked
         ctx.set_materialize_grads(False)
         return full, sp
 
     @staticmethod
     def backward(ctx, dout, dsp):
-        snps, p = ctx.saved_tensors
+        snps, p, *sp = ctx.saved_tensors
         if dout is None and dsp is None:
             return None, None, None
         b, s = snps.shape
+        dsnps = None
+        if sp and dout is not None:                 # d snps = (plain half's gradient +) the masked gradient * sigmoid(p)
+            dsnps = _f32(dout[b:] if ctx.stacked else dout) * sp[0].view(1, -1)
+            if ctx.stacked:
+                dsnps = dsnps + dout[:b]
         if dout is not None and ctx.stacked:
             dout = dout[b:]
         dp = torch.empty_like(p)
         call("igcn_snps_mask_bwd", b, s, ptr(snps), ptr(p), ptr(_f32(dout)) if dout is not None else None,
              ptr(_f32(dsp)) if dsp is not None else None, ptr(dp), stream_ptr())
-        return None, dp, None
+        return dsnps, dp, None
 
 
 class HeadInputs(torch.autograd.Function):
@@ -3172,6 +3178,73 @@ def attention_map_accumulate(w, y, sums, counts, state):
         raise ValueError(f"attention_map_accumulate: w {tuple(w.shape)}, y {tuple(y.shape)}, sums {tuple(sums.shape)}, "
                          f"counts {tuple(counts.shape)} do not fit")
     call("igcn_attn_map_accumulate", b, lq, lk, c, ptr(w), ptr(y), ptr(sums), ptr(counts), ptr(state), stream_ptr())
+
+
+SALIENCY_MAX_ROIS, SALIENCY_MAX_ELEMS, SALIENCY_MAX_STEPS = 512, 8192, 4096      # csrc/saliency.hip
+GRAD_CAM_MAX_WIDTH = 160
+
+
+def saliency_maps(x, dx, rois, base=None, normalize=False):
+    """(attr [B, rois, H0], roi [B, rois]) of igcn_saliency_maps: ``attr = (x - base) * mean_m dx[m]`` and
+    ``roi = sum_h |attr|`` for x [B * rois, H0] and the stacked input gradients dx [M, B * rois, H0] of M path points
+    (a single gradient [B * rois, H0] is M = 1: gradient x input).  ``base``: None (zeros), [rois, H0] broadcast over
+    the subjects, or [B * rois, H0].  ``normalize``: every subject divided by its largest ``roi`` (left as it is when
+    that is 0).  One launch, one writer per element, the same bits every run.  The SNP vector [B, 54] is rois = 54,
+    H0 = 1.  No autograd; shapes outside the kernel's bounds raise ValueError."""
+    rois = int(rois)
+    if x.dtype != torch.float32 or dx.dtype != torch.float32 or (base is not None and base.dtype != torch.float32):
+        raise TypeError("saliency_maps: x, dx and base must be float32")
+    x, dx = x.detach().contiguous(), dx.detach().contiguous()
+    if x.dim() != 2 or rois < 1 or x.shape[0] < rois or x.shape[0] % rois:
+        raise ValueError(f"saliency_maps: x {tuple(x.shape)} is no batch of subjects with rois={rois} rows each")
+    if dx.dim() == 2:
+        dx = dx.unsqueeze(0)
+    n, h0 = x.shape
+    if dx.dim() != 3 or tuple(dx.shape[1:]) != (n, h0):
+        raise ValueError(f"saliency_maps: dx {tuple(dx.shape)} is not [M, {n}, {h0}]")
+    m, b = dx.shape[0], n // rois
+    per_subject = 0
+    if base is not None:
+        base = base.detach().contiguous()
+        if tuple(base.shape) not in ((rois, h0), (n, h0)):
+            raise ValueError(f"saliency_maps: base {tuple(base.shape)} is neither [{rois}, {h0}] nor [{n}, {h0}]")
+        # (a single subject: the two forms coincide)
+        per_subject = int(tuple(base.shape) == (n, h0) and b > 1)
+    if rois > SALIENCY_MAX_ROIS or rois * h0 > SALIENCY_MAX_ELEMS or not 1 <= m <= SALIENCY_MAX_STEPS:
+        raise ValueError(f"saliency_maps: rois={rois}, H0={h0}, M={m}: needs rois <= {SALIENCY_MAX_ROIS}, rois * H0 <= "
+                         f"{SALIENCY_MAX_ELEMS} and 1 <= M <= {SALIENCY_MAX_STEPS}")
+    if not x.is_cuda or dx.device != x.device or (base is not None and base.device != x.device):
+        raise ValueError("saliency_maps: x, dx and base must live on one GPU (igcn_saliency_maps)")
+    attr = torch.empty(b, rois, h0, dtype=torch.float32, device=x.device)
+    roi = torch.empty(b, rois, dtype=torch.float32, device=x.device)
+    call("igcn_saliency_maps", b, rois, h0, m, ptr(x), ptr(base), per_subject, ptr(dx), int(bool(normalize)), ptr(attr),
+         ptr(roi), stream_ptr())
+    return attr, roi
+
+
+def grad_cam(acts, grads, rois, normalize=True, return_alpha=False):
+    """The Grad-CAM map [B, rois] of the taps ``acts`` / ``grads`` [B * rois, K] (kernel/sgcn.py:124-126: the pre-ReLU
+    conv3 activations and their gradient): ``relu(sum_k alpha_k acts[:, k])`` with ``alpha = mean_r grads``
+    (igcn_grad_cam: one launch, fixed-order sums).  ``normalize``: every subject divided by its maximum (an all-zero
+    map stays zero).  ``return_alpha``: (cam, alpha [B, K]).  No autograd."""
+    rois = int(rois)
+    if acts.dtype != torch.float32 or grads.dtype != torch.float32:
+        raise TypeError("grad_cam: acts and grads must be float32")
+    acts, grads = acts.detach().contiguous(), grads.detach().contiguous()
+    if acts.dim() != 2 or acts.shape != grads.shape or rois < 1 or acts.shape[0] < rois or acts.shape[0] % rois:
+        raise ValueError(f"grad_cam: acts {tuple(acts.shape)} and grads {tuple(grads.shape)} are no taps of subjects "
+                         f"with rois={rois} rows each")
+    k = acts.shape[1]
+    if rois > SALIENCY_MAX_ROIS or not 1 <= k <= GRAD_CAM_MAX_WIDTH:
+        raise ValueError(f"grad_cam: rois={rois}, K={k}: needs rois <= {SALIENCY_MAX_ROIS} and 1 <= K <= "
+                         f"{GRAD_CAM_MAX_WIDTH}")
+    if not acts.is_cuda or grads.device != acts.device:
+        raise ValueError("grad_cam: acts and grads must live on one GPU (igcn_grad_cam)")
+    b = acts.shape[0] // rois
+    cam = torch.empty(b, rois, dtype=torch.float32, device=acts.device)
+    alpha = torch.empty(b, k, dtype=torch.float32, device=acts.device)
+    call("igcn_grad_cam", b, rois, k, ptr(acts), ptr(grads), int(bool(normalize)), ptr(cam), ptr(alpha), stream_ptr())
+    return (cam, alpha) if return_alpha else cam
 
 
 def edge_dense_map(values, plan, rois, want_count=False):

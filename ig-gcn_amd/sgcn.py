@@ -133,6 +133,28 @@ class _ImageOnly(torch.nn.Module):
     def gat_attention(self, data, isExplain=False):
         raise ValueError(f"gat_attention: {self.__class__.__name__} has GCNConv layers (no attention coefficients)")
 
+    def input_saliency(self, data, temperature=None, device=None, target=None, isExplain=False, inputs="image",
+                       normalize=False):
+        """``SGCN_GCN_IMGSNP.input_saliency`` of an image-only model: gradient x input of the target class's
+        log-probability, a dict of ``attr`` [B, rois, H0], ``roi`` [B, rois] and ``target`` [B]; ``temperature`` and
+        ``device`` are accepted for the sibling's signature, ``inputs`` other than "image" raises ValueError."""
+        from . import saliency
+        return saliency.input_saliency(self, data, temperature, device, target, isExplain, inputs, normalize)
+
+    def integrated_gradients(self, data, temperature=None, device=None, target=None, isExplain=False, inputs="image",
+                             normalize=False, steps=16, baseline=None):
+        """``SGCN_GCN_IMGSNP.integrated_gradients`` of an image-only model (midpoint rule; ``delta`` [B] in the dict)."""
+        from . import saliency
+        return saliency.integrated_gradients(self, data, temperature, device, target, isExplain, inputs, normalize,
+                                             steps, baseline)
+
+    def grad_cam(self, data, target=None, isExplain=False, normalize=True):
+        """The Grad-CAM map [B, rois] of ``SGCN_Ori``'s taps (kernel/sgcn.py:124-126): relu(sum_k alpha_k acts_k) with
+        alpha the node mean of d score / d acts, of an eval-mode pass and the target class's log-probability
+        (igcn_grad_cam).  Every other class raises ValueError: the reference never fills ``final_conv_acts`` there."""
+        from . import saliency
+        return saliency.grad_cam(self, data, target, isExplain, normalize)
+
     def _check_stack(self, plan, x, explain_flags):
         pass
 

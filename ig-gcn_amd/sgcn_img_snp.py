@@ -396,6 +396,36 @@ class SGCN_GCN_IMGSNP(torch.nn.Module):
     def gat_attention(self, data, isExplain=False):
         raise ValueError(f"gat_attention: {self.__class__.__name__} has GCNConv layers (no attention coefficients)")
 
+    def input_saliency(self, data, temperature=None, device=None, target=None, isExplain=False, inputs="image",
+                       normalize=False):
+        """Gradient x input of every subject — which regions, in which imaging modality, drive its class: what
+        ``data.x.requires_grad = True`` (:210-211) is there for.  One eval-mode forward and one backward of the target
+        class's log-probability (first output; a one-hot cotangent serves the whole batch).  Returns a dict: ``attr``
+        [B, rois, H0] = x * d score / d x, ``roi`` [B, rois] = sum_h |attr|, ``target`` [B] (int64) and, with ``inputs``
+        "snps" or "both", ``snps`` [B, 54] = snps_feat * d score / d snps_feat.  ``target``: None (the predicted class,
+        taken on the device), an int, or an int64 tensor [B] (``data.y``).  ``normalize``: every subject divided by its
+        largest ``roi`` (``snps``: by its largest entry's magnitude).  The model is left as it was (``saliency``
+        module); no parameter gradient is formed."""
+        from . import saliency
+        return saliency.input_saliency(self, data, temperature, device, target, isExplain, inputs, normalize)
+
+    def integrated_gradients(self, data, temperature=None, device=None, target=None, isExplain=False, inputs="image",
+                             normalize=False, steps=16, baseline=None):
+        """Integrated gradients by the midpoint rule, alpha_m = (m + 1/2) / steps, from ``baseline`` (None: zeros,
+        [rois, H0] or [B * rois, H0]) to ``data.x``; with ``inputs`` "snps" / "both" the SNP vector moves from zero by
+        the same alpha ("snps": the SNP vector alone — no ``attr`` / ``roi``).  The dict of ``input_saliency`` plus
+        ``delta`` [B] = sum attr (+ sum snps) - (score(x) - score(baseline)), the quadrature gap (of the un-normalised
+        attributions; returned, never gated).  ``target=None`` is the prediction at the unscaled input.  ``steps``
+        forward / backward passes run one after another on the batch's one plan and igcn_saliency_maps reduces their
+        stacked gradients."""
+        from . import saliency
+        return saliency.integrated_gradients(self, data, temperature, device, target, isExplain, inputs, normalize,
+                                             steps, baseline)
+
+    def grad_cam(self, data, target=None, isExplain=False, normalize=True):
+        from . import saliency
+        return saliency.grad_cam(self, data, target, isExplain, normalize)     # (raises: SGCN_Ori's taps only)
+
     def _snp_association(self, data, temperature=None, device=None, isExplain=False):
         """(assoc [B, rois, 54], r_top [B, Ntop, 54]) of one batch: ``snp_association`` with the roll-out it used."""
         def tail(w, snps_in):

@@ -1662,6 +1662,95 @@ def connectivity_maps(model, loader, source="mask", weighted=False, isExplain=Fa
     return out
 
 
+def saliency_maps(model, loader, method="gradxinput", target=None, inputs="image", isExplain=False, steps=16,
+                  baseline=None, normalize=True, num_classes=None, top_k=10, temperature=None, device=None):
+    """The ROI x modality saliency table of a cohort — which regions, in which imaging modality, drive the predicted
+    class.  ``method``: "gradxinput" (``model.input_saliency``), "ig" (``model.integrated_gradients`` with ``steps`` and
+    ``baseline``) or "gradcam" (``SGCN_Ori.grad_cam``).  ``target``: None (every subject's predicted class), "label"
+    (``data.y``) or an int.  Every batch's maps are summed per class of ``data.y`` on the device
+    (igcn_attn_map_accumulate: fp64, sample order; one call per quantity) and read once at the end.  Returns a dict:
+    ``mean`` [C, R, H0] ([C, R] for "gradcam"; fp32, zeros for a class without subjects), ``roi_mean`` [C, R] (the
+    class mean of the per-subject ``roi`` = sum_h |attr|; the map itself for "gradcam"), ``overall`` / ``roi_overall``
+    [R] (the means over all subjects), ``count`` [C] (int64), ``n`` (subjects), ``top_regions`` [top_k] (int64: the
+    regions of the largest ``roi_overall``, largest first); with ``inputs`` "snps" / "both" also ``snps_mean`` [C, 54]
+    and ``top_snps`` [top_k] (by the magnitude of the mean over all subjects); for "ig" ``mean_abs_delta`` (a float:
+    the mean quadrature gap).  "ig" with ``inputs="snps"`` moves the SNP vector alone: the image keys are absent.  A
+    label outside [0, C) raises IgcnError after the pass."""
+    from . import ops
+    if method not in ("gradxinput", "ig", "gradcam"):
+        raise ValueError(f"saliency_maps: method={method!r} ('gradxinput', 'ig' or 'gradcam')")
+    if not (target is None or target == "label" or (isinstance(target, int) and not isinstance(target, bool))):
+        raise ValueError(f"saliency_maps: target={target!r} (None, 'label' or an int)")
+    if method == "gradcam" and inputs != "image":
+        raise ValueError("saliency_maps: 'gradcam' maps the image branch only (inputs='image')")
+    if num_classes is None:
+        head = (model.lin2_classify if getattr(model, "clusterlabel", False) else
+                model.lin2 if hasattr(model, "lin2") else model.fc3)
+        num_classes = head.weight.shape[0]
+    c = int(num_classes)
+    if c <= 0:
+        raise ValueError(f"saliency_maps: num_classes={c}")
+    acc = {}                                                     # quantity -> (sums [C, Lq, Lk], counts [C])
+    state = delta_sum = None
+    n = 0
+
+    def add(name, t, y):
+        if name not in acc:
+            acc[name] = (torch.zeros(c, t.shape[1], t.shape[2], dtype=torch.float64, device=t.device),
+                         torch.zeros(c, dtype=torch.int64, device=t.device))
+        ops.attention_map_accumulate(t.contiguous(), y, *acc[name], state)
+
+    for data in _batches(loader, device):
+        tgt = data.y.view(-1) if isinstance(target, str) else target
+        if method == "gradcam":
+            r = {"roi": model.grad_cam(data, target=tgt, isExplain=isExplain, normalize=normalize)}
+        elif method == "ig":
+            r = model.integrated_gradients(data, temperature, device, target=tgt, isExplain=isExplain, inputs=inputs,
+                                           normalize=normalize, steps=steps, baseline=baseline)
+        else:
+            r = model.input_saliency(data, temperature, device, target=tgt, isExplain=isExplain, inputs=inputs,
+                                     normalize=normalize)
+        dev = r["roi" if "roi" in r else "snps"].device
+        if state is None:
+            state = torch.zeros(1, dtype=torch.int64, device=dev)
+        y = data.y.view(-1).to(device=dev, dtype=torch.int64).contiguous()
+        for name in ("attr", "roi", "snps"):
+            if name in r:
+                t = r[name]
+                add(name, t if t.dim() == 3 else t.unsqueeze(2), y)
+        if "delta" in r:
+            d = r["delta"].double().abs().sum()
+            delta_sum = d if delta_sum is None else delta_sum + d
+        n += int(data.num_graphs)
+    if n == 0:
+        raise ValueError("saliency_maps: the loader is empty")
+    skipped = int(state.item()) // len(acc)                      # the pass's one synchronisation
+    if skipped:
+        raise _lib.IgcnError(f"saliency_maps: {skipped} of {n} labels lie outside [0, {c})")
+
+    def table(name):
+        sums, counts = acc[name]
+        return (sums / counts.clamp(min=1).view(c, 1, 1).double()).float(), (sums.sum(0) / float(n)).float(), counts
+
+    out = {"n": n}
+    if "roi" in acc:
+        roi_mean, roi_overall, out["count"] = table("roi")
+        out.update({"roi_mean": roi_mean[:, :, 0], "roi_overall": roi_overall[:, 0]})
+        if method == "gradcam":                                  # (the map is its own regional summary)
+            out.update({"mean": out["roi_mean"], "overall": out["roi_overall"]})
+        else:
+            out["mean"], out["overall"], _ = table("attr")
+        out["top_regions"] = torch.topk(out["roi_overall"], min(int(top_k), out["roi_overall"].numel())).indices
+    if "snps" in acc:
+        snps_mean, snps_overall, counts = table("snps")
+        out.setdefault("count", counts)
+        out["snps_mean"] = snps_mean[:, :, 0]
+        out["top_snps"] = torch.topk(snps_overall[:, 0].abs(), min(int(top_k), snps_overall.shape[0])).indices
+    if delta_sum is not None:
+        out["mean_abs_delta"] = float(delta_sum) / n
+    return out
+
+
 def output_importance(model):
     """The arrays util/output.py:20-32 writes per fold: node / SNP importance and the edge-mask weights."""
     out = {"node_importance": model.prob.detach().cpu().numpy(),

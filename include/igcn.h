@@ -31,7 +31,7 @@ extern "C" {
 /* ABI revision: bumped whenever a prototype below changes (argument added, removed or re-ordered).  igcn_version()
  * returns the revision the library was built from; a binding written against a different one must refuse to call
  * (igcn_amd/_lib.py does). */
-#define IGCN_ABI_VERSION 433
+#define IGCN_ABI_VERSION 434
 int igcn_version(void);
 const char* igcn_last_error(void);
 /* A/B switches, set ONCE by the binding when it loads the library (from the IGCN_* environment variables): bit 0 no tiled
@@ -168,6 +168,31 @@ int igcn_edge_dense_map_supported(int R, int want_count);
 int igcn_edge_dense_map(int64_t n_graphs, int R, int64_t n_edges, const float* values, const int32_t* src32,
                         const int32_t* dst32, const int32_t* tgt_ptr, const int32_t* tgt_perm, float* map,
                         float* cnt /*or NULL*/, int32_t* status /*or NULL*/, void* stream);
+
+/* ROI x modality saliency maps.  Every reference forward sets data.x.requires_grad = True and keeps self.input
+ * (kernel/sgcn_img_snp.py:210-211, kernel/sgcn.py:113,362, kernel/gcn_img_snp.py) only so that data.x.grad can be read as
+ * an input-gradient saliency, and SGCN_Ori fills the Grad-CAM taps final_conv_acts / final_conv_grads
+ * (kernel/sgcn.py:16-17,72,124-126); the reference forms no map from either.
+ *
+ * igcn_saliency_maps: gradient x input (M = 1, base NULL) and midpoint-rule integrated gradients (M path points).
+ *   x [B R, H0]; base NULL (zeros), [R, H0] broadcast over subjects (base_per_subject = 0) or [B R, H0]
+ *   (base_per_subject = 1); dx [M, B R, H0]: the input gradients of the M path points.
+ *   attr [B, R, H0] = (x - base) * ((1/M) * sum_m dx[m]), m ascending;  roi [B, R] = sum_h |attr|, h ascending.
+ *   norm = 1: a subject's attr and roi are divided by that subject's largest roi; a subject whose largest roi is 0 is
+ *   left as it is.  The SNP vector is R = 54, H0 = 1.
+ * igcn_grad_cam: acts, grads [B R, K] (the pre-ReLU conv3 activations and their gradient);
+ *   alpha [B, K] = (1/R) sum_r grads[b,r,k];  cam [B, R] = max(0, sum_k alpha[b,k] acts[b,r,k]);
+ *   norm = 1: cam divided by the subject's maximum; a subject whose maximum is 0 stays at zero.
+ * Both: one workgroup per subject, fixed-order reductions, no atomics, every output element stored exactly once (zeros
+ * included), bit-identical from run to run.  LDS: igcn_saliency_maps holds the subject's attr tile and roi, 34 KB static
+ * — R <= 512, R * H0 <= 8192, M <= 4096; igcn_grad_cam holds alpha, its partial sums and the R cam values, 4 KB static,
+ * and streams acts and grads from global memory once each (no tile is staged, nothing re-read) — R <= 512, K <= 160.
+ * IGCN_ERR_UNSUPPORTED outside these bounds, before anything runs; nothing is truncated.  Per-class cohort sums:
+ * igcn_attn_map_accumulate with Lq = R, Lk = H0 (or 1). */
+int igcn_saliency_maps(int B, int R, int H0, int M, const float* x, const float* base /*or NULL*/, int base_per_subject,
+                       const float* dx, int norm, float* attr, float* roi, void* stream);
+int igcn_grad_cam(int B, int R, int K, const float* acts, const float* grads, int norm, float* cam, float* alpha,
+                  void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Learned regional / connective importance masks — cal_probability, kernel/sgcn_img_snp.py:133-151.
