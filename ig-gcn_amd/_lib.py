@@ -14,7 +14,7 @@ from . import switches
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libigcn.so")
 
-ABI_VERSION = 434        # include/igcn.h IGCN_ABI_VERSION this table was written against (tests/test_abi.py compares)
+ABI_VERSION = 435       # include/igcn.h IGCN_ABI_VERSION this table was written against (tests/test_abi.py compares)
 
 P, I, L, F, Z = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
 
@@ -118,6 +118,8 @@ SIGNATURES = {
     "igcn_node_linear_bn_scratch_floats": (Z, [I, I, I]),
     "igcn_node_linear_bn_supported": (I, [I, I]),
     "igcn_node_linear_bn_fwd": (I, [I, I, I, I, I, P, P, P, P, P, P, I, F, F, P, P, P, P, P, P]),
+    "igcn_node_linear_bn_apply_map_ok": (I, [I, I, I, I, L]),
+    "igcn_node_linear_bn_apply_map_fwd": (I, [I, I, I, I, P, P, P, P, P, P, I, F, F, P, P, P, P, P, I, L, P, P, P, L, P, P]),
     "igcn_node_linear_bn_bwd_scratch_floats": (Z, [I, I, I, I, I]),
     "igcn_node_linear_bn_bwd": (I, [I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "igcn_node_linear_bn_pair_supported": (I, [I, I, I]),

@@ -6,6 +6,7 @@
 // Replaces per call: a permute copy, a K=5 rocBLAS GEMM, ~6 BatchNorm kernels, a clamp, and in the backward the
 // K = B*N weight-gradient GEMMs that rocBLAS runs at ~190 us each.
 #include "common.h"
+#include "spmm_long.h"
 #include <type_traits>
 
 #define RO_T 256
@@ -182,6 +183,18 @@ k_nlbn_finalize(int B, int N, int groups, int cpg, int training, float eps, floa
 }
 
 // ---- forward pass 3: normalise + ReLU, write [B,N,D] ---------------------------------------------
+// scale and shift of a node's normalisation, and the kept ReLU output of one pre-activation: spelled once for the
+// apply pass and for the launch that stages the D == 1 read-out for the gene decoding (k_nlbn_apply_map)
+struct RoAffine { float sc, sh; };
+__device__ __forceinline__ RoAffine ro_affine(float rstd, float gamma, float beta, float mean) {
+  RoAffine a;
+  a.sc = rstd * gamma;
+  a.sh = beta - mean * a.sc;
+  return a;
+}
+__device__ __forceinline__ float ro_apply_kept(float pre, const RoAffine a, float kp) {
+  return fmaxf(pre * a.sc + a.sh, 0.f) * kp;
+}
 template <int F, int D>
 __device__ __forceinline__ void
 nlbn_apply_body(const RoBlk rb, int B, int N, int groups, const float* __restrict__ x, const float* __restrict__ W,
@@ -194,7 +207,8 @@ nlbn_apply_body(const RoBlk rb, int B, int N, int groups, const float* __restric
   if (n >= N) return;
   const RoChunk ch = ro_chunk(B, groups, rb);
   const int b0 = ch.b0, b1 = ch.b1;
-  const float sc = rstd[(int64_t)ch.g * N + n] * gamma[n], sh = beta[n] - mean[(int64_t)ch.g * N + n] * sc;
+  const RoAffine af = ro_affine(rstd[(int64_t)ch.g * N + n], gamma[n], beta[n], mean[(int64_t)ch.g * N + n]);
+  const float sc = af.sc, sh = af.sh;
   for (int b = b0 + sg; b < b1; b += RO_SG) {
     float xv[F], pre[D];
 #pragma unroll
@@ -214,7 +228,7 @@ nlbn_apply_body(const RoBlk rb, int B, int N, int groups, const float* __restric
     } else {
       const float kp = keep ? keep[(int64_t)b * N + n] : 1.f;          // fused dropout of the read-out (D == 1)
 #pragma unroll
-      for (int d = 0; d < D; ++d) o[d] = fmaxf(pre[d] * sc + sh, 0.f) * kp;
+      for (int d = 0; d < D; ++d) o[d] = ro_apply_kept(pre[d], af, kp);
     }
   }
 }
@@ -969,6 +983,73 @@ extern "C" int igcn_node_linear_bn_fwd(int B, int F, int N, int D, int groups, c
   RO_DISPATCH(F, D, CALL)
 #undef CALL
   IGCN_CHECK_LAUNCH("node_linear_bn_fwd");
+  return IGCN_OK;
+}
+
+// ---- the D == 1 read-out in front of the gene decoding: apply pass + map forward as one launch ----
+// k_spmm_long_lds (sum_c == 0, C == 1) loads out_d[b, :] into LDS; k_nlbn_apply<F, 1> wrote that row one launch
+// earlier, element-wise from x[b, :, n] and five per-node vectors.  Here the workgroup of sample b computes the row
+// (ro_affine / ro_apply_kept: the apply pass's expression), stores it to LDS and to out_d (both backward passes read
+// it), and walks the lists (spmm_long_walk: the map kernel's sums).
+template <int F>
+__global__ void __launch_bounds__(SPMM_LT, 4)
+k_nlbn_apply_map(int B, int N, int groups, const float* __restrict__ x, const float* __restrict__ W,
+                 const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ mean,
+                 const float* __restrict__ rstd, const float* __restrict__ keep /*[B,N] or NULL*/,
+                 float* __restrict__ out_d, int n_out, int64_t vs, const int32_t* __restrict__ row_ptr,
+                 const int32_t* __restrict__ col, const float* __restrict__ val, float* __restrict__ y) {
+  extern __shared__ float ro_vec[];                    // [N]
+  const float* __restrict__ w = W;
+  const int b = blockIdx.x, g = b / (B / groups);
+  for (int n = threadIdx.x; n < N; n += SPMM_LT) {
+    const RoAffine af = ro_affine(rstd[(int64_t)g * N + n], gamma[n], beta[n], mean[(int64_t)g * N + n]);
+    float xv[F], pre[1];
+#pragma unroll
+    for (int c = 0; c < F; ++c) xv[c] = x[((int64_t)b * F + c) * N + n];
+    ro_pre<F, 1>(w, xv, pre);
+    const float kp = keep ? keep[(int64_t)b * N + n] : 1.f;
+    const float v = ro_apply_kept(pre[0], af, kp);
+    ro_vec[n] = v;
+    out_d[(int64_t)b * N + n] = v;
+  }
+  __syncthreads();
+  spmm_long_walk(ro_vec, b, 1, N, n_out, vs, 0, row_ptr, col, (const int32_t*)nullptr, val, y);
+}
+
+// host only: the fused launch covers this read-out (F inputs, D outputs per node, N nodes) in front of a one-channel
+// map with J rows and nnz non-zeros: the kernel is built for it, the row fits 64 KB of LDS, and igcn_spmm_fwd would
+// walk the rows with k_spmm_long_lds (the same sums).  0 under IGCN_OPT_NO_MAP_FUSED / IGCN_OPT_SPMM_NO_LDS.
+extern "C" int igcn_node_linear_bn_apply_map_ok(int F, int D, int N, int J, int64_t nnz) {
+  if (igcn_opt(IGCN_OPT_NO_MAP_FUSED) || igcn_opt(IGCN_OPT_SPMM_NO_LDS)) return 0;
+  return F == 2 && D == 1 && N > 0 && J > 0 && (size_t)N * sizeof(float) <= 64 * 1024 && nnz > (int64_t)8 * J;
+}
+
+// igcn_node_linear_bn_fwd (D == 1: out [B,N]) followed by igcn_spmm_fwd_strided(B, 1, J, N, nnz, ..., out, y): the
+// statistics and finalize launches as there, then ONE launch for the apply pass and the map.  y [B,1,J].
+extern "C" int igcn_node_linear_bn_apply_map_fwd(int B, int F, int N, int groups, const float* x, const float* W,
+                                                 const float* gamma, const float* beta, float* running_mean,
+                                                 float* running_var, int training, float momentum, float eps,
+                                                 const float* keep, float* out, float* save_mean, float* save_rstd,
+                                                 float* scratch, int J, int64_t nnz, const int32_t* row_ptr,
+                                                 const int32_t* col, const float* val, int64_t val_stride, float* y,
+                                                 void* stream) {
+  IGCN_REQUIRE(B > 0 && N > 0 && groups >= 1 && groups <= RO_FIN_MAXG && B % groups == 0,
+               "node_linear_bn_apply_map_fwd: bad sizes (1 <= groups <= 8, B divisible by groups)");
+  IGCN_REQUIRE(!training || B / groups > 1, "node_linear_bn_apply_map_fwd: need more than one value per node and group to train");
+  IGCN_REQUIRE(val_stride >= nnz, "node_linear_bn_apply_map_fwd: val_stride < nnz");
+  if (!igcn_node_linear_bn_apply_map_ok(F, 1, N, J, nnz)) {
+    igcn_set_error("node_linear_bn_apply_map_fwd: shape not covered (igcn_node_linear_bn_apply_map_ok)");
+    return IGCN_ERR_UNSUPPORTED;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int cpg = ro_cpg(B, groups);
+  dim3 grid((unsigned)igcn_cdiv(N, RO_NL), groups * cpg);
+  if (training) hipLaunchKernelGGL((k_nlbn_stats<2, 1>), grid, dim3(RO_T), 0, st, B, N, groups, x, W, scratch);
+  hipLaunchKernelGGL((k_nlbn_finalize<2, 1>), dim3((unsigned)igcn_cdiv(N, 64)), dim3(256), 0, st, B, N, groups, cpg,
+                     training, eps, momentum, x, W, scratch, running_mean, running_var, save_mean, save_rstd);
+  hipLaunchKernelGGL((k_nlbn_apply_map<2>), dim3(B), dim3(SPMM_LT), (size_t)N * sizeof(float), st, B, N, groups, x, W,
+                     gamma, beta, save_mean, save_rstd, keep, out, J, val_stride, row_ptr, col, val, y);
+  IGCN_CHECK_LAUNCH("node_linear_bn_apply_map_fwd");
   return IGCN_OK;
 }
 

@@ -144,12 +144,16 @@ class Gene_ontology_network(nn.Module):
     def _drop(self, x, p):
         return F.dropout(x, p, True) if (self.training and self._dropout_enabled) else x
 
-    def _node_linear_bn(self, x, weight, bn, groups=1, keep=None):
-        """dropout(relu(bn(linear(x)))) with bn = BatchNorm1d(#nodes): one fused op (igcn_node_linear_bn_*)."""
+    def _node_linear_bn(self, x, weight, bn, groups=1, keep=None, rider=None):
+        """dropout(relu(bn(linear(x)))) with bn = BatchNorm1d(#nodes): one fused op (igcn_node_linear_bn_*).
+        ``rider``: the map that consumes the output (ops.NodeLinearBN)."""
         if self.training and bn.track_running_stats:
             self._tracked.append(bn.num_batches_tracked)
+        if rider is None:
+            return ops.NodeLinearBN.apply(x, weight, bn.weight, bn.bias, bn.running_mean, bn.running_var,
+                                          self.training, bn.momentum, bn.eps, groups, keep)
         return ops.NodeLinearBN.apply(x, weight, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                                      self.training, bn.momentum, bn.eps, groups, keep)
+                                      self.training, bn.momentum, bn.eps, groups, keep, rider)
 
     def _bn_relu(self, x, bn, groups=1, keep=None):
         """dropout(relu(bn(x))) for the latent MLP's BatchNorm1d layers (igcn_bn1d_*)."""
@@ -226,7 +230,13 @@ class Gene_ontology_network(nn.Module):
             x = ops.GoDecodeLN.apply(x, self.w_out[j].weight, self.w_s_loop_out[j].weight, csr, self.G_B_D[j].weight,
                                      self.G_B_D[j].bias, keeps[self.n_l + j], self.G_B_D[j].eps)
         # gene decoding (:278-282)
-        out_d = self._node_linear_bn(x, self.conc_D.weight, self.B_D[0], groups, masks["out_d"]).squeeze(2)   # [B,N]
+        # on the CSR route (from 256 samples up) the read-out's apply pass runs inside the map's forward launch
+        rider = (self.gene_t_csr, self.t_D[0]) \
+            if ops.node_linear_bn_map_supported(x, self.conc_D.weight, self.gene_t_csr, self.t_D[0]) else None
+        out_d3 = self._node_linear_bn(x, self.conc_D.weight, self.B_D[0], groups, masks["out_d"], rider)
+        out_d = out_d3.squeeze(2)                                                                # [B,N]
+        if rider is not None:
+            out_d._igcn_map_fwd = rider + (out_d3._igcn_map_y,)
         x_d = ops.SparseMap.apply(out_d, self.gene_t_csr, self.t_D[0]).squeeze(1)               # [B, 54]
         # latent projection (:138-146,285)
         h = self._lin_bn_relu(inp_out.view(bsz, -1), self.latent[0], self.latent[1], groups, masks["h"])

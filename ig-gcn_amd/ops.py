@@ -1894,6 +1894,13 @@ class SparseMap(torch.autograd.Function):
             y = gemm_nt(x, t.view(c * csr.n_rows, csr.n_cols)).view(b, c, csr.n_rows)
             ctx.save_for_backward(x, val)
             return y
+        # ``x._igcn_map_fwd = (csr, value vector, y)`` (set by the producer of x): y = this map of x is already there — the
+        # launch that computed x staged it in LDS and walked the lists on its way (NodeLinearBN's ``rider``)
+        pre = getattr(x, "_igcn_map_fwd", None)
+        if (pre is not None and pre[0] is csr and len(vals) == 1 and pre[1] is vals[0] and not stacked
+                and tuple(pre[2].shape) == (b, 1, csr.n_rows)):
+            ctx.save_for_backward(x, val)
+            return pre[2]
         y = torch.empty(b, c, csr.n_rows, dtype=torch.float32, device=x.device)
         if ctx.vstride is not None:
             call("igcn_spmm_fwd_strided", b, c, csr.n_rows, csr.n_cols, csr.nnz, ptr(csr.row_ptr), ptr(csr.col), ptr(val),
@@ -2279,8 +2286,14 @@ class NodeLinearBN(torch.autograd.Function):
     ``groups``: consecutive sample groups with independent batch statistics (passes batched into one launch)."""
 
     @staticmethod
-    def forward(ctx, x, weight, gamma, beta, running_mean, running_var, training, momentum, eps, groups=1, keep=None):
-        """``keep`` [B,N] (D == 1 only): dropout factors of the output, applied inside the kernels."""
+    def forward(ctx, x, weight, gamma, beta, running_mean, running_var, training, momentum, eps, groups=1, keep=None,
+                rider=None):
+        """``keep`` [B,N] (D == 1 only): dropout factors of the output, applied inside the kernels.
+        ``rider`` = (csr, val [nnz]) (D == 1, ``node_linear_bn_map_supported``): the one-channel map SparseMap(out[..., 0],
+        csr, val) that consumes the output.  The apply pass then runs inside the map's forward launch
+        (igcn_node_linear_bn_apply_map_fwd: the workgroup of a sample computes its row into LDS and walks the lists) and
+        the map's output [B,1,J] is left in ``out._igcn_map_y`` for the caller to hand to SparseMap
+        (``x._igcn_map_fwd``); both ops keep their own backward."""
         x, weight, gamma, beta = _f32(x), _f32(weight), _f32(gamma), _f32(beta)
         keep = _f32(keep) if keep is not None else None
         b, f, n = x.shape
@@ -2292,9 +2305,18 @@ class NodeLinearBN(torch.autograd.Function):
         rstd = torch.empty(groups, n, dtype=torch.float32, device=dev)
         scratch = torch.empty(int(lib.igcn_node_linear_bn_scratch_floats(b, n, groups)), dtype=torch.float32,
                               device=dev)
-        call("igcn_node_linear_bn_fwd", b, f, n, d, groups, ptr(x), ptr(weight), ptr(gamma), ptr(beta),
-             ptr(running_mean), ptr(running_var), int(training), float(momentum), float(eps), ptr(keep), ptr(out),
-             ptr(mean), ptr(rstd), ptr(scratch), stream_ptr())
+        if rider is not None:
+            csr, val = rider
+            y = torch.empty(b, 1, csr.n_rows, dtype=torch.float32, device=dev)
+            call("igcn_node_linear_bn_apply_map_fwd", b, f, n, groups, ptr(x), ptr(weight), ptr(gamma), ptr(beta),
+                 ptr(running_mean), ptr(running_var), int(training), float(momentum), float(eps), ptr(keep), ptr(out),
+                 ptr(mean), ptr(rstd), ptr(scratch), csr.n_rows, csr.nnz, ptr(csr.row_ptr), ptr(csr.col), ptr(_f32(val)),
+                 csr.nnz, ptr(y), stream_ptr())
+            out._igcn_map_y = y
+        else:
+            call("igcn_node_linear_bn_fwd", b, f, n, d, groups, ptr(x), ptr(weight), ptr(gamma), ptr(beta),
+                 ptr(running_mean), ptr(running_var), int(training), float(momentum), float(eps), ptr(keep), ptr(out),
+                 ptr(mean), ptr(rstd), ptr(scratch), stream_ptr())
         ctx.save_for_backward(x, weight, gamma, beta, mean, rstd, keep)
         ctx.training, ctx.groups = int(training), groups
         ctx.final = _leaves(weight, gamma, beta)
@@ -2316,7 +2338,19 @@ class NodeLinearBN(torch.autograd.Function):
             call("igcn_node_linear_bn_bwd", b, f, n, d, ctx.groups, ctx.training, ptr(x), ptr(weight), ptr(gamma),
                  ptr(beta), ptr(mean), ptr(rstd), ptr(dout), ptr(keep), ptr(dx), ptr(dw), ptr(dgb), ptr(scratch),
                  stream_ptr())
-        return dx, dw, dgb[0], dgb[1], None, None, None, None, None, None, None
+        return dx, dw, dgb[0], dgb[1], None, None, None, None, None, None, None, None
+
+
+def node_linear_bn_map_supported(x, weight, csr, val):
+    """The D == 1 read-out of ``x`` [B,F,N] can carry the one-channel map behind it as NodeLinearBN's ``rider``: the map
+    takes the CSR route at this batch size and the library covers the shape (igcn_node_linear_bn_apply_map_ok)."""
+    if not (x.is_cuda and x.dim() == 3 and val.is_cuda and val.dim() == 1 and val.dtype == torch.float32
+            and val.is_contiguous() and val.numel() == csr.nnz and csr.n_cols == x.shape[2]):
+        return False
+    if SparseMap._use_dense(x.shape[0], 1, csr):
+        return False
+    return bool(_lib.load().igcn_node_linear_bn_apply_map_ok(int(x.shape[1]), int(weight.shape[0]), int(x.shape[2]),
+                                                             csr.n_rows, csr.nnz))
 
 
 def node_linear_bn_supported(f, d):

@@ -47,6 +47,7 @@ LIBRARY = (
     ("IGCN_ATTN_FP32_CORE", "bf16 feature transforms: keep the fp32 attention core instead of the bf16-operand one"),
     ("IGCN_ATTN_BWD_TWICE", "exact-fp32 attention backward: the two-orientation kernel instead of the shared-tile one"),
     ("IGCN_ATTN_EXACT_FP32", "attention core, head_dim 16: the exact-fp32 MFMA kernels instead of the split-bf16 ones"),
+    ("IGCN_NO_MAP_FUSED", "gene decoding: the read-out's apply pass and the map forward as two launches, not one"),
 )
 
 # integer knobs handed to igcn_configure: sweep parameters of tools/gemm_sweep.py, exempt from the switch tests (they

@@ -31,12 +31,12 @@ extern "C" {
 /* ABI revision: bumped whenever a prototype below changes (argument added, removed or re-ordered).  igcn_version()
  * returns the revision the library was built from; a binding written against a different one must refuse to call
  * (igcn_amd/_lib.py does). */
-#define IGCN_ABI_VERSION 434
+#define IGCN_ABI_VERSION 435
 int igcn_version(void);
 const char* igcn_last_error(void);
 /* A/B switches, set ONCE by the binding when it loads the library (from the IGCN_* environment variables): bit 0 no tiled
  * list walks, 1 no LDS-staged dense aggregation, 2 untiled CSR map kernels, 3 global-memory GO attention backward, 4 print
- * deferred reductions, 5 fp32 attention core under bf16 transforms; gemm_bn_cap > 0 caps the GEMM tile width, attn_chunk_rows > 0 the rows per LDS chunk of the streamed
+ * deferred reductions, 5 fp32 attention core under bf16 transforms, 8 gene read-out apply pass and gene decoding as two launches; gemm_bn_cap > 0 caps the GEMM tile width, attn_chunk_rows > 0 the rows per LDS chunk of the streamed
  * attention kernels (sweeps).  No launch path reads the environment. */
 int igcn_configure(unsigned options, int gemm_bn_cap, int attn_chunk_rows);
 
@@ -687,6 +687,20 @@ int igcn_node_linear_bn_fwd(int B, int F, int N, int D, int groups, const float*
                             const float* keep /*[B,N] dropout factors of the output, D == 1 only; NULL = none*/,
                             float* out, float* save_mean /*[groups,N]*/, float* save_rstd /*[groups,N]*/,
                             float* scratch, void* stream);
+/* The D == 1 read-out in front of the gene decoding (go_model.py:278-282) with its map: igcn_node_linear_bn_fwd (out
+ * [B,N]) followed by igcn_spmm_fwd_strided(B, 1, J, N, nnz, row_ptr, col, val, val_stride, out, y) with the apply pass
+ * and the map forward as ONE launch — the workgroup of a sample computes its row of `out` into LDS (and stores it: both
+ * backward passes read it) and walks the J lists there.  Same expressions and sums as the two calls: out, y [B,1,J],
+ * the saved and the running statistics are theirs bit for bit.  igcn_node_linear_bn_apply_map_ok: covered (F = 2, D = 1,
+ * the row fits 64 KB of LDS, the map's rows are long lists; 0 under option bit 8, IGCN_NO_MAP_FUSED) — anything else:
+ * IGCN_ERR_UNSUPPORTED.  Backward: igcn_node_linear_bn_bwd and igcn_spmm_bwd as for the two calls. */
+int igcn_node_linear_bn_apply_map_ok(int F, int D, int N, int J, int64_t nnz);
+int igcn_node_linear_bn_apply_map_fwd(int B, int F, int N, int groups, const float* x, const float* W,
+                                      const float* gamma, const float* beta, float* running_mean, float* running_var,
+                                      int training, float momentum, float eps, const float* keep, float* out,
+                                      float* save_mean, float* save_rstd, float* scratch, int J, int64_t nnz,
+                                      const int32_t* row_ptr, const int32_t* col, const float* val, int64_t val_stride,
+                                      float* y, void* stream);
 /* Outputs dx [B,F,N], dW [D,F], dgb [2,N] = (dgamma, dbeta).  dW = sum_{b,n} dpre[b,n,:] (x) x[b,:,n] is formed in
  * registers when D*F <= 16 or the rows are 16-byte quads handled by the row-coalesced kernels (D = 16, 32, 64..160: one
  * [D,F] partial per workgroup, summed in order), else on the MFMA batched-sum GEMM.
