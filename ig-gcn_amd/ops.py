@@ -3531,3 +3531,83 @@ class GuideGate(torch.autograd.Function):
         dbias = dpar[o:o + 2 * k].view(k, 2)
         da = dpar[o + 2 * k:o + 2 * k + 1].view_as(slope)
         return dimg, dbias, dw1, da, dw2, None, None, None, None, None
+
+
+# =================================================================================================
+# Per-fold KNN imputation of the clinical scores (csrc/knn_impute.hip); the fold logic lives in impute.py
+# =================================================================================================
+def _knn_rows(rows, x, what):
+    if rows is None:
+        return None, int(x.shape[0])
+    if not torch.is_tensor(rows) or rows.dtype != torch.int64 or rows.dim() != 1 or rows.device != x.device:
+        raise ValueError(f"knn_impute: {what} must be an int64 vector on the matrix's device")
+    return rows.contiguous(), int(rows.numel())
+
+
+def _knn_matrix(x):
+    if not torch.is_tensor(x) or x.dim() != 2:
+        raise ValueError("knn_impute: the matrix must be [S, F]")
+    if not x.is_cuda:
+        raise ValueError("knn_impute: the matrix must live on the GPU (igcn_knn_impute)")
+    return _f32(x.detach())
+
+
+def knn_impute_stats(x, rows_fit=None):
+    """Per column of x [S, F] (NaN = missing) over the training rows ``rows_fit`` (int64, None = all): (counts [F] int64
+    of observed values, means [F] of them; igcn_knn_impute_stats).  Every count is -1 when a row index lies outside x."""
+    x = _knn_matrix(x)
+    rows_fit, n_fit = _knn_rows(rows_fit, x, "rows_fit")
+    f = x.shape[1]
+    counts = torch.empty(f, dtype=torch.int64, device=x.device)
+    means = torch.empty(f, dtype=torch.float32, device=x.device)
+    call("igcn_knn_impute_stats", int(x.shape[0]), f, ptr(x), ptr(rows_fit), n_fit, ptr(counts), ptr(means), stream_ptr())
+    return counts, means
+
+
+def knn_impute(x, means, k, rows_fit=None, rows_q=None, scale=None, shift=None, select=None, into=None, want_full=True,
+               want_donors=False):
+    """sklearn's ``KNNImputer(n_neighbors=k)`` transform (uniform weights, nan_euclidean) of the receivers ``rows_q`` of
+    x [S, F] from the training rows ``rows_fit`` (int64 vectors, None = all rows) with the column means of
+    ``knn_impute_stats`` (igcn_knn_impute: ties to the lower training position, ordered fp32 mean, the same bits every
+    run).  ``select`` (int32 [n_sel]): also ``imputed[:, select] * scale[select] + shift[select]`` (scale / shift [F] or
+    None) — a new [n_q, n_sel] tensor, or with ``into`` [S, n_sel] written to the rows ``rows_q`` of it in place.
+    Returns (full [n_q, F] or None, selected or None, donors [n_q, F, k] int32 or None, status): status is the int64
+    device count of entries filled by the column mean (negative: that many receiver indices lie outside x)."""
+    x = _knn_matrix(x)
+    rows_fit, n_fit = _knn_rows(rows_fit, x, "rows_fit")
+    rows_q, n_q = _knn_rows(rows_q, x, "rows_q")
+    s, f = int(x.shape[0]), int(x.shape[1])
+    k = int(k)
+    dev = x.device
+
+    def vec(t, what):
+        if t is None:
+            return None
+        t = _f32(t.detach())
+        if t.numel() != f or t.device != dev:
+            raise ValueError(f"knn_impute: {what} must hold one float per column on the matrix's device")
+        return t
+    means, scale, shift = vec(means, "means"), vec(scale, "scale"), vec(shift, "shift")
+    sel_out, n_sel, scatter = None, 0, 0
+    if select is not None:
+        if select.dtype != torch.int32 or select.dim() != 1 or select.device != dev or not select.numel():
+            raise ValueError("knn_impute: select must be a non-empty int32 vector on the matrix's device")
+        select = select.contiguous()
+        n_sel = int(select.numel())
+        if into is not None:
+            if (into.dtype != torch.float32 or not into.is_contiguous() or into.device != dev
+                    or into.numel() != s * n_sel or into.shape[0] != s):
+                raise ValueError(f"knn_impute: the destination must be a contiguous float32 [{s}, {n_sel}] on the "
+                                 f"matrix's device, got {tuple(into.shape)}")
+            sel_out, scatter = into, 1
+        else:
+            sel_out = torch.empty(n_q, n_sel, dtype=torch.float32, device=dev)
+    elif into is not None:
+        raise ValueError("knn_impute: a destination without selected columns")
+    full = torch.empty(n_q, f, dtype=torch.float32, device=dev) if want_full else None
+    donors = torch.empty(n_q, f, max(k, 0), dtype=torch.int32, device=dev) if want_donors else None
+    status = torch.empty(1, dtype=torch.int64, device=dev)
+    scratch = torch.empty(int(_lib.load().igcn_knn_impute_scratch_floats(n_q, n_fit)), dtype=torch.float32, device=dev)
+    call("igcn_knn_impute", s, f, k, ptr(x), ptr(rows_fit), n_fit, ptr(rows_q), n_q, ptr(means), ptr(scale), ptr(shift),
+         ptr(select), n_sel, scatter, ptr(full), ptr(sel_out), ptr(donors), ptr(status), ptr(scratch), stream_ptr())
+    return full, sel_out, donors, status

@@ -31,7 +31,7 @@ extern "C" {
 /* ABI revision: bumped whenever a prototype below changes (argument added, removed or re-ordered).  igcn_version()
  * returns the revision the library was built from; a binding written against a different one must refuse to call
  * (igcn_amd/_lib.py does). */
-#define IGCN_ABI_VERSION 435
+#define IGCN_ABI_VERSION 436
 int igcn_version(void);
 const char* igcn_last_error(void);
 /* A/B switches, set ONCE by the binding when it loads the library (from the IGCN_* environment variables): bit 0 no tiled
@@ -1348,6 +1348,39 @@ int igcn_guide_gate_bwd(int B, int K, int H, int L, int training, const float* i
                         const float* bias, const float* tau, float tau_value, const float* dimp1, const float* W1,
                         const float* slope, const float* keep, const float* W2, const float* dlatent, float* dimg,
                         float* dparams, float* scratch, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Per-fold KNN imputation of the clinical scores (csrc/knn_impute.hip): util/tool.py:44-47 and :90-92
+ * (KNNImputer(n_neighbors=k).fit_transform(train), .transform(val / test): sklearn's weights="uniform",
+ * metric="nan_euclidean", NaN = not measured), :48-50 / :93-94 (scaler4score.transform as x * scale + shift) and :51-72 /
+ * :95-110 (the [:, select_index] columns overwrite every subject's clini_score).
+ * X [S, F] fp32 holds the demographics; rows_fit [n_fit] / rows_q [n_q] int64 name the training rows and the receivers
+ * (NULL: all S rows in order), so a fold reads a resident dataset through its index vectors.  1 <= F <= 32, 1 <= k <= 32,
+ * n_fit >= 1, n_q >= 0.
+ * dist(q, t) = sqrt(sum over the columns P observed in both of (q_c - t_c)^2 / |P| * F), undefined for empty P.  A missing
+ * entry (q, c) = the mean of column c over the min(k, #candidates) nearest candidates (training rows that observe c and
+ * have a defined distance to q), ordered by (distance, position in rows_fit): equal distances go to the lower position,
+ * the donors' values are added in that order in fp32 and divided once.  No candidate: means[c].  Observed entries pass
+ * through bit-identical.  Exact fp32, no atomics, one writer per element.
+ * igcn_knn_impute_stats: counts [F] int64 = observed training values per column (a column with 0 cannot be imputed: the
+ * caller refuses it), means [F] = their mean (fp64 sum in a fixed order, rounded once).
+ * igcn_knn_impute: any of the outputs may be NULL —
+ *   out_full [n_q, F]    the imputed rows, unscaled;
+ *   out_sel              imputed[:, sel[j]] * scale[sel[j]] + shift[sel[j]], j < n_sel (sel int32; scale / shift [F] or
+ *                        NULL = 1 / 0): [n_q, n_sel] dense (scatter = 0), or row rows_q[i] of an [S, n_sel] destination
+ *                        (scatter = 1: clini_score written in place, other rows untouched; rows_q must not repeat);
+ *   donors [n_q, F, k]   int32 positions in rows_fit in selection order, -1 for unused slots and observed entries;
+ *   status [1] int64     the number of entries filled by means[c] (required).
+ * A row index outside [0, S) is never dereferenced: the row counts as all-missing, a scattered row is not written, and
+ * it is reported — every count = -1 (stats), status = minus the number of such receivers (impute).
+ * scratch: igcn_knn_impute_scratch_floats(n_q, n_fit). */
+int igcn_knn_impute_stats(int64_t S, int F, const float* X, const int64_t* rows_fit, int64_t n_fit, int64_t* counts,
+                          float* means, void* stream);
+size_t igcn_knn_impute_scratch_floats(int64_t n_q, int64_t n_fit);
+int igcn_knn_impute(int64_t S, int F, int k, const float* X, const int64_t* rows_fit, int64_t n_fit,
+                    const int64_t* rows_q, int64_t n_q, const float* means, const float* scale, const float* shift,
+                    const int32_t* sel, int n_sel, int scatter, float* out_full, float* out_sel, int32_t* donors,
+                    int64_t* status, float* scratch, void* stream);
 
 #ifdef __cplusplus
 }
