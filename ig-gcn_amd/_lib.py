@@ -14,7 +14,7 @@ from . import switches
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libigcn.so")
 
-ABI_VERSION = 436       # include/igcn.h IGCN_ABI_VERSION this table was written against (tests/test_abi.py compares)
+ABI_VERSION = 437      # include/igcn.h IGCN_ABI_VERSION this table was written against (tests/test_abi.py compares)
 
 P, I, L, F, Z = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
 
@@ -134,6 +134,8 @@ SIGNATURES = {
     "igcn_bn1d_fwd_supported": (I, [I, I]),
     "igcn_bn1d_fwd_slabs": (I, [I, I, I, P, I, P, P, P, P, P, I, F, F, I, P, P, P, P, P]),
     "igcn_gemm_effective_split": (I, [L, I]),
+    "igcn_gemm_plan": (I, [I, L, L, L, P, L, L, P, L, L, L, I, I, I, P]),
+    "igcn_gemm_group_plan": (I, [I, P, P]),
     "igcn_dropout_state_words": (I, []),
     "igcn_dropout_max_segments": (I, []),
     "igcn_dropout_masks": (I, [L, I, P, P, P, P, I, P, L, P]),

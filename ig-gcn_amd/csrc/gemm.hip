@@ -491,23 +491,26 @@ static void launch_f32_t(dim3 grid, hipStream_t st, const GemmArgs& g) {
                      g.N, g.K, g.A, g.sam, g.sak, g.B, g.sbn, g.sbk, g.bias, g.C, g.ldc, g.act, g.kps, g.slab, g.a_zs,
                      g.b_zs, g.zsplit);
 }
+// (the leaf = the five numbers of the launch plan, gemm_plan below: nothing is decided here)
 template <int BN, int VW, int PF>
-static void launch_f32_l(dim3 grid, hipStream_t st, const GemmArgs& g) {
-  const bool arf = (g.sam == 1 && g.sak != 1), brf = (g.sbn == 1 && g.sbk != 1);
+static void launch_f32_l(bool arf, bool brf, dim3 grid, hipStream_t st, const GemmArgs& g) {
   if (arf) { if (brf) launch_f32_t<BN, VW, PF, true, true>(grid, st, g); else launch_f32_t<BN, VW, PF, true, false>(grid, st, g); }
   else     { if (brf) launch_f32_t<BN, VW, PF, false, true>(grid, st, g); else launch_f32_t<BN, VW, PF, false, false>(grid, st, g); }
 }
 template <int BN, int VW>
-static void launch_f32_p(dim3 grid, hipStream_t st, const GemmArgs& g) {
-  const int64_t span = g.kps < g.K ? g.kps : g.K;
-  if (igcn_cdiv(span, G_BK) <= 2) launch_f32_l<BN, VW, 1>(grid, st, g); else launch_f32_l<BN, VW, 2>(grid, st, g);
+static void launch_f32_p(int pf, bool arf, bool brf, dim3 grid, hipStream_t st, const GemmArgs& g) {
+  if (pf == 1) launch_f32_l<BN, VW, 1>(arf, brf, grid, st, g); else launch_f32_l<BN, VW, 2>(arf, brf, grid, st, g);
 }
 template <int BN>
-static void launch_f32_v(int vw, dim3 grid, hipStream_t st, const GemmArgs& g) {
-  if (vw == 4) launch_f32_p<BN, 4>(grid, st, g); else if (vw == 2) launch_f32_p<BN, 2>(grid, st, g); else launch_f32_p<BN, 1>(grid, st, g);
+static void launch_f32_v(int vw, int pf, bool arf, bool brf, dim3 grid, hipStream_t st, const GemmArgs& g) {
+  if (vw == 4) launch_f32_p<BN, 4>(pf, arf, brf, grid, st, g);
+  else if (vw == 2) launch_f32_p<BN, 2>(pf, arf, brf, grid, st, g);
+  else launch_f32_p<BN, 1>(pf, arf, brf, grid, st, g);
 }
-static void launch_f32(int bn, int vw, dim3 grid, hipStream_t st, const GemmArgs& g) {
-  if (bn == 16) launch_f32_v<16>(vw, grid, st, g); else if (bn == 32) launch_f32_v<32>(vw, grid, st, g); else launch_f32_v<64>(vw, grid, st, g);
+static void launch_f32(int bn, int vw, int pf, bool arf, bool brf, dim3 grid, hipStream_t st, const GemmArgs& g) {
+  if (bn == 16) launch_f32_v<16>(vw, pf, arf, brf, grid, st, g);
+  else if (bn == 32) launch_f32_v<32>(vw, pf, arf, brf, grid, st, g);
+  else launch_f32_v<64>(vw, pf, arf, brf, grid, st, g);
 }
 
 // sum over the split_k slabs of one output element, in slab order, eight loads in flight per batch.  [`#pragma unroll 8`
@@ -587,19 +590,88 @@ extern "C" int igcn_gemm_f32_split_k(int64_t M, int64_t N, int64_t K) {
   return (int)(sk < 1 ? 1 : sk);
 }
 
-// the slab sum behind a split product: deferred to the backward's flush (parameter gradients), a block-per-output tree
-// (few outputs, many slabs), or the plain column walk with bias / activation
-static int gemm_sum_slabs(int split_k, bool final_grad, int64_t M, int64_t N, float* scratch, const float* bias,
-                          float* C, int64_t ldc, int act, hipStream_t st) {
-  if (split_k <= 1) return IGCN_OK;
-  if (final_grad && ldc == N && bias == nullptr && act == 0 && M * N < ((int64_t)1 << 31))
-    return igcn_launch_reduce_rows_final(scratch, split_k, M * N, (int)(M * N), C, st);
-  if (ldc == N && M * N <= 4096 && split_k > 32 && bias == nullptr && act == 0)
-    return igcn_launch_reduce_rows(scratch, split_k, M * N, (int)(M * N), C, 0, st);   // block-per-output tree
-  hipLaunchKernelGGL(k_gemm_splitk_reduce, dim3((unsigned)igcn_cdiv(M * N, 256)), dim3(256), 0, st, M, N, split_k,
-                     scratch, bias, C, ldc, act, (int64_t)0);
-  IGCN_CHECK_LAUNCH("gemm_splitk_reduce");
-  return IGCN_OK;
+// the K slices a product asked to split `split_k` ways really runs in: whole 32-deep steps per slice (*kps), no more
+// slices than K has steps
+static int gemm_split(int64_t K, int split_k, int64_t* kps_out) {
+  if (split_k < 1) split_k = 1;
+  if (split_k > K / G_BK) split_k = (int)(K / G_BK > 0 ? K / G_BK : 1);
+  int64_t kps = igcn_cdiv(igcn_cdiv(K, split_k), G_BK) * G_BK;
+  if (kps == 0) kps = G_BK;
+  *kps_out = kps;
+  return (int)igcn_cdiv(K > 0 ? K : 1, kps);
+}
+
+// ---- the launch plan: EVERY host-side decision of a product, taken in one place ------------------------------------
+// Which entry point asks (they differ in how K is sliced, in the tile-width rule and in the slab sums they own):
+enum { GEMM_SINGLE = 0, GEMM_MEMBER = 1, GEMM_BATCHED = 2, GEMM_BATCHED_SUM = 3 };
+// The slab sum that follows the product launch (sum_form of igcn_gemm_plan, include/igcn.h).  A group member whose own
+// form is GEMM_SUM_WALK and that is no parameter gradient shares k_gemm_splitk_reduce_multi with its like.
+enum { GEMM_SUM_NONE = 0, GEMM_SUM_WALK = 1, GEMM_SUM_TREE = 2, GEMM_SUM_FINAL = 3, GEMM_SUM_LEFT = 4 };
+struct GemmPlan {
+  int bn, vw, pf;            // template parameters of the instantiation
+  bool arf, brf;             // operand layouts: the row axis is the contiguous one
+  int split;                 // K slices per product (gridDim.z = batch * split)
+  int64_t kps;               // K elements per slice (a multiple of G_BK)
+  int sum_form;
+};
+
+// `act` carries the 0x100 / 0x200 flags; `batch`, `a_batch`, `b_batch` only matter to the batched entry points
+// (GEMM_BATCHED_SUM ignores `split_k`: it slices K by its own rule).  Reads the low address bits of A and B, nothing
+// behind them.
+static GemmPlan gemm_plan(int entry, int64_t M, int64_t N, int64_t K, const float* A, int64_t sam, int64_t sak,
+                          const float* B, int64_t sbn, int64_t sbk, int64_t ldc, bool has_bias, int act, int split_k,
+                          int batch, int64_t a_batch, int64_t b_batch) {
+  GemmPlan p;
+  const bool final_grad = (act & 0x100) != 0, leave_slabs = (act & 0x200) != 0;
+  act &= 0xff;
+  if (entry == GEMM_BATCHED_SUM) {
+    // long K per product: also slice K so that ~2k workgroups are in flight (slabs = batch * ksplit)
+    int ksplit = 1;
+    while (ksplit < 16 && (int64_t)batch * ksplit * 2 <= 2048 && K / (ksplit * 2) >= 128) ksplit *= 2;
+    p.kps = igcn_cdiv(igcn_cdiv(K, ksplit), G_BK) * G_BK;
+    p.split = (int)igcn_cdiv(K, p.kps);
+    p.bn = N <= 16 ? 16 : (N <= 32 ? 32 : 64);
+  } else {
+    p.split = gemm_split(K, split_k, &p.kps);
+    p.bn = gemm_tile_n(M, N);
+    if (entry == GEMM_SINGLE && g_igcn_gemm_bn_cap > 0 && g_igcn_gemm_bn_cap < p.bn)
+      p.bn = g_igcn_gemm_bn_cap;                                                            // sweeps only (igcn_configure)
+  }
+  p.vw = min_int(vec_width(A, sam, sak, M, K), vec_width(B, sbn, sbk, N, K));
+  if (entry == GEMM_BATCHED || entry == GEMM_BATCHED_SUM)
+    while (p.vw > 1 && (a_batch % p.vw != 0 || b_batch % p.vw != 0)) p.vw >>= 1;
+  p.pf = igcn_cdiv(p.kps < K ? p.kps : K, G_BK) <= 2 ? 1 : 2;
+  p.arf = (sam == 1 && sak != 1);
+  p.brf = (sbn == 1 && sbk != 1);
+  // the slab sum: deferred to the backward's flush (parameter gradients), a block-per-output tree (few outputs, many
+  // slabs), or the plain column walk with bias / activation
+  const int slabs = entry == GEMM_BATCHED_SUM ? batch * p.split : p.split;
+  const bool plain = ldc == N && !has_bias && act == 0;
+  if (entry == GEMM_BATCHED_SUM) p.sum_form = plain && M * N <= 4096 && slabs > 32 ? GEMM_SUM_TREE : GEMM_SUM_WALK;
+  else if (p.split <= 1) p.sum_form = GEMM_SUM_NONE;
+  else if (leave_slabs && entry == GEMM_SINGLE) p.sum_form = GEMM_SUM_LEFT;
+  else if (final_grad && entry != GEMM_BATCHED && plain && M * N < ((int64_t)1 << 31)) p.sum_form = GEMM_SUM_FINAL;
+  else if (plain && M * N <= 4096 && slabs > 32) p.sum_form = GEMM_SUM_TREE;
+  else p.sum_form = GEMM_SUM_WALK;
+  return p;
+}
+
+static int gemm_sum_slabs(const GemmPlan& p, int64_t M, int64_t N, float* scratch, const float* bias, float* C,
+                          int64_t ldc, int act, hipStream_t st) {
+  switch (p.sum_form) {
+    case GEMM_SUM_NONE:
+    case GEMM_SUM_LEFT:
+      return IGCN_OK;
+    case GEMM_SUM_FINAL:
+      return igcn_launch_reduce_rows_final(scratch, p.split, M * N, (int)(M * N), C, st);
+    case GEMM_SUM_TREE:
+      return igcn_launch_reduce_rows(scratch, p.split, M * N, (int)(M * N), C, 0, st);
+    default:
+      hipLaunchKernelGGL(k_gemm_splitk_reduce, dim3((unsigned)igcn_cdiv(M * N, 256)), dim3(256), 0, st, M, N, p.split,
+                         scratch, bias, C, ldc, act & 0xff, (int64_t)0);
+      IGCN_CHECK_LAUNCH("gemm_splitk_reduce");
+      return IGCN_OK;
+  }
 }
 
 static int gemm_launch(bool bf16, int64_t M, int64_t N, int64_t K, const float* A, int64_t sam, int64_t sak,
@@ -615,18 +687,16 @@ static int gemm_launch(bool bf16, int64_t M, int64_t N, int64_t K, const float* 
   IGCN_REQUIRE(!leave_slabs || (bias == nullptr && act == 0 && !final_grad && ldc == N),
                "%s: act | 0x200 (leave the slabs) takes no bias / activation / deferral and a dense C", nm);
   hipStream_t st = (hipStream_t)stream;
-  if (split_k > K / G_BK) split_k = (int)(K / G_BK > 0 ? K / G_BK : 1);
-  int64_t kps = igcn_cdiv(igcn_cdiv(K, split_k), G_BK) * G_BK;
-  if (kps == 0) kps = G_BK;
-  split_k = (int)igcn_cdiv(K > 0 ? K : 1, kps);
+  const GemmPlan pl = gemm_plan(GEMM_SINGLE, M, N, K, A, sam, sak, B, sbn, sbk, ldc, bias != nullptr,
+                                act | (final_grad ? 0x100 : 0) | (leave_slabs ? 0x200 : 0), split_k, 1, 0, 0);
+  split_k = pl.split;
+  const int64_t kps = pl.kps;
   const bool split = split_k > 1;
   float* out = split ? scratch : C;
   const int64_t ld = split ? N : ldc;
   const int64_t slab = split ? M * N : 0;
-  int bn = gemm_tile_n(M, N);
-  if (g_igcn_gemm_bn_cap > 0 && g_igcn_gemm_bn_cap < bn) bn = g_igcn_gemm_bn_cap;         // sweeps only (igcn_configure)
+  const int bn = pl.bn, vw = pl.vw;
   dim3 grid((unsigned)igcn_cdiv(M, G_BM), (unsigned)igcn_cdiv(N, bn), (unsigned)split_k);
-  const int vw = min_int(vec_width(A, sam, sak, M, K), vec_width(B, sbn, sbk, N, K));
   if (bf16) {
 #define LAUNCH_G(BNV, VECV)                                                                                        \
   hipLaunchKernelGGL((k_gemm_bf16<BNV, VECV>), grid, dim3(256), gemm_bf16_lds_bytes(BNV, kps), st, M, N, K, A, sam,  \
@@ -641,21 +711,31 @@ static int gemm_launch(bool bf16, int64_t M, int64_t N, int64_t K, const float* 
 #undef LAUNCH_G
   } else {
     const GemmArgs g = {M, N, K, A, sam, sak, B, sbn, sbk, bias, out, ld, act, kps, slab, 0, 0, split_k};
-    launch_f32(bn, vw, grid, st, g);
+    launch_f32(bn, vw, pl.pf, pl.arf, pl.brf, grid, st, g);
   }
   IGCN_CHECK_LAUNCH(nm);
-  if (leave_slabs) return IGCN_OK;                // igcn_gemm_effective_split(K, split_k) slabs in scratch (1: C is final)
-  return gemm_sum_slabs(split_k, final_grad, M, N, scratch, bias, C, ldc, act, st);
+  // GEMM_SUM_LEFT: igcn_gemm_effective_split(K, split_k) slabs stay in scratch (an effective split of 1: C is final)
+  return gemm_sum_slabs(pl, M, N, scratch, bias, C, ldc, act, st);
 }
 
 // the number of K-slices a product asked to split `split_k` ways really runs in (whole 32-deep steps per slice): what a
 // caller that sums the slabs itself (act | 0x200) has to read
 extern "C" int igcn_gemm_effective_split(int64_t K, int split_k) {
-  if (split_k < 1) split_k = 1;
-  if (split_k > K / G_BK) split_k = (int)(K / G_BK > 0 ? K / G_BK : 1);
-  int64_t kps = igcn_cdiv(igcn_cdiv(K, split_k), G_BK) * G_BK;
-  if (kps == 0) kps = G_BK;
-  return (int)igcn_cdiv(K > 0 ? K : 1, kps);
+  int64_t kps;
+  return gemm_split(K, split_k, &kps);
+}
+
+// The launch plan of igcn_gemm_f32 (bf16 == 0) / igcn_gemm_bf16 for these arguments.  Host only: A and B are never
+// dereferenced.
+extern "C" int igcn_gemm_plan(int bf16, int64_t M, int64_t N, int64_t K, const float* A, int64_t sam, int64_t sak,
+                              const float* B, int64_t sbn, int64_t sbk, int64_t ldc, int has_bias, int act, int split_k,
+                              int64_t* out) {
+  IGCN_REQUIRE(M > 0 && N > 0 && K >= 0 && split_k >= 1 && out != nullptr, "gemm_plan: bad sizes M=%lld N=%lld K=%lld split=%d",
+               (long long)M, (long long)N, (long long)K, split_k);
+  const GemmPlan p = gemm_plan(GEMM_SINGLE, M, N, K, A, sam, sak, B, sbn, sbk, ldc, has_bias != 0, act, split_k, 1, 0, 0);
+  out[0] = p.bn; out[1] = p.vw; out[2] = bf16 ? 0 : p.pf;                  // (k_gemm_bf16 has no pipeline depth)
+  out[3] = p.arf; out[4] = p.brf; out[5] = p.split; out[6] = p.kps; out[7] = p.sum_form;
+  return IGCN_OK;
 }
 
 extern "C" int igcn_gemm_f32(int64_t M, int64_t N, int64_t K, const float* A, int64_t sam, int64_t sak,
@@ -689,22 +769,16 @@ int igcn_gemm_f32_batched_sum_impl(int64_t M, int64_t N, int64_t K, int batch, c
                                    int64_t b_batch, float* C, int64_t ldc, float* scratch, hipStream_t st) {
   IGCN_REQUIRE(M > 0 && N > 0 && K > 0 && batch >= 1 && scratch != nullptr && (a_batch != 0 || b_batch != 0),
                "gemm_f32_batched_sum: bad arguments");
-  const int bn = N <= 16 ? 16 : (N <= 32 ? 32 : 64);
-  // long K per product: also slice K so that ~2k workgroups are in flight (slabs = batch * ksplit)
-  int ksplit = 1;
-  while (ksplit < 16 && (int64_t)batch * ksplit * 2 <= 2048 && K / (ksplit * 2) >= 128) ksplit *= 2;
-  const int64_t kps = igcn_cdiv(igcn_cdiv(K, ksplit), G_BK) * G_BK;
-  ksplit = (int)igcn_cdiv(K, kps);
-  const int slabs = batch * ksplit;
-  dim3 grid((unsigned)igcn_cdiv(M, G_BM), (unsigned)igcn_cdiv(N, bn), (unsigned)slabs);
-  int vw = min_int(vec_width(A, sam, sak, M, K), vec_width(B, sbn, sbk, N, K));
-  while (vw > 1 && (a_batch % vw != 0 || b_batch % vw != 0)) vw >>= 1;
+  const GemmPlan pl = gemm_plan(GEMM_BATCHED_SUM, M, N, K, A, sam, sak, B, sbn, sbk, ldc, false, 0, 1, batch, a_batch,
+                                b_batch);
+  const int slabs = batch * pl.split;
+  dim3 grid((unsigned)igcn_cdiv(M, G_BM), (unsigned)igcn_cdiv(N, pl.bn), (unsigned)slabs);
   {
-    const GemmArgs g = {M, N, K, A, sam, sak, B, sbn, sbk, nullptr, scratch, N, 0, kps, M * N, a_batch, b_batch, ksplit};
-    launch_f32(bn, vw, grid, st, g);
+    const GemmArgs g = {M, N, K, A, sam, sak, B, sbn, sbk, nullptr, scratch, N, 0, pl.kps, M * N, a_batch, b_batch, pl.split};
+    launch_f32(pl.bn, pl.vw, pl.pf, pl.arf, pl.brf, grid, st, g);
   }
   IGCN_CHECK_LAUNCH("gemm_f32_batched_sum");
-  if (ldc == N && M * N <= 4096 && slabs > 32)     // few outputs, many slabs: block-per-output tree reduce
+  if (pl.sum_form == GEMM_SUM_TREE)                // few outputs, many slabs: block-per-output tree reduce
     return igcn_launch_reduce_rows(scratch, slabs, M * N, (int)(M * N), C, 0, st);
   hipLaunchKernelGGL(k_gemm_splitk_reduce, dim3((unsigned)igcn_cdiv(M * N, 256)), dim3(256), 0, st, M, N, slabs,
                      scratch, (const float*)nullptr, C, ldc, 0, (int64_t)0);
@@ -724,23 +798,20 @@ extern "C" int igcn_gemm_f32_batched(int64_t M, int64_t N, int64_t K, int batch,
   IGCN_REQUIRE(M > 0 && N > 0 && K > 0 && batch >= 1 && split_k >= 1, "gemm_f32_batched: bad sizes");
   IGCN_REQUIRE(split_k == 1 || scratch != nullptr, "gemm_f32_batched: split_k > 1 needs scratch");
   hipStream_t st = (hipStream_t)stream;
-  if (split_k > K / G_BK) split_k = (int)(K / G_BK > 0 ? K / G_BK : 1);
-  int64_t kps = igcn_cdiv(igcn_cdiv(K, split_k), G_BK) * G_BK;
-  split_k = (int)igcn_cdiv(K, kps);
+  const GemmPlan pl = gemm_plan(GEMM_BATCHED, M, N, K, A, sam, sak, B, sbn, sbk, ldc, false, 0, split_k, batch, a_batch,
+                                b_batch);
+  split_k = pl.split;
   const bool split = split_k > 1;
-  const int bn = gemm_tile_n(M, N);
-  dim3 grid((unsigned)igcn_cdiv(M, G_BM), (unsigned)igcn_cdiv(N, bn), (unsigned)(batch * split_k));
-  int vw = min_int(vec_width(A, sam, sak, M, K), vec_width(B, sbn, sbk, N, K));
-  while (vw > 1 && (a_batch % vw != 0 || b_batch % vw != 0)) vw >>= 1;
+  dim3 grid((unsigned)igcn_cdiv(M, G_BM), (unsigned)igcn_cdiv(N, pl.bn), (unsigned)(batch * split_k));
   // split: slab (z, k) of the scratch, row stride N; unsplit: straight into C_z (the kernel's slab stride = c_batch)
-  const GemmArgs g = {M, N, K, A, sam, sak, B, sbn, sbk, nullptr, split ? scratch : C, split ? N : ldc, 0, kps,
+  const GemmArgs g = {M, N, K, A, sam, sak, B, sbn, sbk, nullptr, split ? scratch : C, split ? N : ldc, 0, pl.kps,
                       split ? M * N : c_batch, a_batch, b_batch, split_k};
-  launch_f32(bn, vw, grid, st, g);
+  launch_f32(pl.bn, pl.vw, pl.pf, pl.arf, pl.brf, grid, st, g);
   IGCN_CHECK_LAUNCH("gemm_f32_batched");
   if (split) {
     // few outputs, many slabs (the 32 x 32 Gram matrices of configs[4]: 256 slabs each): a thread walking its output's
     // slabs is a chain of 32 dependent batches of loads (15.8 us for 2 MB); 16 x 16 tiles with 16 row groups instead
-    if (ldc == N && M * N <= 4096 && split_k > 32)
+    if (pl.sum_form == GEMM_SUM_TREE)
       return igcn_launch_reduce_rows_batched(scratch, split_k, M * N, (int)(M * N), C, batch, (int64_t)split_k * M * N,
                                              c_batch, st);
     hipLaunchKernelGGL(k_gemm_splitk_reduce, dim3((unsigned)igcn_cdiv(M * N, 256), (unsigned)batch), dim3(256), 0, st, M,
@@ -828,6 +899,39 @@ extern "C" int igcn_gemm_rider_flush(void* stream) {
   return igcn_gemm_f32_grouped((int)(r.size() / 16), r.data(), stream);
 }
 
+// The plan of a grouped launch: every member's own plan (K slices, layouts, slab sum), and the tile width, vector width
+// and pipeline depth common to the launch — the narrowest tile, the narrowest loads, the deepest pipeline any member
+// asks for.  grouped == false: one ordinary launch per member (a single member, or one that only allows scalar loads).
+struct GemmGroupPlan { int bn, vw, pf; bool grouped; GemmPlan m[GG_MAX]; };
+static int gemm_group_plan(int n, const int64_t* table, GemmGroupPlan* gp) {
+  IGCN_REQUIRE(n >= 1 && n <= GG_MAX && table != nullptr, "gemm_f32_grouped: 1..%d problems", GG_MAX);
+  gp->bn = 64; gp->vw = 4; gp->pf = 1;
+  for (int i = 0; i < n; ++i) {
+    const int64_t* t = table + 16 * i;
+    const int split_k = (int)t[13];
+    IGCN_REQUIRE(t[0] > 0 && t[1] > 0 && t[2] > 0 && split_k >= 1 && (split_k == 1 || t[14] != 0),
+                 "gemm_f32_grouped: bad problem %d", i);
+    const GemmPlan m = gemm_plan(GEMM_MEMBER, t[0], t[1], t[2], (const float*)t[3], t[4], t[5], (const float*)t[6], t[7],
+                                 t[8], t[11], t[9] != 0, (int)t[12], split_k, 1, 0, 0);
+    gp->m[i] = m;
+    gp->bn = m.bn < gp->bn ? m.bn : gp->bn;
+    gp->vw = m.vw < gp->vw ? m.vw : gp->vw;
+    if (m.pf == 2) gp->pf = 2;
+  }
+  gp->grouped = !(gp->vw < 2 || n == 1);
+  return IGCN_OK;
+}
+
+// The launch igcn_gemm_f32_grouped makes of this table (riders are not looked at).  Host only.
+extern "C" int igcn_gemm_group_plan(int n, const int64_t* table, int64_t* out) {
+  IGCN_REQUIRE(out != nullptr, "gemm_group_plan: no output");
+  GemmGroupPlan gp;
+  const int rc = gemm_group_plan(n, table, &gp);
+  if (rc) return rc;
+  out[0] = gp.bn; out[1] = gp.vw; out[2] = table[15] != 0 ? 0 : gp.pf; out[3] = gp.grouped ? 1 : 0;
+  return IGCN_OK;
+}
+
 extern "C" int igcn_gemm_f32_grouped(int n, const int64_t* table, void* stream) {
   IGCN_REQUIRE(n >= 1 && n <= GG_MAX && table != nullptr, "gemm_f32_grouped: 1..%d problems", GG_MAX);
   hipStream_t st = (hipStream_t)stream;
@@ -841,47 +945,39 @@ extern "C" int igcn_gemm_f32_grouped(int n, const int64_t* table, void* stream) 
       table = merged;
     }
   }
+  GemmGroupPlan gp;
+  {
+    const int rc = gemm_group_plan(n, table, &gp);
+    if (rc) return rc;
+  }
   GemmGroup G;
   G.n = n;
-  int bn = 64, vw = 4, pf = 1, wgs = 0, split_of[GG_MAX];
+  const int bn = gp.bn, vw = gp.vw, pf = gp.pf;
+  int wgs = 0, split_of[GG_MAX];
   bool fgrad[GG_MAX];
   size_t lds = 0;
   for (int i = 0; i < n; ++i) {
     const int64_t* t = table + 16 * i;
+    const GemmPlan& m = gp.m[i];
     GemmProb& p = G.p[i];
     p.M = t[0]; p.N = t[1]; p.K = t[2];
     p.A = (const float*)t[3]; p.sam = t[4]; p.sak = t[5];
     p.B = (const float*)t[6]; p.sbn = t[7]; p.sbk = t[8];
     p.bias = (const float*)t[9];
-    float* C = (float*)t[10];
-    const int64_t ldc = t[11];
-    int act = (int)t[12], split_k = (int)t[13];
-    float* scratch = (float*)t[14];
-    fgrad[i] = (act & 0x100) != 0;
-    act &= 0xff;
-    IGCN_REQUIRE(p.M > 0 && p.N > 0 && p.K > 0 && split_k >= 1 && (split_k == 1 || scratch != nullptr),
-                 "gemm_f32_grouped: bad problem %d", i);
-    if (split_k > p.K / G_BK) split_k = (int)(p.K / G_BK > 0 ? p.K / G_BK : 1);
-    const int64_t kps = igcn_cdiv(igcn_cdiv(p.K, split_k), G_BK) * G_BK;
-    split_k = (int)igcn_cdiv(p.K, kps);
-    split_of[i] = split_k;
-    const bool split = split_k > 1;
-    p.C = split ? scratch : C;
-    p.ldc = split ? p.N : ldc;
-    p.act = act;
-    p.kps = kps;
+    fgrad[i] = ((int)t[12] & 0x100) != 0;
+    split_of[i] = m.split;
+    const bool split = m.split > 1;
+    p.C = split ? (float*)t[14] : (float*)t[10];
+    p.ldc = split ? p.N : t[11];
+    p.act = (int)t[12] & 0xff;
+    p.kps = m.kps;
     p.slab = split ? p.M * p.N : 0;
-    p.zsplit = split_k;
-    p.arf = (p.sam == 1 && p.sak != 1);
-    p.brf = (p.sbn == 1 && p.sbk != 1);
-    const int b = gemm_tile_n(p.M, p.N);
-    bn = b < bn ? b : bn;
-    const int v = min_int(vec_width(p.A, p.sam, p.sak, p.M, p.K), vec_width(p.B, p.sbn, p.sbk, p.N, p.K));
-    vw = v < vw ? v : vw;
-    if (igcn_cdiv(kps < p.K ? kps : p.K, G_BK) > 2) pf = 2;
+    p.zsplit = m.split;
+    p.arf = m.arf;
+    p.brf = m.brf;
   }
   const bool bf16 = table[15] != 0;
-  if (vw < 2 || n == 1) {                              // not groupable: the ordinary launches, one after the other
+  if (!gp.grouped) {                                   // not groupable: the ordinary launches, one after the other
     for (int i = 0; i < n; ++i) {
       const int64_t* t = table + 16 * i;
       const int rc = gemm_launch(bf16, t[0], t[1], t[2], (const float*)t[3], t[4], t[5], (const float*)t[6], t[7], t[8],
@@ -925,8 +1021,7 @@ extern "C" int igcn_gemm_f32_grouped(int n, const int64_t* table, void* stream) 
     int64_t blocks = 0;
     for (int k = 0; k < n; ++k) {
       const int64_t* u = table + 16 * k;
-      const bool tree = u[11] == u[1] && u[0] * u[1] <= 4096 && split_of[k] > 32 && u[9] == 0 && ((int)u[12] & 0xff) == 0;
-      if (!(split_of[k] > 1 && !fgrad[k] && !tree)) continue;
+      if (!(gp.m[k].sum_form == GEMM_SUM_WALK && !fgrad[k])) continue;
       q.slabs[cnt] = (const float*)u[14]; q.bias[cnt] = (const float*)u[9]; q.C[cnt] = (float*)u[10];
       q.split[cnt] = split_of[k];
       q.M[cnt] = u[0]; q.N[cnt] = u[1]; q.ldc[cnt] = u[11]; q.act[cnt] = (int)u[12] & 0xff;
@@ -943,7 +1038,7 @@ extern "C" int igcn_gemm_f32_grouped(int n, const int64_t* table, void* stream) 
   for (int i = 0; i < n; ++i) {
     if (done[i]) continue;
     const int64_t* t = table + 16 * i;
-    const int rc = gemm_sum_slabs(split_of[i], fgrad[i], t[0], t[1], (float*)t[14], (const float*)t[9], (float*)t[10], t[11],
+    const int rc = gemm_sum_slabs(gp.m[i], t[0], t[1], (float*)t[14], (const float*)t[9], (float*)t[10], t[11],
                                   (int)t[12] & 0xff, st);
     if (rc) return rc;
   }

@@ -31,7 +31,7 @@ extern "C" {
 /* ABI revision: bumped whenever a prototype below changes (argument added, removed or re-ordered).  igcn_version()
  * returns the revision the library was built from; a binding written against a different one must refuse to call
  * (igcn_amd/_lib.py does). */
-#define IGCN_ABI_VERSION 436
+#define IGCN_ABI_VERSION 437
 int igcn_version(void);
 const char* igcn_last_error(void);
 /* A/B switches, set ONCE by the binding when it loads the library (from the IGCN_* environment variables): bit 0 no tiled
@@ -611,6 +611,21 @@ int igcn_gemm_bf16(int64_t M, int64_t N, int64_t K,
  * `scratch` ([igcn_gemm_effective_split(K, split_k)][M, N], slab order = K order) for a consumer that sums them while it
  * loads them (igcn_bn1d_fwd_slabs); with an effective split of 1 the product is written to C as usual. */
 int igcn_gemm_effective_split(int64_t K, int split_k);
+/* The launch plan of igcn_gemm_f32 (bf16 == 0) / igcn_gemm_bf16 (bf16 != 0) for these arguments: the function those
+ * entry points run to choose their kernel instantiation, as a query.  Host only (no GPU needed): A and B are never
+ * dereferenced, only their low address bits are read.  `act` with its 0x100 / 0x200 bits as passed to the product.
+ * out [8] (host) = { bn, vw, pf, arf, brf, split_eff, kps, sum_form }:
+ *   bn         tile width (16, 32, 64)                 vw   floats per operand load (4, 2, 1)
+ *   pf         K tiles in flight ahead of LDS (1, 2; 0 for bf16: that kernel has no such parameter)
+ *   arf, brf   A / B is read with its row axis as the contiguous one
+ *   split_eff  K slices that run (= igcn_gemm_effective_split)       kps   K elements per slice
+ *   sum_form   what follows the product launch: 0 nothing (split_eff == 1), 1 the column walk over the slabs (with bias /
+ *              activation; members of a grouped launch share one such launch), 2 the block-per-output tree, 3 the
+ *              final row sum of a parameter gradient (deferred inside igcn_reduce_defer), 4 nothing: the slabs are left
+ *              to the caller (act | 0x200). */
+int igcn_gemm_plan(int bf16, int64_t M, int64_t N, int64_t K, const float* A, int64_t sam, int64_t sak,
+                   const float* B, int64_t sbn, int64_t sbk, int64_t ldc, int has_bias, int act, int split_k,
+                   int64_t* out);
 
 /* Batched-sum variant: C = sum_z A_z . B_z^T with A_z = A + z*a_batch, B_z = B + z*b_batch (element offsets),
  * every z covering the whole K; slabs are summed in z order.  Used for weight gradients whose reduction index is
@@ -634,6 +649,11 @@ int igcn_gemm_f32_batched(int64_t M, int64_t N, int64_t K, int batch, const floa
  * points choose their slab sum by shape (a tree for few outputs x many slabs, igcn_gemm_f32_batched likewise), so a split
  * product agrees with them to fp32 rounding, not bit for bit.  Within one entry point results are reproducible run to run. */
 int igcn_gemm_f32_grouped(int n, const int64_t* table, void* stream);
+/* The launch igcn_gemm_f32_grouped makes of `table` on its own (waiting riders are not looked at; host only, nothing
+ * behind the table's pointers is read): out [4] (host) = { bn, vw, pf, grouped } — the instantiation common to the
+ * members (pf 0 for bf16) and grouped = 1, or grouped = 0 when the members run as ordinary launches one after the other
+ * (n == 1, or a member that only allows scalar loads).  Fails where igcn_gemm_f32_grouped refuses the table. */
+int igcn_gemm_group_plan(int n, const int64_t* table, int64_t* out);
 /* Products QUEUED for `stream` (same table format; at most 4 waiting) and carried by the next igcn_gemm_f32_grouped on it
  * — if they fit beside its own products (4 in all) and share its operand type — as further members of that launch,
  * slab sums included.  For products that are ready together but issued by different parts of the host code (the heads'
