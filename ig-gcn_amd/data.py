@@ -138,3 +138,9 @@ class DataLoader(torch.utils.data.DataLoader):
     def __init__(self, dataset, batch_size=1, shuffle=False, **kwargs):
         super().__init__(dataset, batch_size, shuffle,
                          collate_fn=lambda items: Batch.from_data_list(items), **kwargs)
+
+
+def _batches(loader, device):
+    """The batches of ``loader``, moved to ``device`` when one is given (the sweep of every evaluation and map pass)."""
+    for data in loader:
+        yield data.to(device) if device is not None else data

@@ -14,6 +14,8 @@ from . import _lib
 from . import switches
 from ._lib import call, ptr, stream_ptr
 from .capture import GradTable, ShapeCache, _capture, kept_trainer, rolled_back
+from .data import _batches
+from .maps import association_maps, attention_maps, connectivity_maps, saliency_maps  # noqa: F401  (re-exported)
 
 # sgcn_hyperparameters.py:18-23
 HP = SimpleNamespace(lamda_x_l1=0.1, lamda_e_l1=0.1, lamda_x_ent=0.1, lamda_e_ent=0.1, lamda_mi=1, lamda_ce=1)
@@ -1210,11 +1212,6 @@ def fit_epoch(model, optimizer, loader, temperature=None, lambda_loss=DEFAULT_LA
     return tr.fit_epoch(loader, device)
 
 
-def _batches(loader, device):
-    for data in loader:
-        yield data.to(device) if device is not None else data
-
-
 @torch.no_grad()
 def eval_loss(model, loader, lambda_loss=DEFAULT_LAMBDA, hp=HP, temperature=None, device=None):
     """eval_loss() kernel/train_eval_sgcn_img_snps.py:564-600 (and kernel/train_eval_sgcn.py:328-347): the
@@ -1504,251 +1501,6 @@ def eval_scores_of(r):
     regression = (true_clin.tolist(), pred_clin.tolist(), r["corr"], r["r2"], r["rmse"])
     return (r["y"].cpu().numpy(), r["pred"].cpu().numpy(), r["accuracy"], r["auc"], r["f1"], r["sensitivity"],
             r["specificity"], r["out_lin"].cpu(), r["sbjID"].cpu(), r["linear_outf"].cpu(), regression)
-
-
-def attention_maps(model, loader, temperature=None, device=None, isExplain=False, num_classes=None, top_k=10):
-    """The ROI x GO-term attention table of a cohort: ``model.attention_weights`` (the weights
-    ``self.multihead_attn`` returns at kernel/sgcn_img_snp.py:240, which the reference discards) of every batch of
-    ``loader``, summed per class of ``data.y`` on the device (igcn_attn_map_accumulate: fp64, sample order) and read
-    once at the end.  Returns a dict: ``mean`` [C, rois, Ntop] (fp32; zeros for a class without subjects), ``count`` [C]
-    (int64), ``overall`` [rois, Ntop] (the count-weighted mean over the classes), ``go_rows`` [Ntop] (int64: the GO node
-    behind every key row — the encoder drops the two deepest levels, which lead the builder's node order, so the rows
-    are nodes N - Ntop .. N - 1), ``top_terms`` [rois, top_k] (int64: the GO nodes of the ``top_k`` largest entries
-    of every row of ``overall``) and ``n`` (subjects).  A label outside [0, C) raises IgcnError after the pass."""
-    from . import ops
-    head = model.lin2_classify if getattr(model, "clusterlabel", False) else model.lin2
-    c = int(num_classes) if num_classes is not None else int(head.weight.shape[0])
-    if c <= 0:
-        raise ValueError(f"attention_maps: num_classes={c}")
-    sums = counts = state = None
-    n = 0
-    for data in _batches(loader, device):
-        w = model.attention_weights(data, temperature, device, isExplain)
-        if sums is None:
-            sums = torch.zeros(c, w.shape[1], w.shape[2], dtype=torch.float64, device=w.device)
-            counts = torch.zeros(c, dtype=torch.int64, device=w.device)
-            state = torch.zeros(1, dtype=torch.int64, device=w.device)
-        y = data.y.view(-1).to(device=w.device, dtype=torch.int64).contiguous()
-        ops.attention_map_accumulate(w, y, sums, counts, state)
-        n += int(data.num_graphs)
-    if n == 0:
-        raise ValueError("attention_maps: the loader is empty")
-    skipped = int(state.item())                                  # the pass's one synchronisation
-    if skipped:
-        raise _lib.IgcnError(f"attention_maps: {skipped} of {n} labels lie outside [0, {c})")
-    mean = (sums / counts.clamp(min=1).view(c, 1, 1).double()).float()
-    overall = (sums.sum(0) / float(n)).float()
-    n_top, n_nodes = overall.shape[1], int(model.go_network.n_nodes)
-    go_rows = torch.arange(n_nodes - n_top, n_nodes, dtype=torch.int64, device=overall.device)
-    top = torch.topk(overall, min(int(top_k), n_top), dim=1).indices
-    return {"mean": mean, "count": counts, "overall": overall, "go_rows": go_rows, "top_terms": go_rows[top], "n": n}
-
-
-def association_maps(model, loader, temperature=None, device=None, isExplain=False, num_classes=None, top_k=10):
-    """The ROI x SNP association table of a cohort: ``model.snp_association`` — the cross-attention weights of
-    kernel/sgcn_img_snp.py:240 times the attention roll-out of the GO encoder (go_model.py:208-251) down to the 54
-    SNPs — of every batch of ``loader``, summed per class of ``data.y`` on the device (igcn_attn_map_accumulate with
-    Lk = 54: fp64, sample order) and read once at the end.  Returns a dict: ``mean`` [C, rois, 54] (fp32; zeros for a
-    class without subjects), ``count`` [C] (int64), ``overall`` [rois, 54] (the mean over all subjects), ``go_to_snp``
-    [Ntop, 54] (the cohort mean of the roll-out R_top itself), ``go_rows`` [Ntop] (int64: the GO node behind every row
-    of ``go_to_snp``, as in ``attention_maps``), ``top_snps`` [rois, top_k] (int64: the SNP columns of the ``top_k``
-    largest entries of every row of ``overall``) and ``n`` (subjects).  A label outside [0, C) raises IgcnError after
-    the pass."""
-    from . import ops
-    head = model.lin2_classify if getattr(model, "clusterlabel", False) else model.lin2
-    c = int(num_classes) if num_classes is not None else int(head.weight.shape[0])
-    if c <= 0:
-        raise ValueError(f"association_maps: num_classes={c}")
-    sums = counts = state = go_sums = go_counts = zero_y = None
-    n = 0
-    for data in _batches(loader, device):
-        a, r_top = model._snp_association(data, temperature, device, isExplain)
-        if sums is None:
-            dev = a.device
-            sums = torch.zeros(c, a.shape[1], a.shape[2], dtype=torch.float64, device=dev)
-            go_sums = torch.zeros(1, r_top.shape[1], r_top.shape[2], dtype=torch.float64, device=dev)
-            counts, go_counts = (torch.zeros(k, dtype=torch.int64, device=dev) for k in (c, 1))
-            state = torch.zeros(1, dtype=torch.int64, device=dev)
-        y = data.y.view(-1).to(device=a.device, dtype=torch.int64).contiguous()
-        ops.attention_map_accumulate(a, y, sums, counts, state)
-        if zero_y is None or zero_y.numel() != y.numel():
-            zero_y = torch.zeros_like(y)
-        ops.attention_map_accumulate(r_top.contiguous(), zero_y, go_sums, go_counts, state)
-        n += int(data.num_graphs)
-    if n == 0:
-        raise ValueError("association_maps: the loader is empty")
-    skipped = int(state.item())                                  # the pass's one synchronisation
-    if skipped:
-        raise _lib.IgcnError(f"association_maps: {skipped} of {n} labels lie outside [0, {c})")
-    mean = (sums / counts.clamp(min=1).view(c, 1, 1).double()).float()
-    overall = (sums.sum(0) / float(n)).float()
-    go_to_snp = (go_sums[0] / float(n)).float()
-    n_top, n_nodes = go_to_snp.shape[0], int(model.go_network.n_nodes)
-    go_rows = torch.arange(n_nodes - n_top, n_nodes, dtype=torch.int64, device=overall.device)
-    top = torch.topk(overall, min(int(top_k), overall.shape[1]), dim=1).indices
-    return {"mean": mean, "count": counts, "overall": overall, "go_to_snp": go_to_snp, "go_rows": go_rows,
-            "top_snps": top, "n": n}
-
-
-def connectivity_maps(model, loader, source="mask", weighted=False, isExplain=False, num_classes=None, top_k=10,
-                      symmetric=False, temperature=None, device=None):
-    """The ROI x ROI connectivity table of a cohort — the brain connections the model keeps.  ``source="mask"``:
-    ``model.edge_importance`` (the connective-importance mask of cal_probability, kernel/sgcn_img_snp.py:133-151;
-    ``weighted``: times the edge weight); ``source="gat"``: ``model.gat_attention`` (the per-edge GATConv attention of
-    every layer, kernel/sgcn.py:235-267 / kernel/gcn_img_snp.py:217-221; ``isExplain``: of the masked pass).  Every
-    batch's maps are summed per class of ``data.y`` on the device (igcn_attn_map_accumulate: fp64, sample order; one
-    call per quantity) and read once at the end.  Maps are indexed [source region, target region], like ``data.A``.
-    Returns a dict: ``mean`` [C, R, R] ([C, L, R, R] for "gat"; fp32, zeros for a class without subjects), ``count`` [C]
-    (int64), ``overall`` [R, R] ([L, R, R]: the mean over all subjects), ``strength`` [R] ((row sum + column sum) / 2 of
-    ``overall``; of its layer mean for "gat"), ``top_edges`` [top_k, 2] (int64: the (source, target) pairs of the largest
-    entries of ``overall`` / its layer mean, largest first), ``n`` (subjects) and, for "mask" only, ``present`` [R, R]
-    (the mean number of stored copies of the edge per subject) and ``mean_present`` [R, R] (``overall / present`` where
-    ``present > 0``, else 0: the mean mask over the subjects that store the edge).  ``symmetric``: ``mean``, ``overall``,
-    ``mean_present`` and ``present`` are returned as (M + M^T) / 2 (per layer for "gat"), applied once to the finished
-    tables; ``strength`` and ``top_edges`` are taken from the ``overall`` that is returned.  ``temperature`` is accepted
-    for the signature of the sibling passes (no GO network runs here).  A label outside [0, C) raises IgcnError after the
-    pass."""
-    from . import ops
-    if source not in ("mask", "gat"):
-        raise ValueError(f"connectivity_maps: source={source!r} ('mask' or 'gat')")
-    if num_classes is None:
-        head = (model.lin2_classify if getattr(model, "clusterlabel", False) else
-                model.lin2 if hasattr(model, "lin2") else model.fc3)
-        num_classes = head.weight.shape[0]
-    c = int(num_classes)
-    if c <= 0:
-        raise ValueError(f"connectivity_maps: num_classes={c}")
-    sums = counts = state = cp_sums = cp_counts = zero_y = None
-    n, shape = 0, None
-    for data in _batches(loader, device):
-        if source == "mask":
-            m, cnt = model.edge_importance(data, weighted=weighted, return_count=True)
-        else:
-            m, cnt = model.gat_attention(data, isExplain=isExplain), None
-        if sums is None:
-            dev, shape = m.device, tuple(m.shape[1:])
-            r = shape[-1]
-            sums = torch.zeros(c, m.numel() // (m.shape[0] * r), r, dtype=torch.float64, device=dev)
-            counts = torch.zeros(c, dtype=torch.int64, device=dev)
-            state = torch.zeros(1, dtype=torch.int64, device=dev)
-            if cnt is not None:
-                cp_sums = torch.zeros(1, r, r, dtype=torch.float64, device=dev)
-                cp_counts = torch.zeros(1, dtype=torch.int64, device=dev)
-        y = data.y.view(-1).to(device=m.device, dtype=torch.int64).contiguous()
-        ops.attention_map_accumulate(m.view(m.shape[0], -1, m.shape[-1]), y, sums, counts, state)
-        if cnt is not None:
-            if zero_y is None or zero_y.numel() != y.numel():
-                zero_y = torch.zeros_like(y)
-            ops.attention_map_accumulate(cnt, zero_y, cp_sums, cp_counts, state)
-        n += int(data.num_graphs)
-    if n == 0:
-        raise ValueError("connectivity_maps: the loader is empty")
-    skipped = int(state.item())                                  # the pass's one synchronisation
-    if skipped:
-        raise _lib.IgcnError(f"connectivity_maps: {skipped} of {n} labels lie outside [0, {c})")
-    sym = (lambda t: (t + t.transpose(-1, -2)) / 2) if symmetric else (lambda t: t)
-    mean = sums / counts.clamp(min=1).view(c, 1, 1).double()
-    overall = sums.sum(0) / float(n)
-    out = {"mean": sym(mean.view(c, *shape)).float(), "count": counts, "overall": sym(overall.view(shape)).float(), "n": n}
-    if cp_sums is not None:
-        present = cp_sums[0] / float(n)
-        mean_present = torch.where(present > 0, overall / present.clamp(min=1e-300), torch.zeros_like(overall))
-        out["present"], out["mean_present"] = sym(present).float(), sym(mean_present).float()
-    flat = out["overall"] if len(shape) == 2 else out["overall"].double().mean(0).float()
-    r = flat.shape[-1]
-    out["strength"] = ((flat.double().sum(1) + flat.double().sum(0)) / 2).float()
-    top = torch.topk(flat.reshape(-1), min(int(top_k), r * r)).indices
-    out["top_edges"] = torch.stack((top // r, top % r), dim=1)
-    return out
-
-
-def saliency_maps(model, loader, method="gradxinput", target=None, inputs="image", isExplain=False, steps=16,
-                  baseline=None, normalize=True, num_classes=None, top_k=10, temperature=None, device=None):
-    """The ROI x modality saliency table of a cohort — which regions, in which imaging modality, drive the predicted
-    class.  ``method``: "gradxinput" (``model.input_saliency``), "ig" (``model.integrated_gradients`` with ``steps`` and
-    ``baseline``) or "gradcam" (``SGCN_Ori.grad_cam``).  ``target``: None (every subject's predicted class), "label"
-    (``data.y``) or an int.  Every batch's maps are summed per class of ``data.y`` on the device
-    (igcn_attn_map_accumulate: fp64, sample order; one call per quantity) and read once at the end.  Returns a dict:
-    ``mean`` [C, R, H0] ([C, R] for "gradcam"; fp32, zeros for a class without subjects), ``roi_mean`` [C, R] (the
-    class mean of the per-subject ``roi`` = sum_h |attr|; the map itself for "gradcam"), ``overall`` / ``roi_overall``
-    [R] (the means over all subjects), ``count`` [C] (int64), ``n`` (subjects), ``top_regions`` [top_k] (int64: the
-    regions of the largest ``roi_overall``, largest first); with ``inputs`` "snps" / "both" also ``snps_mean`` [C, 54]
-    and ``top_snps`` [top_k] (by the magnitude of the mean over all subjects); for "ig" ``mean_abs_delta`` (a float:
-    the mean quadrature gap).  "ig" with ``inputs="snps"`` moves the SNP vector alone: the image keys are absent.  A
-    label outside [0, C) raises IgcnError after the pass."""
-    from . import ops
-    if method not in ("gradxinput", "ig", "gradcam"):
-        raise ValueError(f"saliency_maps: method={method!r} ('gradxinput', 'ig' or 'gradcam')")
-    if not (target is None or target == "label" or (isinstance(target, int) and not isinstance(target, bool))):
-        raise ValueError(f"saliency_maps: target={target!r} (None, 'label' or an int)")
-    if method == "gradcam" and inputs != "image":
-        raise ValueError("saliency_maps: 'gradcam' maps the image branch only (inputs='image')")
-    if num_classes is None:
-        head = (model.lin2_classify if getattr(model, "clusterlabel", False) else
-                model.lin2 if hasattr(model, "lin2") else model.fc3)
-        num_classes = head.weight.shape[0]
-    c = int(num_classes)
-    if c <= 0:
-        raise ValueError(f"saliency_maps: num_classes={c}")
-    acc = {}                                                     # quantity -> (sums [C, Lq, Lk], counts [C])
-    state = delta_sum = None
-    n = 0
-
-    def add(name, t, y):
-        if name not in acc:
-            acc[name] = (torch.zeros(c, t.shape[1], t.shape[2], dtype=torch.float64, device=t.device),
-                         torch.zeros(c, dtype=torch.int64, device=t.device))
-        ops.attention_map_accumulate(t.contiguous(), y, *acc[name], state)
-
-    for data in _batches(loader, device):
-        tgt = data.y.view(-1) if isinstance(target, str) else target
-        if method == "gradcam":
-            r = {"roi": model.grad_cam(data, target=tgt, isExplain=isExplain, normalize=normalize)}
-        elif method == "ig":
-            r = model.integrated_gradients(data, temperature, device, target=tgt, isExplain=isExplain, inputs=inputs,
-                                           normalize=normalize, steps=steps, baseline=baseline)
-        else:
-            r = model.input_saliency(data, temperature, device, target=tgt, isExplain=isExplain, inputs=inputs,
-                                     normalize=normalize)
-        dev = r["roi" if "roi" in r else "snps"].device
-        if state is None:
-            state = torch.zeros(1, dtype=torch.int64, device=dev)
-        y = data.y.view(-1).to(device=dev, dtype=torch.int64).contiguous()
-        for name in ("attr", "roi", "snps"):
-            if name in r:
-                t = r[name]
-                add(name, t if t.dim() == 3 else t.unsqueeze(2), y)
-        if "delta" in r:
-            d = r["delta"].double().abs().sum()
-            delta_sum = d if delta_sum is None else delta_sum + d
-        n += int(data.num_graphs)
-    if n == 0:
-        raise ValueError("saliency_maps: the loader is empty")
-    skipped = int(state.item()) // len(acc)                      # the pass's one synchronisation
-    if skipped:
-        raise _lib.IgcnError(f"saliency_maps: {skipped} of {n} labels lie outside [0, {c})")
-
-    def table(name):
-        sums, counts = acc[name]
-        return (sums / counts.clamp(min=1).view(c, 1, 1).double()).float(), (sums.sum(0) / float(n)).float(), counts
-
-    out = {"n": n}
-    if "roi" in acc:
-        roi_mean, roi_overall, out["count"] = table("roi")
-        out.update({"roi_mean": roi_mean[:, :, 0], "roi_overall": roi_overall[:, 0]})
-        if method == "gradcam":                                  # (the map is its own regional summary)
-            out.update({"mean": out["roi_mean"], "overall": out["roi_overall"]})
-        else:
-            out["mean"], out["overall"], _ = table("attr")
-        out["top_regions"] = torch.topk(out["roi_overall"], min(int(top_k), out["roi_overall"].numel())).indices
-    if "snps" in acc:
-        snps_mean, snps_overall, counts = table("snps")
-        out.setdefault("count", counts)
-        out["snps_mean"] = snps_mean[:, :, 0]
-        out["top_snps"] = torch.topk(snps_overall[:, 0].abs(), min(int(top_k), snps_overall.shape[0])).indices
-    if delta_sum is not None:
-        out["mean_abs_delta"] = float(delta_sum) / n
-    return out
 
 
 def output_importance(model):

@@ -237,7 +237,8 @@ def test_attention_maps_vs_fp64():
     r2 = attention_maps(model, DataLoader(graphs, batch_size=8), device="cuda", num_classes=5)
     assert r2["count"].cpu().tolist() == cnt.tolist() + [0, 0] and float(r2["mean"][3:].abs().max()) == 0.0
     from igcn_amd import _lib
-    with pytest.raises(_lib.IgcnError, match="labels"):
+    bad = int((y >= 2).sum())                                    # (> 0: class 2 has subjects, above)
+    with pytest.raises(_lib.IgcnError, match=rf"attention_maps: {bad} of 12 labels lie outside \[0, 2\)"):
         attention_maps(model, DataLoader(graphs, batch_size=8), device="cuda", num_classes=2)
 
 

@@ -372,5 +372,6 @@ def test_association_maps_vs_per_batch_means():
     assert r["go_rows"].cpu().tolist() == list(range(68 - 13, 68))
     assert tuple(r["top_snps"].shape) == (90, 4)
     assert torch.equal(r["top_snps"], torch.topk(r["overall"], 4, dim=1).indices)
-    with pytest.raises(_lib.IgcnError, match="labels"):
+    bad = labels.count(2)                                                               # 6 of the 11
+    with pytest.raises(_lib.IgcnError, match=rf"association_maps: {bad} of 11 labels lie outside \[0, 2\)"):
         association_maps(model, DataLoader(graphs, batch_size=4), device="cuda", num_classes=2)

@@ -622,3 +622,6 @@ def test_saliency_maps_empty_loader_and_bad_label():
         saliency_maps(model, DataLoader(graphs, batch_size=3), target="label", device="cuda")
     with pytest.raises(ValueError, match="never fills final_conv_acts"):
         saliency_maps(model, DataLoader(graphs, batch_size=3), method="gradcam", device="cuda")
+    # three quantities (attr, roi, snps) bump the one state word: the subject is still counted once
+    with pytest.raises(_lib.IgcnError, match=r"saliency_maps: 1 of 4 labels lie outside \[0, 3\)"):
+        saliency_maps(_model("imgsnp"), DataLoader(graphs, batch_size=3), inputs="both", device="cuda")
