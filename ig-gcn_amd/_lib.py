@@ -14,7 +14,7 @@ from . import switches
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libigcn.so")
 
-ABI_VERSION = 437      # include/igcn.h IGCN_ABI_VERSION this table was written against (tests/test_abi.py compares)
+ABI_VERSION = 438      # include/igcn.h IGCN_ABI_VERSION this table was written against (tests/test_abi.py compares)
 
 P, I, L, F, Z = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
 
@@ -248,6 +248,15 @@ SIGNATURES = {
     "igcn_knn_impute_stats": (I, [L, I, P, P, L, P, P, P]),
     "igcn_knn_impute_scratch_floats": (Z, [L, L]),
     "igcn_knn_impute": (I, [L, I, I, P, P, L, P, L, P, P, P, P, I, I, P, P, P, P, P, P]),
+    "igcn_tsne_sqdist": (I, [I, I, P, P, P]),
+    "igcn_tsne_joint_p_scratch_doubles": (Z, [I]),
+    "igcn_tsne_joint_p": (I, [I, ctypes.c_double, P, P, P, P, P, P]),
+    "igcn_tsne_grad": (I, [I, I, P, P, P, P, P]),
+    "igcn_tsne_update": (I, [I, F, F, F, I, P, P, P, P, P, P, P, P, P]),
+    "igcn_kmeans_scratch_floats": (Z, [L, I, I]),
+    "igcn_kmeans_assign": (I, [L, I, I, P, P, P, P, P, P, P, P, P]),
+    "igcn_kmeans_update": (I, [L, I, I, P, P, P, P, P, P, P, P]),
+    "igcn_kmeanspp_step": (I, [L, I, I, P, P, P, P, P, P]),
 }
 
 _lib = None

@@ -3611,3 +3611,145 @@ def knn_impute(x, means, k, rows_fit=None, rows_q=None, scale=None, shift=None, 
     call("igcn_knn_impute", s, f, k, ptr(x), ptr(rows_fit), n_fit, ptr(rows_q), n_q, ptr(means), ptr(scale), ptr(shift),
          ptr(select), n_sel, scatter, ptr(full), ptr(sel_out), ptr(donors), ptr(status), ptr(scratch), stream_ptr())
     return full, sel_out, donors, status
+
+
+# =================================================================================================
+# Cluster labels: exact t-SNE and KMeans (csrc/tsne.hip, csrc/kmeans.hip); the algorithms live in cluster_labels.py
+# =================================================================================================
+TSNE_MAX_S, TSNE_MAX_D, KMEANS_MAX_N, KMEANS_MAX_D, KMEANS_MAX_K = 4096, 1024, 65536, 1024, 16
+
+
+def cl_matrix(x, what, lo_rows, hi_rows, hi_cols):
+    """The one check of a cluster-label input (also cluster_labels.py's): a float32 [rows, columns] tensor inside the
+    supported range on the GPU — the shape first, so that an unsupported size is refused wherever the tensor lives.
+    Returns it detached and contiguous; ``ValueError`` otherwise."""
+    if not torch.is_tensor(x) or x.dim() != 2:
+        raise ValueError(f"{what}: needs a 2-D float32 tensor")
+    n, d = int(x.shape[0]), int(x.shape[1])
+    if not (lo_rows <= n <= hi_rows and 1 <= d <= hi_cols):
+        raise ValueError(f"{what}: shape {(n, d)} outside {lo_rows} <= rows <= {hi_rows}, 1 <= columns <= {hi_cols}")
+    if not x.is_cuda:
+        raise ValueError(f"{what}: the tensor must live on the GPU (there is no host path)")
+    if x.dtype != torch.float32:
+        raise ValueError(f"{what}: needs float32, got {x.dtype}")
+    return x.detach().contiguous()
+
+
+def _f64(n, dev):
+    return torch.zeros(n, dtype=torch.float64, device=dev)
+
+
+def tsne_sqdist(x):
+    """[S, S] squared Euclidean distances of x [S, D] by direct differences (igcn_tsne_sqdist): symmetric bits, the
+    diagonal exactly 0."""
+    x = cl_matrix(x, "tsne_sqdist", 4, TSNE_MAX_S, TSNE_MAX_D)
+    s, d = x.shape
+    dist = torch.empty(s, s, dtype=torch.float32, device=x.device)
+    call("igcn_tsne_sqdist", s, d, ptr(x), ptr(dist), stream_ptr())
+    return dist
+
+
+def tsne_joint_p(dist, perplexity):
+    """sklearn's ``_joint_probabilities`` of the squared distances dist [S, S] — symmetric bit for bit, as
+    ``tsne_sqdist`` returns them: d_ji is read as d_ij — (igcn_tsne_joint_p): (P [S, S] float32
+    with a zero diagonal, betas [S] float64, pstats [2] float64 = (sum P log P, sum P))."""
+    dist = cl_matrix(dist, "tsne_joint_p", 4, TSNE_MAX_S, TSNE_MAX_S)
+    s = dist.shape[0]
+    if dist.shape[1] != s:
+        raise ValueError("tsne_joint_p: the distances must be [S, S]")
+    if not 0.0 < float(perplexity) < s:
+        raise ValueError(f"tsne_joint_p: perplexity {perplexity} must be less than n_samples {s}")
+    dev = dist.device
+    p = torch.empty(s, s, dtype=torch.float32, device=dev)
+    betas, pstats = _f64(s, dev), _f64(2, dev)
+    scratch = _f64(int(_lib.load().igcn_tsne_joint_p_scratch_doubles(s)), dev)
+    call("igcn_tsne_joint_p", s, float(perplexity), ptr(dist), ptr(p), ptr(betas), ptr(pstats), ptr(scratch), stream_ptr())
+    return p, betas, pstats
+
+
+class TsneState:
+    """The buffers of a t-SNE descent at fixed addresses (a captured block replays on them): P [S, S] and pstats [2] of
+    ``tsne_joint_p``, Y / update / gains [S, 2], the per-row accumulators, and the status record (float64 [4]: KL, norm
+    of the gains-scaled gradient, Z, number of check iterations written)."""
+
+    def __init__(self, p, pstats, y):
+        s = int(p.shape[0])
+        if tuple(p.shape) != (s, s) or tuple(y.shape) != (s, 2) or not 4 <= s <= TSNE_MAX_S:
+            raise ValueError(f"TsneState: P {tuple(p.shape)} / Y {tuple(y.shape)} are not [S, S] / [S, 2], 4 <= S <= 4096")
+        dev = p.device
+        self.s, self.p, self.pstats = s, _f32(p), pstats
+        self.y = _f32(y.detach()).clone()
+        self.update = torch.zeros_like(self.y)
+        self.gains = torch.ones_like(self.y)
+        self.grad = torch.zeros_like(self.y)
+        self.rowacc = torch.zeros(5, s, dtype=torch.float32, device=dev)
+        self.klpart = _f64(s, dev)
+        self.status = _f64(4, dev)
+
+
+def tsne_grad(st, want_kl=False):
+    """The gradient pass over P at ``st.y`` (igcn_tsne_grad) into ``st.rowacc`` (and ``st.klpart``)."""
+    call("igcn_tsne_grad", st.s, int(bool(want_kl)), ptr(st.p), ptr(st.y), ptr(st.rowacc), ptr(st.klpart), stream_ptr())
+
+
+def tsne_update(st, exaggeration, momentum, lr, check=False):
+    """sklearn's ``_gradient_descent`` step in place on ``st`` from ``st.rowacc`` (igcn_tsne_update); ``st.grad``
+    receives the gradient; ``check``: the status record is written (needs a ``want_kl`` gradient pass)."""
+    if float(exaggeration) < 1.0:
+        raise ValueError(f"tsne_update: early exaggeration {exaggeration} below 1")
+    call("igcn_tsne_update", st.s, float(exaggeration), float(momentum), float(lr), int(bool(check)), ptr(st.rowacc),
+         ptr(st.klpart), ptr(st.pstats), ptr(st.y), ptr(st.update), ptr(st.gains), ptr(st.grad), ptr(st.status),
+         stream_ptr())
+
+
+def _km_centers(x, centers, what):
+    if (not torch.is_tensor(centers) or centers.dim() != 2 or centers.device != x.device or centers.dtype != torch.float32
+            or centers.shape[1] != x.shape[1]):
+        raise ValueError(f"{what}: the centres must be float32 [k, {x.shape[1]}] on the points' device")
+    if not 1 <= centers.shape[0] <= KMEANS_MAX_K:
+        raise ValueError(f"{what}: {centers.shape[0]} clusters outside 1..{KMEANS_MAX_K}")
+    return centers.contiguous()
+
+
+def kmeans_assign(x, centers, labels=None, want_sums=True):
+    """Nearest centre of every row of x [N, d] (igcn_kmeans_assign; ties to the lower centre).  Returns (labels [N] int64,
+    mind [N], counts [k] int64 or None, sums [k, d] float64 or None, stats float64 [4]): stats[0] the inertia, stats[1] how
+    many labels differ from ``labels`` as passed in (overwritten in place; None: a fresh vector of -1)."""
+    x = cl_matrix(x, "kmeans_assign", 1, KMEANS_MAX_N, KMEANS_MAX_D)
+    centers = _km_centers(x, centers, "kmeans_assign")
+    n, d, k, dev = x.shape[0], x.shape[1], centers.shape[0], x.device
+    if labels is None:
+        labels = torch.full((n,), -1, dtype=torch.int64, device=dev)
+    elif labels.dtype != torch.int64 or labels.shape != (n,) or labels.device != dev or not labels.is_contiguous():
+        raise ValueError("kmeans_assign: labels must be a contiguous int64 [N] on the points' device")
+    mind = torch.empty(n, dtype=torch.float32, device=dev)
+    counts = torch.empty(k, dtype=torch.int64, device=dev) if want_sums else None
+    sums = torch.empty(k, d, dtype=torch.float64, device=dev) if want_sums else None
+    stats = _f64(4, dev)
+    scratch = _f64((int(_lib.load().igcn_kmeans_scratch_floats(n, d, k)) + 1) // 2, dev)      # (8-byte aligned)
+    call("igcn_kmeans_assign", n, d, k, ptr(x), ptr(centers), ptr(labels), ptr(mind), ptr(counts), ptr(sums), ptr(stats),
+         ptr(scratch), stream_ptr())
+    return labels, mind, counts, sums, stats
+
+
+def kmeans_update(x, centers, labels, mind, counts, sums, stats):
+    """New centres from an assignment's counts and sums, IN PLACE on ``centers`` (igcn_kmeans_update: sklearn's rule for
+    empty clusters); ``stats[2]`` receives the total squared centre shift, ``stats[3]`` 1.0 when the assignment changed a
+    label, else 0.0."""
+    x = cl_matrix(x, "kmeans_update", 1, KMEANS_MAX_N, KMEANS_MAX_D)
+    if not centers.is_contiguous():
+        raise ValueError("kmeans_update: the centres are updated in place and must be contiguous")
+    _km_centers(x, centers, "kmeans_update")
+    call("igcn_kmeans_update", x.shape[0], x.shape[1], centers.shape[0], ptr(x), ptr(labels), ptr(mind), ptr(counts),
+         ptr(sums), ptr(centers), ptr(stats), stream_ptr())
+    return centers
+
+
+def kmeanspp_step(x, u, closest, pot, chosen):
+    """One greedy k-means++ step (igcn_kmeanspp_step): ``u`` float64 [t] uniform numbers on the device; ``closest`` [N]
+    float32, ``pot`` float64 [1] and ``chosen`` int64 [1] are updated in place."""
+    x = cl_matrix(x, "kmeanspp_step", 1, KMEANS_MAX_N, KMEANS_MAX_D)
+    if u.dtype != torch.float64 or u.dim() != 1 or not 1 <= u.numel() <= 8 or u.device != x.device:
+        raise ValueError("kmeanspp_step: u must hold 1..8 float64 numbers on the points' device")
+    call("igcn_kmeanspp_step", x.shape[0], x.shape[1], int(u.numel()), ptr(x), ptr(u.contiguous()), ptr(closest), ptr(pot),
+         ptr(chosen), stream_ptr())

@@ -31,7 +31,7 @@ extern "C" {
 /* ABI revision: bumped whenever a prototype below changes (argument added, removed or re-ordered).  igcn_version()
  * returns the revision the library was built from; a binding written against a different one must refuse to call
  * (igcn_amd/_lib.py does). */
-#define IGCN_ABI_VERSION 437
+#define IGCN_ABI_VERSION 438
 int igcn_version(void);
 const char* igcn_last_error(void);
 /* A/B switches, set ONCE by the binding when it loads the library (from the IGCN_* environment variables): bit 0 no tiled
@@ -1401,6 +1401,53 @@ int igcn_knn_impute(int64_t S, int F, int k, const float* X, const int64_t* rows
                     const int64_t* rows_q, int64_t n_q, const float* means, const float* scale, const float* shift,
                     const int32_t* sel, int n_sel, int scatter, float* out_full, float* out_sel, int32_t* donors,
                     int64_t* status, float* scratch, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Cluster labels (csrc/tsne.hip, csrc/kmeans.hip): util/image_cluster.py:148-282 — sklearn's exact t-SNE of the image
+ * features (tsne_fdim), KMeans on the embedding (clust_y) and the inertia curve (calculate_WSS), restated on fp32 device
+ * tensors.  4 <= S <= 4096 subjects, 1 <= D <= 1024 features, 2 embedding dimensions; KMeans: 1 <= N <= 65536 points of
+ * width 1 <= d <= 1024, 1 <= k <= 16 clusters.  No atomics, one writer per element, fixed-order reductions.
+ * igcn_tsne_sqdist: dist [S, S] = squared Euclidean distances of X [S, D] by direct differences (fp32 fma chain in feature
+ *   order; dist[i][j] and dist[j][i] hold the same bits, the diagonal is exactly 0).
+ * igcn_tsne_joint_p: _binary_search_perplexity (fp64, at most 100 bisection steps on beta against log(perplexity),
+ *   tolerance 1e-5, row sums floored at 1e-8) and _joint_probabilities (symmetrised, divided by the total, clamped at
+ *   double epsilon, rounded once to fp32) -> P [S, S] with a zero diagonal, betas [S] fp64 (the beta each row's P was
+ *   evaluated at), pstats [2] fp64 = (sum P log P, sum P) of the stored P.  scratch: igcn_tsne_joint_p_scratch_doubles(S).
+ *   dist must be symmetric bit for bit (igcn_tsne_sqdist's is): the symmetrising pass reads d_ji as d_ij.
+ * igcn_tsne_grad: rowacc [5, S] = per row i the sums over j of P_ij num_ij (y_i - y_j) (x, y), num_ij^2 (y_i - y_j) (x, y)
+ *   and num_ij (j != i), num_ij = 1 / (1 + |y_i - y_j|^2), in fp32 from Y [S, 2].  want_kl: a second launch writes
+ *   klpart [S] fp64 = sum_{j != i} P_ij log max(num_ij / Z, eps) with Z reduced from rowacc as the update reduces it.
+ * igcn_tsne_update: grad = 4 (exaggeration attr - rep / Z) and sklearn's _gradient_descent step in place: gains + 0.2
+ *   where update grad < 0, else x 0.8, floored at 0.01; update = momentum update - lr gains grad; Y += update.
+ *   grad_out [S, 2] (or NULL) receives grad.  check: status [4] fp64 = (KL divergence of the exaggerated P, norm of
+ *   gains grad, Z, status[3] + 1); requires klpart of a want_kl pass over the same Y and pstats.
+ * igcn_kmeans_assign: labels [N] int64 = the nearest of centers [k, d] (direct differences; ties to the lower centre),
+ *   mind [N] = the squared distance to it; counts [k] int64 and sums [k, d] fp64 (both or neither) per cluster, summed per
+ *   workgroup of 64 points and combined in workgroup order; stats[0] = inertia, stats[1] = the number of labels that differ
+ *   from what `labels` held on entry (stats: [4] fp64).  scratch: igcn_kmeans_scratch_floats(N, d, k), 8-byte aligned.
+ * igcn_kmeans_update: centers <- sums / counts; clusters that came empty, in ascending order, take the points farthest
+ *   from their own centre in descending order (ties: the lower point); sums is updated accordingly; a cluster left
+ *   without points takes the centre of the largest one.  stats[2] = the total squared centre shift, stats[3] = 1 when
+ *   the assignment before it changed a label (stats[1] != 0), else 0.
+ * igcn_kmeanspp_step: one greedy k-means++ step from closest [N] (squared distance to the nearest chosen centre), pot [1]
+ *   fp64 (their sum) and u [t] fp64 uniform numbers on the device, 1 <= t <= 8: candidates = left search of u_c pot in the
+ *   fp64 inclusive scan of closest, clipped to N - 1; the candidate with the smallest new potential (ties: the first) is
+ *   written to chosen [1], closest and pot are updated in place. */
+int igcn_tsne_sqdist(int S, int D, const float* X, float* dist, void* stream);
+size_t igcn_tsne_joint_p_scratch_doubles(int S);
+int igcn_tsne_joint_p(int S, double perplexity, const float* dist, float* P, double* betas, double* pstats,
+                      double* scratch, void* stream);
+int igcn_tsne_grad(int S, int want_kl, const float* P, const float* Y, float* rowacc, double* klpart, void* stream);
+int igcn_tsne_update(int S, float exaggeration, float momentum, float lr, int check, const float* rowacc,
+                     const double* klpart, const double* pstats, float* Y, float* update, float* gains, float* grad_out,
+                     double* status, void* stream);
+size_t igcn_kmeans_scratch_floats(int64_t N, int d, int k);
+int igcn_kmeans_assign(int64_t N, int d, int k, const float* X, const float* centers, int64_t* labels, float* mind,
+                       int64_t* counts, double* sums, double* stats, float* scratch, void* stream);
+int igcn_kmeans_update(int64_t N, int d, int k, const float* X, const int64_t* labels, const float* mind,
+                       const int64_t* counts, double* sums, float* centers, double* stats, void* stream);
+int igcn_kmeanspp_step(int64_t N, int d, int t, const float* X, const double* u, float* closest, double* pot,
+                       int64_t* chosen, void* stream);
 
 #ifdef __cplusplus
 }
