@@ -11,34 +11,8 @@
 
 #include "common.h"
 
-// attn_mfma.hip
-size_t igcn_attn_mfma_lds_bytes(int D, int H, int Lq, int Lk, int backward);
-int igcn_attn_mfma_fwd(int B, int D, int H, int Lq, int Lk, const float* q, const float* kv, float* o, float* lse,
-                       hipStream_t st);
-int igcn_attn_mfma_bwd(int B, int D, int H, int Lq, int Lk, const float* q, const float* kv, const float* o,
-                       const float* lse, const float* dout, float* dq, float* dkv, hipStream_t st);
-size_t igcn_attn_mfma_chunked_scratch_floats(int B, int H, int Lq);
-int igcn_attn_mfma_fwd_chunked(int B, int D, int H, int Lq, int Lk, const float* q, const float* kv, float* o,
-                               float* lse, hipStream_t st);
-int igcn_attn_mfma_bwd_chunked(int B, int D, int H, int Lq, int Lk, const float* q, const float* kv, const float* o,
-                               const float* lse, const float* dout, float* dq, float* dkv, float* delta,
-                               hipStream_t st);
-int igcn_attn_mfma_weights_supported(int D, int H, int Lq, int Lk);
-int igcn_attn_mfma_weights_chunk_rows(int D, int H, int Lq, int Lk);
-int igcn_attn_mfma_weights(int B, int D, int H, int Lq, int Lk, const float* q, const float* kv, float* w,
-                           hipStream_t st);
-int igcn_attn_mfma_map_accumulate(int B, int Lq, int Lk, int C, const float* w, const int64_t* y, double* sums,
-                                  int64_t* counts, int64_t* state, hipStream_t st);
-
-// attn_split.hip: head_dim 16 on split bf16 operands (fp32-grade results, bf16 matrix rate) — the default for that width;
-// IGCN_ATTN_EXACT_FP32=1 keeps the exact-fp32 kernels
-extern "C" int igcn_attn_core_split_supported(int D, int H, int Lq, int Lk);
-extern "C" int igcn_attn_core_split_bwd_supported(int D, int H, int Lq, int Lk);
-extern "C" int igcn_attn_core_split_fwd(int B, int D, int H, int Lq, int Lk, const float* q, const float* kv, float* o,
-                                        float* lse, void* stream);
-extern "C" int igcn_attn_core_split_bwd(int B, int D, int H, int Lq, int Lk, const float* q, const float* kv,
-                                        const float* o, const float* lse, const float* dout, float* dq, float* dkv,
-                                        float* scratch, void* stream);
+// attn_split.hip (igcn_attn_core_split_*): head_dim 16 on split bf16 operands (fp32-grade results, bf16 matrix rate) —
+// the default for that width; IGCN_ATTN_EXACT_FP32=1 keeps the exact-fp32 kernels
 static bool aligned16(const void* a, const void* b, const void* c, const void* d) {
   return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 15) == 0;
 }

@@ -131,8 +131,6 @@ k_cluster_loss_final(const float* __restrict__ parts, int nparts, const float* _
 // the regulariser or its un-reduced partials, wts [5] DEVICE = {hp_ce, hp_mi, lambda0, B, predict_cluster}; out [8] = loss,
 // ce, ce_cluster, mi, mi_cluster, prob, recon, 0.  While the stream defers its reductions the job joins the flush as
 // igcn_loss_final's does (the same queue entry, told apart by its missing Gram partials); else a launch of its own.
-int igcn_queue_loss_final(const float* parts, int nparts, const float* gram, int gram_rows, const float* prob,
-                          int prob_rows, const float* wts, float* out, hipStream_t st);      // plan.hip
 extern "C" int igcn_cluster_loss_final(const float* parts, int nparts, const float* prob, int prob_rows, const float* wts,
                                        float* out, void* stream) {
   IGCN_REQUIRE(parts && nparts >= 1 && prob && prob_rows >= 1 && wts && out, "cluster_loss_final: bad arguments");

@@ -81,7 +81,7 @@ __device__ __forceinline__ float wave_sum_all(float v) {
 }
 
 // GO attention backward, output j of dparams [2 FOUT FIN + 3 FOUT] from the block partials gpart [(2 FOUT + 3) FIN][parts]
-// (go.hip k_go_attn_bwd_finish and, deferred, plan.hip k_multi_reduce: ONE body so that both give the same bits).  A
+// (go.hip k_go_attn_bwd_finish and, deferred, reduce.hip k_multi_reduce: ONE body so that both give the same bits).  A
 // weight-gradient output is one entry's sum, an attention-vector output the dot product of a weight row with FIN entry
 // sums; every entry is summed by ONE wave (lanes stride the partials, fixed tree), waves take entries d = w, w + nw, ...
 // G: >= FIN floats of LDS.  All threads of the workgroup must call (barrier inside).
@@ -184,3 +184,40 @@ int igcn_launch_reduce_rows_batched(const float* partial, int64_t rows, int64_t 
                                     int64_t p_batch, int64_t o_batch, hipStream_t st);
 int igcn_launch_reduce_rows_final(const float* partial, int64_t rows, int64_t ld, int n, float* out,
                                   hipStream_t st);
+
+// Work of other shapes as an entry of the same flush (pending.hip; performed by k_multi_reduce, reduce.hip): queued while
+// the stream defers (returns 1), else not handled here (returns 0: the caller launches its own kernel) — the loss value of
+// a train step from its partial sums (loss.hip: k_loss_final); the GO attention backward's dparams [2 FOUT FIN + 3 FOUT]
+// from gpart [(2 FOUT + 3) FIN][parts] (go.hip: k_go_attn_bwd_finish); out = parts[0] + ... + parts[k-1] (misc.hip: k_sum_n)
+int igcn_queue_loss_final(const float* parts, int nparts, const float* gram, int gram_rows, const float* prob,
+                          int prob_rows, const float* wts, float* out, hipStream_t st);
+int igcn_queue_go_finish(const float* gpart, int64_t parts, int fin, int fout, const float* w_inc, const float* w_s,
+                         float* dparams, hipStream_t st);
+int igcn_queue_sum_final(const float* const* parts, int k, int64_t numel, float* out, hipStream_t st);
+// The dropout job waiting on the stream, if any, for the launch that carries it (plan.hip, sgcn_fused.hip, sgcn_dense.hip)
+struct DropJob;
+bool igcn_rider_dropout_take(hipStream_t st, DropJob& job);
+
+// gemm.hip, for go.hip and readout.hip: igcn_gemm_f32_batched_sum on a stream handle
+int igcn_gemm_f32_batched_sum_impl(int64_t M, int64_t N, int64_t K, int batch, const float* A, int64_t sam,
+                                   int64_t sak, int64_t a_batch, const float* B, int64_t sbn, int64_t sbk,
+                                   int64_t b_batch, float* C, int64_t ldc, float* scratch, hipStream_t st);
+
+// attn_mfma.hip, for the shape dispatch of attn_core.hip
+size_t igcn_attn_mfma_lds_bytes(int D, int H, int Lq, int Lk, int backward);
+int igcn_attn_mfma_fwd(int B, int D, int H, int Lq, int Lk, const float* q, const float* kv, float* o, float* lse,
+                       hipStream_t st);
+int igcn_attn_mfma_bwd(int B, int D, int H, int Lq, int Lk, const float* q, const float* kv, const float* o,
+                       const float* lse, const float* dout, float* dq, float* dkv, hipStream_t st);
+size_t igcn_attn_mfma_chunked_scratch_floats(int B, int H, int Lq);
+int igcn_attn_mfma_fwd_chunked(int B, int D, int H, int Lq, int Lk, const float* q, const float* kv, float* o,
+                               float* lse, hipStream_t st);
+int igcn_attn_mfma_bwd_chunked(int B, int D, int H, int Lq, int Lk, const float* q, const float* kv, const float* o,
+                               const float* lse, const float* dout, float* dq, float* dkv, float* delta,
+                               hipStream_t st);
+int igcn_attn_mfma_weights_supported(int D, int H, int Lq, int Lk);
+int igcn_attn_mfma_weights_chunk_rows(int D, int H, int Lq, int Lk);
+int igcn_attn_mfma_weights(int B, int D, int H, int Lq, int Lk, const float* q, const float* kv, float* w,
+                           hipStream_t st);
+int igcn_attn_mfma_map_accumulate(int B, int Lq, int Lk, int C, const float* w, const int64_t* y, double* sums,
+                                  int64_t* counts, int64_t* state, hipStream_t st);

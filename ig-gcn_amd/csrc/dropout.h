@@ -2,22 +2,7 @@
 // RIDE in (plan.hip: the per-graph plan build; igcn_rider_dropout).
 #pragma once
 #include "common.h"
-
-#define DM_MAXSEG 32
-struct DropSegs {
-  int64_t end[DM_MAXSEG];
-  float p[DM_MAXSEG];
-  int n;
-};
-// int64 device counters the launch bumps by `inc` (BatchNorm's num_batches_tracked of the model's five BatchNorms: the
-// masks are drawn once per training forward, which is exactly when those counters advance — a torch._foreach_add_
-// launch less per step)
-#define DM_MAXCNT 8
-struct DropCounters {
-  long long* c[DM_MAXCNT];
-  int n;
-  long long inc;
-};
+#include "dropout_job.h"
 
 __device__ __forceinline__ uint32_t dm_hash(uint32_t x) {       // lowbias32
   x ^= x >> 16; x *= 0x7feb352dU;
@@ -79,16 +64,6 @@ __device__ __forceinline__ void dropout_masks_body(unsigned blk, unsigned nblk, 
   }
 }
 
-
-// one mask-generation job as the host hands it over (igcn_dropout_masks / igcn_rider_dropout)
-struct DropJob {
-  int64_t total;
-  DropSegs sg;
-  unsigned long long* state;
-  float* out;
-  DropCounters cnt;
-  unsigned blocks;
-};
 int igcn_dropout_launch(const DropJob& job, hipStream_t st);
 int igcn_dropout_job(DropJob& job, const char* who, int64_t total, int n_segments, const int64_t* seg_end, const float* seg_p,
                      void* state, float* out, int n_counters, int64_t* const* counters, int64_t counter_inc);

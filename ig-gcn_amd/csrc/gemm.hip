@@ -7,6 +7,7 @@
 // gradient) and TN (weight gradient) all read global memory coalesced.  Long-K / few-tile problems are split over gridDim.z into partial
 // slabs that a second kernel sums in slab order (deterministic).
 #include "common.h"
+#include "pending.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -289,7 +290,6 @@ k_gemm_f32(int64_t M, int64_t N, int64_t K, const float* __restrict__ A, int64_t
 // the upstream gradient and nothing else): the workgroups of all problems form one flat grid, so the small grids of a
 // backward pass fill the chip together instead of one after the other.  Tile width, vector width and pipeline depth are
 // common to the group (host: the narrowest / safest of the members); the operand layouts are per problem.
-#define GG_MAX 4
 struct GemmProb {
   int64_t M, N, K;
   const float* A; int64_t sam, sak;
@@ -753,10 +753,6 @@ extern "C" int igcn_gemm_bf16(int64_t M, int64_t N, int64_t K, const float* A, i
 
 // sum_z A_z . B_z^T : gridDim.z = batch, every z covers the whole K; slabs reduced in z order.
 // Used for weight gradients whose reduction index is (sample, node) with a non-affine address (channel-major x).
-int igcn_gemm_f32_batched_sum_impl(int64_t M, int64_t N, int64_t K, int batch, const float* A, int64_t sam,
-                                   int64_t sak, int64_t a_batch, const float* B, int64_t sbn, int64_t sbk,
-                                   int64_t b_batch, float* C, int64_t ldc, float* scratch, hipStream_t st);
-
 extern "C" int igcn_gemm_f32_batched_sum(int64_t M, int64_t N, int64_t K, int batch, const float* A, int64_t sam,
                                          int64_t sak, int64_t a_batch, const float* B, int64_t sbn, int64_t sbk,
                                          int64_t b_batch, float* C, int64_t ldc, float* scratch, void* stream) {
@@ -833,71 +829,7 @@ static size_t gemm_lds_bytes(int bn, int64_t k_per_split, bool a_rfast, bool b_r
 // other — the heads' first layers (lin1 | lin1_regr) and the per-pass Gram matrices of the batch losses — but are issued
 // by different parts of the host code (the model's forward; the loss function).  The later one is QUEUED before the
 // earlier one launches (igcn_gemm_rider, same table format) and joins its grid: one launch of four products instead of
-// two launches of two.  igcn_gemm_rider_flush launches products nobody carried.
-#include <map>
-#include <mutex>
-#include <vector>
-static std::mutex g_gr_mutex;
-static std::map<hipStream_t, std::vector<int64_t>> g_gemm_riders;      // 16 words per product
-
-extern "C" int igcn_gemm_rider(void* stream, int n, const int64_t* table) {
-  IGCN_REQUIRE(n >= 1 && n <= GG_MAX && table != nullptr, "gemm_rider: 1..%d products", GG_MAX);
-  std::lock_guard<std::mutex> lk(g_gr_mutex);
-  std::vector<int64_t>& q = g_gemm_riders[(hipStream_t)stream];
-  IGCN_REQUIRE(q.size() / 16 + (size_t)n <= GG_MAX, "gemm_rider: more than %d products waiting on this stream", GG_MAX);
-  q.insert(q.end(), table, table + 16 * n);
-  return IGCN_OK;
-}
-
-static std::vector<int64_t> gemm_riders_take(hipStream_t st, int room, bool bf16) {
-  std::lock_guard<std::mutex> lk(g_gr_mutex);
-  auto it = g_gemm_riders.find(st);
-  std::vector<int64_t> r;
-  if (it == g_gemm_riders.end()) return r;
-  // carried only whole, and only by a launch of the same operand type (the table's word 15)
-  if ((int)(it->second.size() / 16) <= room && (it->second[15] != 0) == bf16) {
-    r.swap(it->second);
-    g_gemm_riders.erase(it);
-  }
-  return r;
-}
-
-void igcn_rider_dropout_cancel(hipStream_t st);         // plan.hip
-// Forget every rider still waiting on the stream (mask job and products) WITHOUT launching it: for the start of a step
-// that may follow one which failed between queueing a rider and the launch that would have carried it — the buffers it
-// points at may be gone.
-extern "C" int igcn_rider_cancel(void* stream) {
-  igcn_rider_dropout_cancel((hipStream_t)stream);
-  std::lock_guard<std::mutex> lk(g_gr_mutex);
-  g_gemm_riders.erase((hipStream_t)stream);
-  return IGCN_OK;
-}
-
-// Everything the library still holds for `stream` on the host side and has NOT launched: deferred reductions (entries),
-// the dropout rider (0 / 1), product riders (products).  0 at the end of every step; see the header for each queue's
-// ordering contract.
-int igcn_reduce_pending_on(hipStream_t st);            // plan.hip
-int igcn_rider_dropout_waiting(hipStream_t st);        // plan.hip
-extern "C" int igcn_stream_pending(void* stream) {
-  int n = igcn_reduce_pending_on((hipStream_t)stream) + igcn_rider_dropout_waiting((hipStream_t)stream);
-  std::lock_guard<std::mutex> lk(g_gr_mutex);
-  auto it = g_gemm_riders.find((hipStream_t)stream);
-  if (it != g_gemm_riders.end()) n += (int)(it->second.size() / 16);
-  return n;
-}
-
-extern "C" int igcn_gemm_f32_grouped(int n, const int64_t* table, void* stream);
-extern "C" int igcn_gemm_rider_flush(void* stream) {
-  std::vector<int64_t> r;
-  {
-    std::lock_guard<std::mutex> lk(g_gr_mutex);
-    auto it = g_gemm_riders.find((hipStream_t)stream);
-    if (it == g_gemm_riders.end()) return IGCN_OK;
-    r.swap(it->second);
-    g_gemm_riders.erase(it);
-  }
-  return igcn_gemm_f32_grouped((int)(r.size() / 16), r.data(), stream);
-}
+// two launches of two.  igcn_gemm_rider_flush launches products nobody carried.  (Kept by pending.h, as is GG_MAX.)
 
 // The plan of a grouped launch: every member's own plan (K slices, layouts, slab sum), and the tile width, vector width
 // and pipeline depth common to the launch — the narrowest tile, the narrowest loads, the deepest pipeline any member
@@ -937,7 +869,7 @@ extern "C" int igcn_gemm_f32_grouped(int n, const int64_t* table, void* stream) 
   hipStream_t st = (hipStream_t)stream;
   int64_t merged[16 * GG_MAX];
   {
-    const std::vector<int64_t> r = gemm_riders_take(st, GG_MAX - n, table[15] != 0);
+    const std::vector<int64_t> r = pending::take_products(st, GG_MAX - n, table[15] != 0);
     if (!r.empty()) {                                  // the queued products join this launch
       for (int i = 0; i < 16 * n; ++i) merged[i] = table[i];
       for (size_t i = 0; i < r.size(); ++i) merged[16 * n + i] = r[i];

@@ -1031,10 +1031,6 @@ k_go_attn_bwd_main(int B, int N, const int32_t* __restrict__ row_ptr, const int3
   }
 }
 
-int igcn_gemm_f32_batched_sum_impl(int64_t M, int64_t N, int64_t K, int batch, const float* A, int64_t sam,
-                                   int64_t sak, int64_t a_batch, const float* B, int64_t sbn, int64_t sbk,
-                                   int64_t b_batch, float* C, int64_t ldc, float* scratch, hipStream_t st);
-
 extern "C" size_t igcn_go_attn_bwd_scratch_floats(int B, int N, int fin, int fout) {
   // channel-major kernels: statistics [B,N] float4 + one partial per wave; the LDS-resident kernel needs only one
   // partial per sample, which is less
@@ -1604,9 +1600,6 @@ extern "C" int igcn_go_attn_walk_order(int N, int fin, int fout, const int32_t* 
 // IGCN_GO_ATTN_CM=1 (A/B runs): the global-memory kernels (attention backward, decoder forward / backward) even when a
 // sample fits LDS — these are also the fallbacks for hierarchies too large for LDS
 static bool go_attn_force_cm(void) { return igcn_opt(IGCN_OPT_GO_ATTN_CM); }
-
-int igcn_queue_go_finish(const float* gpart, int64_t parts, int fin, int fout, const float* w_inc, const float* w_s,
-                         float* dparams, hipStream_t st);                                       // plan.hip
 
 static bool go_ln_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 static bool go_attn_bwd_in_lds(int N, int fin, int fout) {

@@ -724,8 +724,6 @@ extern "C" int igcn_head_loss_gram_fwd(int B, int K, int C, int NR, int S, const
 
 // The loss value from its partial sums (loss_final.h): wts [10] DEVICE = {lam[0..5], hp_ce, hp_mi, B, NR}; out [8] = loss,
 // terms[7].  While the stream defers its reductions (igcn_reduce_defer) the job joins the flush; else a launch of its own.
-int igcn_queue_loss_final(const float* parts, int nparts, const float* gram, int gram_rows, const float* prob,
-                          int prob_rows, const float* wts, float* out, hipStream_t st);      // plan.hip
 extern "C" int igcn_loss_final(const float* parts, int nparts, const float* gram, int gram_rows, const float* prob,
                                int prob_rows, const float* wts, float* out, void* stream) {
   IGCN_REQUIRE(parts && nparts >= 1 && gram && gram_rows >= 1 && prob && prob_rows >= 1 && wts && out &&

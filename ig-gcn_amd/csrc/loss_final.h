@@ -3,7 +3,7 @@
 // loss kernel (rows of [consist_1, orth_1, consist_2, orth_2]) and the mask regulariser (loss_probability's partials):
 // column sums, the seven lam-weighted terms and their weighted sum.  Nothing of the backward depends on it (every
 // gradient is known where its term is computed), so it runs wherever a workgroup is free: as an entry of the backward's
-// deferred flush (k_multi_reduce, plan.hip) or as a launch of its own (k_loss_final, loss.hip).
+// deferred flush (k_multi_reduce, reduce.hip) or as a launch of its own (k_loss_final, loss.hip).
 #pragma once
 #include "common.h"
 

@@ -549,7 +549,6 @@ extern "C" int igcn_sum_n(int64_t numel, int n, const float* const* parts /*HOST
 // igcn_sum_n for a gradient nothing reads before the optimiser (a LEAF with several consumers): joins the deferred
 // final reductions (igcn_reduce_defer / igcn_reduce_flush) when they are on — the buffers must then stay alive until
 // the flush — and is igcn_sum_n otherwise.  Same summation order either way.
-int igcn_queue_sum_final(const float* const* parts, int k, int64_t numel, float* out, hipStream_t st);   // plan.hip
 extern "C" int igcn_sum_n_final(int64_t numel, int n, const float* const* parts /*HOST array*/, float* out,
                                 void* stream) {
   IGCN_REQUIRE(numel >= 0 && n >= 1 && n <= 4 && parts && out, "sum_n_final: 1..4 parts");

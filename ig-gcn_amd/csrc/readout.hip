@@ -1053,10 +1053,6 @@ extern "C" int igcn_node_linear_bn_apply_map_fwd(int B, int F, int N, int groups
   return IGCN_OK;
 }
 
-int igcn_gemm_f32_batched_sum_impl(int64_t M, int64_t N, int64_t K, int batch, const float* A, int64_t sam,
-                                   int64_t sak, int64_t a_batch, const float* B, int64_t sbn, int64_t sbk,
-                                   int64_t b_batch, float* C, int64_t ldc, float* scratch, hipStream_t st);
-
 extern "C" size_t igcn_node_linear_bn_bwd_scratch_floats(int B, int F, int N, int D, int groups) {
   const size_t cpg = ro_cpg(B, groups);
   const size_t stats = (size_t)groups * cpg * 2 * N + (size_t)groups * 2 * N;

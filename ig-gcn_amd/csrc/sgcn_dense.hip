@@ -30,8 +30,6 @@
 #include "common.h"
 #include "dropout.h"
 
-bool igcn_rider_dropout_take(hipStream_t st, DropJob& job);        // plan.hip
-
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #define DS_F 16

@@ -877,8 +877,6 @@ extern "C" size_t igcn_sgcn_front_lds_bytes(int R, int max_edges, int H0, int F,
   return (size_t)sf_layout(R, max_edges, H0, F, L, 0, 1).total * 4;
 }
 
-bool igcn_rider_dropout_take(hipStream_t st, DropJob& job);        // plan.hip
-
 // The front of the image branch of a train step (see k_sgcn_front_fwd): plan of the batch + of its 2-copy replica, the
 // stacked (plain | masked) inputs x_in [2N, H0] / ew_in [2E], the edge mask e [E], loss_probability as reg_partial
 // [n_graphs] (their sum), the SNP mask snps_full [2 n_graphs, n_snps], and xcat [2N, L F] — one launch, which also

@@ -681,7 +681,8 @@ int igcn_rider_cancel(void* stream);
  * A rider is only ever picked up by the entry point named above: any other launch on the stream passes it by, so the
  * caller issues rider -> (independent launches) -> carrier or flush and must not read the rider's outputs before that.
  * igcn_rider_cancel forgets 2 and 3 without launching (start of a step that may follow a failed one).
- * igcn_stream_pending(stream) = entries of 1 + jobs of 2 + products of 3 still waiting on that stream. */
+ * igcn_stream_pending(stream) = entries of 1 + jobs of 2 + products of 3 still waiting on that stream.
+ * Implementation: ig-gcn_amd/csrc/pending.h — one record per stream for all three, one map, one lock. */
 int igcn_stream_pending(void* stream);
 
 /* ------------------------------------------------------------------------------------------------

@@ -472,7 +472,7 @@ def test_gemm_is_exact_fp32_fma_chain(ops):
 
 
 def test_final_reductions_deferred_and_immediate_give_the_same_bits(ops):
-    """Every form of the partial-row sums (plan.hip rr_form: in-order thread per column, 16-byte wide, wave per column,
+    """Every form of the partial-row sums (reduce.hip rr_form: in-order thread per column, 16-byte wide, wave per column,
     16 x 16 tiles, four row groups) — launched on its own and as one entry of the deferred launch (k_multi_reduce) —
     against an fp64 sum, and bit-identical between the two ways."""
     import ctypes
@@ -546,6 +546,93 @@ def test_deferred_reductions_are_kept_per_stream(ops):
             with torch.cuda.stream(s2):
                 assert not ops._DEFER["on"]                             # another stream: its own state
         assert not ops._DEFER["on"]
+
+
+def _reduce_rows_final(lib):
+    import ctypes
+    fn = lib.igcn_debug_reduce_rows_final
+    fn.restype = ctypes.c_int
+    fn.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    return fn
+
+
+def test_stream_pending_counts_all_three_queues(ops):
+    """The three host-side queues of one stream (csrc/pending.h) held at once: igcn_stream_pending counts entries + job +
+    products of THAT stream, igcn_rider_cancel forgets the riders without launching them and leaves the reductions, and
+    the reductions flushed afterwards are the immediate launch's bits."""
+    from igcn_amd import _lib
+    lib = _lib.load()
+    fn = _reduce_rows_final(lib)
+    side, other = torch.cuda.Stream(), torch.cuda.Stream()
+    sp = side.cuda_stream
+    torch.manual_seed(11)
+    parts = [torch.randn(4, 8, device="cuda") for _ in range(2)]
+    now = [torch.full((8,), 7.0, device="cuda") for _ in range(2)]
+    later = [torch.full((8,), 9.0, device="cuda") for _ in range(2)]
+    a, b = torch.randn(16, 16, device="cuda"), torch.randn(16, 16, device="cuda")
+    prod = torch.full((16, 16), -3.0, device="cuda")
+    state = ops.DropoutState("cuda")
+    torch.cuda.synchronize()
+    with torch.cuda.stream(side):
+        for p, o in zip(parts, now):                                    # immediate
+            assert fn(p.data_ptr(), 4, 8, 8, o.data_ptr(), sp) == 0
+        assert lib.igcn_reduce_defer(sp, 1) == 0
+        try:
+            for p, o in zip(parts, later):
+                assert fn(p.data_ptr(), 4, 8, 8, o.data_ptr(), sp) == 0
+            (mask,) = ops.dropout_masks([((8,), 0.5)], state, ride=True)
+            mask.fill_(-3.0)
+            _, hold = ops.gemm_group([("nt", a, b, prod, None, False)], ride=True)
+            assert lib.igcn_stream_pending(sp) == 4 and lib.igcn_stream_pending(other.cuda_stream) == 0
+            assert lib.igcn_rider_cancel(sp) == 0
+            assert lib.igcn_stream_pending(sp) == 2
+            assert lib.igcn_rider_flush(sp) == 0 and lib.igcn_gemm_rider_flush(sp) == 0   # nothing waits: no launch
+            assert lib.igcn_reduce_defer(sp, 0) == 0
+            assert lib.igcn_stream_pending(sp) == 2                     # queued entries outlive the defer mode
+            assert lib.igcn_reduce_flush(sp) == 0
+            assert lib.igcn_stream_pending(sp) == 0 and lib.igcn_reduce_pending() == 0
+        finally:
+            lib.igcn_rider_cancel(sp)
+            lib.igcn_reduce_defer(sp, 0)
+            lib.igcn_reduce_flush(sp)
+    side.synchronize()
+    assert bool((mask == -3.0).all()) and bool((prod == -3.0).all())    # the cancelled riders never ran
+    for p, o1, o2 in zip(parts, now, later):
+        assert torch.equal(o1, o2) and torch.allclose(o1, p.sum(0), atol=1e-5)
+
+
+def test_flush_beyond_one_table_ticks_once(ops):
+    """50 queued entries = two launches of the deferred kernel (48 per table): all of them are performed, bit-equal to
+    the immediate launches, and the step counter advances by exactly 1 — as it does for a flush with nothing queued."""
+    from igcn_amd import _lib
+    lib = _lib.load()
+    fn = _reduce_rows_final(lib)
+    side = torch.cuda.Stream()
+    sp = side.cuda_stream
+    torch.manual_seed(12)
+    parts = torch.randn(50, 2, 4, device="cuda")
+    now, later = torch.full((50, 4), 7.0, device="cuda"), torch.full((50, 4), 9.0, device="cuda")
+    tick = torch.zeros(1, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    with torch.cuda.stream(side):
+        for k in range(50):                                             # immediate
+            assert fn(parts[k].data_ptr(), 2, 4, 4, now[k].data_ptr(), sp) == 0
+        assert lib.igcn_reduce_defer(sp, 1) == 0
+        try:
+            for k in range(50):
+                assert fn(parts[k].data_ptr(), 2, 4, 4, later[k].data_ptr(), sp) == 0
+            assert lib.igcn_stream_pending(sp) == 50
+            assert lib.igcn_reduce_flush_tick(sp, tick.data_ptr()) == 0
+            assert lib.igcn_stream_pending(sp) == 0
+            side.synchronize()
+            assert int(tick) == 1
+            assert lib.igcn_reduce_flush_tick(sp, tick.data_ptr()) == 0   # nothing queued: the tick alone
+            side.synchronize()
+            assert int(tick) == 2
+        finally:
+            lib.igcn_reduce_defer(sp, 0)
+            lib.igcn_reduce_flush(sp)
+    assert torch.equal(now, later) and torch.allclose(now, parts.sum(1), atol=1e-5)
 
 
 # ------------------------------------------------------------------------------------------------ GO ops
