@@ -14,7 +14,7 @@ from . import switches
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libigcn.so")
 
-ABI_VERSION = 438      # include/igcn.h IGCN_ABI_VERSION this table was written against (tests/test_abi.py compares)
+ABI_VERSION = 439      # include/igcn.h IGCN_ABI_VERSION this table was written against (tests/test_abi.py compares)
 
 P, I, L, F, Z = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
 
@@ -243,6 +243,8 @@ SIGNATURES = {
     "igcn_gdc_topk_max_rois": (I, []),
     "igcn_gdc_topk": (I, [I, I, I, ctypes.c_double, P, P, P, P, P]),
     "igcn_gdc_topk_of": (I, [I, I, I, ctypes.c_double, P, L, P, P, P, P, P]),
+    "igcn_gdc_max_rois": (I, [I]),
+    "igcn_gdc_diffuse": (I, [I, I, I, ctypes.c_double, I, I, ctypes.c_double, P, L, P, P, P, P, P]),
     "igcn_eval_collect": (I, [I, I, I, I, I, P, P, P, P, P, P, P, P, L, P, P, P, P, P, P, P, P, P, P, P]),
     "igcn_eval_metrics": (I, [L, I, I, P, P, P, P, P, P, P, P, P, P]),
     "igcn_knn_impute_stats": (I, [L, I, P, P, L, P, P, P]),

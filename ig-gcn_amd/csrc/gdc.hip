@@ -4,7 +4,12 @@
 //                                         column by its sum (columns whose sum is <= 0 are left unscaled)
 //   util_gdc.py:82-86  coo_matrix(A_res)  non-zeros in row-major order, edge_index = [row; col], edge_attr = f32
 // plus the block-diagonal node offset of Batch.from_data_list (batch.py:98-104): graph g's indices are shifted by g*R.
+// The other kernel and the other sparsifier of util_gdc.py share the selection and the emission (igcn_gdc_diffuse):
+//   util_gdc.py:16-23  get_heat_matrix     S = expm(-t (I - D^-1/2 A D^-1/2))            -> k_gdc_heat, further down
+//   util_gdc.py:33-38  get_clipped_matrix  keep the entries >= eps, divide each column by the sum of what it kept
+//                                          (R slots per column instead of k)
 //
+// The PPR kernel (k_gdc_ppr):
 // One workgroup per graph; the R x R system lives in LDS in fp64 (the reference computes in numpy float64 and the
 // top-k SELECTION must not flip on rounding), inverted in place by Gauss-Jordan elimination with partial pivoting.
 // Graph g owns the output slots [g*R*k, (g+1)*R*k): entries in (row, col) order, then (-1, -1, 0) padding when
@@ -69,11 +74,145 @@ extern "C" int igcn_debug_gdc_probe(long long* out) {
 #define GDC_LAP_END
 #endif
 
+// ---- shared by the PPR and the heat kernel: what is kept of the diffusion matrix, and its COO image -----------------
+// How the diffusion matrix S = scale * M is sparsified (igcn.h IGCN_GDC_TOPK / IGCN_GDC_THRESHOLD) and where graph g's
+// edges go: `cap` slots per column (k for top-k, R for the threshold).
+struct GdcSparsify {
+  int mode, k, cap;
+  double eps;
+};
+
+// a graph that is not read (subject index outside the dataset): all slots padding, count 0
+__device__ __forceinline__ void gdc_emit_empty(int g, int R, int cap, int64_t* __restrict__ ei_row,
+                                               int64_t* __restrict__ ei_col, float* __restrict__ ew,
+                                               int32_t* __restrict__ counts) {
+  const int tid = threadIdx.x;
+  const int64_t s0 = (int64_t)g * R * cap;
+  for (int64_t t = s0 + tid; t < s0 + (int64_t)R * cap; t += GDC_T) {
+    ei_row[t] = -1;
+    ei_col[t] = -1;
+    ew[t] = 0.f;
+  }
+  if (tid == 0) counts[g] = 0;
+}
+
+// Selection per column, column normalisation and COO emission of graph g.  M [R][ld] (LDS, fp64) holds the diffusion
+// matrix up to the factor `scale` and is complete (a barrier lies behind its last write); rowmask [128][2] is zero;
+// rowcnt [R+2].  Called by all GDC_T threads.  Every output slot of the graph has exactly one writer.
+__device__ __forceinline__ void gdc_select_emit(double* M, int ld, int R, double scale, GdcSparsify sp,
+                                                unsigned long long* rowmask, int* rowcnt, int g,
+                                                int64_t* __restrict__ ei_row, int64_t* __restrict__ ei_col,
+                                                float* __restrict__ ew, int32_t* __restrict__ counts) {
+  const int tid = threadIdx.x, k = sp.k;
+  // ---- per column (thread = column): the rows that stay as a bit set, their final weights in place --------------
+  // top-k, order of preference: larger value, then LARGER row (a stable ascending argsort keeps the later of two equals)
+  unsigned long long tk0 = 0ull, tk1 = 0ull;           // rows of this column that stay
+  if (tid < R) {
+    const int j = tid;
+    double norm = 0.0;
+    if (sp.mode == IGCN_GDC_THRESHOLD) {
+      // util_gdc.py:33-38: entries below eps are zeroed, the column is divided by the sum of the rest (rows ascending)
+      for (int i = 0; i < R; ++i) {
+        const double v = scale * M[i * ld + j];
+        if (v >= sp.eps) {
+          norm += v;
+          if (i < 64) tk0 |= 1ull << i; else tk1 |= 1ull << (i - 64);
+        }
+      }
+    } else if (k <= 4) {
+      // one sweep with the best four in registers: rows arrive in ascending order, so a newcomer beats an equal value
+      double v0 = -HUGE_VAL, v1 = -HUGE_VAL, v2 = -HUGE_VAL, v3 = -HUGE_VAL;
+      int b0 = -1, b1 = -1, b2 = -1, b3 = -1;
+#pragma unroll 4
+      for (int i = 0; i < R; ++i) {
+        const double v = scale * M[i * ld + j];
+        if (v >= v3) {
+          if (v >= v2) {
+            v3 = v2; b3 = b2;
+            if (v >= v1) {
+              v2 = v1; b2 = b1;
+              if (v >= v0) { v1 = v0; b1 = b0; v0 = v; b0 = i; } else { v1 = v; b1 = i; }
+            } else { v2 = v; b2 = i; }
+          } else { v3 = v; b3 = i; }
+        }
+      }
+      const double vs[4] = {v0, v1, v2, v3};
+      const int bs[4] = {b0, b1, b2, b3};
+#pragma unroll
+      for (int s2 = 0; s2 < 4; ++s2)
+        if (s2 < k && bs[s2] >= 0) {
+          norm += vs[s2];
+          if (bs[s2] < 64) tk0 |= 1ull << bs[s2]; else tk1 |= 1ull << (bs[s2] - 64);
+        }
+    } else {
+      for (int s2 = 0; s2 < k && s2 < R; ++s2) {
+        double best = 0.0;
+        int bi = -1;
+        for (int i = 0; i < R; ++i) {
+          const double v = scale * M[i * ld + j];
+          const bool taken = ((i < 64 ? tk0 >> i : tk1 >> (i - 64)) & 1ull) != 0;
+          if (!taken && (bi < 0 || v >= best)) { best = v; bi = i; }
+        }
+        if (bi < 64) tk0 |= 1ull << bi; else tk1 |= 1ull << (bi - 64);
+        norm += best;
+      }
+    }
+    const double den = (norm <= 0.0) ? 1.0 : norm;
+    for (int h = 0; h < 2; ++h) {
+      unsigned long long m = h ? tk1 : tk0;
+      while (m) {
+        const int i = h * 64 + __ffsll((long long)m) - 1;
+        m &= m - 1;
+        const double w = (scale * M[i * ld + j]) / den;
+        M[i * ld + j] = w;
+        if (w != 0.0) atomicOr(rowmask + 2 * i + (j >> 6), 1ull << (j & 63));     // (a kept 0 is not an edge for coo_matrix)
+      }
+    }
+  }
+  __syncthreads();
+  GDC_PROBE(6);
+  // ---- COO emission in row-major order: slot = row start + edges of the row in lower columns ---------------------
+  if (tid < R) rowcnt[tid] = __popcll(rowmask[2 * tid]) + __popcll(rowmask[2 * tid + 1]);
+  __syncthreads();
+  GDC_PROBE(7);
+  const int64_t slot0 = (int64_t)g * R * sp.cap, off = (int64_t)g * R;
+  int total = 0;
+  for (int t = 0; t < R; ++t) total += rowcnt[t];       // (every thread for itself: R independent LDS reads)
+  if (tid < R) {
+    const int j = tid;
+    int start = 0, upto = 0;                            // edges in the rows below `upto` (the kept rows come ascending)
+    for (int h = 0; h < 2; ++h) {
+      unsigned long long m = h ? tk1 : tk0;
+      while (m) {
+        const int i = h * 64 + __ffsll((long long)m) - 1;
+        m &= m - 1;
+        const double w = M[i * ld + j];
+        if (w == 0.0) continue;
+        for (; upto < i; ++upto) start += rowcnt[upto];
+        const unsigned long long m0 = rowmask[2 * i], m1 = rowmask[2 * i + 1];
+        const int before = j < 64 ? __popcll(m0 & ((1ull << j) - 1ull))
+                                  : __popcll(m0) + __popcll(m1 & ((1ull << (j - 64)) - 1ull));
+        const int64_t s2 = slot0 + start + before;
+        ei_row[s2] = off + i;
+        ei_col[s2] = off + j;
+        ew[s2] = (float)w;
+      }
+    }
+  }
+  if (tid == 0) counts[g] = total;
+  // padding behind the last edge of the graph
+  for (int64_t s2 = slot0 + total + tid; s2 < slot0 + (int64_t)R * sp.cap; s2 += GDC_T) {
+    ei_row[s2] = -1;
+    ei_col[s2] = -1;
+    ew[s2] = 0.f;
+  }
+}
+
 template <int NR>                                       // rows of its column a thread keeps: NR * (GDC_T / cw) >= R
 __global__ void __launch_bounds__(GDC_T)
-k_gdc_topk(int R, int k, double alpha, const float* __restrict__ A, int64_t* __restrict__ ei_row,
-           int64_t* __restrict__ ei_col, float* __restrict__ ew, int32_t* __restrict__ counts,
-           const int64_t* __restrict__ subject, int64_t n_subjects) {
+k_gdc_ppr(int R, GdcSparsify sp, double alpha, const float* __restrict__ A, int64_t* __restrict__ ei_row,
+          int64_t* __restrict__ ei_col, float* __restrict__ ew, int32_t* __restrict__ counts,
+          const int64_t* __restrict__ subject, int64_t n_subjects) {
   extern __shared__ double smem_d[];
   const int ld = gdc_ld(R), g = blockIdx.x, tid = threadIdx.x;
   const int cw = R <= 64 ? 64 : 128, nsl = GDC_T / cw;  // a wave lies inside one row slice
@@ -90,13 +229,7 @@ k_gdc_topk(int R, int k, double alpha, const float* __restrict__ A, int64_t* __r
   if (subject && (sj < 0 || sj >= n_subjects)) {
     // an index outside the dataset: no read — the graph is handed over EMPTY (all slots padding, count 0), which the
     // consumer's plan build reports in its status word (uniform over the workgroup: no barrier has been reached yet)
-    const int64_t s0 = (int64_t)g * R * k;
-    for (int64_t t = s0 + tid; t < s0 + (int64_t)R * k; t += GDC_T) {
-      ei_row[t] = -1;
-      ei_col[t] = -1;
-      ew[t] = 0.f;
-    }
-    if (tid == 0) counts[g] = 0;
+    gdc_emit_empty(g, R, sp.cap, ei_row, ei_col, ew, counts);
     return;
   }
   const float* a = A + sj * R * R;
@@ -212,100 +345,155 @@ k_gdc_topk(int R, int k, double alpha, const float* __restrict__ A, int64_t* __r
   __syncthreads();
 
   GDC_PROBE(5);
-  // ---- top-k per column (thread = column): the winners as a row bit set, their final weights in place ----------
-  // order of preference: larger value, then LARGER row (a stable ascending argsort keeps the later of two equals)
-  unsigned long long tk0 = 0ull, tk1 = 0ull;           // rows of this column that stay
-  if (tid < R) {
-    const int j = tid;
-    double norm = 0.0;
-    if (k <= 4) {
-      // one sweep with the best four in registers: rows arrive in ascending order, so a newcomer beats an equal value
-      double v0 = -HUGE_VAL, v1 = -HUGE_VAL, v2 = -HUGE_VAL, v3 = -HUGE_VAL;
-      int b0 = -1, b1 = -1, b2 = -1, b3 = -1;
-#pragma unroll 4
-      for (int i = 0; i < R; ++i) {
-        const double v = alpha * M[i * ld + j];
-        if (v >= v3) {
-          if (v >= v2) {
-            v3 = v2; b3 = b2;
-            if (v >= v1) {
-              v2 = v1; b2 = b1;
-              if (v >= v0) { v1 = v0; b1 = b0; v0 = v; b0 = i; } else { v1 = v; b1 = i; }
-            } else { v2 = v; b2 = i; }
-          } else { v3 = v; b3 = i; }
-        }
-      }
-      const double vs[4] = {v0, v1, v2, v3};
-      const int bs[4] = {b0, b1, b2, b3};
-#pragma unroll
-      for (int s2 = 0; s2 < 4; ++s2)
-        if (s2 < k && bs[s2] >= 0) {
-          norm += vs[s2];
-          if (bs[s2] < 64) tk0 |= 1ull << bs[s2]; else tk1 |= 1ull << (bs[s2] - 64);
-        }
-    } else {
-      for (int s2 = 0; s2 < k && s2 < R; ++s2) {
-        double best = 0.0;
-        int bi = -1;
-        for (int i = 0; i < R; ++i) {
-          const double v = alpha * M[i * ld + j];
-          const bool taken = ((i < 64 ? tk0 >> i : tk1 >> (i - 64)) & 1ull) != 0;
-          if (!taken && (bi < 0 || v >= best)) { best = v; bi = i; }
-        }
-        if (bi < 64) tk0 |= 1ull << bi; else tk1 |= 1ull << (bi - 64);
-        norm += best;
-      }
-    }
-    const double den = (norm <= 0.0) ? 1.0 : norm;
-    for (int h = 0; h < 2; ++h) {
-      unsigned long long m = h ? tk1 : tk0;
-      while (m) {
-        const int i = h * 64 + __ffsll((long long)m) - 1;
-        m &= m - 1;
-        const double w = (alpha * M[i * ld + j]) / den;
-        M[i * ld + j] = w;
-        if (w != 0.0) atomicOr(rowmask + 2 * i + (j >> 6), 1ull << (j & 63));     // (a kept 0 is not an edge for coo_matrix)
-      }
-    }
-  }
-  __syncthreads();
-  GDC_PROBE(6);
-  // ---- COO emission in row-major order: slot = row start + edges of the row in lower columns ---------------------
-  if (tid < R) rowcnt[tid] = __popcll(rowmask[2 * tid]) + __popcll(rowmask[2 * tid + 1]);
-  __syncthreads();
-  GDC_PROBE(7);
-  const int64_t slot0 = (int64_t)g * R * k, off = (int64_t)g * R;
-  int total = 0;
-  for (int t = 0; t < R; ++t) total += rowcnt[t];       // (every thread for itself: R independent LDS reads)
-  if (tid < R) {
-    const int j = tid;
-    for (int h = 0; h < 2; ++h) {
-      unsigned long long m = h ? tk1 : tk0;
-      while (m) {
-        const int i = h * 64 + __ffsll((long long)m) - 1;
-        m &= m - 1;
-        const double w = M[i * ld + j];
-        if (w == 0.0) continue;
-        int start = 0;
-        for (int t = 0; t < i; ++t) start += rowcnt[t];
-        const unsigned long long m0 = rowmask[2 * i], m1 = rowmask[2 * i + 1];
-        const int before = j < 64 ? __popcll(m0 & ((1ull << j) - 1ull))
-                                  : __popcll(m0) + __popcll(m1 & ((1ull << (j - 64)) - 1ull));
-        const int64_t s2 = slot0 + start + before;
-        ei_row[s2] = off + i;
-        ei_col[s2] = off + j;
-        ew[s2] = (float)w;
-      }
-    }
-  }
-  if (tid == 0) counts[g] = total;
-  // padding behind the last edge of the graph
-  for (int64_t s2 = slot0 + total + tid; s2 < slot0 + (int64_t)R * k; s2 += GDC_T) {
-    ei_row[s2] = -1;
-    ei_col[s2] = -1;
-    ew[s2] = 0.f;
-  }
+  gdc_select_emit(M, ld, R, alpha, sp, rowmask, rowcnt, g, ei_row, ei_col, ew, counts);
   GDC_PROBE(8);
+}
+
+// ---- heat kernel (util_gdc.py:16-23): S = expm(-t (I - H)) = e^-t expm(t H),  H = D^-1/2 A D^-1/2 ------------------------
+// One workgroup per graph, two fp64 matrices in LDS: X = t H / 2^s and the running T, both Rp x (Rp | 1) with
+// Rp = R rounded up to 16 by zero rows and columns (their block of expm is the identity and touches nothing else).
+// Scaling and squaring of a Taylor polynomial in Horner form:
+//     T_m = I + X / m,   T_j = I + X T_(j+1) / j  (j = m-1 .. 1),   expm(t H) = T_1 ^ (2^s)
+//   * s is chosen PER GRAPH: the smallest s >= 0 with |X|_1 = |t H|_1 / 2^s <= 1/2 (|.|_1: largest column sum);
+//   * m = GDC_HEAT_DEGREE = 14: with theta = |X|_1 <= 1/2 the remainder is
+//         sum_{j>m} theta^j / j!  <=  theta^(m+1) / (m+1)! / (1 - theta / (m+2))  <=  2.4e-17,
+//     and X >= 0 entrywise gives |expm(X)|_1 >= 1, so the remainder is below 2^-53 = 1.1e-16 of the result's norm
+//     (m = 13 leaves 7.2e-16).  All terms are non-negative: nothing cancels, and the factor e^-t (the `scale` of the
+//     selection, applied where the matrix is read) never meets a subtraction.
+// The m - 1 + s products are the hot path: v_mfma_f64_16x16x4_f64, the 2 x 2 waves each owning every other 16 x 16 tile
+// in both directions (3 x 3 tiles at Rp = 96: three A and three B fragments feed nine MFMAs per k-step).  A product
+// accumulates in registers while T is only read; T is rewritten behind a barrier and read again behind a second one.
+#define GDC_HEAT_DEGREE 14
+typedef double gdc_d4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ int gdc_heat_pad(int R) { return (R + 15) & ~15; }
+
+// acc[a][b] = tile (wr + 2a, wc + 2b) of L * Rm   (both [Rp][ld] in LDS; nt = Rp / 16 tiles a side)
+// operands of the f64 MFMA: lane l holds A[row l & 15][k = l >> 4] and B[k = l >> 4][col l & 15]
+__device__ __forceinline__ void gdc_heat_mm(const double* L, const double* Rm, int ld, int nt, int wr, int wc, int lane,
+                                            gdc_d4 (&acc)[3][3]) {
+  const int lr = lane & 15, lk = lane >> 4;
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b) acc[a][b] = gdc_d4{0.0, 0.0, 0.0, 0.0};
+  for (int k0 = 0; k0 < nt * 16; k0 += 4) {
+    double fa[3], fb[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const int tr = wr + 2 * a;                        // (wave-uniform)
+      fa[a] = tr < nt ? L[(tr * 16 + lr) * ld + k0 + lk] : 0.0;
+    }
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+      const int tc = wc + 2 * b;
+      fb[b] = tc < nt ? Rm[(k0 + lk) * ld + tc * 16 + lr] : 0.0;
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int b = 0; b < 3; ++b)
+        if (wr + 2 * a < nt && wc + 2 * b < nt)
+          acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[a], fb[b], acc[a][b], 0, 0, 0);
+  }
+}
+
+// T = eye * I + acc * mul, through the f64 C/D map: col = lane & 15, row = (lane >> 4) + 4 reg
+__device__ __forceinline__ void gdc_heat_store(double* T, int ld, int nt, int wr, int wc, int lane,
+                                               const gdc_d4 (&acc)[3][3], double eye, double mul) {
+  const int lr = lane & 15, lk = lane >> 4;
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+      const int tr = wr + 2 * a, tc = wc + 2 * b;
+      if (tr < nt && tc < nt) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int i = tr * 16 + lk + 4 * q, j = tc * 16 + lr;
+          T[i * ld + j] = (i == j ? eye : 0.0) + acc[a][b][q] * mul;
+        }
+      }
+    }
+}
+
+__global__ void __launch_bounds__(GDC_T)
+k_gdc_heat(int R, GdcSparsify sp, double t, double exp_mt, const float* __restrict__ A, int64_t* __restrict__ ei_row,
+           int64_t* __restrict__ ei_col, float* __restrict__ ew, int32_t* __restrict__ counts,
+           const int64_t* __restrict__ subject, int64_t n_subjects) {
+  extern __shared__ double smem_d[];
+  const int Rp = gdc_heat_pad(R), ld = gdc_ld(Rp), nt = Rp >> 4, g = blockIdx.x, tid = threadIdx.x;
+  double* dinv = smem_d;                                // [128]  scale factors d^-1/2
+  double* csum = dinv + 128;                            // [128]  column sums of |t H|
+  unsigned long long* rowmask = (unsigned long long*)(csum + 128);   // [128][2]  edges of row i as a column bit set
+  double* X = (double*)(rowmask + 256);                 // [Rp][ld]
+  double* T = X + (size_t)Rp * ld;                      // [Rp][ld]
+  int* rowcnt = (int*)(T + (size_t)Rp * ld);            // [R+2]
+  const int64_t sj = subject ? subject[g] : (int64_t)g;
+  if (subject && (sj < 0 || sj >= n_subjects)) {        // (uniform over the workgroup: no barrier has been reached yet)
+    gdc_emit_empty(g, R, sp.cap, ei_row, ei_col, ew, counts);
+    return;
+  }
+  const float* a = A + sj * R * R;
+
+  // ---- X = t D^-1/2 A D^-1/2 / 2^s, zero padded ------------------------------------------------------
+  for (int e = tid; e < Rp * Rp; e += GDC_T) {
+    const int i = e / Rp, j = e - i * Rp;
+    X[i * ld + j] = (i < R && j < R) ? (double)a[i * R + j] : 0.0;
+  }
+  for (int e = tid; e < 256; e += GDC_T) rowmask[e] = 0ull;
+  __syncthreads();
+  for (int i = tid; i < R; i += GDC_T) {
+    double s = 0.0;
+    for (int j = 0; j < R; ++j) s += X[i * ld + j];
+    dinv[i] = 1.0 / sqrt(s);
+  }
+  __syncthreads();
+  for (int e = tid; e < R * R; e += GDC_T) {
+    const int i = e / R, j = e - i * R;
+    X[i * ld + j] = t * (dinv[i] * X[i * ld + j] * dinv[j]);
+  }
+  __syncthreads();
+  for (int j = tid; j < R; j += GDC_T) {
+    double s = 0.0;
+    for (int i = 0; i < R; ++i) s += fabs(X[i * ld + j]);
+    csum[j] = s;
+  }
+  __syncthreads();
+  double nrm = 0.0;
+  for (int j = 0; j < R; ++j) nrm = fmax(nrm, csum[j]); // (every thread for itself: the same value in all of them)
+  int s = 0;
+  while (nrm > 0.5 && s < 64) {                         // (s < 64: an input outside the contract must not spin here)
+    nrm *= 0.5;
+    ++s;
+  }
+  s = __builtin_amdgcn_readfirstlane(s);
+  const double down = ldexp(1.0, -s);
+  for (int e = tid; e < Rp * Rp; e += GDC_T) {
+    const int i = e / Rp, j = e - i * Rp;
+    const double x = X[i * ld + j] * down;              // (a power of two: exact)
+    X[i * ld + j] = x;
+    T[i * ld + j] = (i == j ? 1.0 : 0.0) + x / (double)GDC_HEAT_DEGREE;
+  }
+  __syncthreads();
+
+  // ---- Horner steps, then s squarings ------------------------------------------------------------------
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  const int wr = wave >> 1, wc = wave & 1;
+  gdc_d4 acc[3][3];
+  for (int j = GDC_HEAT_DEGREE - 1; j >= 1; --j) {
+    gdc_heat_mm(X, T, ld, nt, wr, wc, lane, acc);
+    __syncthreads();                                    // every wave has read T
+    gdc_heat_store(T, ld, nt, wr, wc, lane, acc, 1.0, 1.0 / (double)j);
+    __syncthreads();
+  }
+  for (int q = 0; q < s; ++q) {
+    gdc_heat_mm(T, T, ld, nt, wr, wc, lane, acc);
+    __syncthreads();
+    gdc_heat_store(T, ld, nt, wr, wc, lane, acc, 0.0, 1.0);
+    __syncthreads();
+  }
+  gdc_select_emit(T, ld, R, exp_mt, sp, rowmask, rowcnt, g, ei_row, ei_col, ew, counts);
 }
 
 static int gdc_rows(int R) {                            // NR of the kernel instance that serves R
@@ -329,22 +517,60 @@ extern "C" int igcn_gdc_topk_max_rois(void) {
   return r;
 }
 
-static int gdc_topk(int B, int R, int k, double alpha, const float* A, const int64_t* subject, int64_t n_subjects,
-                    int64_t* edge_index, float* edge_attr, int32_t* counts, void* stream) {
-  IGCN_REQUIRE(B >= 0 && R > 0 && k > 0 && k <= R, "gdc_topk: bad sizes B=%d R=%d k=%d", B, R, k);
-  IGCN_REQUIRE(alpha > 0.0 && alpha <= 1.0, "gdc_topk: alpha=%g outside (0,1]", alpha);
-  if (R > igcn_gdc_topk_max_rois()) {
-    igcn_set_error("gdc_topk: R=%d exceeds the kernel's limit (max R = %d)", R, igcn_gdc_topk_max_rois());
+static size_t gdc_heat_lds_bytes(int R) {
+  const size_t rp = (size_t)((R + 15) & ~15), ld = rp | 1;
+  const size_t b = (2 * rp * ld + 2 * 128 + 256) * sizeof(double) + ((size_t)R + 2) * sizeof(int);
+  return (b + 15) & ~(size_t)15;
+}
+
+extern "C" int igcn_gdc_max_rois(int kernel) {
+  if (kernel == IGCN_GDC_PPR) return igcn_gdc_topk_max_rois();
+  if (kernel != IGCN_GDC_HEAT) return 0;
+  int r = 16;
+  while (r < 128 && gdc_heat_lds_bytes(r + 1) <= 160 * 1024) ++r;  // (128: the selection's row bit set)
+  return r;
+}
+
+// `who`: the entry point, for messages
+static int gdc_diffuse(const char* who, int B, int R, int kernel, double param, int sparsify, int k, double eps,
+                       const float* A, const int64_t* subject, int64_t n_subjects, int64_t* edge_index,
+                       float* edge_attr, int32_t* counts, void* stream) {
+  IGCN_REQUIRE(kernel == IGCN_GDC_PPR || kernel == IGCN_GDC_HEAT, "%s: unknown kernel %d", who, kernel);
+  IGCN_REQUIRE(sparsify == IGCN_GDC_TOPK || sparsify == IGCN_GDC_THRESHOLD, "%s: unknown sparsifier %d", who, sparsify);
+  if (sparsify == IGCN_GDC_TOPK) {
+    IGCN_REQUIRE(B >= 0 && R > 0 && k > 0 && k <= R, "%s: bad sizes B=%d R=%d k=%d", who, B, R, k);
+  } else {
+    IGCN_REQUIRE(B >= 0 && R > 0, "%s: bad sizes B=%d R=%d", who, B, R);
+    IGCN_REQUIRE(eps == eps, "%s: eps is not a number", who);
+  }
+  if (kernel == IGCN_GDC_PPR)
+    IGCN_REQUIRE(param > 0.0 && param <= 1.0, "%s: alpha=%g outside (0,1]", who, param);
+  else
+    IGCN_REQUIRE(param > 0.0 && param <= 64.0, "%s: t=%g outside (0,64]", who, param);
+  if (R > igcn_gdc_max_rois(kernel)) {
+    igcn_set_error("%s: R=%d exceeds the kernel's limit (max R = %d)", who, R, igcn_gdc_max_rois(kernel));
     return IGCN_ERR_UNSUPPORTED;
   }
-  const size_t lds = gdc_lds_bytes(R);
   if (B == 0) return IGCN_OK;
-  const int64_t slots = (int64_t)B * R * k;
+  GdcSparsify sp;
+  sp.mode = sparsify;
+  sp.k = sparsify == IGCN_GDC_TOPK ? k : R;
+  sp.cap = sp.k;
+  sp.eps = eps;
+  const int64_t slots = (int64_t)B * R * sp.cap;
+  if (kernel == IGCN_GDC_HEAT) {
+    IGCN_ALLOW_BIG_LDS(k_gdc_heat);
+    hipLaunchKernelGGL(k_gdc_heat, dim3(B), dim3(GDC_T), gdc_heat_lds_bytes(R), (hipStream_t)stream, R, sp, param,
+                       exp(-param), A, edge_index, edge_index + slots, edge_attr, counts, subject, n_subjects);
+    IGCN_CHECK_LAUNCH(who);
+    return IGCN_OK;
+  }
+  const size_t lds = gdc_lds_bytes(R);
 #define GDC_LAUNCH(NR)                                                                                              \
   case NR:                                                                                                          \
-    IGCN_ALLOW_BIG_LDS(k_gdc_topk<NR>);                                                                             \
-    hipLaunchKernelGGL(k_gdc_topk<NR>, dim3(B), dim3(GDC_T), lds, (hipStream_t)stream, R, k, alpha, A, edge_index,   \
-                       edge_index + slots, edge_attr, counts, subject, n_subjects);                                             \
+    IGCN_ALLOW_BIG_LDS(k_gdc_ppr<NR>);                                                                              \
+    hipLaunchKernelGGL(k_gdc_ppr<NR>, dim3(B), dim3(GDC_T), lds, (hipStream_t)stream, R, sp, param, A, edge_index,   \
+                       edge_index + slots, edge_attr, counts, subject, n_subjects);                                 \
     break
   switch (gdc_rows(R)) {
     GDC_LAUNCH(8);
@@ -355,18 +581,28 @@ static int gdc_topk(int B, int R, int k, double alpha, const float* A, const int
     GDC_LAUNCH(64);
   }
 #undef GDC_LAUNCH
-  IGCN_CHECK_LAUNCH("gdc_topk");
+  IGCN_CHECK_LAUNCH(who);
   return IGCN_OK;
 }
 
 extern "C" int igcn_gdc_topk(int B, int R, int k, double alpha, const float* A, int64_t* edge_index, float* edge_attr,
                              int32_t* counts, void* stream) {
-  return gdc_topk(B, R, k, alpha, A, nullptr, B, edge_index, edge_attr, counts, stream);
+  return gdc_diffuse("gdc_topk", B, R, IGCN_GDC_PPR, alpha, IGCN_GDC_TOPK, k, 0.0, A, nullptr, B, edge_index,
+                     edge_attr, counts, stream);
 }
 
 extern "C" int igcn_gdc_topk_of(int B, int R, int k, double alpha, const float* A, int64_t n_subjects,
                                 const int64_t* subject, int64_t* edge_index, float* edge_attr, int32_t* counts,
                                 void* stream) {
   IGCN_REQUIRE(subject != nullptr && n_subjects > 0, "gdc_topk_of: the subject list is missing");
-  return gdc_topk(B, R, k, alpha, A, subject, n_subjects, edge_index, edge_attr, counts, stream);
+  return gdc_diffuse("gdc_topk", B, R, IGCN_GDC_PPR, alpha, IGCN_GDC_TOPK, k, 0.0, A, subject, n_subjects,
+                     edge_index, edge_attr, counts, stream);
+}
+
+extern "C" int igcn_gdc_diffuse(int B, int R, int kernel, double param, int sparsify, int k, double eps, const float* A,
+                                int64_t n_subjects, const int64_t* subject, int64_t* edge_index, float* edge_attr,
+                                int32_t* counts, void* stream) {
+  IGCN_REQUIRE(subject == nullptr || n_subjects > 0, "gdc_diffuse: a subject list needs n_subjects > 0");
+  return gdc_diffuse("gdc_diffuse", B, R, kernel, param, sparsify, k, eps, A, subject, n_subjects, edge_index,
+                     edge_attr, counts, stream);
 }

@@ -400,11 +400,20 @@ class DeviceGdcFeeder(_AheadOnSideStream):
     """Dense connectivity matrices resident in HBM -> graph-diffusion pre-transform (util_gdc.py:7-31,71-86) + collation
     (batch.py:24-123) of every batch ON THE DEVICE, one batch ahead of the train step on a side stream: the fp64
     Gauss-Jordan of batch k + 1 (igcn_gdc_topk, one workgroup per graph) runs beside the replay of step k.
+    ``kernel="heat"``: the heat kernel with ``t`` (util_gdc.py:16-23, igcn_gdc_diffuse) in its place.  Top-k only: a
+    captured step needs a fixed edge count, which the eps threshold does not give.
 
     ``cols``: per-subject tensors [S, ...] on the device (x [S, R, H0], snps_feat, y, clini_score, tsne_fdim, clust_y)."""
 
-    def __init__(self, adj, cols, batch_size, steps, top_k=3, alpha=0.05, seed=0, shuffle=True, depth=2):
-        from .gdc import batch_from_dense
+    def __init__(self, adj, cols, batch_size, steps, top_k=3, alpha=0.05, seed=0, shuffle=True, depth=2, kernel="ppr",
+                 t=5.0, eps=None):
+        from .gdc import KERNELS, batch_from_dense
+        if eps is not None:
+            raise ValueError("DeviceGdcFeeder is top-k only: a captured step needs a fixed edge count (eps= keeps a "
+                             "data-dependent one); use gdc.batch_from_dense(..., eps=) per batch")
+        if kernel not in KERNELS:
+            raise ValueError(f"kernel must be 'ppr' or 'heat', got {kernel!r}")
+        self.kernel, self.t = kernel, float(t)
         if adj.device.type != "cuda":
             raise ValueError("DeviceGdcFeeder reads device-resident matrices")
         self.adj, self.cols, self.bsz = adj, cols, int(batch_size)
@@ -424,18 +433,24 @@ class DeviceGdcFeeder(_AheadOnSideStream):
         for k, v in sel.items():
             per[k] = v.reshape(b, -1) if k in ("snps_feat", "tsne_fdim", "clini_score") else v.reshape(-1)
         out = self._make(torch.index_select(self.adj, 0, idx), x, top_k=self.top_k, alpha=self.alpha, check=check,
-                         **per)
+                         kernel=self.kernel, t=self.t, **per)
         out.A = None                                    # the dense matrices are not an input of the step
         return out
 
     def _fill(self, slot, idx):
         """Three launches on the side stream: the per-subject attributes (igcn_gather_batch), the diffusion of the
-        drawn matrices read in place (igcn_gdc_topk_of) straight into the slot's edge list, the edge offsets."""
+        drawn matrices read in place (igcn_gdc_topk_of, igcn_gdc_diffuse for the heat kernel) straight into the slot's
+        edge list, the edge offsets."""
         from ._lib import call, ptr, stream_ptr
+        from .gdc import KERNELS
         b, r = int(idx.numel()), int(self.adj.shape[1])
         gather_rows(idx, r, [(getattr(slot, k), v, False) for k, v in self.cols.items()])
-        call("igcn_gdc_topk_of", b, r, self.top_k, self.alpha, ptr(self.adj), int(self.adj.shape[0]), ptr(idx), ptr(slot.edge_index),
-             ptr(slot.edge_attr), ptr(self._counts), stream_ptr())
+        if self.kernel == "ppr":
+            call("igcn_gdc_topk_of", b, r, self.top_k, self.alpha, ptr(self.adj), int(self.adj.shape[0]), ptr(idx), ptr(slot.edge_index),
+                 ptr(slot.edge_attr), ptr(self._counts), stream_ptr())
+        else:
+            call("igcn_gdc_diffuse", b, r, KERNELS["heat"], self.t, 0, self.top_k, 0.0, ptr(self.adj), int(self.adj.shape[0]), ptr(idx),
+                 ptr(slot.edge_index), ptr(slot.edge_attr), ptr(self._counts), stream_ptr())
         torch.cumsum(self._counts, 0, out=slot.edge_ptr[1:])
 
 

@@ -31,7 +31,7 @@ extern "C" {
 /* ABI revision: bumped whenever a prototype below changes (argument added, removed or re-ordered).  igcn_version()
  * returns the revision the library was built from; a binding written against a different one must refuse to call
  * (igcn_amd/_lib.py does). */
-#define IGCN_ABI_VERSION 438
+#define IGCN_ABI_VERSION 439
 int igcn_version(void);
 const char* igcn_last_error(void);
 /* A/B switches, set ONCE by the binding when it loads the library (from the IGCN_* environment variables): bit 0 no tiled
@@ -1283,6 +1283,31 @@ int igcn_gdc_topk(int B, int R, int k, double alpha, const float* A, int64_t* ed
  * not read: graph g comes out empty (counts[g] = 0, all its slots padding). */
 int igcn_gdc_topk_of(int B, int R, int k, double alpha, const float* A, int64_t n_subjects, const int64_t* subject,
                      int64_t* edge_index, float* edge_attr, int32_t* counts, void* stream);
+/* All of util_gdc.py: either diffusion kernel with either sparsifier.
+ *   kernel    IGCN_GDC_PPR   get_ppr_matrix  :7-14,  param = alpha in (0,1]
+ *             IGCN_GDC_HEAT  get_heat_matrix :16-23, param = t in (0,64] (a condition of the interface; GDC uses
+ *                            1-10): S = expm(-t (I - D^-1/2 A D^-1/2)) in fp64, scaling and squaring with the scaling
+ *                            exponent chosen per graph from |t H|_1 (csrc/gdc.hip)
+ *   sparsify  IGCN_GDC_TOPK       get_top_k_matrix   :25-31 with `k` (eps unused)
+ *             IGCN_GDC_THRESHOLD  get_clipped_matrix :33-38 with `eps` (k unused): entries S[i][j] >= eps stay, each
+ *                                 column is divided by the sum of what it kept (a sum <= 0 leaves it unscaled); a kept
+ *                                 exact zero is not an edge, a column that keeps nothing has no edges
+ * A need not be symmetric.  subject == NULL: graph g is matrix g of A [B,R,R]; otherwise graph g is matrix subject[g]
+ * of A [n_subjects,R,R], and an index outside [0, n_subjects) is not read and yields an empty graph.
+ * Output as igcn_gdc_topk with cap slots per column, cap = k (top-k) or R (threshold): edge_index int64 [2, B*R*cap],
+ * edge_attr f32 [B*R*cap]; graph g owns slots [g*R*cap, (g+1)*R*cap): its edges in (row, col) order, both endpoints
+ * offset by g*R, then (-1,-1,0) padding; counts int32 [B].  Every slot has one writer, no atomics on global memory:
+ * the result is bit-reproducible.  igcn_gdc_diffuse(PPR, TOPK) equals igcn_gdc_topk bit for bit.
+ * R <= igcn_gdc_max_rois(kernel), else IGCN_ERR_UNSUPPORTED (PPR: igcn_gdc_topk_max_rois(); heat: two R x R fp64
+ * matrices, R padded to a multiple of 16, in LDS).
+ * A matrix with a zero row sum is outside the contract of both kernels (the reference divides by zero there, :12 and
+ * :21): the values are then unspecified, the writes still stay inside the graph's slots. */
+enum { IGCN_GDC_PPR = 0, IGCN_GDC_HEAT = 1 };
+enum { IGCN_GDC_TOPK = 0, IGCN_GDC_THRESHOLD = 1 };
+int igcn_gdc_max_rois(int kernel);
+int igcn_gdc_diffuse(int B, int R, int kernel, double param, int sparsify, int k, double eps, const float* A,
+                     int64_t n_subjects, const int64_t* subject /* NULL: graph g = matrix g */, int64_t* edge_index,
+                     float* edge_attr, int32_t* counts, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Epoch evaluation on the device (csrc/eval.hip): replaces the per-batch host work of eval_loss :564-600, eval_acc

@@ -5,7 +5,7 @@
     python3 tools/replay_trace.py --summarise <dir> [<out.csv>]
 
 K fed steps between two marker launches (k_launch_floor): the summary lists, per step, the launches of the side
-stream's chain (index_select, k_gdc_topk, cumsum, the copies into the slot), of ``load`` and of the replay."""
+stream's chain (index_select, k_gdc_ppr, cumsum, the copies into the slot), of ``load`` and of the replay."""
 import os
 import sys
 

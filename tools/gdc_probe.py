@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Phase times inside k_gdc_topk (workgroup 0, thread 0): build with IGCN_HIPCC_EXTRA=-DGDC_PROBE_ON.
+"""Phase times inside k_gdc_ppr (workgroup 0, thread 0): build with IGCN_HIPCC_EXTRA=-DGDC_PROBE_ON.
 
     IGCN_HIPCC_EXTRA=-DGDC_PROBE_ON python ig-gcn_amd/build.py --force && python tools/gdc_probe.py [B R]"""
 import ctypes
