@@ -14,7 +14,7 @@ from . import switches
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libigcn.so")
 
-ABI_VERSION = 439      # include/igcn.h IGCN_ABI_VERSION this table was written against (tests/test_abi.py compares)
+ABI_VERSION = 440      # include/igcn.h IGCN_ABI_VERSION this table was written against (tests/test_abi.py compares)
 
 P, I, L, F, Z = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
 
@@ -172,6 +172,7 @@ SIGNATURES = {
     "igcn_spmm_bwd_scratch_floats": (Z, [I, I, I, I, L]),
     "igcn_spmm_bwd": (I, [I, I, I, I, L, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "igcn_spmm_bwd_dval_multi": (I, [I, P, P]),
+    "igcn_spmm_route": (I, [I, I, I, I, I, L, P]),
     "igcn_spmm_fwd_strided": (I, [I, I, I, I, L, P, P, P, L, P, P, P]),
     "igcn_spmm_bwd_strided": (I, [I, I, I, I, L, P, P, P, P, P, P, P, L, P, P, P, P, P, P]),
     "igcn_go_attn_fwd": (I, [I, I, I, I, P, P, P, P, P, P, P, P, P]),
@@ -196,6 +197,7 @@ SIGNATURES = {
     "igcn_go_decode_ln_bwd": (I, [I, I, I, I, I] + [P] * 19),
     "igcn_go_decode_bwd_scratch_floats": (Z, [I, I, I, I]),
     "igcn_go_decode_bwd": (I, [I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P]),
+    "igcn_go_route": (I, [I, I, I, I, I, I, I, P]),
     "igcn_nodes_ln_prelu_fwd": (I, [I, I, I, I, F, P, P, P, P, P, P, P, P, P]),
     "igcn_nodes_ln_prelu_bwd_scratch_floats": (Z, [I, I, I]),
     "igcn_nodes_ln_prelu_bwd": (I, [I, I, I, I] + [P] * 13),

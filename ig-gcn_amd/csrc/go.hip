@@ -289,23 +289,51 @@ static int spmm_dval_tile(int C, int L, int S) {
 }
 static bool spmm_no_lds(void) { return igcn_opt(IGCN_OPT_SPMM_NO_LDS); }     // the first versions (A/B runs)
 
+// The kernel choice of the map entry points, spelled ONCE: the launch wrappers below and the query igcn_spmm_route read
+// the same answer.  route: IGCN_SPMM_* (include/igcn.h); tile: samples per workgroup; lds: dynamic LDS bytes.
+struct SpmmRoute { int route, tile; size_t lds; };
+// a walk over n_out lists whose entries gather from a per-sample operand vector of L floats per channel:
+// the forward (n_out = I, L = J, sum_c = 0) and the input gradient (n_out = J, L = I, sum_c = 1: C * I floats)
+static SpmmRoute spmm_list_route(int C, int n_out, int L, int64_t nnz, int sum_c) {
+  const bool longlists = nnz > (int64_t)8 * n_out;
+  const size_t vec_bytes = spmm_long_lds_bytes(C, L, nnz, sum_c);
+  const int64_t row_floats = sum_c ? (int64_t)C * L : L;
+  if (!spmm_no_lds() && longlists && vec_bytes <= 150 * 1024) return {IGCN_SPMM_LONG_LDS, 1, vec_bytes};
+  if (!spmm_no_lds() && !longlists && row_floats <= 1024)
+    return {IGCN_SPMM_ROWS_TILED, SPMM_SB, (size_t)SPMM_SB * row_floats * sizeof(float)};
+  return {longlists ? IGCN_SPMM_WAVE : IGCN_SPMM_THREAD, 1, 0};
+}
+// value gradients: the LONG side of the map (per-sample vector with a channel axis only if it is dy) goes to LDS per
+// sample, the short side rides along; x has no channel axis, so with C > 1 it cannot be the long side
+struct SpmmDvalRoute { int route, tile, L, S; bool rows_long; size_t lds; };
+static SpmmDvalRoute spmm_dval_route(int C, int I, int J) {
+  SpmmDvalRoute R;
+  R.rows_long = I >= J;
+  R.L = R.rows_long ? I : J;
+  R.S = R.rows_long ? J : I;
+  R.tile = (R.rows_long || C == 1) ? spmm_dval_tile(C, R.L, R.S) : 0;
+  if (spmm_no_lds() || R.tile < 1) R.tile = 0;
+  R.route = R.tile >= 1 ? IGCN_SPMM_DVAL_LDS : IGCN_SPMM_DVAL_GLOBAL;
+  R.lds = (size_t)R.tile * ((size_t)C * R.L + R.S) * sizeof(float);
+  return R;
+}
+
 // vs = floats between the value rows of consecutive channels (nnz when val is one [C, nnz] tensor; the kernels below
 // take it in the place of `nnz`, which they use for nothing else)
 static int spmm_fwd_impl(int B, int C, int I, int J, int64_t nnz, int64_t vs, const int32_t* row_ptr, const int32_t* col,
                          const float* val, const float* x, float* y, void* stream) {
   IGCN_REQUIRE(B > 0 && C > 0 && I > 0 && J > 0 && vs >= nnz, "spmm_fwd: bad sizes");
   hipStream_t st = (hipStream_t)stream;
-  const bool longrows = nnz > (int64_t)8 * I;
-  if (!spmm_no_lds() && longrows && spmm_long_lds_bytes(C, J, nnz, 0) <= 150 * 1024) {
-    const size_t lds = spmm_long_lds_bytes(C, J, nnz, 0);
-    if (lds > 64 * 1024) IGCN_ALLOW_BIG_LDS(k_spmm_long_lds);
-    hipLaunchKernelGGL(k_spmm_long_lds, dim3(B), dim3(SPMM_LT), lds, st, C, J, I, vs, 0, row_ptr, col,
+  const SpmmRoute R = spmm_list_route(C, I, J, nnz, 0);
+  if (R.route == IGCN_SPMM_LONG_LDS) {
+    if (R.lds > 64 * 1024) IGCN_ALLOW_BIG_LDS(k_spmm_long_lds);
+    hipLaunchKernelGGL(k_spmm_long_lds, dim3(B), dim3(SPMM_LT), R.lds, st, C, J, I, vs, 0, row_ptr, col,
                        (const int32_t*)nullptr, val, x, y);
-  } else if (!spmm_no_lds() && !longrows && J <= 1024) {
+  } else if (R.route == IGCN_SPMM_ROWS_TILED) {
     hipLaunchKernelGGL(k_spmm_rows_tiled, dim3((unsigned)igcn_cdiv(I, GO_T), (unsigned)igcn_cdiv(B, SPMM_SB)),
-                       dim3(GO_T), (size_t)SPMM_SB * J * sizeof(float), st, B, C, I, J, vs, 0, row_ptr, col,
+                       dim3(GO_T), R.lds, st, B, C, I, J, vs, 0, row_ptr, col,
                        (const int32_t*)nullptr, val, x, y);
-  } else if (longrows) {
+  } else if (R.route == IGCN_SPMM_WAVE) {
     hipLaunchKernelGGL(k_spmm_fwd_wave, dim3((unsigned)igcn_cdiv((int64_t)B * I, GO_T / 64)), dim3(GO_T), 0, st, B, C,
                        I, J, vs, row_ptr, col, val, x, y);
   } else {
@@ -411,17 +439,16 @@ static int spmm_bwd_impl(int B, int C, int I, int J, int64_t nnz, int64_t vs, co
   hipStream_t st = (hipStream_t)stream;
   if (dx) {
     // dx[b, j] = sum over column j's entries q, over channels c: val[c, t_k[q]] * dy[b, c, t_row[q]]
-    const bool longcols = nnz > (int64_t)8 * J;
-    const size_t vec_bytes = spmm_long_lds_bytes(C, I, nnz, 1);
-    if (!spmm_no_lds() && longcols && vec_bytes <= 150 * 1024) {
-      if (vec_bytes > 64 * 1024) IGCN_ALLOW_BIG_LDS(k_spmm_long_lds);
-      hipLaunchKernelGGL(k_spmm_long_lds, dim3(B), dim3(SPMM_LT), vec_bytes, st, C, I, J, vs, 1, t_ptr, t_row, t_k,
+    const SpmmRoute R = spmm_list_route(C, J, I, nnz, 1);
+    if (R.route == IGCN_SPMM_LONG_LDS) {
+      if (R.lds > 64 * 1024) IGCN_ALLOW_BIG_LDS(k_spmm_long_lds);
+      hipLaunchKernelGGL(k_spmm_long_lds, dim3(B), dim3(SPMM_LT), R.lds, st, C, I, J, vs, 1, t_ptr, t_row, t_k,
                          val, dy, dx);
-    } else if (!spmm_no_lds() && !longcols && (int64_t)C * I <= 1024) {
+    } else if (R.route == IGCN_SPMM_ROWS_TILED) {
       hipLaunchKernelGGL(k_spmm_rows_tiled, dim3((unsigned)igcn_cdiv(J, GO_T), (unsigned)igcn_cdiv(B, SPMM_SB)),
-                         dim3(GO_T), (size_t)SPMM_SB * C * I * sizeof(float), st, B, C, J, I, vs, 1, t_ptr, t_row, t_k,
+                         dim3(GO_T), R.lds, st, B, C, J, I, vs, 1, t_ptr, t_row, t_k,
                          val, dy, dx);
-    } else if (longcols) {
+    } else if (R.route == IGCN_SPMM_WAVE) {
       hipLaunchKernelGGL(k_spmm_bwd_dx_wave, dim3((unsigned)igcn_cdiv((int64_t)B * J, GO_T / 64)), dim3(GO_T), 0, st,
                          B, C, I, J, vs, t_ptr, t_row, t_k, val, dy, dx);
     } else {
@@ -434,12 +461,12 @@ static int spmm_bwd_impl(int B, int C, int I, int J, int64_t nnz, int64_t vs, co
     IGCN_REQUIRE(scratch != nullptr, "spmm_bwd: dval needs scratch (igcn_spmm_bwd_scratch_floats)");
     // dval[c, k] = sum_b dy[b, c, row_of[k]] * x[b, col[k]]: the LONG side of the map (per-sample vector with a channel
     // axis only if it is dy) goes to LDS per sample, the short side rides along
-    const bool rows_long = I >= J;
-    const int L = rows_long ? I : J, S = rows_long ? J : I;
-    const int tile = (rows_long || C == 1) ? spmm_dval_tile(C, L, S) : 0;     // x has no channel axis
-    if (!spmm_no_lds() && tile >= 1) {
+    const SpmmDvalRoute R = spmm_dval_route(C, I, J);
+    const bool rows_long = R.rows_long;
+    const int L = R.L, S = R.S, tile = R.tile;
+    if (R.route == IGCN_SPMM_DVAL_LDS) {
       const int64_t wgs = igcn_cdiv(B, tile);
-      const size_t lds = (size_t)tile * ((size_t)C * L + S) * sizeof(float);
+      const size_t lds = R.lds;
       if (lds > 64 * 1024) IGCN_ALLOW_BIG_LDS(k_spmm_dval_lds);
       hipLaunchKernelGGL(k_spmm_dval_lds, dim3((unsigned)wgs), dim3(SPMM_DT), lds, st, B, C, L, S, nnz, tile,
                          rows_long ? row_of : col, rows_long ? col : row_of, rows_long ? dy : x, rows_long ? x : dy,
@@ -491,10 +518,10 @@ extern "C" int igcn_spmm_bwd_dval_multi(int n, const int64_t* table, void* strea
     float* scratch = (float*)t[10];
     IGCN_REQUIRE(B > 0 && C > 0 && I > 0 && J > 0 && scratch != nullptr, "spmm_bwd_dval_multi: bad map %d", i);
     if (nnz <= 0) continue;
-    const bool rows_long = I >= J;
-    const int L = rows_long ? I : J, S = rows_long ? J : I;
-    const int tile = (rows_long || C == 1) ? spmm_dval_tile(C, L, S) : 0;
-    if (spmm_no_lds() || tile < 1) {
+    const SpmmDvalRoute R = spmm_dval_route(C, I, J);
+    const bool rows_long = R.rows_long;
+    const int L = R.L, S = R.S, tile = R.tile;
+    if (R.route == IGCN_SPMM_DVAL_GLOBAL) {
       const int bch = B < SPMM_BCH ? B : SPMM_BCH;
       hipLaunchKernelGGL(k_spmm_bwd_dval, dim3((unsigned)igcn_cdiv(nnz, GO_T), C, bch), dim3(GO_T), 0, st, B, C, I, J,
                          nnz, col, row_of, x, dy, scratch);
@@ -512,8 +539,7 @@ extern "C" int igcn_spmm_bwd_dval_multi(int n, const int64_t* table, void* strea
     const int w = (int)igcn_cdiv(B, tile);
     wgs += w;
     rows_of[i] = w;
-    const size_t l = (size_t)tile * ((size_t)C * L + S) * sizeof(float);
-    lds = l > lds ? l : lds;
+    lds = R.lds > lds ? R.lds : lds;
   }
   if (G.n > 0) {
     if (G.n == 1) G.p[1] = G.p[0];
@@ -528,6 +554,33 @@ extern "C" int igcn_spmm_bwd_dval_multi(int n, const int64_t* table, void* strea
     const int rc = igcn_launch_reduce_rows_final((float*)t[10], rows_of[i], cn, (int)cn, (float*)t[9], st);
     if (rc) return rc;
   }
+  return IGCN_OK;
+}
+
+// the choices above as a query (host only): out = {route, tile, lds_bytes, workgroups}
+extern "C" int igcn_spmm_route(int pass, int B, int C, int I, int J, int64_t nnz, int64_t* out) {
+  IGCN_REQUIRE(B > 0 && C > 0 && I > 0 && J > 0 && nnz >= 0 && out != nullptr, "spmm_route: bad sizes");
+  IGCN_REQUIRE(pass == IGCN_SPMM_PASS_FWD || pass == IGCN_SPMM_PASS_DX || pass == IGCN_SPMM_PASS_DVAL,
+               "spmm_route: unknown pass %d", pass);
+  if (pass == IGCN_SPMM_PASS_DVAL) {
+    const SpmmDvalRoute R = spmm_dval_route(C, I, J);
+    out[0] = R.route;
+    out[1] = R.tile;
+    out[2] = (int64_t)R.lds;
+    out[3] = R.route == IGCN_SPMM_DVAL_LDS ? igcn_cdiv(B, R.tile)
+                                           : igcn_cdiv(nnz, GO_T) * C * (B < SPMM_BCH ? B : SPMM_BCH);
+    return IGCN_OK;
+  }
+  const bool fwd = pass == IGCN_SPMM_PASS_FWD;
+  const int n_out = fwd ? I : J;
+  const SpmmRoute R = fwd ? spmm_list_route(C, I, J, nnz, 0) : spmm_list_route(C, J, I, nnz, 1);
+  out[0] = R.route;
+  out[1] = R.tile;
+  out[2] = (int64_t)R.lds;
+  out[3] = R.route == IGCN_SPMM_LONG_LDS     ? B
+           : R.route == IGCN_SPMM_ROWS_TILED ? igcn_cdiv(n_out, GO_T) * igcn_cdiv(B, SPMM_SB)
+           : R.route == IGCN_SPMM_WAVE       ? igcn_cdiv((int64_t)B * n_out, GO_T / 64)
+                                             : igcn_cdiv(n_out, GO_T) * B;
   return IGCN_OK;
 }
 
@@ -1612,6 +1665,15 @@ extern "C" int igcn_go_attn_ln_fused_ok(int N, int fin, int fout, int pool) {
   if (N <= 0 || pool < 0 || pool >= N || N % 4 || pool % 4) return 0;
   return go_attn_bwd_in_lds(N, fin, fout) && N / 4 <= go_abl_threads(N, fin, fout) ? 1 : 0;
 }
+// The kernel choice of the GO layer entry points, spelled ONCE for the launch wrappers and the query igcn_go_route.
+// route: IGCN_GO_ROUTE_*; threads: workgroup size; passes: see include/igcn.h; lds: dynamic LDS bytes (0: global)
+struct GoRoute { int route, threads, passes; size_t lds; };
+static GoRoute go_attn_bwd_route(int N, int fin, int fout) {
+  if (!go_attn_bwd_in_lds(N, fin, fout)) return {IGCN_GO_ROUTE_GLOBAL, GO_T, 0, 0};
+  const int TT = go_abl_threads(N, fin, fout);
+  const int iters = (int)igcn_cdiv(N, TT);              // <= GO_ABL_MAXIT (go_attn_bwd_in_lds)
+  return {IGCN_GO_ROUTE_LDS, TT, iters < 1 ? 1 : iters, go_abl_lds_bytes(N, fin, fout, TT)};
+}
 extern "C" size_t igcn_go_ln_part_floats(int B, int N) { return (size_t)B * 2 * (size_t)N + 64; }   // (N - pool columns used)
 
 static int go_attn_bwd_impl(int B, int N, int fin, int fout, const int32_t* row_ptr, const int32_t* col,
@@ -1619,11 +1681,12 @@ static int go_attn_bwd_impl(int B, int N, int fin, int fout, const int32_t* row_
                             const float* w_inc, const float* w_s, const float* a_in, const float* a_s, const float* dy,
                             float* dx, float* dparams, float* scratch, const LnFuse& L, hipStream_t st) {
   const int64_t rows = 2 * fout + 3;
-  const int TT = go_abl_threads(N, fin, fout);
-  const size_t abl_lds = go_abl_lds_bytes(N, fin, fout, TT);
-  if (go_attn_bwd_in_lds(N, fin, fout)) {
+  const GoRoute R = go_attn_bwd_route(N, fin, fout);
+  const int TT = R.threads;
+  const size_t abl_lds = R.lds;
+  if (R.route == IGCN_GO_ROUTE_LDS) {
     float* gpart = scratch;                                         // [rows * fin][B] block partials
-    const int iters = (int)igcn_cdiv(N, TT);
+    const int iters = R.passes;
 #define CALLLI(FI, FO, MI, TV)                                                                                    \
   {                                                                                                               \
     IGCN_ALLOW_BIG_LDS((k_go_attn_bwd_lds<FI, FO, MI, TV>));                                                      \
@@ -1906,14 +1969,22 @@ static size_t go_dec_lds_bytes(int fin, int Nin) {
   return ((((size_t)fin * Nin + 3) & ~(size_t)3) + GO_DEC_T * GO_DEC_ITERS + 4 + GO_DEC_COLCAP) * sizeof(float);
 }
 
+static GoRoute go_decode_fwd_route(int Nin, int Nout, int fin) {
+  const size_t lds = go_dec_lds_bytes(fin, Nin);
+  if (go_attn_force_cm() || lds > 64 * 1024) return {IGCN_GO_ROUTE_GLOBAL, GO_T, 0, 0};
+  return {IGCN_GO_ROUTE_LDS, GO_DEC_T, (int)igcn_cdiv(Nout, GO_DEC_T * GO_DEC_ITERS), lds};
+}
+
 extern "C" int igcn_go_decode_fwd(int B, int Nin, int Nout, int fin, int fout, const int32_t* row_ptr,
                                   const int32_t* col, const float* x, const float* w_out, const float* w_sout,
                                   float* y, void* stream) {
   IGCN_REQUIRE(B > 0 && Nin > 0 && Nout >= Nin, "go_decode_fwd: bad sizes");
   hipStream_t st = (hipStream_t)stream;
-  const size_t lds = go_dec_lds_bytes(fin, Nin);
-  if (!go_attn_force_cm() && lds <= 64 * 1024 && ((uintptr_t)x % 16) == 0) {
-    dim3 lgrid((unsigned)igcn_cdiv(Nout, GO_DEC_T * GO_DEC_ITERS), B);
+  const GoRoute R = go_decode_fwd_route(Nin, Nout, fin);
+  const size_t lds = R.lds;
+  // (the one condition the route does not see: the slab is copied with 16-byte loads from x)
+  if (R.route == IGCN_GO_ROUTE_LDS && ((uintptr_t)x % 16) == 0) {
+    dim3 lgrid((unsigned)R.passes, B);
 #define CALL(FI, FO)                                                                                                \
   hipLaunchKernelGGL((k_go_decode_fwd_lds<FI, FO>), lgrid, dim3(GO_DEC_T), lds, st, Nin, Nout, row_ptr, col, x, w_out, \
                      w_sout, y)
@@ -2170,16 +2241,46 @@ extern "C" int igcn_go_decode_ln_fused_ok(int Nin, int Nout, int fin, int fout) 
   return go_decode_bwd_in_lds(Nin, Nout, fin, fout) && Nout / 4 <= go_dbl_threads(Nin, Nout, fin, fout) ? 1 : 0;
 }
 
+// one workgroup per sample fills the chip from ~128 samples on; below that (configs[4]: 64) the thread-per-node
+// kernel — 2 500 workgroups, a sample's blocks on one XCD — is the faster one (12.1 against 14.4 us at 64 x 10 000),
+// unless the LayerNorm backward rides along (only the LDS-resident kernel forms it)
+static GoRoute go_decode_bwd_route(int B, int Nin, int Nout, int fin, int fout, bool with_ln) {
+  if (!(go_decode_bwd_in_lds(Nin, Nout, fin, fout) && (B >= 128 || with_ln))) return {IGCN_GO_ROUTE_GLOBAL, GO_T, 0, 0};
+  const int TT = go_dbl_threads(Nin, Nout, fin, fout);
+  return {IGCN_GO_ROUTE_LDS, TT, 0, go_dbl_lds_bytes(Nout, fin, fout, TT)};
+}
+
+// the three choices as a query (host only): out = {route, threads, passes, lds_bytes}
+extern "C" int igcn_go_route(int op, int B, int Nin, int Nout, int fin, int fout, int with_ln, int64_t* out) {
+  IGCN_REQUIRE(B > 0 && Nin > 0 && Nout >= Nin && out != nullptr, "go_route: bad sizes");
+  IGCN_REQUIRE((fin == 2 || fin == 5) && (fout == 2 || fout == 5),
+               "go_route: unsupported GO feature dims fin=%d fout=%d", fin, fout);
+  GoRoute R = {};
+  if (op == IGCN_GO_OP_ATTN_BWD) {
+    IGCN_REQUIRE(Nin == Nout, "go_route: an encoder layer is square (Nin == Nout)");
+    R = go_attn_bwd_route(Nin, fin, fout);
+  } else if (op == IGCN_GO_OP_DECODE_FWD || op == IGCN_GO_OP_DECODE_BWD) {
+    R = op == IGCN_GO_OP_DECODE_FWD ? go_decode_fwd_route(Nin, Nout, fin)
+                                    : go_decode_bwd_route(B, Nin, Nout, fin, fout, with_ln != 0);
+  } else {
+    IGCN_REQUIRE(false, "go_route: unknown op %d", op);
+  }
+  out[0] = R.route;
+  out[1] = R.threads;
+  out[2] = R.passes;
+  out[3] = (int64_t)R.lds;
+  return IGCN_OK;
+}
+
 static int go_decode_bwd_impl(int B, int Nin, int Nout, int fin, int fout, const int32_t* row_ptr, const int32_t* t_ptr,
                               const int32_t* t_row, const float* x, const float* w_out, const float* w_sout,
                               const float* dy, float* dx, float* dparams, float* scratch, const LnFuse& L,
                               hipStream_t st) {
   const int nw = 2 * fout * fin;
-  const int TT = go_dbl_threads(Nin, Nout, fin, fout);
-  const size_t lds = go_dbl_lds_bytes(Nout, fin, fout, TT);
-  // one workgroup per sample fills the chip from ~128 samples on; below that (configs[4]: 64) the thread-per-node
-  // kernel — 2 500 workgroups, a sample's blocks on one XCD — is the faster one (12.1 against 14.4 us at 64 x 10 000)
-  if (go_decode_bwd_in_lds(Nin, Nout, fin, fout) && (B >= 128 || L.y != nullptr)) {
+  const GoRoute R = go_decode_bwd_route(B, Nin, Nout, fin, fout, L.y != nullptr);
+  const int TT = R.threads;
+  const size_t lds = R.lds;
+  if (R.route == IGCN_GO_ROUTE_LDS) {
 #define CALLT(FI, FO, TV)                                                                                        \
   {                                                                                                               \
     IGCN_ALLOW_BIG_LDS((k_go_decode_bwd_lds<FI, FO, TV>));                                                        \

@@ -31,7 +31,7 @@ extern "C" {
 /* ABI revision: bumped whenever a prototype below changes (argument added, removed or re-ordered).  igcn_version()
  * returns the revision the library was built from; a binding written against a different one must refuse to call
  * (igcn_amd/_lib.py does). */
-#define IGCN_ABI_VERSION 439
+#define IGCN_ABI_VERSION 440
 int igcn_version(void);
 const char* igcn_last_error(void);
 /* A/B switches, set ONCE by the binding when it loads the library (from the IGCN_* environment variables): bit 0 no tiled
@@ -946,6 +946,24 @@ int igcn_spmm_bwd_strided(int B, int C, int I, int J, int64_t nnz, const int32_t
 /* The value-gradient half of igcn_spmm_bwd for one or two maps in ONE launch (call igcn_spmm_bwd with dval = NULL for
  * the input gradients): table [n][12] int64 = {B, C, I, J, nnz, col, row_of, x, dy, dval, scratch, 0} per map. */
 int igcn_spmm_bwd_dval_multi(int n, const int64_t* table, void* stream);
+/* Which kernel the map entry points above launch for these sizes: the function they run to choose it, as a query.  Host
+ * only (no GPU needed, nothing is launched or dereferenced).  pass: IGCN_SPMM_PASS_FWD (y), IGCN_SPMM_PASS_DX (the dx half
+ * of igcn_spmm_bwd), IGCN_SPMM_PASS_DVAL (its dval half, and each map of igcn_spmm_bwd_dval_multi).
+ * out [4] (host) = { route, tile, lds_bytes, workgroups }:
+ *   route  FWD / DX: IGCN_SPMM_LONG_LDS (lists of more than 8 entries on average, the operand vector of a sample — J
+ *          floats, C * I for dx — within 150 KB of LDS), IGCN_SPMM_ROWS_TILED (shorter lists, operand rows of at most
+ *          1024 floats), IGCN_SPMM_WAVE / IGCN_SPMM_THREAD (the untiled kernels for what fits neither: long / short lists)
+ *          DVAL: IGCN_SPMM_DVAL_LDS (`tile` samples' vectors in LDS per workgroup) or IGCN_SPMM_DVAL_GLOBAL (tile 0:
+ *          one sample does not fit 120 KB, or the long side is x and C > 1)
+ *   tile   DVAL: samples per workgroup (4, 3, 2, 1; 0 = global); FWD / DX: samples per workgroup of the tiled kernel (8),
+ *          else 1
+ *   lds_bytes   dynamic LDS of the launch (above 64 KB the kernel's limit is raised first)
+ *   workgroups  of the launch (DVAL global: of its first kernel)
+ * IGCN_SPMM_NO_LDS (igcn_configure) is honoured: the untiled kernels everywhere. */
+enum { IGCN_SPMM_PASS_FWD = 0, IGCN_SPMM_PASS_DX = 1, IGCN_SPMM_PASS_DVAL = 2 };
+enum { IGCN_SPMM_LONG_LDS = 0, IGCN_SPMM_ROWS_TILED = 1, IGCN_SPMM_WAVE = 2, IGCN_SPMM_THREAD = 3,
+       IGCN_SPMM_DVAL_LDS = 4, IGCN_SPMM_DVAL_GLOBAL = 5 };
+int igcn_spmm_route(int pass, int B, int C, int I, int J, int64_t nnz, int64_t* out);
 
 /* ------------------------------------------------------------------------------------------------
  * GO attention-GCN encoder layer, all samples at once — replaces the dense transforms, the edge gathers
@@ -1063,6 +1081,21 @@ int igcn_go_decode_bwd(int B, int Nin, int Nout, int fin, int fout, const int32_
                        const int32_t* t_ptr, const int32_t* t_row,
                        const float* x, const float* w_out, const float* w_sout, const float* dy,
                        float* dx, float* dparams, float* scratch, void* stream);
+/* Which kernel the GO layer entry points launch for these sizes: the functions they run to choose it, as a query.  Host
+ * only.  op: IGCN_GO_OP_ATTN_BWD (igcn_go_attn_bwd / igcn_go_attn_ln_bwd; Nin = Nout = N), IGCN_GO_OP_DECODE_FWD,
+ * IGCN_GO_OP_DECODE_BWD (igcn_go_decode_bwd; with_ln != 0: igcn_go_decode_ln_bwd, whose LayerNorm rides along).
+ * out [4] (host) = { route, threads, passes, lds_bytes }:
+ *   route    IGCN_GO_ROUTE_LDS (one workgroup holds a sample in LDS) or IGCN_GO_ROUTE_GLOBAL (thread per node; for
+ *            DECODE_BWD also whenever B < 128 and no LayerNorm rides along: that many samples do not fill the chip)
+ *   threads  workgroup size (ATTN_BWD, DECODE_BWD: 512 or 1024 when LDS; DECODE_FWD: 1024 when LDS; 256 when global)
+ *   passes   ATTN_BWD, LDS: passes of the workgroup over the nodes = the MAXIT instance (1..4); DECODE_FWD, LDS:
+ *            workgroups per sample (3072 rows each); else 0
+ *   lds_bytes  dynamic LDS of the LDS-resident launch (0 when global)
+ * igcn_go_decode_fwd takes the LDS kernel only when x is 16-byte aligned as well: the probe sees no pointer and assumes
+ * it is.  IGCN_GO_ATTN_CM (igcn_configure) is honoured: global everywhere. */
+enum { IGCN_GO_OP_ATTN_BWD = 0, IGCN_GO_OP_DECODE_FWD = 1, IGCN_GO_OP_DECODE_BWD = 2 };
+enum { IGCN_GO_ROUTE_LDS = 0, IGCN_GO_ROUTE_GLOBAL = 1 };
+int igcn_go_route(int op, int B, int Nin, int Nout, int fin, int fout, int with_ln, int64_t* out);
 
 /* ------------------------------------------------------------------------------------------------
  * Adam step over a flat fp32 parameter buffer — torch.optim.Adam(lr, weight_decay=0) at

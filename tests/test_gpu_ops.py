@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import go_structures as gst
 from conftest import assert_matches
 
 pytestmark = pytest.mark.gpu
@@ -659,16 +660,8 @@ def test_go_attention_layer(ops, bsz, pool, fin, seed):
     par = [torch.from_numpy(rng.standard_normal(s) * 0.5).float() for s in ((5, fin), (5, fin), (1, 10), (1, 5))]
     cot = torch.from_numpy(rng.standard_normal((bsz, nj, 5))).float()
 
-    def ref(xd, w_inc, w_s, a_in, a_s):
-        x_in, x_s = xd @ w_inc.t(), xd @ w_s.t()
-        v = torch.exp(torch.tanh(torch.cat([x_in[:, row], x_in[:, col]], 2) @ a_in.t())).squeeze(2)
-        z = torch.zeros(bsz, nj, dtype=xd.dtype).index_add(1, row, v)
-        alpha = v / z[:, row]
-        return torch.zeros(bsz, nj, 5, dtype=xd.dtype).index_add(1, row, alpha.unsqueeze(2) * x_in[:, col]) \
-            + x_s * torch.sigmoid(x_s @ a_s.t())
-
     ref_in = [t.double().requires_grad_(True) for t in [x] + par]
-    y_ref = ref(*ref_in)
+    y_ref = gst.attn_ref(row, col, *ref_in)
     g_ref = torch.autograd.grad((y_ref * cot.double()).sum(), ref_in)
     csr = ops.Csr(row, col, nj, nj, "cuda")
     dev = [x.transpose(1, 2).contiguous().cuda().requires_grad_(True)] + [p.cuda().requires_grad_(True) for p in par]
@@ -736,16 +729,8 @@ def test_go_decoder_layer(ops, bsz, pool, layer, seed):
     par = [torch.from_numpy(rng.standard_normal((fout, fin)) * 0.5).float() for _ in range(2)]
     cot = torch.from_numpy(rng.standard_normal((bsz, n_rows, fout))).float()
 
-    def ref(xd, w_out, w_sout):
-        deg = torch.zeros(n_rows, dtype=xd.dtype).index_add(0, row, torch.ones(row.numel(), dtype=xd.dtype))
-        agg = torch.zeros(bsz, n_rows, fout, dtype=xd.dtype).index_add(
-            1, row, (xd @ w_out.t())[:, col] / deg[row].view(1, -1, 1))
-        pad = torch.zeros_like(agg)
-        pad[:, n_rows - n_cols:] = xd @ w_sout.t()
-        return agg + pad
-
     ref_in = [t.double().requires_grad_(True) for t in [x] + par]
-    y_ref = ref(*ref_in)
+    y_ref = gst.decode_ref(row, col, n_rows, n_cols, *ref_in)
     g_ref = torch.autograd.grad((y_ref * cot.double()).sum(), ref_in)
     csr = ops.Csr(row, col, n_rows, n_cols, "cuda")
     dev = [x.transpose(1, 2).contiguous().cuda().requires_grad_(True)] + [p.cuda().requires_grad_(True) for p in par]
@@ -755,14 +740,6 @@ def test_go_decoder_layer(ops, bsz, pool, layer, seed):
     assert_matches(g[0].transpose(1, 2), g_ref[0].numpy(), TOL, "dx")
     assert_matches(g[1], g_ref[1].numpy(), TOL, "dW_out")
     assert_matches(g[2], g_ref[2].numpy(), TOL, "dW_sout")
-
-
-def _ln_block_ref(y, gamma, beta, keep, pool):
-    """fp64 dropout(relu(LayerNorm_over_nodes(y)))[:, pool:] for y [B, N, f] (go_model.py:246-251)."""
-    z = torch.relu(torch.nn.functional.layer_norm(y.transpose(1, 2), (y.shape[1],), gamma, beta, 1e-5))
-    if keep is not None:
-        z = z * keep.double().unsqueeze(1)
-    return z[:, :, pool:]
 
 
 @pytest.mark.parametrize("bsz,pool,layer,with_keep,seed", [
@@ -788,17 +765,8 @@ def test_go_attention_with_layernorm_backward_in_one_launch(ops, monkeypatch, bs
     keep = torch.from_numpy((rng.random((bsz, nj)) > 0.3) / 0.7).float() if with_keep else None
     cot = torch.from_numpy(rng.standard_normal((bsz, 5, nj - drop))).float()
 
-    def ref(xd, w_inc, w_s, a_in, a_s, g_, b_):
-        x_in, x_s = xd @ w_inc.t(), xd @ w_s.t()
-        v = torch.exp(torch.tanh(torch.cat([x_in[:, row], x_in[:, col]], 2) @ a_in.t())).squeeze(2)
-        z = torch.zeros(bsz, nj, dtype=xd.dtype).index_add(1, row, v)
-        alpha = v / z[:, row]
-        y = torch.zeros(bsz, nj, 5, dtype=xd.dtype).index_add(1, row, alpha.unsqueeze(2) * x_in[:, col]) \
-            + x_s * torch.sigmoid(x_s @ a_s.t())
-        return _ln_block_ref(y, g_, b_, keep, drop)
-
     ref_in = [t.double().requires_grad_(True) for t in [x] + par + [gamma, beta]]
-    z_ref = ref(*ref_in)
+    z_ref = gst.attn_ln_ref(row, col, keep, drop, *ref_in)
     g_ref = torch.autograd.grad((z_ref * cot.double()).sum(), ref_in)
     csr = ops.Csr(row, col, nj, nj, "cuda")
     dev = [x.transpose(1, 2).contiguous().cuda().requires_grad_(True)] + \
@@ -890,16 +858,8 @@ def test_go_decoder_with_layernorm_backward_in_one_launch(ops, monkeypatch, bsz,
     keep = torch.from_numpy((rng.random((bsz, n_rows)) > 0.3) / 0.7).float() if with_keep else None
     cot = torch.from_numpy(rng.standard_normal((bsz, fout, n_rows))).float()
 
-    def ref(xd, w_out, w_sout, g_, b_):
-        deg = torch.zeros(n_rows, dtype=xd.dtype).index_add(0, row, torch.ones(row.numel(), dtype=xd.dtype))
-        agg = torch.zeros(bsz, n_rows, fout, dtype=xd.dtype).index_add(
-            1, row, (xd @ w_out.t())[:, col] / deg[row].view(1, -1, 1))
-        pad = torch.zeros_like(agg)
-        pad[:, n_rows - n_cols:] = xd @ w_sout.t()
-        return _ln_block_ref(agg + pad, g_, b_, keep, 0)
-
     ref_in = [t.double().requires_grad_(True) for t in [x] + par + [gamma, beta]]
-    z_ref = ref(*ref_in)
+    z_ref = gst.decode_ln_ref(row, col, n_rows, n_cols, keep, *ref_in)
     g_ref = torch.autograd.grad((z_ref * cot.double()).sum(), ref_in)
     csr = ops.Csr(row, col, n_rows, n_cols, "cuda")
     dev = [x.transpose(1, 2).contiguous().cuda().requires_grad_(True)] + \
@@ -943,8 +903,7 @@ def test_sparse_map_encode_decode(ops, monkeypatch, bsz, pool, seed, dense):
     val = torch.from_numpy(1 + 0.1 * rng.standard_normal((2, gn.numel()))).float()
     cot = torch.from_numpy(rng.standard_normal((bsz, 2, n))).float()
     ref_in = [snps.double().requires_grad_(True), val.double().requires_grad_(True)]
-    y_ref = torch.stack([torch.zeros(bsz, n, dtype=torch.float64).index_add(1, gn, ref_in[0][:, gs] * ref_in[1][c])
-                         for c in range(2)], dim=1)
+    y_ref = gst.map_ref(gn, gs, n, ref_in[0], ref_in[1])
     g_ref = torch.autograd.grad((y_ref * cot.double()).sum(), ref_in)
     csr = ops.Csr(gn, gs, n, 54, "cuda")
     dev = [snps.cuda().requires_grad_(True), val.cuda().requires_grad_(True)]
@@ -960,7 +919,7 @@ def test_sparse_map_encode_decode(ops, monkeypatch, bsz, pool, seed, dense):
     vald = torch.from_numpy(1 + 0.1 * rng.standard_normal((1, rs.numel()))).float()
     cotd = torch.from_numpy(rng.standard_normal((bsz, 1, 54))).float()
     ref_in = [xg.double().requires_grad_(True), vald.double().requires_grad_(True)]
-    yd_ref = torch.zeros(bsz, 54, dtype=torch.float64).index_add(1, rs, ref_in[0][:, cn] * ref_in[1][0]).unsqueeze(1)
+    yd_ref = gst.map_ref(rs, cn, 54, ref_in[0], ref_in[1])
     gd_ref = torch.autograd.grad((yd_ref * cotd.double()).sum(), ref_in)
     csrd = ops.Csr(rs, cn, 54, n, "cuda")
     dev = [xg.cuda().requires_grad_(True), vald.cuda().requires_grad_(True)]
