@@ -54,7 +54,11 @@ struct DsReg {                                   // loss_probability's constants
 __device__ __forceinline__ float ds_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 __device__ __forceinline__ float ds_sigmoid(float z) { return ds_rcp(1.f + __expf(-z)); }
 // edge mask from the per-node factors a[s] = exp(-u[s]), b[d] = exp(-v[d]): sigmoid(u + v) = 1 / (1 + a b) — one
-// multiply-add and one reciprocal per edge, no exponential (a b = inf -> 0, a b = 0 -> 1: the right limits)
+// multiply-add and one reciprocal per edge, no exponential.  Domain: |u|, |v| <~ 87, where both factors are finite,
+// nonzero fp32 numbers.  ONE saturated factor still gives the right limit (a b = inf -> 0, a b = 0 -> 1) as long as the
+// other logit part is moderate; a = inf (u <= -88.8) against b = 0 (v >= 87.4 where v_exp_f32 flushes, 103.3 at the
+// latest) is inf * 0 = NaN where sigmoid(u + v) is finite: that edge's mask, its target's row of xcat and the
+// regulariser — hence the loss — are NaN (pinned by tests/test_gpu_dense_forms.py)
 __device__ __forceinline__ float ds_mask(float a, float b) { return ds_rcp(fmaf(a, b, 1.f)); }
 __device__ __forceinline__ float ds_reg_term(float p, float l1, float ent, float eps) {
   return l1 * p - ent * (p * __logf(p + eps) + (1.f - p) * __logf((1.f - p) + eps));          // p in (0, 1)

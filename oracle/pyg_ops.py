@@ -37,7 +37,13 @@ def gcn_norm(edge_index, edge_weight, num_nodes):
     dst2 = torch.cat([dst[keep], ar])
     w2 = torch.cat([edge_weight[keep], loop_w])
     deg = torch.zeros(num_nodes, dtype=w2.dtype, device=w2.device).index_add(0, dst2, w2)
-    dis = deg.pow(-0.5)
+    # deg == 0 (a node whose incoming weights, stored loop included, are all zero): deg^-1/2 = inf -> 0, as PyG.  The
+    # power is taken of 1 there, not of 0: the VALUE is the same 0, but autograd of pow-then-masked_fill multiplies the
+    # fill's zero gradient by pow's inf derivative and hands NaN to every weight that enters such a node; the constant 0
+    # has derivative 0, which is what the HIP kernels compute (ddeg = -1/2 dis^2 T = 0).
+    isolated = deg == 0
+    dis = torch.where(isolated, torch.ones_like(deg), deg).pow(-0.5)
+    dis = torch.where(isolated, torch.zeros_like(deg), dis)
     dis = dis.masked_fill(dis == float("inf"), 0.0)
     w_hat = dis[src2] * w2 * dis[dst2]
     return torch.stack([src2, dst2]), w_hat

@@ -2,7 +2,14 @@
 COO, BASELINE configs[4] — whose masks, gcn_norm, GCNConv layers and mask regulariser run on ``edge_attr`` as the dense
 matrix it is.  Against the fp64 oracle (cal_probability kernel/sgcn_img_snp.py:133-151, PyG GCNConv, loss_probability
 :153-181) for one pass (plain / masked) and for both passes of a train step, forward and every gradient; plus the
-structure check that guards the path."""
+structure check that guards the path.
+
+Forms covered HERE at the op level: the GENERIC edge kernels only (R = 64 and 128: one step at a time, k_ds_mask_bwd<L,
+false>), L = 1..3, H0 = 3, grids of 2, 3 and 4 workgroups (XCD remap off), ``status=None``.  The whole-model tests below run
+R = 128 again and, in test_gpu_stress.py, R = 512.  Every other form — pipelined walks (R = 256, 512), the mixed form
+(R = 768, 1024), uneven wave ranges (R = 192, 320), the remap on, L = 4, H0 = 1 and 8, the riding structure check, the dual
+output, zero degrees and saturated masks — has its own oracle case in tests/test_gpu_dense_forms.py, which imports
+``_oracle``, ``_batch`` and ``HP`` from here."""
 from types import SimpleNamespace
 
 import numpy as np

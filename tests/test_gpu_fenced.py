@@ -268,6 +268,12 @@ CASES = [
     ("test_gpu_model", "test_train_mode_at_the_trainers_heads_vs_oracle", dict(case="trainer")),
     # the latent MLP's wide layer takes ops.LinearBN1d only when its product is split: K >= 128 inputs, a 1800-node pool
     ("test_gpu_model", "test_full_model_vs_oracle_larger", dict(bsz=16, pool=(1800, 800, 300, 99, 1), explain=True)),
+    # ------------------------------------------------------------------------------------------- dense-block forms
+    # (appended: the ids of the cases whose parameters come from a table carry their position in this list)
+    # the pipelined form | odd R / 64 with 12 rows of `dup` in the backward workspace | L = 4 with H0 = 1
+    ("test_gpu_dense_forms", "test_dense_forms_vs_fp64_oracle", dict(rois=256, n_graphs=2, layers=2, h0=3, mode="both")),
+    ("test_gpu_dense_forms", "test_dense_forms_vs_fp64_oracle", dict(rois=192, n_graphs=8, layers=2, h0=3, mode="both")),
+    ("test_gpu_dense_forms", "test_dense_forms_vs_fp64_oracle", dict(rois=128, n_graphs=2, layers=4, h0=1, mode="masked")),
 ]
 
 # ------------------------------------------------------------------------------------------- routes no existing test takes
