@@ -247,6 +247,9 @@ SIGNATURES = {
     "igcn_gdc_topk_of": (I, [I, I, I, ctypes.c_double, P, L, P, P, P, P, P]),
     "igcn_gdc_max_rois": (I, [I]),
     "igcn_gdc_diffuse": (I, [I, I, I, ctypes.c_double, I, I, ctypes.c_double, P, L, P, P, P, P, P]),
+    "igcn_gdc_tiled_max_rois": (I, []),
+    "igcn_gdc_tiled_workspace_bytes": (Z, [I, I, I]),
+    "igcn_gdc_diffuse_tiled": (I, [I, I, I, ctypes.c_double, I, I, ctypes.c_double, P, L, P, P, P, P, P, Z, P]),
     "igcn_eval_collect": (I, [I, I, I, I, I, P, P, P, P, P, P, P, P, L, P, P, P, P, P, P, P, P, P, P, P]),
     "igcn_eval_metrics": (I, [L, I, I, P, P, P, P, P, P, P, P, P, P]),
     "igcn_knn_impute_stats": (I, [L, I, P, P, L, P, P, P]),

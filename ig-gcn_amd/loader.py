@@ -402,12 +402,16 @@ class DeviceGdcFeeder(_AheadOnSideStream):
     Gauss-Jordan of batch k + 1 (igcn_gdc_topk, one workgroup per graph) runs beside the replay of step k.
     ``kernel="heat"``: the heat kernel with ``t`` (util_gdc.py:16-23, igcn_gdc_diffuse) in its place.  Top-k only: a
     captured step needs a fixed edge count, which the eps threshold does not give.
+    ``route``: as ``gdc.diffusion_routed`` — 'resident' (the default: the LDS kernels, refused above their limit), 'tiled'
+    (igcn_gdc_diffuse_tiled, R <= 512) or 'auto'.  The tiled route's workspace for one batch is allocated here, once:
+    nothing is allocated per step.
 
     ``cols``: per-subject tensors [S, ...] on the device (x [S, R, H0], snps_feat, y, clini_score, tsne_fdim, clust_y)."""
 
     def __init__(self, adj, cols, batch_size, steps, top_k=3, alpha=0.05, seed=0, shuffle=True, depth=2, kernel="ppr",
-                 t=5.0, eps=None):
-        from .gdc import KERNELS, batch_from_dense
+                 t=5.0, eps=None, route="resident"):
+        from .gdc import KERNELS, _check_route, _resolve_route, batch_from_dense, tiled_workspace
+        _check_route(route)
         if eps is not None:
             raise ValueError("DeviceGdcFeeder is top-k only: a captured step needs a fixed edge count (eps= keeps a "
                              "data-dependent one); use gdc.batch_from_dense(..., eps=) per batch")
@@ -423,6 +427,9 @@ class DeviceGdcFeeder(_AheadOnSideStream):
         self._counts = torch.empty(self.bsz, dtype=torch.int32, device=adj.device)
         if adj.dtype != torch.float32 or not adj.is_contiguous():
             raise ValueError("DeviceGdcFeeder: adj must be a contiguous float32 [S, R, R]")
+        self.route = _resolve_route(route, int(adj.shape[1]), kernel)
+        self._ws, self._ws_bytes = (tiled_workspace(self.bsz, adj.shape[1], kernel, adj.device)
+                                    if self.route == "tiled" else (None, 0))
         self._init_slots(adj.device, steps, depth)
 
     def _build(self, idx, check=False):
@@ -433,19 +440,24 @@ class DeviceGdcFeeder(_AheadOnSideStream):
         for k, v in sel.items():
             per[k] = v.reshape(b, -1) if k in ("snps_feat", "tsne_fdim", "clini_score") else v.reshape(-1)
         out = self._make(torch.index_select(self.adj, 0, idx), x, top_k=self.top_k, alpha=self.alpha, check=check,
-                         kernel=self.kernel, t=self.t, **per)
+                         kernel=self.kernel, t=self.t, route=self.route, **per)
         out.A = None                                    # the dense matrices are not an input of the step
         return out
 
     def _fill(self, slot, idx):
         """Three launches on the side stream: the per-subject attributes (igcn_gather_batch), the diffusion of the
-        drawn matrices read in place (igcn_gdc_topk_of, igcn_gdc_diffuse for the heat kernel) straight into the slot's
-        edge list, the edge offsets."""
+        drawn matrices read in place (igcn_gdc_topk_of, igcn_gdc_diffuse for the heat kernel; the launch sequence of
+        igcn_gdc_diffuse_tiled on the tiled route) straight into the slot's edge list, the edge offsets."""
         from ._lib import call, ptr, stream_ptr
         from .gdc import KERNELS
         b, r = int(idx.numel()), int(self.adj.shape[1])
         gather_rows(idx, r, [(getattr(slot, k), v, False) for k, v in self.cols.items()])
-        if self.kernel == "ppr":
+        if self.route == "tiled":
+            param = self.alpha if self.kernel == "ppr" else self.t
+            call("igcn_gdc_diffuse_tiled", b, r, KERNELS[self.kernel], param, 0, self.top_k, 0.0, ptr(self.adj),
+                 int(self.adj.shape[0]), ptr(idx), ptr(slot.edge_index), ptr(slot.edge_attr), ptr(self._counts),
+                 ptr(self._ws), self._ws_bytes, stream_ptr())
+        elif self.kernel == "ppr":
             call("igcn_gdc_topk_of", b, r, self.top_k, self.alpha, ptr(self.adj), int(self.adj.shape[0]), ptr(idx), ptr(slot.edge_index),
                  ptr(slot.edge_attr), ptr(self._counts), stream_ptr())
         else:

@@ -1341,6 +1341,32 @@ int igcn_gdc_max_rois(int kernel);
 int igcn_gdc_diffuse(int B, int R, int kernel, double param, int sparsify, int k, double eps, const float* A,
                      int64_t n_subjects, const int64_t* subject /* NULL: graph g = matrix g */, int64_t* edge_index,
                      float* edge_attr, int32_t* counts, void* stream);
+/* The same transform for graphs beyond the LDS limit (csrc/gdc_tiled.hip): all of util_gdc.py — get_ppr_matrix :7-14,
+ * get_heat_matrix :16-23, get_top_k_matrix :25-31, get_clipped_matrix :33-38, coo_matrix :82-86 — with every graph's
+ * fp64 system in a caller-supplied global-memory workspace and the products on the fp64 matrix cores.  Arguments,
+ * output layout, padding, counts and the subject list as igcn_gdc_diffuse; any R in [1, igcn_gdc_tiled_max_rois()].
+ *   PPR   P = alpha (I - G)^-1 as prod_{j<J} (I + G^(2^j)), G = (1 - alpha) H, J = ceil(log2(ln 2^-60 / ln(1 - alpha)))
+ *         (10 at alpha = 0.05, 8 at 0.15): 2 (J - 1) products.  alpha in [0.001, 1]: the smallest alpha with J <= 16.
+ *   heat  the scheme of igcn_gdc_diffuse (degree-14 Taylor polynomial, s squarings, s per graph from |t H|_1); t in
+ *         (0,64].  13 + smax products, smax = ceil(log2(2 t sqrt(R))) >= s for every symmetric A (|H|_1 <= sqrt(R)); a
+ *         graph whose own s is smaller passes through the remaining launches unchanged.  For an A that is not symmetric
+ *         s is capped at smax: beyond |t H|_1 = t sqrt(R) the Taylor remainder grows with the excess.
+ * The results differ from igcn_gdc_diffuse in the last bits of the weights (another summation order), not in the
+ * contract.  The library allocates nothing: `workspace` (device, 16-byte aligned) holds at least
+ * igcn_gdc_tiled_workspace_bytes(B, R, kernel) bytes — per graph four (PPR) or three (heat) Rp x Rp fp64 matrices,
+ * Rp = R rounded up to 64, plus 32 Rp + 80 bytes; linear in B, 0 for sizes outside the interface.  Its contents need no
+ * initialisation and mean nothing afterwards.  A workspace that is too small: IGCN_ERR_UNSUPPORTED, the message names
+ * the bytes needed; R above the limit: IGCN_ERR_UNSUPPORTED ("max R = 512").  B <= 65535 per call.
+ * A matrix with a zero row sum is outside the contract exactly as for igcn_gdc_diffuse: the values are then
+ * unspecified, the writes still stay inside the graph's slots and the workspace.
+ * No atomics, one writer per element, fixed summation order: two runs give the same bits, and so does a batch
+ * processed in several calls of fewer graphs. */
+int igcn_gdc_tiled_max_rois(void);
+size_t igcn_gdc_tiled_workspace_bytes(int B, int R, int kernel);
+int igcn_gdc_diffuse_tiled(int B, int R, int kernel, double param, int sparsify, int k, double eps, const float* A,
+                           int64_t n_subjects, const int64_t* subject /* NULL: graph g = matrix g */,
+                           int64_t* edge_index, float* edge_attr, int32_t* counts, void* workspace,
+                           size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Epoch evaluation on the device (csrc/eval.hip): replaces the per-batch host work of eval_loss :564-600, eval_acc
