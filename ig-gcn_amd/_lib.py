@@ -14,7 +14,7 @@ from . import switches
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libigcn.so")
 
-ABI_VERSION = 440      # include/igcn.h IGCN_ABI_VERSION this table was written against (tests/test_abi.py compares)
+ABI_VERSION = 441     # include/igcn.h IGCN_ABI_VERSION this table was written against (tests/test_abi.py compares)
 
 P, I, L, F, Z = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
 
@@ -264,6 +264,11 @@ SIGNATURES = {
     "igcn_kmeans_assign": (I, [L, I, I, P, P, P, P, P, P, P, P, P]),
     "igcn_kmeans_update": (I, [L, I, I, P, P, P, P, P, P, P, P]),
     "igcn_kmeanspp_step": (I, [L, I, I, P, P, P, P, P, P]),
+    "igcn_perm_planes_bytes": (Z, [I, I]),
+    "igcn_perm_plane_dims": (I, [I, I, P]),
+    "igcn_perm_prepare": (I, [L, I, I, P, P, I, P, P, P, P, P]),
+    "igcn_perm_maxsum_scratch_bytes": (Z, [I, I]),
+    "igcn_perm_maxsum": (I, [I, I, I, P, L, P, P, P, P, P, P, Z, P]),
 }
 
 _lib = None

@@ -1,0 +1,348 @@
+// Max-T permutation test of a two-group difference over the E entries of a per-subject map table x [S_all, E]
+// (include/igcn.h: igcn_perm_prepare, igcn_perm_maxsum).  For P relabellings of the S subjects under test the work is
+//   G[p, e] = sum_s member[p, s] z[s, e],      member 0/1 (row p = group A of relabelling p), z the standardised column,
+// a [P, S] x [S, E] product that is never stored: the epilogue keeps max_e |G[p, e]| per relabelling and, per entry, the
+// number of relabellings with |G[p, e]| >= |g_obs[e]|.  After standardisation every column has the same sum of squares,
+// so |t| is one increasing function of |G| for all columns and comparing |G| is comparing |t|.
+//
+// Exact operands on the bf16 matrix unit: z (fp32) is split into three bf16 planes hi = bf16(z), mid = bf16(z - hi),
+// lo = bf16(z - hi - mid), every residual exact in fp32, so hi + mid + lo == z for every z whose residuals stay normal;
+// member widens to bf16 0.0 / 1.0.  Every product is exact and the three planes accumulate into the SAME fp32
+// accumulators: the only rounding is the fp32 accumulation.
+//
+// Layout of the planes: [3][Ep][Sp] bf16, Ep = E rounded up to PT_BN, Sp = S rounded up to PT_BK, the subject axis
+// contiguous (the B fragment of v_mfma_f32_16x16x32_bf16 — col = lane & 15, k = 8 (lane >> 4) .. + 7 — is one 16-byte
+// read of a row), zeros in the padding.
+//
+// Launch sequence of igcn_perm_maxsum: k_perm_maxsum (per-tile partials) -> k_perm_fold_max, k_perm_fold_cnt.
+// One writer per element, no atomics, fixed order: the accumulation order along S of a row is k-steps ascending, planes
+// hi, mid, lo inside a step, whichever tile or launch the row sits in.
+#include <math.h>
+
+#include "common.h"
+
+#define PT_BM 128                                      // relabellings per workgroup: 4 waves x 2 fragments of 16 rows
+#define PT_BN 64                                       // map entries per workgroup: 4 fragments of 16 columns per wave
+#define PT_BK 32                                       // subjects per step: one v_mfma_f32_16x16x32_bf16 deep
+#define PT_LD (PT_BK + 8)                              // LDS row: 32 bf16 + 8 pad (80 B), as k_gemm_bf16 (csrc/gemm.hip)
+#define PT_T 256
+#define PT_MIN_S 4
+#define PT_MAX_S 4096
+#define PT_MAX_E (1 << 20)
+#define PT_MAX_P 65536
+#define PT_MAX_G_ROWS 8                                // g is written for P <= 8 (the observed pass: P = 1)
+
+typedef __bf16 pt_bf16x8 __attribute__((ext_vector_type(8)));
+typedef float pt_f32x4 __attribute__((ext_vector_type(4)));
+
+static inline int pt_ep(int E) { return (E + PT_BN - 1) / PT_BN * PT_BN; }
+static inline int pt_sp(int S) { return (S + PT_BK - 1) / PT_BK * PT_BK; }
+
+// ---- prepare ----------------------------------------------------------------------------------------------------------
+// Thread = column (adjacent threads read adjacent floats of a row); the listed rows in list order, fp64 throughout:
+// the mean, then the centred sum of squares, then z.  A row index outside [0, S_all) reads as NaN (never out of bounds).
+__device__ __forceinline__ unsigned short pt_bits(__bf16 v) { return __builtin_bit_cast(unsigned short, v); }
+
+__global__ void __launch_bounds__(256)
+k_perm_prepare(int64_t S_all, int S, int E, int Ep, int Sp, const float* __restrict__ x,
+               const int64_t* __restrict__ rows, int standardize, double* __restrict__ mean, double* __restrict__ sd,
+               uint8_t* __restrict__ constant, unsigned short* __restrict__ planes) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= Ep) return;
+  const size_t plane = (size_t)Ep * Sp;
+  unsigned short* ph = planes + (size_t)e * Sp;
+  if (e >= E) {                                         // a padded column: zeros in all three planes
+    for (int s = 0; s < Sp; ++s) {
+      ph[s] = 0;
+      ph[plane + s] = 0;
+      ph[2 * plane + s] = 0;
+    }
+    return;
+  }
+  const float nanf_ = __builtin_nanf("");
+  auto at = [&](int s) -> float {
+    const int64_t r = rows[s];
+    return (r < 0 || r >= S_all) ? nanf_ : x[r * (int64_t)E + e];
+  };
+  double sum = 0.0;
+  float lo = at(0), hi = lo;
+  for (int s = 0; s < S; ++s) {
+    const float v = at(s);
+    sum += (double)v;
+    lo = fminf(lo, v);
+    hi = fmaxf(hi, v);
+  }
+  const double m = sum / (double)S;
+  double ss = 0.0;
+  for (int s = 0; s < S; ++s) {
+    const double d = (double)at(s) - m;
+    ss += d * d;
+  }
+  const double dev = sqrt(ss / (double)S);
+  const bool is_const = hi == lo;
+  mean[e] = m;
+  sd[e] = dev;
+  constant[e] = is_const ? 1 : 0;
+  for (int s = 0; s < Sp; ++s) {
+    float z = 0.f;
+    if (s < S) {
+      const float v = at(s);
+      z = !standardize ? v : is_const ? 0.f : (float)(((double)v - m) / dev);
+    }
+    const __bf16 b0 = (__bf16)z;                        // round to nearest even
+    const float r1 = z - (float)b0;                     // exact: the residual of an 8-bit rounding of a 24-bit value
+    const __bf16 b1 = (__bf16)r1;
+    const float r2 = r1 - (float)b1;                    // exact
+    const __bf16 b2 = (__bf16)r2;
+    ph[s] = pt_bits(b0);
+    ph[plane + s] = pt_bits(b1);
+    ph[2 * plane + s] = pt_bits(b2);
+  }
+}
+
+// ---- the product and its epilogue --------------------------------------------------------------------------------------
+// Grid (row tiles, column tiles): the workgroups in flight share the column tiles of the planes and all of member.
+// Wave w owns rows 32 w .. 32 w + 31 of the tile (two A fragments) and all 64 columns (four B fragments):
+//   acc[a][b][r] = G[m0 + 32 w + 16 a + 4 (lane >> 4) + r][n0 + 16 b + (lane & 15)]
+// member is staged one row half (16 bytes) per thread: as one 16-byte load when every row of member starts 16-byte
+// aligned (ldm % 16 == 0 and an aligned base; the bytes behind S of a row are then inside the row's stride), else byte
+// by byte; both give the same LDS image.
+struct PtStage {
+  uint4 a;                                              // 16 member bytes
+  uint4 b[3];                                           // 8 bf16 of each plane
+};
+
+__device__ __forceinline__ void pt_load(PtStage& st, const uint8_t* __restrict__ member, int64_t ldm, bool vec, int P,
+                                        int S, int m0, const unsigned short* __restrict__ planes, size_t plane, int Sp,
+                                        int n0, int k0, int tid) {
+  const int ar = tid >> 1, ak = k0 + (tid & 1) * 16;
+  const int p = m0 + ar;
+  st.a = make_uint4(0u, 0u, 0u, 0u);
+  if (p < P && ak < S) {
+    const uint8_t* src = member + (int64_t)p * ldm + ak;
+    if (vec) {
+      st.a = *reinterpret_cast<const uint4*>(src);
+    } else {
+      unsigned w[4] = {0u, 0u, 0u, 0u};
+      const int n = S - ak < 16 ? S - ak : 16;
+      for (int j = 0; j < n; ++j) w[j >> 2] |= (unsigned)src[j] << (8 * (j & 3));
+      st.a = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+  }
+  const int br = tid >> 2, bk = k0 + (tid & 3) * 8;      // (Ep, Sp are whole tiles: no bound to check)
+  const unsigned short* src = planes + (size_t)(n0 + br) * Sp + bk;
+#pragma unroll
+  for (int q = 0; q < 3; ++q) st.b[q] = *reinterpret_cast<const uint4*>(src + q * plane);
+}
+
+__device__ __forceinline__ void pt_store(const PtStage& st, unsigned short (*As)[PT_LD],
+                                         unsigned short (*Bs)[PT_BN][PT_LD], int S, int k0, int tid) {
+  const int ar = tid >> 1, ah = (tid & 1) * 16, ak = k0 + ah;
+  const unsigned w[4] = {st.a.x, st.a.y, st.a.z, st.a.w};
+  unsigned o[8];
+#pragma unroll
+  for (int j = 0; j < 16; j += 2) {                     // member byte -> bf16 0.0 / 1.0 (0x3F80); nothing behind S
+    const unsigned lo = ((w[j >> 2] >> (8 * (j & 3))) & 0xFFu) && ak + j < S ? 0x3F80u : 0u;
+    const unsigned hi = ((w[(j + 1) >> 2] >> (8 * ((j + 1) & 3))) & 0xFFu) && ak + j + 1 < S ? 0x3F80u : 0u;
+    o[j >> 1] = lo | (hi << 16);
+  }
+  uint4* ad = reinterpret_cast<uint4*>(&As[ar][ah]);
+  ad[0] = make_uint4(o[0], o[1], o[2], o[3]);
+  ad[1] = make_uint4(o[4], o[5], o[6], o[7]);
+  const int br = tid >> 2, bk = (tid & 3) * 8;
+#pragma unroll
+  for (int q = 0; q < 3; ++q) *reinterpret_cast<uint4*>(&Bs[q][br][bk]) = st.b[q];
+}
+
+__global__ void __launch_bounds__(PT_T)
+k_perm_maxsum(int P, int S, int E, int Sp, const uint8_t* __restrict__ member, int64_t ldm, int vec,
+              const unsigned short* __restrict__ planes, size_t plane, const float* __restrict__ g_obs,
+              float* __restrict__ pmax, int tiles_e, int32_t* __restrict__ pcnt, float* __restrict__ g) {
+  __shared__ __attribute__((aligned(16))) unsigned short As[2][PT_BM][PT_LD];
+  __shared__ __attribute__((aligned(16))) unsigned short Bs[2][3][PT_BN][PT_LD];
+  __shared__ int cnt_s[PT_T / 64][PT_BN];
+  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lr = lane & 15, lg = lane >> 4;
+  const int m0 = blockIdx.x * PT_BM, n0 = blockIdx.y * PT_BN;
+
+  pt_f32x4 acc[2][4];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[a][b] = (pt_f32x4){0.f, 0.f, 0.f, 0.f};
+
+  PtStage st;
+  pt_load(st, member, ldm, vec != 0, P, S, m0, planes, plane, Sp, n0, 0, tid);
+  pt_store(st, As[0], Bs[0], S, 0, tid);
+  __syncthreads();
+  int buf = 0;
+  for (int k0 = 0; k0 < Sp; k0 += PT_BK) {
+    const bool more = k0 + PT_BK < Sp;
+    if (more) pt_load(st, member, ldm, vec != 0, P, S, m0, planes, plane, Sp, n0, k0 + PT_BK, tid);
+    pt_bf16x8 fa[2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a) fa[a] = *reinterpret_cast<const pt_bf16x8*>(&As[buf][w * 32 + a * 16 + lr][lg * 8]);
+#pragma unroll
+    for (int q = 0; q < 3; ++q)                         // planes hi, mid, lo into the same accumulators
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        const pt_bf16x8 fb = *reinterpret_cast<const pt_bf16x8*>(&Bs[buf][q][b * 16 + lr][lg * 8]);
+#pragma unroll
+        for (int a = 0; a < 2; ++a) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[a], fb, acc[a][b], 0, 0, 0);
+      }
+    if (more) pt_store(st, As[buf ^ 1], Bs[buf ^ 1], S, k0 + PT_BK, tid);
+    __syncthreads();
+    buf ^= 1;
+  }
+
+  // ---- epilogue: G stays in registers ----
+  const int prow = m0 + w * 32 + lg * 4;                // + 16 a + r
+  if (g_obs == nullptr) {                               // the observed pass: G itself, P <= PT_MAX_G_ROWS
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 4; ++b)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int p = prow + 16 * a + r, e = n0 + 16 * b + lr;
+          if (p < P && e < E) g[(size_t)p * E + e] = acc[a][b][r];
+        }
+  }
+  // maxabs partial: over the tile's real columns, for each of the lane's 8 rows; lanes of one 16-group hold the columns
+  float mx[2][4];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float v = 0.f;
+#pragma unroll
+      for (int b = 0; b < 4; ++b)
+        if (n0 + 16 * b + lr < E) v = fmaxf(v, fabsf(acc[a][b][r]));
+#pragma unroll
+      for (int o = 8; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+      mx[a][r] = v;
+    }
+  if (lr == 0) {
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int p = prow + 16 * a + r;
+        if (p < P) pmax[(size_t)p * tiles_e + blockIdx.y] = mx[a][r];
+      }
+  }
+  if (g_obs != nullptr) {                               // exceedance partial: over the tile's real rows, per column
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int e = n0 + 16 * b + lr;
+      const float thr = e < E ? fabsf(g_obs[e]) : 0.f;
+      int c = 0;
+#pragma unroll
+      for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) c += (prow + 16 * a + r < P && fabsf(acc[a][b][r]) >= thr) ? 1 : 0;
+      c += __shfl_xor(c, 16, 64);
+      c += __shfl_xor(c, 32, 64);
+      if (lg == 0) cnt_s[w][16 * b + lr] = c;
+    }
+    __syncthreads();
+    if (tid < PT_BN && n0 + tid < E)
+      pcnt[(size_t)blockIdx.x * E + n0 + tid] = cnt_s[0][tid] + cnt_s[1][tid] + cnt_s[2][tid] + cnt_s[3][tid];
+  }
+}
+
+// maxabs[p] = max_t pmax[p][t], tiles ascending
+__global__ void __launch_bounds__(256)
+k_perm_fold_max(int P, int tiles_e, const float* __restrict__ pmax, float* __restrict__ maxabs) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= P) return;
+  const float* src = pmax + (size_t)p * tiles_e;
+  float v = 0.f;
+  for (int t = 0; t < tiles_e; ++t) v = fmaxf(v, src[t]);
+  maxabs[p] = v;
+}
+
+// exceed[e] = sum_t pcnt[t][e], tiles ascending
+__global__ void __launch_bounds__(256)
+k_perm_fold_cnt(int E, int tiles_p, const int32_t* __restrict__ pcnt, int32_t* __restrict__ exceed) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= E) return;
+  int32_t c = 0;
+  for (int t = 0; t < tiles_p; ++t) c += pcnt[(size_t)t * E + e];
+  exceed[e] = c;
+}
+
+// ---- host -------------------------------------------------------------------------------------------------------------
+static bool pt_sizes_ok(int S, int E) { return S >= PT_MIN_S && S <= PT_MAX_S && E >= 1 && E <= PT_MAX_E; }
+
+extern "C" size_t igcn_perm_planes_bytes(int S, int E) {
+  if (!pt_sizes_ok(S, E)) return 0;
+  return (size_t)3 * pt_ep(E) * pt_sp(S) * sizeof(unsigned short);
+}
+
+extern "C" int igcn_perm_plane_dims(int S, int E, int* dims) {
+  IGCN_REQUIRE(dims != nullptr, "perm_plane_dims: dims is null");
+  IGCN_REQUIRE(pt_sizes_ok(S, E), "perm_plane_dims: S=%d outside [%d,%d] or E=%d outside [1,%d]", S, PT_MIN_S, PT_MAX_S,
+               E, PT_MAX_E);
+  dims[0] = pt_ep(E);
+  dims[1] = pt_sp(S);
+  return IGCN_OK;
+}
+
+extern "C" int igcn_perm_prepare(int64_t S_all, int S, int E, const float* x, const int64_t* rows, int standardize,
+                                 double* mean, double* sd, uint8_t* constant, void* planes, void* stream) {
+  const char* who = "perm_prepare";
+  IGCN_REQUIRE(S >= PT_MIN_S && S <= PT_MAX_S, "%s: S=%d subjects outside [%d,%d]", who, S, PT_MIN_S, PT_MAX_S);
+  IGCN_REQUIRE(E >= 1 && E <= PT_MAX_E, "%s: E=%d map entries outside [1,%d]", who, E, PT_MAX_E);
+  IGCN_REQUIRE(S_all >= 1, "%s: S_all=%lld rows in the table", who, (long long)S_all);
+  IGCN_REQUIRE(x && rows && mean && sd && constant && planes, "%s: a null buffer", who);
+  IGCN_REQUIRE(((uintptr_t)planes & 15) == 0, "%s: the planes must be 16-byte aligned", who);
+  const int Ep = pt_ep(E), Sp = pt_sp(S);
+  hipLaunchKernelGGL(k_perm_prepare, dim3((Ep + 255) / 256), dim3(256), 0, (hipStream_t)stream, S_all, S, E, Ep, Sp, x,
+                     rows, standardize, mean, sd, constant, (unsigned short*)planes);
+  IGCN_CHECK_LAUNCH(who);
+  return IGCN_OK;
+}
+
+extern "C" size_t igcn_perm_maxsum_scratch_bytes(int P, int E) {
+  if (P < 1 || P > PT_MAX_P || E < 1 || E > PT_MAX_E) return 0;
+  const size_t tiles_p = (P + PT_BM - 1) / PT_BM, tiles_e = (E + PT_BN - 1) / PT_BN;
+  return (size_t)P * tiles_e * sizeof(float) + tiles_p * (size_t)E * sizeof(int32_t);
+}
+
+extern "C" int igcn_perm_maxsum(int P, int S, int E, const uint8_t* member, int64_t ldm, const void* planes,
+                                const float* g_obs, float* maxabs, int32_t* exceed, float* g, void* scratch,
+                                size_t scratch_bytes, void* stream) {
+  const char* who = "perm_maxsum";
+  IGCN_REQUIRE(S >= PT_MIN_S && S <= PT_MAX_S, "%s: S=%d subjects outside [%d,%d]", who, S, PT_MIN_S, PT_MAX_S);
+  IGCN_REQUIRE(E >= 1 && E <= PT_MAX_E, "%s: E=%d map entries outside [1,%d]", who, E, PT_MAX_E);
+  IGCN_REQUIRE(P >= 1 && P <= PT_MAX_P, "%s: P=%d relabellings in one launch outside [1,%d]", who, P, PT_MAX_P);
+  IGCN_REQUIRE(ldm >= S, "%s: member row stride %lld below S=%d", who, (long long)ldm, S);
+  IGCN_REQUIRE(member && planes && maxabs && scratch, "%s: a null buffer", who);
+  if (g_obs) {
+    IGCN_REQUIRE(exceed != nullptr, "%s: g_obs without an exceed buffer", who);
+  } else {
+    IGCN_REQUIRE(g != nullptr && P <= PT_MAX_G_ROWS, "%s: without g_obs the call writes g itself, for P <= %d (P=%d)", who,
+                 PT_MAX_G_ROWS, P);
+  }
+  IGCN_REQUIRE(((uintptr_t)planes & 15) == 0 && ((uintptr_t)scratch & 15) == 0,
+               "%s: the planes and the scratch must be 16-byte aligned", who);
+  const size_t need = igcn_perm_maxsum_scratch_bytes(P, E);
+  if (scratch_bytes < need) {
+    igcn_set_error("%s: the scratch holds %zu bytes, P=%d E=%d needs %zu bytes", who, scratch_bytes, P, E, need);
+    return IGCN_ERR_UNSUPPORTED;
+  }
+  const int Ep = pt_ep(E), Sp = pt_sp(S);
+  const int tiles_p = (P + PT_BM - 1) / PT_BM, tiles_e = Ep / PT_BN;
+  float* pmax = (float*)scratch;
+  int32_t* pcnt = (int32_t*)(pmax + (size_t)P * tiles_e);
+  const int vec = (ldm % 16 == 0 && ((uintptr_t)member & 15) == 0) ? 1 : 0;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_perm_maxsum, dim3(tiles_p, tiles_e), dim3(PT_T), 0, st, P, S, E, Sp, member, ldm, vec,
+                     (const unsigned short*)planes, (size_t)Ep * Sp, g_obs, pmax, tiles_e, pcnt, g);
+  hipLaunchKernelGGL(k_perm_fold_max, dim3((P + 255) / 256), dim3(256), 0, st, P, tiles_e, pmax, maxabs);
+  if (g_obs)
+    hipLaunchKernelGGL(k_perm_fold_cnt, dim3((E + 255) / 256), dim3(256), 0, st, E, tiles_p, pcnt, exceed);
+  IGCN_CHECK_LAUNCH(who);
+  return IGCN_OK;
+}

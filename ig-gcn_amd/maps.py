@@ -1,7 +1,8 @@
 """The cohort explanation passes — ``attention_maps``, ``association_maps``, ``connectivity_maps`` and ``saliency_maps``
 — over one per-class accumulator (``ClassSums``).  Every pass runs a model method per batch, sums what it returns per
 class of ``data.y`` on the device (igcn_attn_map_accumulate: fp64, sample order; one call per quantity and batch) and
-reads the device once at the end.  None of them trains; ``igcn_amd.train`` re-exports the four names.
+reads the device once at the end.  ``group_difference`` is a pass of its own: it keeps every subject's map and hands the
+table to the max-T permutation test of ``igcn_amd.stats``.  None of them trains; ``igcn_amd.train`` re-exports the five names.
 """
 import torch
 
@@ -215,4 +216,70 @@ def saliency_maps(model, loader, method="gradxinput", target=None, inputs="image
         out["top_snps"] = torch.topk(snps_overall.abs(), min(int(top_k), snps_overall.shape[0])).indices
     if delta_sum is not None:
         out["mean_abs_delta"] = float(delta_sum) / out["n"]
+    return out
+
+
+QUANTITIES = ("association", "attention", "connectivity", "saliency")
+
+
+def _subject_maps(model, data, quantity, kw):
+    """[B, ...] fp32: the per-subject maps of one batch, from the model method the corresponding cohort pass calls."""
+    temperature, device, explain = kw.get("temperature"), kw.get("device"), kw.get("isExplain", False)
+    if quantity == "attention":
+        return model.attention_weights(data, temperature, device, explain)
+    if quantity == "association":
+        return model.snp_association(data, temperature, device, explain)
+    if quantity == "connectivity":
+        if kw.get("source", "mask") == "mask":
+            return model.edge_importance(data, weighted=kw.get("weighted", False))
+        return model.gat_attention(data, isExplain=explain)
+    target = kw.get("target")
+    tgt = data.y.view(-1) if isinstance(target, str) else target
+    return model.input_saliency(data, temperature, device, target=tgt, isExplain=explain,
+                                inputs=kw.get("inputs", "image"), normalize=kw.get("normalize", True))["attr"]
+
+
+def group_difference(model, loader, quantity="association", groups=(0, 1), permutations=10000, seed=0, members=None,
+                     top_k=10, **pass_kw):
+    """Which entries of a cohort map differ between two diagnosis groups, corrected over the whole map: the two-sample
+    max-T permutation test (``stats.permutation_test``) on the per-subject maps of ``quantity`` — "association"
+    (``model.snp_association``), "attention" (``model.attention_weights``), "connectivity" (``model.edge_importance``,
+    or ``model.gat_attention`` with ``source="gat"``) or "saliency" (``model.input_saliency``'s ``attr``).  ``pass_kw``
+    are the keywords of the corresponding cohort pass (``temperature``, ``device``, ``isExplain``; ``source``,
+    ``weighted``; ``target``, ``inputs``, ``normalize``).  A pass of its own: every batch's maps are copied into one
+    preallocated [S_all, E] device buffer, the labels beside it, and nothing is summed per class.  Returns the dict of
+    ``stats.permutation_test`` in the map's shape plus ``significant`` (int64: the flat indices of the entries with
+    ``p_fwe <= 0.05``, largest |t| first, at most ``top_k``).  A group with fewer than 2 subjects raises ValueError."""
+    from . import stats
+    if quantity not in QUANTITIES:
+        raise ValueError(f"group_difference: quantity={quantity!r} (one of {QUANTITIES})")
+    known = set(("temperature", "device", "isExplain") + {"connectivity": ("source", "weighted"),
+                                                          "saliency": ("target", "inputs", "normalize")}.get(quantity, ()))
+    if set(pass_kw) - known:
+        raise TypeError(f"group_difference: {quantity!r} takes no {sorted(set(pass_kw) - known)}")
+    if pass_kw.get("source", "mask") not in ("mask", "gat"):
+        raise ValueError(f"group_difference: source={pass_kw['source']!r} ('mask' or 'gat')")
+    total = len(loader.dataset) if hasattr(loader, "dataset") else sum(int(d.num_graphs) for d in loader)
+    buf = labels = None
+    n = 0
+    for data in _batches(loader, pass_kw.get("device")):
+        m = _subject_maps(model, data, quantity, pass_kw).detach()
+        b = int(m.shape[0])
+        if buf is None:
+            shape = tuple(m.shape[1:])
+            buf = ops._buffer((total, m[0].numel()), torch.float32, m.device)
+            labels = ops._buffer((total,), torch.int64, m.device)
+        if n + b > total:
+            raise ValueError(f"group_difference: the loader yields more than its {total} subjects")
+        buf[n:n + b] = m.reshape(b, -1)
+        labels[n:n + b] = data.y.view(-1)
+        n += b
+    if n == 0:
+        raise ValueError("group_difference: the loader is empty")
+    out = stats.permutation_test(buf[:n].view(n, *shape), labels[:n], groups=groups, permutations=permutations, seed=seed,
+                                 members=members)
+    t_abs = out["t"].reshape(-1).abs()
+    hit = torch.nonzero(out["p_fwe"].reshape(-1) <= 0.05).view(-1)
+    order = torch.argsort(t_abs[hit], descending=True, stable=True)[:max(int(top_k), 0)]
+    out["significant"] = hit[order]
     return out

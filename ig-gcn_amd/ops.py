@@ -3753,3 +3753,80 @@ def kmeanspp_step(x, u, closest, pot, chosen):
         raise ValueError("kmeanspp_step: u must hold 1..8 float64 numbers on the points' device")
     call("igcn_kmeanspp_step", x.shape[0], x.shape[1], int(u.numel()), ptr(x), ptr(u.contiguous()), ptr(closest), ptr(pot),
          ptr(chosen), stream_ptr())
+
+
+from .gdc import _empty as _buffer  # noqa: E402  (the package's one device-buffer helper: (shape, dtype, device))
+
+PERM_MIN_S, PERM_MAX_S, PERM_MAX_E, PERM_MAX_P, PERM_MAX_G_ROWS = 4, 4096, 1 << 20, 65536, 8      # csrc/perm_test.hip
+
+
+def perm_plane_dims(s, e):
+    """(Ep, Sp) of the bf16 planes [3, Ep, Sp] that igcn_perm_prepare writes for S subjects and E map entries."""
+    dims = (ctypes.c_int * 2)()
+    call("igcn_perm_plane_dims", int(s), int(e), ctypes.addressof(dims))
+    return int(dims[0]), int(dims[1])
+
+
+def perm_prepare(x, rows, standardize=True):
+    """Column statistics and the exact bf16 split of a map table (igcn_perm_prepare): x [S_all, E] fp32, rows [S] int64
+    (the subjects under test).  Returns (mean [E] fp64, sd [E] fp64 (population), constant [E] uint8, planes
+    [3, Ep, Sp] bf16): ``planes[0] + planes[1] + planes[2]`` (in fp32) is ``z[s, e]`` at [e, s], z the standardised column
+    (0 for a constant one; x itself with ``standardize=False``), zeros in the padding."""
+    if x.dtype != torch.float32 or x.dim() != 2 or not x.is_contiguous():
+        raise TypeError("perm_prepare: x must be a contiguous float32 [S_all, E]")
+    if rows.dtype != torch.int64 or rows.dim() != 1 or rows.device != x.device:
+        raise TypeError("perm_prepare: rows must be int64 [S] on x's device")
+    s, e, dev = int(rows.numel()), int(x.shape[1]), x.device
+    if not PERM_MIN_S <= s <= PERM_MAX_S or not 1 <= e <= PERM_MAX_E:
+        raise ValueError(f"perm_prepare: S={s} outside [{PERM_MIN_S}, {PERM_MAX_S}] or E={e} outside [1, {PERM_MAX_E}]")
+    ep, sp = perm_plane_dims(s, e)
+    mean, sd = _buffer((e,), torch.float64, dev), _buffer((e,), torch.float64, dev)
+    constant = _buffer((e,), torch.uint8, dev)
+    planes = _buffer((3, ep, sp), torch.bfloat16, dev)
+    call("igcn_perm_prepare", int(x.shape[0]), s, e, ptr(x), ptr(rows.contiguous()), int(bool(standardize)), ptr(mean),
+         ptr(sd), ptr(constant), ptr(planes), stream_ptr())
+    return mean, sd, constant, planes
+
+
+def perm_planes_to_z(planes, s, e):
+    """z [S, E] fp32 back from the planes of ``perm_prepare`` (hi + mid + lo in fp32: exact)."""
+    p = planes[:, :e, :s].float()
+    return ((p[0] + p[1]) + p[2]).t().contiguous()
+
+
+def perm_maxsum(member, planes, e, g_obs=None):
+    """The relabelled group sums of igcn_perm_maxsum, never stored: member [P, S] uint8 (0/1; row p = group A of
+    relabelling p; any row stride), planes of ``perm_prepare`` for the same S and ``e`` entries.  With ``g_obs`` [E] fp32:
+    (maxabs [P], exceed [E] int32) = (max_e |G[p, e]|, #{p : |G[p, e]| >= |g_obs[e]|}).  Without: (maxabs [P], g [P, E])
+    for P <= 8, the observed pass."""
+    if member.dtype != torch.uint8 or member.dim() != 2 or member.stride(1) != 1 or member.device != planes.device:
+        raise TypeError("perm_maxsum: member must be uint8 [P, S] with unit column stride on the planes' device")
+    p, s, e, dev = int(member.shape[0]), int(member.shape[1]), int(e), planes.device
+    if not 1 <= p <= PERM_MAX_P:
+        raise ValueError(f"perm_maxsum: P={p} relabellings in one launch outside [1, {PERM_MAX_P}]")
+    if not PERM_MIN_S <= s <= PERM_MAX_S or not 1 <= e <= PERM_MAX_E:
+        raise ValueError(f"perm_maxsum: S={s} outside [{PERM_MIN_S}, {PERM_MAX_S}] or E={e} outside [1, {PERM_MAX_E}]")
+    if (planes.dtype != torch.bfloat16 or not planes.is_contiguous() or tuple(planes.shape) != (3,) + perm_plane_dims(s, e)):
+        raise ValueError(f"perm_maxsum: planes {tuple(planes.shape)} are not those of perm_prepare for S={s}, E={e}")
+    ldm = int(member.stride(0)) if p > 1 else max(int(member.stride(0)), s)
+    if ldm < s:
+        raise ValueError("perm_maxsum: the rows of member overlap")
+    if not member.is_cuda:
+        raise _lib.IgcnError("libigcn operates on device memory only; got a CPU tensor")
+    mptr = member.data_ptr()                                     # (rows may be strided: ldm)
+    maxabs = _buffer((p,), torch.float32, dev)
+    nbytes = int(_lib.load().igcn_perm_maxsum_scratch_bytes(p, e))
+    scratch = _buffer(((nbytes + 3) // 4,), torch.int32, dev)
+    if g_obs is None:
+        if p > PERM_MAX_G_ROWS:
+            raise ValueError(f"perm_maxsum: without g_obs the sums themselves are returned, for P <= {PERM_MAX_G_ROWS}")
+        g = _buffer((p, e), torch.float32, dev)
+        call("igcn_perm_maxsum", p, s, e, mptr, ldm, ptr(planes), None, ptr(maxabs), None, ptr(g), ptr(scratch),
+             nbytes, stream_ptr())
+        return maxabs, g
+    if g_obs.dtype != torch.float32 or g_obs.numel() != e or g_obs.device != dev or not g_obs.is_contiguous():
+        raise ValueError(f"perm_maxsum: g_obs must be a contiguous float32 [{e}] on the planes' device")
+    exceed = _buffer((e,), torch.int32, dev)
+    call("igcn_perm_maxsum", p, s, e, mptr, ldm, ptr(planes), ptr(g_obs), ptr(maxabs), ptr(exceed), None,
+         ptr(scratch), nbytes, stream_ptr())
+    return maxabs, exceed

@@ -31,7 +31,7 @@ extern "C" {
 /* ABI revision: bumped whenever a prototype below changes (argument added, removed or re-ordered).  igcn_version()
  * returns the revision the library was built from; a binding written against a different one must refuse to call
  * (igcn_amd/_lib.py does). */
-#define IGCN_ABI_VERSION 440
+#define IGCN_ABI_VERSION 441
 int igcn_version(void);
 const char* igcn_last_error(void);
 /* A/B switches, set ONCE by the binding when it loads the library (from the IGCN_* environment variables): bit 0 no tiled
@@ -1533,6 +1533,37 @@ int igcn_kmeans_update(int64_t N, int d, int k, const float* X, const int64_t* l
                        const int64_t* counts, double* sums, float* centers, double* stats, void* stream);
 int igcn_kmeanspp_step(int64_t N, int d, int t, const float* X, const double* u, float* closest, double* pot,
                        int64_t* chosen, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Max-T permutation test of a two-group difference over the entries of a per-subject map table (csrc/perm_test.hip).
+ * x [S_all, E] fp32 holds one map of E entries per subject; rows [S] lists the subjects of the two groups under test.
+ * igcn_perm_prepare: per column over the listed rows, in fp64 and in list order: mean[e], the population sd[e] and
+ *   constant[e] (1 when the column's max equals its min over the listed rows: an exact test).  z = fp32((x - mean) / sd),
+ *   formed in fp64 and rounded once; z = 0 for a constant column; standardize = 0: z = x.  z is written as three bf16
+ *   planes hi = bf16(z), mid = bf16(z - hi), lo = bf16(z - hi - mid) (round to nearest, every residual exact in fp32:
+ *   hi + mid + lo == z for every z whose residuals stay normal), laid out [3][Ep][Sp] with the subject axis contiguous
+ *   and zeros in the padding; igcn_perm_plane_dims writes dims = {Ep, Sp} (E rounded up to 64, S to 32) and
+ *   igcn_perm_planes_bytes is 3 Ep Sp 2 (0 outside the limits).  A row index outside [0, S_all) reads as NaN.
+ * igcn_perm_maxsum: G[p, e] = sum_s member[p, s] z[s, e] on v_mfma_f32_16x16x32_bf16 for member [P, S] uint8 with row
+ *   stride ldm bytes (non-zero = 1; row p = group A of relabelling p), widened to bf16 0.0 / 1.0 while it is staged;
+ *   the three planes accumulate into the same fp32 accumulators, so every product is exact and the only rounding is the
+ *   fp32 accumulation.  G is never stored: maxabs[p] = max_e |G[p, e]| and, with g_obs [E] given,
+ *   exceed[e] = #{p : |G[p, e]| >= |g_obs[e]|} (int32).  With g_obs NULL the call writes g [P, E] itself, for P <= 8 (the
+ *   observed pass, P = 1, through the same tile code), and exceed is not touched.  Rows of member that start 16-byte
+ *   aligned (ldm % 16 == 0, aligned base: all ldm bytes of every row must then be readable) are staged with 16-byte
+ *   loads; the result does not depend on it.
+ *   Per-tile partials ([P, tiles_E] maxima, [tiles_P, E] counts) in `scratch` (device, 16-byte aligned,
+ *   igcn_perm_maxsum_scratch_bytes(P, E); 0 outside the limits) are folded in tile order by two small kernels.  One
+ *   writer per element, no atomics: two runs give the same bits, and a row's results do not depend on the tile, the
+ *   launch or the chunk it sits in (the accumulation order along S is the same for every row).  The library allocates
+ *   nothing.  Limits: 4 <= S <= 4096, 1 <= E <= 2^20, 1 <= P <= 65536 per launch. */
+size_t igcn_perm_planes_bytes(int S, int E);
+int igcn_perm_plane_dims(int S, int E, int* dims);
+int igcn_perm_prepare(int64_t S_all, int S, int E, const float* x, const int64_t* rows, int standardize, double* mean,
+                      double* sd, uint8_t* constant, void* planes, void* stream);
+size_t igcn_perm_maxsum_scratch_bytes(int P, int E);
+int igcn_perm_maxsum(int P, int S, int E, const uint8_t* member, int64_t ldm, const void* planes, const float* g_obs,
+                     float* maxabs, int32_t* exceed, float* g, void* scratch, size_t scratch_bytes, void* stream);
 
 #ifdef __cplusplus
 }
