@@ -1,19 +1,16 @@
 // Graph-diffusion pre-transform of a batch of dense brain adjacencies, on the device:
 //   util_gdc.py:7-15   get_ppr_matrix     P = alpha * (I - (1-alpha) * D^-1/2 A D^-1/2)^-1,  D = diag(row sums of A)
-//   util_gdc.py:25-31  get_top_k_matrix   keep the k largest entries of every column, zero the rest, divide each
-//                                         column by its sum (columns whose sum is <= 0 are left unscaled)
+//   util_gdc.py:25-31  get_top_k_matrix   the k largest entries of every column, the column divided by their sum
 //   util_gdc.py:82-86  coo_matrix(A_res)  non-zeros in row-major order, edge_index = [row; col], edge_attr = f32
 // plus the block-diagonal node offset of Batch.from_data_list (batch.py:98-104): graph g's indices are shifted by g*R.
 // The other kernel and the other sparsifier of util_gdc.py share the selection and the emission (igcn_gdc_diffuse):
 //   util_gdc.py:16-23  get_heat_matrix     S = expm(-t (I - D^-1/2 A D^-1/2))            -> k_gdc_heat, further down
-//   util_gdc.py:33-38  get_clipped_matrix  keep the entries >= eps, divide each column by the sum of what it kept
-//                                          (R slots per column instead of k)
+//   util_gdc.py:33-38  get_clipped_matrix  the entries >= eps, the column divided by their sum (R slots, not k)
+// What exactly is kept and how it is emitted is the contract both routes share: csrc/gdc_common.h.
 //
 // The PPR kernel (k_gdc_ppr):
 // One workgroup per graph; the R x R system lives in LDS in fp64 (the reference computes in numpy float64 and the
 // top-k SELECTION must not flip on rounding), inverted in place by Gauss-Jordan elimination with partial pivoting.
-// Graph g owns the output slots [g*R*k, (g+1)*R*k): entries in (row, col) order, then (-1, -1, 0) padding when
-// fewer than R*k non-zeros survive (a kept entry that is exactly 0 is not an edge for coo_matrix); counts[g] = #edges.
 //
 // The elimination is a chain of R dependent rank-1 updates: its time is instruction issue and barriers, not arithmetic.
 // Round 3 kept the matrix in LDS and spent five barriers and ~45 dependent LDS read-modify-writes per thread on every
@@ -29,7 +26,7 @@
 //     registers with one fma per row — the thread of column p, whose registers ARE the multipliers, gets the in-place
 //     inverse column from the same fma with the factor 1 + 1/pivot — and the thread of column p + 1 leaves the next
 //     multipliers in LDS.
-#include "common.h"
+#include "gdc_common.h"
 
 #define GDC_T 256
 
@@ -75,13 +72,6 @@ extern "C" int igcn_debug_gdc_probe(long long* out) {
 #endif
 
 // ---- shared by the PPR and the heat kernel: what is kept of the diffusion matrix, and its COO image -----------------
-// How the diffusion matrix S = scale * M is sparsified (igcn.h IGCN_GDC_TOPK / IGCN_GDC_THRESHOLD) and where graph g's
-// edges go: `cap` slots per column (k for top-k, R for the threshold).
-struct GdcSparsify {
-  int mode, k, cap;
-  double eps;
-};
-
 // a graph that is not read (subject index outside the dataset): all slots padding, count 0
 __device__ __forceinline__ void gdc_emit_empty(int g, int R, int cap, int64_t* __restrict__ ei_row,
                                                int64_t* __restrict__ ei_col, float* __restrict__ ew,
@@ -98,14 +88,13 @@ __device__ __forceinline__ void gdc_emit_empty(int g, int R, int cap, int64_t* _
 
 // Selection per column, column normalisation and COO emission of graph g.  M [R][ld] (LDS, fp64) holds the diffusion
 // matrix up to the factor `scale` and is complete (a barrier lies behind its last write); rowmask [128][2] is zero;
-// rowcnt [R+2].  Called by all GDC_T threads.  Every output slot of the graph has exactly one writer.
+// rowcnt [R+2].  Called by all GDC_T threads.  The contract (tie rule, threshold, padding): csrc/gdc_common.h.
 __device__ __forceinline__ void gdc_select_emit(double* M, int ld, int R, double scale, GdcSparsify sp,
                                                 unsigned long long* rowmask, int* rowcnt, int g,
                                                 int64_t* __restrict__ ei_row, int64_t* __restrict__ ei_col,
                                                 float* __restrict__ ew, int32_t* __restrict__ counts) {
   const int tid = threadIdx.x, k = sp.k;
   // ---- per column (thread = column): the rows that stay as a bit set, their final weights in place --------------
-  // top-k, order of preference: larger value, then LARGER row (a stable ascending argsort keeps the later of two equals)
   unsigned long long tk0 = 0ull, tk1 = 0ull;           // rows of this column that stay
   if (tid < R) {
     const int j = tid;
@@ -165,7 +154,7 @@ __device__ __forceinline__ void gdc_select_emit(double* M, int ld, int R, double
         m &= m - 1;
         const double w = (scale * M[i * ld + j]) / den;
         M[i * ld + j] = w;
-        if (w != 0.0) atomicOr(rowmask + 2 * i + (j >> 6), 1ull << (j & 63));     // (a kept 0 is not an edge for coo_matrix)
+        if (w != 0.0) atomicOr(rowmask + 2 * i + (j >> 6), 1ull << (j & 63));     // (a kept 0 is not an edge)
       }
     }
   }
@@ -225,10 +214,8 @@ k_gdc_ppr(int R, GdcSparsify sp, double alpha, const float* __restrict__ A, int6
   int* piv = (int*)(M + (size_t)R * ld);                // [R]  row chosen as the pivot of column p
   int* rinv = piv + R;                                  // [R]  step at which row w was the pivot
   int* rowcnt = rinv + R;                               // [R+2]
-  const int64_t sj = subject ? subject[g] : (int64_t)g;               // graph g of the batch = matrix subject[g]
-  if (subject && (sj < 0 || sj >= n_subjects)) {
-    // an index outside the dataset: no read — the graph is handed over EMPTY (all slots padding, count 0), which the
-    // consumer's plan build reports in its status word (uniform over the workgroup: no barrier has been reached yet)
+  const int64_t sj = GDC_SUBJECT_OF(subject, g);
+  if (GDC_NOT_READ(subject, sj, n_subjects)) {          // (uniform over the workgroup: no barrier has been reached yet)
     gdc_emit_empty(g, R, sp.cap, ei_row, ei_col, ew, counts);
     return;
   }
@@ -363,7 +350,6 @@ k_gdc_ppr(int R, GdcSparsify sp, double alpha, const float* __restrict__ A, int6
 // The m - 1 + s products are the hot path: v_mfma_f64_16x16x4_f64, the 2 x 2 waves each owning every other 16 x 16 tile
 // in both directions (3 x 3 tiles at Rp = 96: three A and three B fragments feed nine MFMAs per k-step).  A product
 // accumulates in registers while T is only read; T is rewritten behind a barrier and read again behind a second one.
-#define GDC_HEAT_DEGREE 14
 typedef double gdc_d4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ int gdc_heat_pad(int R) { return (R + 15) & ~15; }
@@ -429,8 +415,8 @@ k_gdc_heat(int R, GdcSparsify sp, double t, double exp_mt, const float* __restri
   double* X = (double*)(rowmask + 256);                 // [Rp][ld]
   double* T = X + (size_t)Rp * ld;                      // [Rp][ld]
   int* rowcnt = (int*)(T + (size_t)Rp * ld);            // [R+2]
-  const int64_t sj = subject ? subject[g] : (int64_t)g;
-  if (subject && (sj < 0 || sj >= n_subjects)) {        // (uniform over the workgroup: no barrier has been reached yet)
+  const int64_t sj = GDC_SUBJECT_OF(subject, g);
+  if (GDC_NOT_READ(subject, sj, n_subjects)) {          // (uniform over the workgroup: no barrier has been reached yet)
     gdc_emit_empty(g, R, sp.cap, ei_row, ei_col, ew, counts);
     return;
   }
@@ -462,12 +448,7 @@ k_gdc_heat(int R, GdcSparsify sp, double t, double exp_mt, const float* __restri
   __syncthreads();
   double nrm = 0.0;
   for (int j = 0; j < R; ++j) nrm = fmax(nrm, csum[j]); // (every thread for itself: the same value in all of them)
-  int s = 0;
-  while (nrm > 0.5 && s < 64) {                         // (s < 64: an input outside the contract must not spin here)
-    nrm *= 0.5;
-    ++s;
-  }
-  s = __builtin_amdgcn_readfirstlane(s);
+  const int s = __builtin_amdgcn_readfirstlane(gdc_scaling_exponent(nrm, 64));
   const double down = ldexp(1.0, -s);
   for (int e = tid; e < Rp * Rp; e += GDC_T) {
     const int i = e / Rp, j = e - i * Rp;
@@ -535,28 +516,9 @@ extern "C" int igcn_gdc_max_rois(int kernel) {
 static int gdc_diffuse(const char* who, int B, int R, int kernel, double param, int sparsify, int k, double eps,
                        const float* A, const int64_t* subject, int64_t n_subjects, int64_t* edge_index,
                        float* edge_attr, int32_t* counts, void* stream) {
-  IGCN_REQUIRE(kernel == IGCN_GDC_PPR || kernel == IGCN_GDC_HEAT, "%s: unknown kernel %d", who, kernel);
-  IGCN_REQUIRE(sparsify == IGCN_GDC_TOPK || sparsify == IGCN_GDC_THRESHOLD, "%s: unknown sparsifier %d", who, sparsify);
-  if (sparsify == IGCN_GDC_TOPK) {
-    IGCN_REQUIRE(B >= 0 && R > 0 && k > 0 && k <= R, "%s: bad sizes B=%d R=%d k=%d", who, B, R, k);
-  } else {
-    IGCN_REQUIRE(B >= 0 && R > 0, "%s: bad sizes B=%d R=%d", who, B, R);
-    IGCN_REQUIRE(eps == eps, "%s: eps is not a number", who);
-  }
-  if (kernel == IGCN_GDC_PPR)
-    IGCN_REQUIRE(param > 0.0 && param <= 1.0, "%s: alpha=%g outside (0,1]", who, param);
-  else
-    IGCN_REQUIRE(param > 0.0 && param <= 64.0, "%s: t=%g outside (0,64]", who, param);
-  if (R > igcn_gdc_max_rois(kernel)) {
-    igcn_set_error("%s: R=%d exceeds the kernel's limit (max R = %d)", who, R, igcn_gdc_max_rois(kernel));
-    return IGCN_ERR_UNSUPPORTED;
-  }
-  if (B == 0) return IGCN_OK;
-  GdcSparsify sp;
-  sp.mode = sparsify;
-  sp.k = sparsify == IGCN_GDC_TOPK ? k : R;
-  sp.cap = sp.k;
-  sp.eps = eps;
+  const int bad = gdc_check_args(who, B, R, kernel, param, sparsify, k, eps, 0.0, 0, igcn_gdc_max_rois(kernel));
+  if (bad != IGCN_OK || B == 0) return bad;
+  const GdcSparsify sp = gdc_sparsify(sparsify, k, eps, R);
   const int64_t slots = (int64_t)B * R * sp.cap;
   if (kernel == IGCN_GDC_HEAT) {
     IGCN_ALLOW_BIG_LDS(k_gdc_heat);

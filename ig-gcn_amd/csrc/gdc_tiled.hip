@@ -18,14 +18,13 @@
 //   -> k_gdct_emit
 #include <math.h>
 
-#include "common.h"
+#include "gdc_common.h"
 
 #define GT_TILE 64                                     // output tile of a workgroup, and the padding unit of R
 #define GT_BK 16                                       // k extent of one staged operand pair
 #define GT_T 256                                       // 2 x 2 waves, each 2 x 2 MFMA tiles of 16 x 16
 #define GT_LDA (GT_BK + 1)                             // odd leading dimensions (in doubles) of the staged operands
 #define GT_LDB (GT_TILE + 1)
-#define GT_HEAT_DEGREE 14                              // as GDC_HEAT_DEGREE (csrc/gdc.hip: the remainder bound)
 #define GT_MAX_R 512
 #define GT_PPR_MAX_TERMS 16
 #define GT_ALPHA_MIN 1e-3                              // J(1e-3) = 16
@@ -36,11 +35,6 @@ struct GdctInfo {                                      // per graph, written by 
   double norm;                                         // |t H|_1 (heat; 0 for PPR)
   int s;                                               // squarings this graph needs (heat; 0 for PPR)
   int valid;                                           // 0: subject index outside the dataset -> empty graph
-};
-
-struct GdctSparsify {
-  int mode, k, cap;
-  double eps;
 };
 
 // where everything lives in the workspace; the ONLY place that knows how many matrices a kernel needs
@@ -88,8 +82,8 @@ __global__ void __launch_bounds__(64)
 k_gdct_rowsum(int R, int Rp, const float* __restrict__ A, const int64_t* __restrict__ subject, int64_t n_subjects,
               double* __restrict__ dinv, GdctInfo* __restrict__ info) {
   const int i = blockIdx.x, g = blockIdx.y, lane = threadIdx.x;
-  const int64_t sj = subject ? subject[g] : (int64_t)g;
-  const bool valid = !(subject && (sj < 0 || sj >= n_subjects));
+  const int64_t sj = GDC_SUBJECT_OF(subject, g);
+  const bool valid = !GDC_NOT_READ(subject, sj, n_subjects);
   if (i == 0 && lane == 0) {
     info[g].valid = valid ? 1 : 0;
     info[g].norm = 0.0;
@@ -113,8 +107,7 @@ k_gdct_colnorm(int R, int Rp, double t, const float* __restrict__ A, const int64
   const int g = blockIdx.y, j = blockIdx.x * GT_TILE + threadIdx.x;
   double s = 0.0;
   if (info[g].valid && j < R) {
-    const int64_t sj = subject ? subject[g] : (int64_t)g;
-    const float* a = A + sj * R * R;
+    const float* a = A + GDC_SUBJECT_OF(subject, g) * R * R;
     const double* d = dinv + (size_t)g * Rp;
     const double dj = d[j];
     for (int i = 0; i < R; ++i) s += fabs(t * (d[i] * (double)a[(size_t)i * R + j] * dj));
@@ -132,22 +125,16 @@ k_gdct_form(int R, int Rp, int kernel, double param, int smax, const float* __re
             GdctInfo* __restrict__ info, double* __restrict__ M0, double* __restrict__ M1) {
   const int g = blockIdx.y;
   if (!info[g].valid) return;
-  const int64_t sj = subject ? subject[g] : (int64_t)g;
-  const float* a = A + sj * R * R;
+  const float* a = A + GDC_SUBJECT_OF(subject, g) * R * R;    // (info.valid: the index is inside the dataset)
   const double* d = dinv + (size_t)g * Rp;
   double down = 1.0;
   if (kernel == IGCN_GDC_HEAT) {
     double nrm = 0.0;
     for (int c = 0; c < Rp / GT_TILE; ++c) nrm = fmax(nrm, cmax[(size_t)g * (GT_MAX_R / GT_TILE) + c]);
-    const double norm = nrm;
-    int s = 0;
-    while (nrm > 0.5 && s < smax) {                     // (s < smax: the host launches no more squarings than that)
-      nrm *= 0.5;
-      ++s;
-    }
+    const int s = gdc_scaling_exponent(nrm, smax);
     down = ldexp(1.0, -s);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-      info[g].norm = norm;
+      info[g].norm = nrm;
       info[g].s = s;
     }
   }
@@ -161,7 +148,7 @@ k_gdct_form(int R, int Rp, int kernel, double param, int smax, const float* __re
   }
   const double eye = i == j ? 1.0 : 0.0;
   M0[base + e] = x;
-  M1[base + e] = kernel == IGCN_GDC_HEAT ? eye + x / (double)GT_HEAT_DEGREE : eye + x;
+  M1[base + e] = kernel == IGCN_GDC_HEAT ? eye + x / (double)GDC_HEAT_DEGREE : eye + x;
 }
 
 // ---- batched fp64 GEMM on v_mfma_f64_16x16x4_f64 ----------------------------------------------------------------------
@@ -247,21 +234,20 @@ k_gdct_gemm(int Rp, const double* __restrict__ L, const double* __restrict__ Rm,
       }
 }
 
-// ---- selection and emission from global memory (the contract of gdc_select_emit, csrc/gdc.hip) ------------------------
-// The diffusion matrix is S = scale * M.  What a column keeps is described by a pair (thrv, thri): entry (i, j) stays iff
+// ---- selection and emission from global memory (the contract: csrc/gdc_common.h) --------------------------------------
+// What a column keeps is described by a pair (thrv, thri): entry (i, j) stays iff
 //   v > thrv[j]  or  (v == thrv[j] and i >= thri[j]),        v = scale * M[i][j]
-// top-k: (thrv, thri) is the k-th entry of the column in the order of preference "larger value, then LARGER row" (a
-// stable ascending argsort keeps the later of two equals); threshold: (eps, 0).  den[j] = sum of what the column kept
-// (top-k: in the order of preference; threshold: rows ascending), 1 where that sum is <= 0.
+// top-k: (thrv, thri) is the k-th entry of the column in the order of preference; threshold: (eps, 0).  den[j] = sum of
+// what the column kept, 1 where that sum is <= 0.
 __device__ __forceinline__ double gdct_weight(double m, int i, double scale, double thrv, int thri, double den) {
   const double v = scale * m;
   const bool kept = v > thrv || (v == thrv && i >= thri);
-  return kept ? v / den : 0.0;                          // (a kept entry that is exactly 0 is not an edge)
+  return kept ? v / den : 0.0;
 }
 
 // thread = column; the 64 columns of a block read every row as one coalesced segment
 __global__ void __launch_bounds__(GT_TILE)
-k_gdct_select(int R, int Rp, double scale, GdctSparsify sp, const double* __restrict__ M,
+k_gdct_select(int R, int Rp, double scale, GdcSparsify sp, const double* __restrict__ M,
               const GdctInfo* __restrict__ info, double* __restrict__ thrv, int* __restrict__ thri,
               double* __restrict__ den) {
   const int g = blockIdx.y, j = blockIdx.x * GT_TILE + threadIdx.x;
@@ -318,7 +304,7 @@ k_gdct_rowcount(int R, int Rp, double scale, const double* __restrict__ M, const
 }
 
 // one wave per row: the row's edges behind those of the rows above it, in column order; the wave of row i also writes
-// the padding slots total + i, total + i + R, ... and the wave of row 0 the count.  One writer per slot.
+// the padding slots total + i, total + i + R, ... and the wave of row 0 the count.
 __global__ void __launch_bounds__(64)
 k_gdct_emit(int R, int Rp, int cap, double scale, const double* __restrict__ M, const GdctInfo* __restrict__ info,
             const double* __restrict__ thrv, const int* __restrict__ thri, const double* __restrict__ den,
@@ -377,23 +363,8 @@ extern "C" int igcn_gdc_diffuse_tiled(int B, int R, int kernel, double param, in
                                       void* stream) {
   const char* who = "gdc_diffuse_tiled";
   IGCN_REQUIRE(subject == nullptr || n_subjects > 0, "%s: a subject list needs n_subjects > 0", who);
-  IGCN_REQUIRE(kernel == IGCN_GDC_PPR || kernel == IGCN_GDC_HEAT, "%s: unknown kernel %d", who, kernel);
-  IGCN_REQUIRE(sparsify == IGCN_GDC_TOPK || sparsify == IGCN_GDC_THRESHOLD, "%s: unknown sparsifier %d", who, sparsify);
-  if (sparsify == IGCN_GDC_TOPK) {
-    IGCN_REQUIRE(B >= 0 && R > 0 && k > 0 && k <= R, "%s: bad sizes B=%d R=%d k=%d", who, B, R, k);
-  } else {
-    IGCN_REQUIRE(B >= 0 && R > 0, "%s: bad sizes B=%d R=%d", who, B, R);
-    IGCN_REQUIRE(eps == eps, "%s: eps is not a number", who);
-  }
-  if (kernel == IGCN_GDC_PPR)
-    IGCN_REQUIRE(param >= GT_ALPHA_MIN && param <= 1.0, "%s: alpha=%g outside [%g,1] (at most %d doubling terms)", who,
-                 param, GT_ALPHA_MIN, GT_PPR_MAX_TERMS);
-  else
-    IGCN_REQUIRE(param > 0.0 && param <= 64.0, "%s: t=%g outside (0,64]", who, param);
-  if (R > GT_MAX_R) {
-    igcn_set_error("%s: R=%d exceeds the kernel's limit (max R = %d)", who, R, GT_MAX_R);
-    return IGCN_ERR_UNSUPPORTED;
-  }
+  const int bad = gdc_check_args(who, B, R, kernel, param, sparsify, k, eps, GT_ALPHA_MIN, GT_PPR_MAX_TERMS, GT_MAX_R);
+  if (bad != IGCN_OK) return bad;
   IGCN_REQUIRE(B <= 65535, "%s: B=%d graphs in one call (at most 65535)", who, B);
   if (B == 0) return IGCN_OK;
   const GdctLayout l = gdct_layout(B, R, kernel);
@@ -415,11 +386,7 @@ extern "C" int igcn_gdc_diffuse_tiled(int B, int R, int kernel, double param, in
   int* rowcnt = (int*)(ws + l.o_rowcnt);
   GdctInfo* info = (GdctInfo*)(ws + l.o_info);
   const int Rp = l.Rp, nt = Rp / GT_TILE;
-  GdctSparsify sp;
-  sp.mode = sparsify;
-  sp.k = sparsify == IGCN_GDC_TOPK ? k : R;
-  sp.cap = sp.k;
-  sp.eps = eps;
+  const GdcSparsify sp = gdc_sparsify(sparsify, k, eps, R);
   const int64_t slots = (int64_t)B * R * sp.cap;
   const int smax = kernel == IGCN_GDC_HEAT ? gdct_heat_max_squarings(param, R) : 0;
 
@@ -437,7 +404,7 @@ extern "C" int igcn_gdc_diffuse_tiled(int B, int R, int kernel, double param, in
     double* X = matrix(0);
     double* T[2] = {matrix(1), matrix(2)};
     int cur = 0;
-    for (int j = GT_HEAT_DEGREE - 1; j >= 1; --j, cur ^= 1)      // T_j = I + X T_(j+1) / j
+    for (int j = GDC_HEAT_DEGREE - 1; j >= 1; --j, cur ^= 1)     // T_j = I + X T_(j+1) / j
       gemm(X, T[cur], nullptr, T[cur ^ 1], GT_FORM_EYE_MUL, 1.0 / (double)j, -1);
     for (int q = 0; q < smax; ++q, cur ^= 1) gemm(T[cur], T[cur], nullptr, T[cur ^ 1], GT_FORM_PLAIN, 1.0, q);
     result = T[cur];

@@ -1,9 +1,9 @@
 """On-device batch construction: the reference's per-subject GDC pre-transform
 ``preprocess_diffusion_imgs_snps`` (util_gdc.py:71-101: personalised-PageRank or heat-kernel diffusion, top-k per column
 or epsilon threshold, column normalisation, COO) and the block-diagonal collation of ``Batch.from_data_list``
-(batch.py:24-123), for a whole batch of dense adjacencies in one kernel launch (igcn_gdc_topk / igcn_gdc_diffuse, fp64
-in LDS).  Graphs beyond the LDS limit (up to 512 regions) take the tiled route: igcn_gdc_diffuse_tiled, fp64 products on
-the matrix cores over a global-memory workspace (``route=``, see ``diffusion_routed``).
+(batch.py:24-123), for a whole batch of dense adjacencies in one kernel launch (igcn_gdc_diffuse, fp64 in LDS).  Graphs
+beyond the LDS limit (up to 512 regions) take the tiled route: igcn_gdc_diffuse_tiled, fp64 products on the matrix cores
+over a global-memory workspace (``route=``).  ``launch_into`` alone names an entry point; ``diffusion_routed`` is the body.
 
 The reference runs the transform once per subject in numpy at dataset-build time and collates in a Python loop per
 batch; at >= 100 k graphs/s of train-step throughput both are far too slow to feed the GPU.
@@ -30,10 +30,14 @@ def _check_route(route):
         raise ValueError(f"route must be one of {ROUTES}, got {route!r}")
 
 
+def _check_kernel(kernel):
+    if kernel not in KERNELS:
+        raise ValueError(f"kernel must be 'ppr' or 'heat', got {kernel!r}")
+
+
 def _resolve_route(route, rois, kernel):
     """'auto': the LDS-resident kernels wherever the graph fits them (they are the faster ones there), the tiled
-    global-memory route (csrc/gdc_tiled.hip) above that."""
-    _check_route(route)
+    global-memory route (csrc/gdc_tiled.hip) above that.  ``route`` has passed ``_check_route``."""
     if route != "auto":
         return route
     return "resident" if rois <= _lib.load().igcn_gdc_max_rois(KERNELS[kernel]) else "tiled"
@@ -56,6 +60,17 @@ def tiled_workspace(graphs, rois, kernel, device):
     return _empty((max(need, 16),), torch.uint8, device), need
 
 
+def launch_into(route, kernel, param, mode, top_k, eps, adj, n_subjects, subject, b, ei, ew, counts, ws=None, ws_bytes=0):
+    """The C entry point of a resolved ``route`` ('resident' / 'tiled' with its workspace) on the current stream, and nothing
+    more: graph g of the ``b`` is matrix ``subject[g]`` (``None``: g) of the ``n_subjects`` in ``adj``.  Allocates nothing."""
+    args = (b, int(adj.shape[-1]), KERNELS[kernel], float(param), mode, int(top_k), float(eps), ptr(adj), int(n_subjects),
+            ptr(subject), ptr(ei), ptr(ew), ptr(counts))
+    if route == "tiled":
+        call("igcn_gdc_diffuse_tiled", *args, ptr(ws), int(ws_bytes), stream_ptr())
+    else:
+        call("igcn_gdc_diffuse", *args, stream_ptr())
+
+
 def _tiled_launch(kernel, param, mode, top_k, eps_arg, workspace_bytes):
     """The ``launch`` of ``_diffuse`` for the tiled route.  The workspace is one allocation of at most ``workspace_bytes``
     (default DEFAULT_WORKSPACE_BYTES); a batch that needs more goes through it in chunks of graphs, each chunk into
@@ -71,8 +86,8 @@ def _tiled_launch(kernel, param, mode, top_k, eps_arg, workspace_bytes):
         ws = _empty((max(have, 16),), torch.uint8, a.device)
 
         def run(g0, n, out_ei, out_ew, out_counts):
-            call("igcn_gdc_diffuse_tiled", n, r, KERNELS[kernel], param, mode, int(top_k), eps_arg, ptr(a[g0:g0 + n]), n,
-                 None, ptr(out_ei), ptr(out_ew), ptr(out_counts), ptr(ws), have, stream_ptr())
+            launch_into("tiled", kernel, param, mode, top_k, eps_arg, a[g0:g0 + n], n, None, n, out_ei, out_ew, out_counts,
+                        ws, have)
 
         if chunk >= b:
             run(0, b, ei, ew, counts)
@@ -89,8 +104,6 @@ def _tiled_launch(kernel, param, mode, top_k, eps_arg, workspace_bytes):
 def _diffuse(adj, cap, check, launch):
     """The launch common to every kernel / sparsifier pair: outputs of ``cap`` slots per column, ``launch(b, r, adj, ei,
     ew, counts)``, the edge offsets, and — with ``check`` — the squeeze of the padding."""
-    if adj.dim() != 3 or adj.shape[1] != adj.shape[2]:
-        raise _lib.IgcnError("adj must be [B,R,R]")
     adj = adj.to(torch.float32).contiguous()
     b, r, _ = adj.shape
     slots = b * r * cap
@@ -114,11 +127,7 @@ def diffusion_topk(adj, top_k=3, alpha=0.05, check=True, route="resident", works
     connected graph is dense), as a per-step producer in front of the graphed train step; a column that kept fewer
     leaves -1 slots behind, which the per-graph plan build reports in its status word.
     ``route``, ``workspace_bytes``: see ``diffusion_routed``."""
-    _check_route(route)
-    if adj.dim() == 3 and _resolve_route(route, adj.shape[-1], "ppr") == "tiled":
-        return _diffuse(adj, int(top_k), check, _tiled_launch("ppr", float(alpha), _TOPK, top_k, 0.0, workspace_bytes))
-    return _diffuse(adj, top_k, check, lambda b, r, a, ei, ew, counts: call(
-        "igcn_gdc_topk", b, r, int(top_k), float(alpha), ptr(a), ptr(ei), ptr(ew), ptr(counts), stream_ptr()))
+    return diffusion_routed(adj, "ppr", alpha, top_k=top_k, check=check, route=route, workspace_bytes=workspace_bytes)
 
 
 def diffusion(adj, kernel="ppr", alpha=0.05, t=5.0, top_k=3, eps=None, check=True):
@@ -143,20 +152,18 @@ def diffusion_routed(adj, kernel="ppr", alpha=0.05, t=5.0, top_k=3, eps=None, ch
     512 regions needs 8 MiB for PPR, 6 MiB for heat).  A batch that needs more is processed in chunks of graphs; the
     result does not depend on the chunk size.  Any other ``route`` raises ValueError before the device is touched."""
     _check_route(route)
-    if kernel not in KERNELS:
-        raise ValueError(f"kernel must be 'ppr' or 'heat', got {kernel!r}")
+    _check_kernel(kernel)
     if eps is not None and not check:
         raise ValueError("the eps threshold keeps a data-dependent number of edges: it needs check=True")
-    if kernel == "ppr" and eps is None:
-        return diffusion_topk(adj, top_k, alpha, check, route, workspace_bytes)
+    if adj.dim() != 3 or adj.shape[1] != adj.shape[2]:
+        raise _lib.IgcnError("adj must be [B,R,R]")
     param = float(alpha if kernel == "ppr" else t)
     mode, eps_arg = (_TOPK, 0.0) if eps is None else (_THRESHOLD, float(eps))
     cap = int(top_k) if eps is None else int(adj.shape[-1])
-    if adj.dim() == 3 and _resolve_route(route, adj.shape[-1], kernel) == "tiled":
+    if _resolve_route(route, adj.shape[-1], kernel) == "tiled":
         return _diffuse(adj, cap, check, _tiled_launch(kernel, param, mode, top_k, eps_arg, workspace_bytes))
-    return _diffuse(adj, cap, check, lambda b, r, a, ei, ew, counts: call(
-        "igcn_gdc_diffuse", b, r, KERNELS[kernel], param, mode, int(top_k), eps_arg, ptr(a), b, None, ptr(ei), ptr(ew),
-        ptr(counts), stream_ptr()))
+    return _diffuse(adj, cap, check, lambda b, r, a, ei, ew, counts: launch_into(
+        "resident", kernel, param, mode, top_k, eps_arg, a, b, None, b, ei, ew, counts))
 
 
 def batch_from_dense(adj, x, top_k=3, alpha=0.05, check=True, kernel="ppr", t=5.0, eps=None, route="resident",

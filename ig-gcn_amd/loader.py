@@ -399,24 +399,23 @@ def _nothing():
 class DeviceGdcFeeder(_AheadOnSideStream):
     """Dense connectivity matrices resident in HBM -> graph-diffusion pre-transform (util_gdc.py:7-31,71-86) + collation
     (batch.py:24-123) of every batch ON THE DEVICE, one batch ahead of the train step on a side stream: the fp64
-    Gauss-Jordan of batch k + 1 (igcn_gdc_topk, one workgroup per graph) runs beside the replay of step k.
-    ``kernel="heat"``: the heat kernel with ``t`` (util_gdc.py:16-23, igcn_gdc_diffuse) in its place.  Top-k only: a
+    Gauss-Jordan of batch k + 1 (k_gdc_ppr, one workgroup per graph) runs beside the replay of step k.
+    ``kernel="heat"``: the heat kernel with ``t`` (util_gdc.py:16-23, k_gdc_heat) in its place.  Top-k only: a
     captured step needs a fixed edge count, which the eps threshold does not give.
     ``route``: as ``gdc.diffusion_routed`` — 'resident' (the default: the LDS kernels, refused above their limit), 'tiled'
-    (igcn_gdc_diffuse_tiled, R <= 512) or 'auto'.  The tiled route's workspace for one batch is allocated here, once:
-    nothing is allocated per step.
+    (R <= 512) or 'auto'.  Every launch goes through ``gdc.launch_into``.  The tiled route's workspace for one batch is
+    allocated here, once: nothing is allocated per step.
 
     ``cols``: per-subject tensors [S, ...] on the device (x [S, R, H0], snps_feat, y, clini_score, tsne_fdim, clust_y)."""
 
     def __init__(self, adj, cols, batch_size, steps, top_k=3, alpha=0.05, seed=0, shuffle=True, depth=2, kernel="ppr",
                  t=5.0, eps=None, route="resident"):
-        from .gdc import KERNELS, _check_route, _resolve_route, batch_from_dense, tiled_workspace
+        from .gdc import _check_kernel, _check_route, _resolve_route, batch_from_dense, tiled_workspace
         _check_route(route)
         if eps is not None:
             raise ValueError("DeviceGdcFeeder is top-k only: a captured step needs a fixed edge count (eps= keeps a "
                              "data-dependent one); use gdc.batch_from_dense(..., eps=) per batch")
-        if kernel not in KERNELS:
-            raise ValueError(f"kernel must be 'ppr' or 'heat', got {kernel!r}")
+        _check_kernel(kernel)
         self.kernel, self.t = kernel, float(t)
         if adj.device.type != "cuda":
             raise ValueError("DeviceGdcFeeder reads device-resident matrices")
@@ -446,23 +445,14 @@ class DeviceGdcFeeder(_AheadOnSideStream):
 
     def _fill(self, slot, idx):
         """Three launches on the side stream: the per-subject attributes (igcn_gather_batch), the diffusion of the
-        drawn matrices read in place (igcn_gdc_topk_of, igcn_gdc_diffuse for the heat kernel; the launch sequence of
-        igcn_gdc_diffuse_tiled on the tiled route) straight into the slot's edge list, the edge offsets."""
-        from ._lib import call, ptr, stream_ptr
-        from .gdc import KERNELS
+        drawn matrices read in place (``gdc.launch_into`` with the subject index: one launch on the resident route, the
+        launch sequence of the tiled route) straight into the slot's edge list, the edge offsets."""
+        from . import gdc
         b, r = int(idx.numel()), int(self.adj.shape[1])
         gather_rows(idx, r, [(getattr(slot, k), v, False) for k, v in self.cols.items()])
-        if self.route == "tiled":
-            param = self.alpha if self.kernel == "ppr" else self.t
-            call("igcn_gdc_diffuse_tiled", b, r, KERNELS[self.kernel], param, 0, self.top_k, 0.0, ptr(self.adj),
-                 int(self.adj.shape[0]), ptr(idx), ptr(slot.edge_index), ptr(slot.edge_attr), ptr(self._counts),
-                 ptr(self._ws), self._ws_bytes, stream_ptr())
-        elif self.kernel == "ppr":
-            call("igcn_gdc_topk_of", b, r, self.top_k, self.alpha, ptr(self.adj), int(self.adj.shape[0]), ptr(idx), ptr(slot.edge_index),
-                 ptr(slot.edge_attr), ptr(self._counts), stream_ptr())
-        else:
-            call("igcn_gdc_diffuse", b, r, KERNELS["heat"], self.t, 0, self.top_k, 0.0, ptr(self.adj), int(self.adj.shape[0]), ptr(idx),
-                 ptr(slot.edge_index), ptr(slot.edge_attr), ptr(self._counts), stream_ptr())
+        gdc.launch_into(self.route, self.kernel, self.alpha if self.kernel == "ppr" else self.t, gdc._TOPK, self.top_k,
+                        0.0, self.adj, self.adj.shape[0], idx, b, slot.edge_index, slot.edge_attr, self._counts,
+                        self._ws, self._ws_bytes)
         torch.cumsum(self._counts, 0, out=slot.edge_ptr[1:])
 
 

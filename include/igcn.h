@@ -1313,7 +1313,9 @@ int igcn_gdc_topk(int B, int R, int k, double alpha, const float* A, int64_t* ed
                   int32_t* counts, void* stream);
 /* The same for a batch DRAWN from a resident dataset A [S,R,R]: graph g of the batch is matrix subject[g] (int64 [B],
  * device) — a per-step producer needs no gathered copy of the B matrices.  A subject[g] outside [0, n_subjects) is
- * not read: graph g comes out empty (counts[g] = 0, all its slots padding). */
+ * not read: graph g comes out empty (counts[g] = 0, all its slots padding).
+ * Both are igcn_gdc_diffuse(IGCN_GDC_PPR, IGCN_GDC_TOPK) under their first names, kept for callers of this interface;
+ * the package's Python launches through igcn_gdc_diffuse alone. */
 int igcn_gdc_topk_of(int B, int R, int k, double alpha, const float* A, int64_t n_subjects, const int64_t* subject,
                      int64_t* edge_index, float* edge_attr, int32_t* counts, void* stream);
 /* All of util_gdc.py: either diffusion kernel with either sparsifier.

@@ -1,9 +1,11 @@
 """GDC pre-transform + on-device collation: oracle vs the reference's own util_gdc.py outputs (CPU),
-igcn_gdc_topk vs oracle / goldens (GPU; edge indices bit-exact, weights to fp32 rounding)."""
+the PPR / top-k launch (gdc.diffusion_topk) vs oracle / goldens (GPU; edge indices bit-exact, weights to fp32 rounding:
+gdc_cases.assert_edges)."""
 import numpy as np
 import pytest
 import torch
 
+from gdc_cases import assert_edges
 from oracle import gdc as OG
 
 
@@ -46,10 +48,7 @@ def test_gdc_kernel_vs_reference_golden(golden):
     store = golden("gdc")
     for c, rois, k, alpha, a, ei, ew in _cases(store):
         adj = torch.from_numpy(a).cuda()[None]
-        got_ei, got_ew, edge_ptr = diffusion_topk(adj, k, alpha)
-        assert edge_ptr.tolist() == [0, ei.shape[1]], c
-        assert np.array_equal(got_ei.cpu().numpy(), ei), c                                   # bit-exact indexing
-        np.testing.assert_allclose(got_ew.cpu().numpy(), ew, rtol=3e-7, atol=0, err_msg=str(c))
+        assert_edges(diffusion_topk(adj, k, alpha), (ei, ew, [0, ei.shape[1]]), f"case {c}")
 
 
 @pytest.mark.gpu
@@ -72,9 +71,7 @@ def test_gdc_batch_vs_oracle(bsz, rois, k):
     x = torch.rand(bsz * rois, 3, device="cuda")
     batch = batch_from_dense(adj, x, top_k=k, snps_feat=torch.rand(bsz, 54, device="cuda"),
                              clini_score=torch.rand(bsz, 3, device="cuda"))
-    assert np.array_equal(batch.edge_index.cpu().numpy(), want_ei)
-    np.testing.assert_allclose(batch.edge_attr.cpu().numpy(), want_ew, rtol=3e-7, atol=0)
-    assert np.array_equal(batch.edge_ptr.cpu().numpy(), want_ptr)
+    assert_edges((batch.edge_index, batch.edge_attr, batch.edge_ptr), (want_ei, want_ew, want_ptr), f"B={bsz} R={rois}")
     assert batch.num_graphs == bsz and batch.clini_score.shape == (bsz * 3,)
     assert batch.batch.tolist() == np.repeat(np.arange(bsz), rois).tolist()
     plan = ops.plan_for(batch)                      # the collated batch feeds the one-launch segmented plan build
@@ -96,9 +93,8 @@ def test_gdc_isolated_entries_are_squeezed_out():
     a[1] = ((r + r.T) / 2 * (1 - np.eye(6))).astype(np.float32)          # no exact ties (tie order is unspecified)
     want_ei, want_ew, want_ptr = OG.diffusion_topk_batch(list(a), 4)
     ei, ew, ptr = diffusion_topk(torch.from_numpy(a).cuda(), 4)
-    assert ptr.tolist() == want_ptr.tolist() and ptr[-1] < 2 * 6 * 4
-    assert np.array_equal(ei.cpu().numpy(), want_ei)
-    np.testing.assert_allclose(ew.cpu().numpy(), want_ew, rtol=3e-7)
+    assert ptr[-1] < 2 * 6 * 4
+    assert_edges((ei, ew, ptr), (want_ei, want_ew, want_ptr), "isolated")
 
 
 @pytest.mark.gpu

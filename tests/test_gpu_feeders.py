@@ -5,33 +5,15 @@ feeder the per-subject ``preprocess_diffusion_imgs_snps`` (util_gdc.py:71-101) i
 import pytest
 import torch
 
+from gdc_cases import COLS, KEYS, batch_of_drawn, need_gpu, same_batch as _same  # noqa: F401  (need_gpu: autouse fixture)
+from gdc_cases import subjects as drawn_subjects
+
 pytestmark = pytest.mark.gpu
-
-KEYS = ("x", "edge_index", "edge_attr", "snps_feat", "y", "clini_score", "tsne_fdim", "clust_y", "batch", "ptr", "edge_ptr")
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    from igcn_amd import _lib
-    _lib.load()
 
 
 @pytest.fixture(scope="module")
 def subjects():
-    from igcn_amd import synth
-    from igcn_amd.data import Data
-    graphs = synth.brain_graph_list(40, seed=5, rois=90, tsne_dim=16)
-    slim = [Data(**{k: v for k, v in g.__dict__.items() if k != "A"}) for g in graphs]
-    return graphs, slim
-
-
-def _same(got, want, keys=KEYS):
-    for k in keys:
-        a, b = getattr(got, k), getattr(want, k)
-        assert a.dtype == b.dtype and a.shape == b.shape, k
-        assert torch.equal(a.cpu().view(torch.uint8), b.cpu().view(torch.uint8)), k
+    return drawn_subjects(40, rois=90)
 
 
 def test_one_launch_gather_equals_from_data_list(subjects):
@@ -105,25 +87,18 @@ def test_device_feeder_writes_a_captured_steps_inputs_in_place(subjects):
 
 
 def test_dense_feeder_equals_the_pre_transform_of_the_drawn_subjects(subjects):
-    """DeviceGdcFeeder (matrices read in place by igcn_gdc_topk_of, attributes by igcn_gather_batch) against
-    ``batch_from_dense`` of the gathered matrices — itself pinned to util_gdc.py by tests/test_gpu_gdc.py."""
-    from igcn_amd.gdc import batch_from_dense
+    """DeviceGdcFeeder (matrices read in place through gdc.launch_into, attributes by igcn_gather_batch) against
+    ``batch_from_dense`` of the gathered matrices — itself pinned to util_gdc.py by tests/test_gdc.py."""
     from igcn_amd.loader import DeviceGdcFeeder, EpochIndex, UniformGraphStore
     graphs, slim = subjects
     adj = torch.stack([g.A for g in graphs]).cuda()
     store = UniformGraphStore(slim, "cuda")
-    cols = {k: store.cols[k] for k in ("x", "snps_feat", "y", "clini_score", "tsne_fdim", "clust_y")}
+    cols = {k: store.cols[k] for k in COLS}
     feeder = DeviceGdcFeeder(adj, cols, 12, steps=5, top_k=3, alpha=0.05, seed=3)
     order = EpochIndex(40, 12, seed=3, device="cuda")
     for batch in feeder:
         torch.cuda.current_stream().wait_event(batch.ready)
-        idx = order.next()
-        sel = {k: torch.index_select(v, 0, idx) for k, v in cols.items()}
-        x = sel.pop("x")
-        per = {k: (v.reshape(12, -1) if k in ("snps_feat", "tsne_fdim", "clini_score") else v.reshape(-1))
-               for k, v in sel.items()}
-        want = batch_from_dense(torch.index_select(adj, 0, idx), x, top_k=3, alpha=0.05, check=True, **per)
-        _same(batch, want)
+        _same(batch, batch_of_drawn(adj, cols, order.next(), top_k=3, alpha=0.05))
         batch.release()
 
 

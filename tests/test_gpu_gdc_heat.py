@@ -7,56 +7,19 @@ import pytest
 import torch
 
 import gdc_heat_ref as HR
+from gdc_cases import (COLS, HEAT, KEYS, PPR, RTOL, THRESHOLD, TOPK, adjacencies, assert_edges, assert_written,
+                       batch_of_drawn, need_gpu, raw, same_batch)  # noqa: F401  (need_gpu: the module's autouse fixture)
+from gdc_cases import subjects as drawn_subjects
 from gdc_heat_ref import MARGIN, threshold_cases, topk_cases
 
 pytestmark = pytest.mark.gpu
-
-RTOL = 3e-7
-PPR, HEAT, TOPK, THRESHOLD = 0, 1, 0, 1
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    from igcn_amd import _lib
-    _lib.load()
-
-
-def _adjacencies(bsz, rois, seed, knn=5):
-    rng = np.random.default_rng(seed)
-    return [HR.synthetic_adjacency(rng, rois, knn).astype(np.float32) for _ in range(bsz)]
-
-
-def _raw(adj, kernel, param, sparsify, k, eps, subject=None, n_subjects=None, bsz=None):
-    """The entry point itself: (edge_index [2, slots], edge_attr [slots], counts [B]) with the padding left in."""
-    from igcn_amd._lib import call, ptr, stream_ptr
-    r = adj.shape[1]
-    b = adj.shape[0] if bsz is None else bsz
-    slots = b * r * (k if sparsify == TOPK else r)
-    ei = torch.empty(2, slots, dtype=torch.int64, device="cuda")
-    ew = torch.empty(slots, dtype=torch.float32, device="cuda")
-    counts = torch.empty(b, dtype=torch.int32, device="cuda")
-    call("igcn_gdc_diffuse", b, r, kernel, float(param), sparsify, int(k), float(eps), ptr(adj),
-         adj.shape[0] if n_subjects is None else n_subjects, ptr(subject), ptr(ei), ptr(ew), ptr(counts), stream_ptr())
-    return ei, ew, counts
-
-
-def _assert_edges(got, want):
-    (ei, ew, edge_ptr), (want_ei, want_ew, want_ptr) = got, want
-    assert edge_ptr.tolist() == list(want_ptr)
-    assert np.array_equal(ei.cpu().numpy(), want_ei)                                   # bit-exact indexing
-    err = np.abs(ew.cpu().numpy().astype(np.float64) - want_ew) / np.abs(want_ew)
-    print(f"edges {want_ei.shape[1]}, largest relative weight error {err.max() if err.size else 0.0:.3g}")
-    np.testing.assert_allclose(ew.cpu().numpy(), want_ew, rtol=RTOL, atol=0)
 
 
 def test_heat_topk_vs_reference_golden(golden):
     from igcn_amd.gdc import diffusion
     for c, rois, k, t, a, ei, ew in topk_cases(golden("gdc_heat")):
         got = diffusion(torch.from_numpy(a).cuda()[None], kernel="heat", t=t, top_k=k)
-        print(f"case {c}:", end=" ")
-        _assert_edges(got, (ei, ew, [0, ei.shape[1]]))
+        assert_edges(got, (ei, ew, [0, ei.shape[1]]), f"case {c}")
 
 
 def test_threshold_vs_reference_golden(golden):
@@ -65,8 +28,7 @@ def test_threshold_vs_reference_golden(golden):
     seen_empty = 0
     for c, kernel, param, eps, empty, a, ei, ew in threshold_cases(golden("gdc_heat")):
         got = diffusion(torch.from_numpy(a).cuda()[None], kernel=kernel, alpha=param, t=param, top_k=1, eps=eps)
-        print(f"case {c} ({kernel}):", end=" ")
-        _assert_edges(got, (ei, ew, [0, ei.shape[1]]))
+        assert_edges(got, (ei, ew, [0, ei.shape[1]]), f"case {c} ({kernel})")
         seen_empty += empty
     assert seen_empty >= 1
 
@@ -75,13 +37,13 @@ def test_threshold_vs_reference_golden(golden):
 def test_heat_batch_vs_restatement(bsz, rois, k):
     from igcn_amd import ops
     from igcn_amd.gdc import batch_from_dense
-    adjs = _adjacencies(bsz, rois, seed=bsz)
+    adjs = adjacencies(bsz, rois, seed=bsz)
     assert min(HR.margins(HR.heat_matrix(a, 5.0), k=k)[0] for a in adjs) >= MARGIN
     want_ei, want_ew, want_ptr = HR.diffusion_batch(adjs, "heat", 5.0, top_k=k)
     adj = torch.from_numpy(np.stack(adjs)).cuda()
     batch = batch_from_dense(adj, torch.rand(bsz * rois, 3, device="cuda"), top_k=k, kernel="heat", t=5.0,
                              snps_feat=torch.rand(bsz, 54, device="cuda"), clini_score=torch.rand(bsz, 3, device="cuda"))
-    _assert_edges((batch.edge_index, batch.edge_attr, batch.edge_ptr), (want_ei, want_ew, want_ptr))
+    assert_edges((batch.edge_index, batch.edge_attr, batch.edge_ptr), (want_ei, want_ew, want_ptr))
     assert batch.num_graphs == bsz and batch._max_edges == rois * k
     plan = ops.plan_for(batch)
     assert plan.segmented
@@ -93,23 +55,23 @@ def test_heat_batch_vs_restatement(bsz, rois, k):
 def test_threshold_batch_vs_restatement(kernel, param, eps):
     """A batch in threshold mode: graphs of different edge counts, squeezed; at eps = 0.05 some columns keep nothing."""
     from igcn_amd.gdc import batch_from_dense
-    adjs = _adjacencies(5, 40, seed=11)
+    adjs = adjacencies(5, 40, seed=11)
     assert min(HR.margins(HR.diffusion_matrix(a, kernel, param), eps=eps)[1] for a in adjs) >= MARGIN
     want_ei, want_ew, want_ptr = HR.diffusion_batch(adjs, kernel, param, eps=eps)
     if eps == 0.05:
         assert 0 < len(np.unique(want_ei[1])) < 5 * 40                                 # empty columns are in the case
     adj = torch.from_numpy(np.stack(adjs)).cuda()
     batch = batch_from_dense(adj, torch.rand(5 * 40, 3, device="cuda"), kernel=kernel, alpha=param, t=param, eps=eps)
-    _assert_edges((batch.edge_index, batch.edge_attr, batch.edge_ptr), (want_ei, want_ew, want_ptr))
+    assert_edges((batch.edge_index, batch.edge_attr, batch.edge_ptr), (want_ei, want_ew, want_ptr))
     assert batch._max_edges == int(np.diff(want_ptr).max())
 
 
 def test_subject_list_with_an_index_outside_the_dataset():
-    adjs = _adjacencies(6, 40, seed=2)
+    adjs = adjacencies(6, 40, seed=2)
     adj = torch.from_numpy(np.stack(adjs)).cuda()
     subject = torch.tensor([4, 6, 0, -1, 4], device="cuda")
     for sparsify, k, eps, cap in ((TOPK, 3, 0.0, 3), (THRESHOLD, 1, 0.02, 40)):
-        ei, ew, counts = _raw(adj, HEAT, 5.0, sparsify, k, eps, subject=subject, n_subjects=6, bsz=5)
+        ei, ew, counts = raw("resident", adj, HEAT, 5.0, sparsify, k, eps, subject=subject, n_subjects=6, bsz=5)
         ei, ew = ei.view(2, 5, 40 * cap), ew.view(5, 40 * cap)
         assert counts.tolist()[1] == 0 and counts.tolist()[3] == 0
         for g in (1, 3):
@@ -129,10 +91,10 @@ def test_largest_supported_graph_and_one_beyond():
     lib = _lib.load()
     rmax = lib.igcn_gdc_max_rois(HEAT)
     assert rmax >= 96 and lib.igcn_gdc_max_rois(PPR) == lib.igcn_gdc_topk_max_rois()
-    a = _adjacencies(1, rmax, seed=9, knn=9)[0]
+    a = adjacencies(1, rmax, seed=9, knn=9)[0]
     assert HR.margins(HR.heat_matrix(a, 5.0), k=3)[0] >= MARGIN
     want_ei, want_ew = HR.diffusion(a, "heat", 5.0, top_k=3)
-    _assert_edges(diffusion(torch.from_numpy(a).cuda()[None], kernel="heat", t=5.0, top_k=3),
+    assert_edges(diffusion(torch.from_numpy(a).cuda()[None], kernel="heat", t=5.0, top_k=3),
                   (want_ei, want_ew, [0, want_ei.shape[1]]))
     with pytest.raises(_lib.IgcnError, match=f"max R = {rmax}"):
         diffusion(torch.rand(1, rmax + 1, rmax + 1, device="cuda"), kernel="heat", top_k=3)
@@ -158,7 +120,7 @@ def test_diffuse_ppr_topk_is_gdc_topk_bit_for_bit(golden):
         ew = torch.full((rois * k,), 7.0, device="cuda")
         counts = torch.full((1,), 7, dtype=torch.int32, device="cuda")
         call("igcn_gdc_topk", 1, rois, k, alpha, ptr(adj), ptr(ei), ptr(ew), ptr(counts), stream_ptr())
-        got_ei, got_ew, got_counts = _raw(adj, PPR, alpha, TOPK, k, 0.0)
+        got_ei, got_ew, got_counts = raw("resident", adj, PPR, alpha, TOPK, k, 0.0)
         assert torch.equal(got_ei, ei) and torch.equal(got_counts, counts), c
         assert torch.equal(got_ew.view(torch.int32), ew.view(torch.int32)), c
         c += 1
@@ -166,10 +128,10 @@ def test_diffuse_ppr_topk_is_gdc_topk_bit_for_bit(golden):
 
 
 def test_two_runs_give_the_same_bits():
-    adj = torch.from_numpy(np.stack(_adjacencies(16, 90, seed=4))).cuda()
+    adj = torch.from_numpy(np.stack(adjacencies(16, 90, seed=4))).cuda()
     for sparsify, k, eps in ((TOPK, 3, 0.0), (THRESHOLD, 1, 0.01)):
-        one = _raw(adj, HEAT, 5.0, sparsify, k, eps)
-        two = _raw(adj, HEAT, 5.0, sparsify, k, eps)
+        one = raw("resident", adj, HEAT, 5.0, sparsify, k, eps)
+        two = raw("resident", adj, HEAT, 5.0, sparsify, k, eps)
         for a, b in zip(one, two):
             assert torch.equal(a, b)
         assert torch.equal(one[1].view(torch.int32), two[1].view(torch.int32))
@@ -179,13 +141,14 @@ def test_two_runs_give_the_same_bits():
 def test_under_fenced_poisoned_allocations(sparsify, k, eps):
     """Every slot, padding included, has a writer, and nothing is written outside the three outputs."""
     from fenced import fenced, unwritten
-    adjs = _adjacencies(3, 33, seed=6)
+    adjs = adjacencies(3, 33, seed=6)
     adj = torch.from_numpy(np.stack(adjs)).cuda()
     with fenced() as f:
-        ei, ew, counts = _raw(adj, HEAT, 5.0, sparsify, k, eps)
+        ei, ew, counts = raw("resident", adj, HEAT, 5.0, sparsify, k, eps)
         torch.cuda.synchronize()
         f.check()
         assert unwritten(ew) == 0
+        assert_written(ei, ew, counts)
     want_ei, want_ew, want_ptr = HR.diffusion_batch(adjs, "heat", 5.0, top_k=k, eps=eps if sparsify else None)
     assert counts.tolist() == np.diff(want_ptr).tolist()
     valid = ei[0] >= 0
@@ -196,25 +159,11 @@ def test_under_fenced_poisoned_allocations(sparsify, k, eps):
 
 @pytest.fixture(scope="module")
 def subjects():
-    from igcn_amd import synth
-    from igcn_amd.data import Data
-    graphs = synth.brain_graph_list(20, seed=5, rois=90, tsne_dim=16)
-    slim = [Data(**{k: v for k, v in g.__dict__.items() if k != "A"}) for g in graphs]
-    return graphs, slim
-
-
-KEYS = ("x", "edge_index", "edge_attr", "snps_feat", "y", "clini_score", "tsne_fdim", "clust_y", "batch", "ptr", "edge_ptr")
-COLS = ("x", "snps_feat", "y", "clini_score", "tsne_fdim", "clust_y")
+    return drawn_subjects(20, rois=90)
 
 
 def _heat_batch(adj, cols, idx):
-    from igcn_amd.gdc import batch_from_dense
-    b = int(idx.numel())
-    sel = {k: torch.index_select(v, 0, idx) for k, v in cols.items()}
-    x = sel.pop("x")
-    per = {k: (v.reshape(b, -1) if k in ("snps_feat", "tsne_fdim", "clini_score") else v.reshape(-1))
-           for k, v in sel.items()}
-    return batch_from_dense(torch.index_select(adj, 0, idx), x, top_k=3, kernel="heat", t=5.0, check=True, **per)
+    return batch_of_drawn(adj, cols, idx, top_k=3, kernel="heat", t=5.0)
 
 
 def test_heat_feeder_equals_batch_from_dense(subjects):
@@ -228,10 +177,7 @@ def test_heat_feeder_equals_batch_from_dense(subjects):
     for batch in feeder:
         torch.cuda.current_stream().wait_event(batch.ready)
         want = _heat_batch(adj, cols, order.next())
-        for k in KEYS:
-            a, b = getattr(batch, k), getattr(want, k)
-            assert a.dtype == b.dtype and a.shape == b.shape, k
-            assert torch.equal(a.cpu().view(torch.uint8), b.cpu().view(torch.uint8)), k
+        same_batch(batch, want, KEYS)
         batch.release()
 
 

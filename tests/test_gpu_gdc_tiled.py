@@ -10,93 +10,16 @@ import torch
 
 import gdc_heat_ref as HR
 import gdc_tiled_ref as TR
+from gdc_cases import (COLS, EPS, HEAT, KERNEL_ID, KEYS, PARAM, RTOL, THRESHOLD, TOPK, adjacencies, assert_edges,
+                       assert_written, batch_of_drawn, matrices, need_gpu, poisoned, poisoned_workspace, raw, same_batch,
+                       want, ws_need)  # noqa: F401  (need_gpu: the module's autouse fixture)
+from gdc_cases import subjects as drawn_subjects
 from gdc_heat_ref import MARGIN, threshold_cases, topk_cases
 
 pytestmark = pytest.mark.gpu
 
-RTOL = 3e-7
-PPR, HEAT, TOPK, THRESHOLD = 0, 1, 0, 1
-KERNEL_ID = {"ppr": PPR, "heat": HEAT}
-PARAM = {"heat": 5.0, "ppr": 0.05}
-EPS = {"heat": 0.02, "ppr": 0.03}
 # an eps at which about half of the columns keep nothing (the median of the column maxima, found on the CPU)
 EMPTY_EPS = {(33, "heat"): 0.052, (33, "ppr"): 0.084, (129, "heat"): 0.036, (129, "ppr"): 0.066}
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    from igcn_amd import _lib
-    _lib.load()
-
-
-_ADJ, _S = {}, {}
-
-
-def _adjacencies(bsz, rois, seed, knn=5):
-    key = (bsz, rois, seed, knn)
-    if key not in _ADJ:
-        rng = np.random.default_rng(seed)
-        _ADJ[key] = [HR.synthetic_adjacency(rng, rois, knn).astype(np.float32) for _ in range(bsz)]
-    return _ADJ[key]
-
-
-def _matrices(tag, adjs, kernel, param):
-    """The dense fp64 diffusion matrices of a named input, computed once and shared (never modified)."""
-    key = (tag, kernel, param)
-    if key not in _S:
-        _S[key] = [HR.diffusion_matrix(a, kernel, param) for a in adjs]
-        for s in _S[key]:
-            s.setflags(write=False)
-    return _S[key]
-
-
-def _want(mats, k=None, eps=None):
-    """(edge_index with graph g offset by g*R, edge_attr, edge_ptr) of a batch from its diffusion matrices, after
-    asserting the margin of every decision."""
-    gap_k, gap_e = zip(*[HR.margins(s, k=k, eps=eps) for s in mats])
-    assert min(gap_k) >= MARGIN and min(gap_e) >= MARGIN, (min(gap_k), min(gap_e))
-    eis, ews, ptr, off = [], [], [0], 0
-    for s in mats:
-        ei, ew = HR.coo(HR.OG.top_k_matrix(s, k) if eps is None else HR.clipped_matrix(s, eps))
-        eis.append(ei + off)
-        ews.append(ew)
-        off += s.shape[0]
-        ptr.append(ptr[-1] + ei.shape[1])
-    return np.concatenate(eis, axis=1), np.concatenate(ews), np.asarray(ptr, dtype=np.int64)
-
-
-def _assert_edges(got, want, what=""):
-    (ei, ew, edge_ptr), (want_ei, want_ew, want_ptr) = got, want
-    assert edge_ptr.tolist() == list(want_ptr), what
-    assert np.array_equal(ei.cpu().numpy(), want_ei), what                              # bit-exact indexing
-    err = np.abs(ew.cpu().numpy().astype(np.float64) - want_ew) / np.abs(want_ew)
-    print(f"{what}: edges {want_ei.shape[1]}, largest relative weight error {err.max() if err.size else 0.0:.3g}")
-    np.testing.assert_allclose(ew.cpu().numpy(), want_ew, rtol=RTOL, atol=0)
-
-
-def _need(bsz, rois, kernel):
-    from igcn_amd import _lib
-    return int(_lib.load().igcn_gdc_tiled_workspace_bytes(bsz, rois, kernel))
-
-
-def _raw(adj, kernel, param, sparsify, k, eps, subject=None, n_subjects=None, bsz=None, ws_bytes=None):
-    """The entry point itself on outputs full of NaN / -7 and a workspace full of NaN:
-    (edge_index [2, slots], edge_attr [slots], counts [B]) with the padding left in."""
-    from igcn_amd._lib import call, ptr, stream_ptr
-    r = adj.shape[1]
-    b = adj.shape[0] if bsz is None else bsz
-    slots = b * r * (k if sparsify == TOPK else r)
-    ei = torch.full((2, slots), -7, dtype=torch.int64, device="cuda")
-    ew = torch.full((slots,), float("nan"), dtype=torch.float32, device="cuda")
-    counts = torch.full((b,), -7, dtype=torch.int32, device="cuda")
-    need = _need(b, r, kernel) if ws_bytes is None else ws_bytes
-    ws = torch.full(((need + 7) // 8 + 2,), float("nan"), dtype=torch.float64, device="cuda")
-    call("igcn_gdc_diffuse_tiled", b, r, kernel, float(param), sparsify, int(k), float(eps), ptr(adj),
-         adj.shape[0] if n_subjects is None else n_subjects, ptr(subject), ptr(ei), ptr(ew), ptr(counts), ptr(ws), need,
-         stream_ptr())
-    return ei, ew, counts
 
 
 # ---- the reference's own outputs through the new route ---------------------------------------------------------------
@@ -105,7 +28,7 @@ def test_heat_topk_vs_reference_golden(golden):
     for c, rois, k, t, a, ei, ew in topk_cases(golden("gdc_heat")):
         assert HR.margins(HR.heat_matrix(a, t), k=k)[0] >= MARGIN
         got = diffusion_routed(torch.from_numpy(a).cuda()[None], kernel="heat", t=t, top_k=k, route="tiled")
-        _assert_edges(got, (ei, ew, [0, ei.shape[1]]), f"case {c}")
+        assert_edges(got, (ei, ew, [0, ei.shape[1]]), f"case {c}")
 
 
 def test_threshold_vs_reference_golden(golden):
@@ -116,7 +39,7 @@ def test_threshold_vs_reference_golden(golden):
         assert HR.margins(HR.diffusion_matrix(a, kernel, param), eps=eps)[1] >= MARGIN
         got = diffusion_routed(torch.from_numpy(a).cuda()[None], kernel=kernel, alpha=param, t=param, top_k=1, eps=eps,
                                route="tiled")
-        _assert_edges(got, (ei, ew, [0, ei.shape[1]]), f"case {c} ({kernel})")
+        assert_edges(got, (ei, ew, [0, ei.shape[1]]), f"case {c} ({kernel})")
         seen_empty += empty
     assert seen_empty >= 1
 
@@ -131,7 +54,7 @@ def test_ppr_topk_vs_reference_golden(golden):
         assert HR.margins(HR.OG.ppr_matrix(a.astype(np.float64), alpha), k=k)[0] >= MARGIN
         want_ei, want_ew = HR.OG.diffusion_topk(a, k, alpha)
         got = diffusion_topk(torch.from_numpy(a).cuda()[None], top_k=k, alpha=alpha, route="tiled")
-        _assert_edges(got, (want_ei, want_ew, [0, want_ei.shape[1]]), f"case {c}")
+        assert_edges(got, (want_ei, want_ew, [0, want_ei.shape[1]]), f"case {c}")
         c += 1
     assert c == 5
 
@@ -144,8 +67,8 @@ def test_ppr_topk_vs_reference_golden(golden):
 def test_tile_seams_vs_restatement(rois, kernel):
     from igcn_amd.gdc import diffusion_routed
     param = PARAM[kernel]
-    adjs = _adjacencies(3, rois, seed=rois)
-    mats = _matrices(("seam", rois), adjs, kernel, param)
+    adjs = adjacencies(3, rois, seed=rois)
+    mats = matrices(("seam", rois), adjs, kernel, param)
     for bsz in (1, 3):
         adj = torch.from_numpy(np.stack(adjs[:bsz])).cuda()
         cases = [dict(top_k=1), dict(top_k=3), dict(top_k=rois), dict(eps=EPS[kernel])]
@@ -153,11 +76,11 @@ def test_tile_seams_vs_restatement(rois, kernel):
             cases.append(dict(eps=EMPTY_EPS[(rois, kernel)]))
         for case in cases:
             k, eps = case.get("top_k"), case.get("eps")
-            want = _want(mats[:bsz], k=k, eps=eps)
+            exp = want(mats[:bsz], k=k, eps=eps)
             if eps is not None and (rois, kernel) in EMPTY_EPS and eps == EMPTY_EPS[(rois, kernel)]:
-                assert 0 < len(np.unique(want[0][1])) < bsz * rois                     # columns that keep nothing
+                assert 0 < len(np.unique(exp[0][1])) < bsz * rois                     # columns that keep nothing
             got = diffusion_routed(adj, kernel=kernel, alpha=param, t=param, top_k=k or 1, eps=eps, route="tiled")
-            _assert_edges(got, want, f"R={rois} B={bsz} {kernel} {case}")
+            assert_edges(got, exp, f"R={rois} B={bsz} {kernel} {case}")
 
 
 @pytest.mark.parametrize("kernel", ["heat", "ppr"])
@@ -165,23 +88,23 @@ def test_512_regions(kernel):
     """The full-size products, once per kernel: eight tiles a side."""
     from igcn_amd.gdc import diffusion_routed
     param = PARAM[kernel]
-    adjs = [_adjacencies(1, 512, seed=9, knn=9)[0], _adjacencies(1, 512, seed=512, knn=5)[0]]
-    mats = _matrices(("512",), adjs, kernel, param)
+    adjs = [adjacencies(1, 512, seed=9, knn=9)[0], adjacencies(1, 512, seed=512, knn=5)[0]]
+    mats = matrices(("512",), adjs, kernel, param)
     adj = torch.from_numpy(np.stack(adjs)).cuda()
     for case in (dict(top_k=3), dict(eps=EPS[kernel])):
         k, eps = case.get("top_k"), case.get("eps")
         got = diffusion_routed(adj, kernel=kernel, alpha=param, t=param, top_k=k or 1, eps=eps, route="tiled")
-        _assert_edges(got, _want(mats, k=k, eps=eps), f"R=512 B=2 {kernel} {case}")
+        assert_edges(got, want(mats, k=k, eps=eps), f"R=512 B=2 {kernel} {case}")
 
 
 @pytest.mark.parametrize("kernel,param", [("heat", 5.0), ("ppr", 0.05)])
 def test_aal_116(kernel, param):
     from igcn_amd.gdc import diffusion_routed
-    adjs = _adjacencies(1, 116, seed=116)
-    mats = _matrices(("aal",), adjs, kernel, param)
+    adjs = adjacencies(1, 116, seed=116)
+    mats = matrices(("aal",), adjs, kernel, param)
     got = diffusion_routed(torch.from_numpy(adjs[0]).cuda()[None], kernel=kernel, alpha=param, t=param, top_k=3,
                            route="tiled")
-    _assert_edges(got, _want(mats, k=3), f"R=116 {kernel}")
+    assert_edges(got, want(mats, k=3), f"R=116 {kernel}")
 
 
 # ---- one batch, different scaling exponents ----------------------------------------------------------------------------
@@ -205,29 +128,29 @@ def test_mixed_scaling_exponents_in_one_batch(t):
     assert s[0] < s[1] <= TR.heat_max_squarings(t, 97)
     for n, e in zip(norms, s):                            # the exponent is not a rounding away from another one
         assert n / 2.0 ** e <= 0.5 * (1 - 1e-9) and (e == 0 or n / 2.0 ** (e - 1) >= 0.5 * (1 + 1e-9))
-    mats = _matrices(("hub",), adjs, "heat", t)
+    mats = matrices(("hub",), adjs, "heat", t)
     for order in ((0, 1), (1, 0, 0)):
         adj = torch.from_numpy(np.stack([adjs[g] for g in order])).cuda()
         got = diffusion_routed(adj, kernel="heat", t=t, top_k=3, route="tiled")
-        _assert_edges(got, _want([mats[g] for g in order], k=3), f"t={t} graphs {order}")
+        assert_edges(got, want([mats[g] for g in order], k=3), f"t={t} graphs {order}")
 
 
 # ---- subject list ------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kernel", ["heat", "ppr"])
 def test_subject_list_with_repeats_and_an_index_outside_the_dataset(kernel):
     rois, param = 97, PARAM[kernel]
-    adjs = _adjacencies(3, rois, seed=rois)
-    mats = _matrices(("seam", rois), adjs, kernel, param)
+    adjs = adjacencies(3, rois, seed=rois)
+    mats = matrices(("seam", rois), adjs, kernel, param)
     adj = torch.from_numpy(np.stack(adjs)).cuda()
     subject = torch.tensor([2, 3, 0, -1, 2], device="cuda")
     for sparsify, k, eps, cap in ((TOPK, 3, 0.0, 3), (THRESHOLD, 1, EPS[kernel], rois)):
-        ei, ew, counts = _raw(adj, KERNEL_ID[kernel], param, sparsify, k, eps, subject=subject, n_subjects=3, bsz=5)
+        ei, ew, counts = raw("tiled", adj, KERNEL_ID[kernel], param, sparsify, k, eps, subject=subject, n_subjects=3, bsz=5)
         ei, ew = ei.view(2, 5, rois * cap), ew.view(5, rois * cap)
         assert counts.tolist()[1] == 0 and counts.tolist()[3] == 0
         for g in (1, 3):
             assert bool((ei[:, g] == -1).all()) and float(ew[g].abs().max()) == 0.0
         for g, s in ((0, 2), (2, 0), (4, 2)):
-            want_ei, want_ew, _ = _want([mats[s]], k=k if sparsify == TOPK else None, eps=eps if sparsify else None)
+            want_ei, want_ew, _ = want([mats[s]], k=k if sparsify == TOPK else None, eps=eps if sparsify else None)
             n = int(counts[g])
             assert n == want_ei.shape[1]
             assert np.array_equal(ei[:, g, :n].cpu().numpy(), want_ei + g * rois)
@@ -241,21 +164,21 @@ def test_every_slot_is_written_and_two_runs_give_the_same_bits(kernel):
     """Outputs full of NaN / -7, workspace full of NaN, everything inside fenced allocations."""
     from fenced import fenced
     rois, param = 33, PARAM[kernel]
-    adjs = _adjacencies(3, rois, seed=rois)
-    mats = _matrices(("seam", rois), adjs, kernel, param)
+    adjs = adjacencies(3, rois, seed=rois)
+    mats = matrices(("seam", rois), adjs, kernel, param)
     adj = torch.from_numpy(np.stack(adjs)).cuda()
     for sparsify, k, eps in ((TOPK, 3, 0.0), (THRESHOLD, 1, EMPTY_EPS[(rois, kernel)])):
         with fenced() as f:
-            one = _raw(adj, KERNEL_ID[kernel], param, sparsify, k, eps)
-            two = _raw(adj, KERNEL_ID[kernel], param, sparsify, k, eps)
+            one = raw("tiled", adj, KERNEL_ID[kernel], param, sparsify, k, eps)
+            two = raw("tiled", adj, KERNEL_ID[kernel], param, sparsify, k, eps)
             torch.cuda.synchronize()
             f.check()
         ei, ew, counts = one
-        assert not bool(torch.isnan(ew).any()) and not bool((ei == -7).any()) and not bool((counts == -7).any())
+        assert_written(ei, ew, counts)
         for a, b in zip(one, two):
             assert torch.equal(a, b)
         assert torch.equal(one[1].view(torch.int32), two[1].view(torch.int32))
-        want_ei, want_ew, want_ptr = _want(mats, k=k if sparsify == TOPK else None, eps=eps if sparsify else None)
+        want_ei, want_ew, want_ptr = want(mats, k=k if sparsify == TOPK else None, eps=eps if sparsify else None)
         assert counts.tolist() == np.diff(want_ptr).tolist()
         valid = ei[0] >= 0
         assert np.array_equal(ei[:, valid].cpu().numpy(), want_ei)
@@ -272,9 +195,9 @@ def test_every_slot_is_written_and_two_runs_give_the_same_bits(kernel):
 def test_chunked_run_equals_one_chunk_bit_for_bit(kernel):
     from igcn_amd.gdc import diffusion_routed
     rois, param = 129, PARAM[kernel]
-    adj = torch.from_numpy(np.stack(_adjacencies(3, rois, seed=rois))).cuda()
-    one = _need(1, rois, KERNEL_ID[kernel])
-    assert _need(3, rois, KERNEL_ID[kernel]) == 3 * one == TR.workspace_bytes(3, rois, kernel)
+    adj = torch.from_numpy(np.stack(adjacencies(3, rois, seed=rois))).cuda()
+    one = ws_need(1, rois, KERNEL_ID[kernel])
+    assert ws_need(3, rois, KERNEL_ID[kernel]) == 3 * one == TR.workspace_bytes(3, rois, kernel)
     for case in (dict(top_k=3), dict(top_k=1, eps=EPS[kernel])):
         whole = diffusion_routed(adj, kernel=kernel, alpha=param, t=param, route="tiled", **case)
         for cap in (one, 2 * one + one // 2):                                   # three chunks of one; two chunks, 2 + 1
@@ -292,8 +215,8 @@ def test_python_surface_inside_fences(kernel):
     from igcn_amd.gdc import diffusion_routed
     from igcn_amd.loader import DeviceGdcFeeder
     rois, param = 97, PARAM[kernel]
-    adj = torch.from_numpy(np.stack(_adjacencies(3, rois, seed=rois))).cuda()
-    one = _need(1, rois, KERNEL_ID[kernel])
+    adj = torch.from_numpy(np.stack(adjacencies(3, rois, seed=rois))).cuda()
+    one = ws_need(1, rois, KERNEL_ID[kernel])
     plain = diffusion_routed(adj, kernel=kernel, alpha=param, t=param, top_k=3, route="tiled")
     with fenced() as f:
         whole = diffusion_routed(adj, kernel=kernel, alpha=param, t=param, top_k=3, route="tiled")
@@ -312,7 +235,7 @@ def test_python_surface_inside_fences(kernel):
     for got in (whole, parts):
         for a, b in zip(plain, got):
             assert torch.equal(a.cpu().view(torch.uint8), b.cpu().view(torch.uint8))
-    _assert_edges(thr, _want(_matrices(("seam", rois), _adjacencies(3, rois, seed=rois), kernel, param), eps=EPS[kernel]),
+    assert_edges(thr, want(matrices(("seam", rois), adjacencies(3, rois, seed=rois), kernel, param), eps=EPS[kernel]),
                   f"fenced threshold {kernel}")
 
 
@@ -322,16 +245,16 @@ def test_python_surface_inside_fences(kernel):
 def test_resident_and_tiled_agree(rois, kernel):
     from igcn_amd.gdc import diffusion_routed
     param = PARAM[kernel]
-    adjs = _adjacencies(3, rois, seed=rois)
-    mats = _matrices(("seam", rois), adjs, kernel, param)
+    adjs = adjacencies(3, rois, seed=rois)
+    mats = matrices(("seam", rois), adjs, kernel, param)
     adj = torch.from_numpy(np.stack(adjs)).cuda()
     for case in (dict(top_k=3), dict(top_k=1, eps=EPS[kernel])):
-        want = _want(mats, k=None if "eps" in case else 3, eps=case.get("eps"))
+        exp = want(mats, k=None if "eps" in case else 3, eps=case.get("eps"))
         res = diffusion_routed(adj, kernel=kernel, alpha=param, t=param, route="resident", **case)
         til = diffusion_routed(adj, kernel=kernel, alpha=param, t=param, route="tiled", **case)
         assert torch.equal(res[0], til[0]) and torch.equal(res[2], til[2])
-        _assert_edges(res, want, f"R={rois} {kernel} resident {case}")
-        _assert_edges(til, want, f"R={rois} {kernel} tiled {case}")
+        assert_edges(res, exp, f"R={rois} {kernel} resident {case}")
+        assert_edges(til, exp, f"R={rois} {kernel} tiled {case}")
         if rois == 90:
             auto = diffusion_routed(adj, kernel=kernel, alpha=param, t=param, route="auto", **case)
             for a, b in zip(auto, res):
@@ -344,23 +267,23 @@ def test_one_past_the_resident_limit():
     lib = _lib.load()
     rois = lib.igcn_gdc_max_rois(HEAT) + 1
     assert rois == 97 and lib.igcn_gdc_tiled_max_rois() == 512
-    adjs = _adjacencies(3, rois, seed=rois)
-    want = _want(_matrices(("seam", rois), adjs, "heat", 5.0), k=3)
+    adjs = adjacencies(3, rois, seed=rois)
+    exp = want(matrices(("seam", rois), adjs, "heat", 5.0), k=3)
     adj = torch.from_numpy(np.stack(adjs)).cuda()
     with pytest.raises(_lib.IgcnError, match=f"max R = {rois - 1}"):
         diffusion(adj, kernel="heat", t=5.0, top_k=3)
     with pytest.raises(_lib.IgcnError, match=f"max R = {rois - 1}"):
         batch_from_dense(adj, torch.rand(3 * rois, 3, device="cuda"), kernel="heat", t=5.0)
     for route in ("auto", "tiled"):
-        _assert_edges(diffusion_routed(adj, kernel="heat", t=5.0, top_k=3, route=route), want, f"R={rois} {route}")
+        assert_edges(diffusion_routed(adj, kernel="heat", t=5.0, top_k=3, route=route), exp, f"R={rois} {route}")
 
 
 def test_preprocess_takes_a_graph_beyond_the_resident_limit():
     from igcn_amd.data import Data
     from igcn_amd.gdc import preprocess_diffusion_imgs_snps
-    a = _adjacencies(3, 129, seed=129)[0]
+    a = adjacencies(3, 129, seed=129)[0]
     for is_ppr, kernel in ((True, "ppr"), (False, "heat")):
-        want_ei, want_ew, _ = _want([_matrices(("seam", 129), _adjacencies(3, 129, seed=129), kernel, PARAM[kernel])[0]], k=5)
+        want_ei, want_ew, _ = want([matrices(("seam", 129), adjacencies(3, 129, seed=129), kernel, PARAM[kernel])[0]], k=5)
         data = Data(x=torch.rand(129, 3), A=torch.from_numpy(a).cuda(), y=torch.tensor([1]), snps_feat=torch.rand(1, 54),
                     clust_y=torch.tensor([0]), sbjID=torch.tensor([7]), tsne_fdim=torch.rand(1, 2),
                     clini_score=torch.rand(3), demographics=torch.rand(2))
@@ -383,11 +306,11 @@ def test_513_regions_are_refused():
 def test_a_workspace_one_byte_short_is_refused(kernel):
     from igcn_amd import _lib
     from igcn_amd.gdc import diffusion_routed
-    need = _need(2, 40, KERNEL_ID[kernel])
+    need = ws_need(2, 40, KERNEL_ID[kernel])
     assert need == TR.workspace_bytes(2, 40, kernel)
-    adj = torch.from_numpy(np.stack(_adjacencies(2, 40, seed=2))).cuda()
+    adj = torch.from_numpy(np.stack(adjacencies(2, 40, seed=2))).cuda()
     with pytest.raises(_lib.IgcnError, match=f"needs {need} bytes"):
-        _raw(adj, KERNEL_ID[kernel], PARAM[kernel], TOPK, 3, 0.0, ws_bytes=need - 1)
+        raw("tiled", adj, KERNEL_ID[kernel], PARAM[kernel], TOPK, 3, 0.0, ws_bytes=need - 1)
     with pytest.raises(_lib.IgcnError, match=f"needs {need // 2} bytes"):               # the Python cap, below one graph
         diffusion_routed(adj, kernel=kernel, route="tiled", workspace_bytes=need // 2 - 1)
 
@@ -403,40 +326,31 @@ def test_t_outside_the_interface_is_refused(t):
 def test_alpha_below_the_minimum_is_refused():
     from igcn_amd import _lib
     from igcn_amd.gdc import diffusion_routed
-    adj = torch.from_numpy(_adjacencies(1, 17, seed=17)[0]).cuda()[None]
+    adj = torch.from_numpy(adjacencies(1, 17, seed=17)[0]).cuda()[None]
     for alpha in (TR.ALPHA_MIN * 0.99, 0.0, 1.5):
         with pytest.raises(_lib.IgcnError, match=r"outside \[0\.001,1\]"):
             diffusion_routed(adj, kernel="ppr", alpha=alpha, top_k=3, route="tiled")
     # both ends of the interval are inside it
-    a = _adjacencies(1, 17, seed=17)
+    a = adjacencies(1, 17, seed=17)
     for alpha in (TR.ALPHA_MIN, 1.0):
         s = [HR.OG.ppr_matrix(a[0].astype(np.float64), alpha)]
         if alpha == 1.0:                                  # P = I: one edge per node, nothing to decide
             ei, ew, ptr = diffusion_routed(adj, kernel="ppr", alpha=alpha, top_k=1, route="tiled")
             assert ei.cpu().tolist() == [list(range(17)), list(range(17))] and ew.cpu().tolist() == [1.0] * 17
         else:
-            _assert_edges(diffusion_routed(adj, kernel="ppr", alpha=alpha, top_k=3, route="tiled"), _want(s, k=3),
+            assert_edges(diffusion_routed(adj, kernel="ppr", alpha=alpha, top_k=3, route="tiled"), want(s, k=3),
                           f"alpha={alpha}")
 
 
 # ---- feeder --------------------------------------------------------------------------------------------------------------
-KEYS = ("x", "edge_index", "edge_attr", "snps_feat", "y", "clini_score", "tsne_fdim", "clust_y", "batch", "ptr", "edge_ptr")
-COLS = ("x", "snps_feat", "y", "clini_score", "tsne_fdim", "clust_y")
-
-
 @pytest.fixture(scope="module")
 def subjects():
-    from igcn_amd import synth
-    from igcn_amd.data import Data
-    graphs = synth.brain_graph_list(6, seed=5, rois=130, tsne_dim=16)
-    slim = [Data(**{k: v for k, v in g.__dict__.items() if k != "A"}) for g in graphs]
-    return graphs, slim
+    return drawn_subjects(6, rois=130)
 
 
 @pytest.mark.parametrize("kernel", ["ppr", "heat"])
 def test_tiled_feeder_equals_batch_from_dense(subjects, kernel):
     from igcn_amd import ops
-    from igcn_amd.gdc import batch_from_dense
     from igcn_amd.loader import DeviceGdcFeeder, EpochIndex, UniformGraphStore
     graphs, slim = subjects
     adj = torch.stack([g.A for g in graphs]).cuda()
@@ -445,21 +359,50 @@ def test_tiled_feeder_equals_batch_from_dense(subjects, kernel):
     store = UniformGraphStore(slim, "cuda")
     cols = {k: store.cols[k] for k in COLS}
     feeder = DeviceGdcFeeder(adj, cols, 2, steps=2, top_k=3, seed=3, kernel=kernel, alpha=param, t=param, route="tiled")
-    assert feeder.route == "tiled" and feeder._ws.numel() == _need(2, 130, KERNEL_ID[kernel])
+    assert feeder.route == "tiled" and feeder._ws.numel() == ws_need(2, 130, KERNEL_ID[kernel])
     order = EpochIndex(6, 2, seed=3, device="cuda")
     for batch in feeder:
         torch.cuda.current_stream().wait_event(batch.ready)
-        idx = order.next()
-        b = int(idx.numel())
-        sel = {k: torch.index_select(v, 0, idx) for k, v in cols.items()}
-        x = sel.pop("x")
-        per = {k: (v.reshape(b, -1) if k in ("snps_feat", "tsne_fdim", "clini_score") else v.reshape(-1))
-               for k, v in sel.items()}
-        want = batch_from_dense(torch.index_select(adj, 0, idx), x, top_k=3, kernel=kernel, alpha=param, t=param,
-                                check=True, route="tiled", **per)
-        for k in KEYS:
-            a, w = getattr(batch, k), getattr(want, k)
-            assert a.dtype == w.dtype and a.shape == w.shape, k
-            assert torch.equal(a.cpu().view(torch.uint8), w.cpu().view(torch.uint8)), k
+        same_batch(batch, batch_of_drawn(adj, cols, order.next(), top_k=3, kernel=kernel, alpha=param, t=param,
+                                         route="tiled"), KEYS)
         ops.plan_for(batch).check()
         batch.release()
+
+
+# ---- the Python surface: one launcher, one body ----------------------------------------------------------------------------
+@pytest.mark.parametrize("sparsify", [TOPK, THRESHOLD])
+@pytest.mark.parametrize("kernel", ["ppr", "heat"])
+@pytest.mark.parametrize("route", ["resident", "tiled"])
+def test_launch_into_is_the_entry_point_and_nothing_more(route, kernel, sparsify):
+    """gdc.launch_into against the C entry point called by hand (gdc_cases.raw), both into poisoned buffers: five graphs
+    drawn from six matrices of 33 regions by a subject list with a repeat, an index past the end and a negative one."""
+    from igcn_amd import gdc
+    rois, k, param = 33, 3, PARAM[kernel]
+    eps = EPS[kernel] if sparsify == THRESHOLD else 0.0
+    adj = torch.from_numpy(np.stack(adjacencies(6, rois, seed=rois))).cuda()
+    subject = torch.tensor([4, 6, 0, -1, 4], device="cuda")
+    by_hand = raw(route, adj, KERNEL_ID[kernel], param, sparsify, k, eps, subject=subject, n_subjects=6, bsz=5)
+    ei, ew, counts = poisoned(5, rois, k if sparsify == TOPK else rois)
+    nbytes = ws_need(5, rois, KERNEL_ID[kernel]) if route == "tiled" else 0
+    ws = poisoned_workspace(nbytes) if route == "tiled" else None
+    gdc.launch_into(route, kernel, param, sparsify, k, eps, adj, 6, subject, 5, ei, ew, counts, ws, nbytes)
+    assert_written(ei, ew, counts)
+    assert torch.equal(ei, by_hand[0]) and torch.equal(counts, by_hand[2])
+    assert torch.equal(ew.view(torch.int32), by_hand[1].view(torch.int32))
+    got = counts.tolist()
+    assert got[1] == 0 and got[3] == 0 and got[0] == got[4] > 0 and got[2] > 0          # the list was followed
+
+
+@pytest.mark.parametrize("route", ["resident", "tiled"])
+def test_the_three_python_surfaces_are_one_body(route):
+    from igcn_amd.gdc import diffusion, diffusion_routed, diffusion_topk
+    adj = torch.from_numpy(np.stack(adjacencies(6, 33, seed=33))).cuda()
+    one = diffusion_topk(adj, 3, route=route)
+    others = [diffusion_routed(adj, "ppr", top_k=3, route=route)]
+    if route == "resident":
+        others.append(diffusion(adj, "ppr", top_k=3))
+    assert int(one[2][-1]) > 0
+    for got in others:
+        for a, b in zip(one, got):
+            assert a.dtype == b.dtype and a.shape == b.shape
+            assert torch.equal(a.cpu().view(torch.uint8), b.cpu().view(torch.uint8))

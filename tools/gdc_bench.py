@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Device time of the GDC pre-transform + collation (igcn_gdc_topk) for one batch of dense adjacencies."""
+"""Device time of the GDC pre-transform + collation (gdc.diffusion_topk: igcn_gdc_diffuse, PPR with top-k) for one batch
+of dense adjacencies."""
 import os
 import sys
 

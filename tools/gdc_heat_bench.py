@@ -18,7 +18,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-TOP_K, T, ALPHA, DEGREE = 3, 5.0, 0.05, 14              # DEGREE: csrc/gdc.hip GDC_HEAT_DEGREE
+TOP_K, T, ALPHA, DEGREE = 3, 5.0, 0.05, 14              # DEGREE: csrc/gdc_common.h GDC_HEAT_DEGREE
 
 
 def stats(xs):

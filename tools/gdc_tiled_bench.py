@@ -22,7 +22,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-TOP_K, T, ALPHA, DEGREE, TILE = 3, 5.0, 0.05, 14, 64      # DEGREE, TILE: csrc/gdc_tiled.hip
+TOP_K, T, ALPHA, DEGREE, TILE = 3, 5.0, 0.05, 14, 64      # csrc/gdc_common.h GDC_HEAT_DEGREE, csrc/gdc_tiled.hip GT_TILE
 PPR, HEAT = 0, 1
 
 
