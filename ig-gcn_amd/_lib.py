@@ -5,6 +5,7 @@ There is NO fallback: if the library is missing or a call fails, an exception is
 """
 import ctypes
 import os
+import re
 import sys
 
 import torch
@@ -13,269 +14,73 @@ from . import switches
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libigcn.so")
-
-ABI_VERSION = 441     # include/igcn.h IGCN_ABI_VERSION this table was written against (tests/test_abi.py compares)
-
-P, I, L, F, Z = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
-
-# name -> (restype, argtypes) ; mirrors include/igcn.h one to one
-SIGNATURES = {
-    "igcn_version": (I, []),
-    "igcn_last_error": (ctypes.c_char_p, []),
-    "igcn_configure": (I, [ctypes.c_uint, I, I]),
-    "igcn_graph_plan_workspace_bytes": (Z, [L, L]),
-    "igcn_graph_plan_build": (I, [L, L, P, P, P, P, P, P, P, P, P, Z, P]),
-    "igcn_graph_plan_build_segmented": (I, [L, L, I, P, P, P, L, L, P, P, P, P, P, P, P, P, P]),
-    "igcn_graph_plan_build_segmented_rep": (I, [L, L, I, P, P, P, L, L, P, P, P, P, P, P, P, P, I, P, P, P, P, P, P, P, P]),
-    "igcn_graph_plan_tiled_workspace_bytes": (Z, [I, L, L]),
-    "igcn_graph_plan_build_tiled": (I, [L, L, I, P, P, P, L, L, P, P, P, P, P, P, P, P, P, Z, P]),
-    "igcn_graph_plan_replicate": (I, [L, L, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
-    "igcn_edge_mask_fwd": (I, [L, L, I, I, P, P, P, P, P, P, P, P, P, P, P, P]),
-    "igcn_edge_mask_bwd": (I, [L, L, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
-    "igcn_edge_mask_reg_blocks": (I, [L, L, I, I, I]),
-    "igcn_edge_mask_fwd_reg": (I, [L, L, I, I, P, P, P, P, P, P, P, P, P, P, P, P, I, F, F, F, F, F, P, P, I, P, P]),
-    "igcn_edge_mask_bwd_reg": (I, [L, L, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, F, F, F, F, F, P, P, P, P, P,
-                                   P, I, P, P]),
-    "igcn_edge_dense_map_supported": (I, [I, I]),
-    "igcn_edge_dense_map": (I, [L, I, L, P, P, P, P, P, P, P, P, P]),
-    "igcn_saliency_maps": (I, [I, I, I, I, P, P, I, P, I, P, P, P]),
-    "igcn_grad_cam": (I, [I, I, I, P, P, I, P, P, P]),
-    "igcn_gcn_norm_fwd": (I, [L, L, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
-    "igcn_gcn_norm_bwd": (I, [L, L, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
-    "igcn_gcn_propagate_fwd": (I, [L, L, I, I, P, L, P, P, P, P, P, L, I, P]),
-    "igcn_gcn_propagate_bwd_scratch_floats": (Z, [L, I]),
-    "igcn_gcn_propagate_bwd": (I, [L, L, I, I, P, L, P, L, I, P, L, P, P, P, P, P, P, L, P, I, P, P, P, P]),
-    "igcn_sgcn_stack_lds_bytes": (Z, [I, I, I, I, I, I]),
-    "igcn_sgcn_stack_param_floats": (I, [I, I, I]),
-    "igcn_sgcn_stack_fwd": (I, [L, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P]),
-    "igcn_sgcn_stack_bwd": (I, [L, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
-    "igcn_sgcn_ori_lds_bytes": (Z, [I, I, I, I, I, I]),
-    "igcn_sgcn_ori_param_floats": (I, [I, I, I]),
-    "igcn_sgcn_ori_fwd": (I, [L, I, I, I, I, I] + [P] * 15),
-    "igcn_sgcn_ori_bwd": (I, [L, I, I, I, I, I] + [P] * 22),
-    "igcn_gat_stack_lds_bytes": (Z, [I, I, I, I, I, I]),
-    "igcn_gat_stack_param_floats": (I, [I, I, I]),
-    "igcn_gat_stack_fwd": (I, [L, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P]),
-    "igcn_gat_stack_alpha_tile": (I, [I, I, I, I, I]),
-    "igcn_gat_stack_alpha": (I, [L, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P]),
-    "igcn_gat_stack_bwd": (I, [L, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
-    "igcn_gat_stack_bwd_ew": (I, [L, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
-    "igcn_sgcn_front_lds_bytes": (Z, [I, I, I, I, I]),
-    "igcn_sgcn_front_fwd": (I, [L, L, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, F, F, F, F, F, P, P, P,
-                                P, P, P, P]),
-    "igcn_proj_bwd_supported": (I, [L, I, I]),
-    "igcn_proj_bwd_blocks": (I, [L]),
-    "igcn_proj_bwd_scratch_floats": (Z, [L, I]),
-    "igcn_proj_bwd": (I, [L, I, I, P, P, P, P, P, P, P]),
-    "igcn_proj_bwd_pair": (I, [L, I, P, P, P, P, P, P, L, I, P, P, P, P, P, P, I, P]),
-    "igcn_proj_bwd_pair_bias": (I, [L, I, P, P, P, P, P, P, P, I, L, I, P, P, P, P, P, P, P, I, I, P]),
-    "igcn_proj_fwd_blocks": (I, [L]),
-    "igcn_proj_fwd_pair": (I, [L, I, P, P, P, P, L, I, P, P, P, P, I, P]),
-    "igcn_head_bwd_supported": (I, [I, I, I]),
-    "igcn_head_bwd_scratch_floats": (Z, [I, I]),
-    "igcn_head_bwd_pair": (I, [I, I, I, P, P, P, P, P, P, P, P, I, P, P, P, P, P, P, P, P, P]),
-    "igcn_dense_blocks_check": (I, [L, I, P, P, P]),
-    "igcn_dense_sgcn_supported": (I, [I, I, I, I]),
-    "igcn_dense_sgcn_ws_floats": (Z, [L, I, I, I]),
-    "igcn_dense_sgcn_bwd_ws_floats": (Z, [L, I, I, I, I]),
-    "igcn_dense_sgcn_reg_blocks": (I, [L, I]),
-    "igcn_dense_sgcn_fwd": (I, [L, I, I, I, I, I, I, P, P, P, P, P, P, P, I, F, F, F, F, F, P, P, P, P, P, P]),
-    "igcn_dense_sgcn_bwd": (I, [L, I, I, I, I, I, I, P, P, P, P, P, P, I, F, F, F, F, F, P, P, P, P, P, P, P, P, P, P, P, P]),
-    "igcn_small_linear_bwd_scratch_floats": (Z, [L, I, I]),
-    "igcn_small_linear_fwd": (I, [L, I, I, P, P, P, P, P, P]),
-    "igcn_small_linear_bwd": (I, [L, I, I, P, P, P, P, P, P, P, P]),
-    "igcn_small_linear_pair_fwd": (I, [L, I, I, P, P, P, P, P, I, P, P, P, P, P, P]),
-    "igcn_small_linear_pair_bwd": (I, [L, I, I, P, P, P, P, P, P, P, I, P, P, P, P, P, P, P, P]),
-    "igcn_snps_mask_fwd": (I, [I, I, P, P, P, P, P, P]),
-    "igcn_snps_mask_bwd": (I, [I, I, P, P, P, P, P, P]),
-    "igcn_head_inputs_fwd": (I, [L, I, I, I, I, P, P, P, P, P, P, P, P, P]),
-    "igcn_head_inputs_bwd": (I, [L, I, I, I, I, P, P, P, P, P, P, P, P, P, P]),
-    "igcn_outproj_head_inputs_fwd": (I, [L, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P]),
-    "igcn_head_inputs_bwd_blocks": (I, [L, I, I]),
-    "igcn_head_inputs_bwd_relu": (I, [L, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, I, P, P, P]),
-    "igcn_concat_cols": (I, [L, I, I, P, P, P]),
-    "igcn_copy_multi": (I, [I, P, P, P, P]),
-    "igcn_image_put": (I, [I, L, P, P, L, P, L, P]),
-    "igcn_image_take": (I, [I, L, P, P, L, P, P]),
-    "igcn_gather_batch": (I, [I, I, L, L, P, P, P, P, P, P]),
-    "igcn_launch_floor": (I, [L, I, I, I, P, P]),
-    "igcn_graph_pool_fwd": (I, [L, I, I, P, P, P, P]),
-    "igcn_graph_pool_bwd": (I, [L, I, I, P, P, P, P]),
-    "igcn_bias_grad_scratch_floats": (Z, [L, I]),
-    "igcn_bias_grad": (I, [L, I, P, P, P, P, P, P]),
-    "igcn_col_sums": (I, [L, I, I, P, P, P, P]),
-    "igcn_bias_grad_pair": (I, [L, I, P, P, P, P, I, P, P, P, P, P, I, P, P]),
-    "igcn_gemm_f32_split_k": (I, [L, L, L]),
-    "igcn_gemm_f32": (I, [L, L, L, P, L, L, P, L, L, P, P, L, I, I, P, P]),
-    "igcn_gemm_bf16": (I, [L, L, L, P, L, L, P, L, L, P, P, L, I, I, P, P]),
-    "igcn_gemm_f32_batched_sum": (I, [L, L, L, I, P, L, L, L, P, L, L, L, P, L, P, P]),
-    "igcn_gemm_f32_batched": (I, [L, L, L, I, P, L, L, L, P, L, L, L, P, L, L, I, P, P]),
-    "igcn_gemm_f32_grouped": (I, [I, P, P]),
-    "igcn_gemm_rider": (I, [P, I, P]),
-    "igcn_gemm_rider_flush": (I, [P]),
-    "igcn_rider_cancel": (I, [P]),
-    "igcn_stream_pending": (I, [P]),
-    "igcn_node_linear_bn_scratch_floats": (Z, [I, I, I]),
-    "igcn_node_linear_bn_supported": (I, [I, I]),
-    "igcn_node_linear_bn_fwd": (I, [I, I, I, I, I, P, P, P, P, P, P, I, F, F, P, P, P, P, P, P]),
-    "igcn_node_linear_bn_apply_map_ok": (I, [I, I, I, I, L]),
-    "igcn_node_linear_bn_apply_map_fwd": (I, [I, I, I, I, P, P, P, P, P, P, I, F, F, P, P, P, P, P, I, L, P, P, P, L, P, P]),
-    "igcn_node_linear_bn_bwd_scratch_floats": (Z, [I, I, I, I, I]),
-    "igcn_node_linear_bn_bwd": (I, [I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P]),
-    "igcn_node_linear_bn_pair_supported": (I, [I, I, I]),
-    "igcn_node_linear_bn_pair_fwd": (I, [I, I, I, I, P, I,
-                                         I, P, P, P, P, P, F, F, P, P, P, P,
-                                         I, P, P, P, P, P, F, F, P, P, P, P, P, P]),
-    "igcn_node_linear_bn_pair_bwd": (I, [I, I, I, I, I, P,
-                                         I, P, P, P, P, P, P, P, P, P, P,
-                                         I, P, P, P, P, P, P, P, P, P, P, P, P]),
-    "igcn_bn1d_fwd": (I, [I, I, I, P, P, P, P, P, I, F, F, I, P, P, P, P, P]),
-    "igcn_bn1d_bwd": (I, [I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P]),
-    "igcn_bn1d_fwd_supported": (I, [I, I]),
-    "igcn_bn1d_fwd_slabs": (I, [I, I, I, P, I, P, P, P, P, P, I, F, F, I, P, P, P, P, P]),
-    "igcn_gemm_effective_split": (I, [L, I]),
-    "igcn_gemm_plan": (I, [I, L, L, L, P, L, L, P, L, L, L, I, I, I, P]),
-    "igcn_gemm_group_plan": (I, [I, P, P]),
-    "igcn_dropout_state_words": (I, []),
-    "igcn_dropout_max_segments": (I, []),
-    "igcn_dropout_masks": (I, [L, I, P, P, P, P, I, P, L, P]),
-    "igcn_rider_dropout": (I, [P, L, I, P, P, P, P, I, P, L]),
-    "igcn_rider_flush": (I, [P]),
-    "igcn_sum_n": (I, [L, I, P, P, P]),
-    "igcn_sum_n_final": (I, [L, I, P, P, P]),
-    "igcn_mask_reg_blocks": (I, [L]),
-    "igcn_mask_reg_fwd": (I, [L, L, L, P, P, P, F, F, F, F, F, P, P, P]),
-    "igcn_mask_reg_bwd": (I, [L, L, L, P, P, P, F, F, F, F, F, P, P, P, P, P]),
-    "igcn_mask_reg3_fwd": (I, [L, L, L, P, P, P, F, F, F, F, F, F, F, P, P, P]),
-    "igcn_mask_reg3_bwd": (I, [L, L, L, P, P, P, F, F, F, F, F, F, F, P, P, P, P, P]),
-    "igcn_rbf_laplacian": (I, [I, I, F, P, P, P]),
-    "igcn_gram_loss_fwd": (I, [I, I, I, P, P, P, P, P]),
-    "igcn_gram_loss_bwd": (I, [I, I, P, P, P, P, P]),
-    "igcn_gram_loss_fwd_rbf": (I, [I, I, I, P, P, I, F, P, P, P, P]),
-    "igcn_gram_loss_fwd_rbf_unit": (I, [I, I, I, P, P, I, F, P, P, P, P, P, P]),
-    "igcn_attn_core_lds_bytes": (Z, [I, I, I, I, I]),
-    "igcn_attn_core_fwd": (I, [I, I, I, I, I, P, P, P, P, P]),
-    "igcn_attn_core_bwd_scratch_floats": (Z, [I, I, I]),
-    "igcn_attn_core_bwd": (I, [I, I, I, I, I, P, P, P, P, P, P, P, P, P]),
-    "igcn_attn_core_bf16_supported": (I, [I, I, I, I]),
-    "igcn_attn_core_bf16_fwd": (I, [I, I, I, I, I, P, P, P, P, P]),
-    "igcn_attn_core_bf16_bwd": (I, [I, I, I, I, I, P, P, P, P, P, P, P, P, P]),
-    "igcn_attn_core_split_supported": (I, [I, I, I, I]),
-    "igcn_attn_core_split_fwd": (I, [I, I, I, I, I, P, P, P, P, P]),
-    "igcn_attn_core_split_bwd_supported": (I, [I, I, I, I]),
-    "igcn_attn_core_split_bwd": (I, [I, I, I, I, I, P, P, P, P, P, P, P, P, P]),
-    "igcn_attn_weights_supported": (I, [I, I, I, I]),
-    "igcn_attn_weights_chunk_rows": (I, [I, I, I, I]),
-    "igcn_attn_weights": (I, [I, I, I, I, I, P, P, P, P]),
-    "igcn_attn_map_accumulate": (I, [I, I, I, I, P, P, P, P, P, P]),
-    "igcn_spmm_fwd": (I, [I, I, I, I, L, P, P, P, P, P, P]),
-    "igcn_spmm_bwd_scratch_floats": (Z, [I, I, I, I, L]),
-    "igcn_spmm_bwd": (I, [I, I, I, I, L, P, P, P, P, P, P, P, P, P, P, P, P, P]),
-    "igcn_spmm_bwd_dval_multi": (I, [I, P, P]),
-    "igcn_spmm_route": (I, [I, I, I, I, I, L, P]),
-    "igcn_spmm_fwd_strided": (I, [I, I, I, I, L, P, P, P, L, P, P, P]),
-    "igcn_spmm_bwd_strided": (I, [I, I, I, I, L, P, P, P, P, P, P, P, L, P, P, P, P, P, P]),
-    "igcn_go_attn_fwd": (I, [I, I, I, I, P, P, P, P, P, P, P, P, P]),
-    "igcn_go_attn_coeffs": (I, [I, I, I, I, P, P, P, P, P, P, P, P, P, P]),
-    "igcn_go_rollout_chunk": (I, [I]),
-    "igcn_go_rollout_layer": (I, [I, I, I, I, P, P, P, P, P, L, P, P]),
-    "igcn_go_attn_bwd_scratch_floats": (Z, [I, I, I, I]),
-    "igcn_go_attn_bwd_threads": (I, [I, I, I]),
-    "igcn_go_attn_walk_slots": (I, [I, I, I]),
-    "igcn_go_attn_walk_order": (I, [I, I, I, P, P]),
-    "igcn_go_attn_bwd": (I, [I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
-    "igcn_nodes_ln_fwd": (I, [I, I, I, I, F, P, P, P, P, P, P, P, P]),
-    "igcn_nodes_ln_bwd_scratch_floats": (Z, [I, I, I]),
-    "igcn_nodes_ln_bwd": (I, [I, I, I, I, P, P, P, P, P, P, P, P, P, P, P]),
-    "igcn_nodes_ln_bwd_dy": (I, [I, I, I, I, P, P, P, P, P, P, P, P, P]),
-    "igcn_nodes_ln_bwd_affine_multi": (I, [I, P, P]),
-    "igcn_go_decode_fwd": (I, [I, I, I, I, I, P, P, P, P, P, P, P]),
-    "igcn_go_attn_ln_fused_ok": (I, [I, I, I, I]),
-    "igcn_go_decode_ln_fused_ok": (I, [I, I, I, I]),
-    "igcn_go_ln_part_floats": (Z, [I, I]),
-    "igcn_go_attn_ln_bwd": (I, [I, I, I, I, P, P, P, P, P, P, P, P, P, P, I] + [P] * 15),
-    "igcn_go_decode_ln_bwd": (I, [I, I, I, I, I] + [P] * 19),
-    "igcn_go_decode_bwd_scratch_floats": (Z, [I, I, I, I]),
-    "igcn_go_decode_bwd": (I, [I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P]),
-    "igcn_go_route": (I, [I, I, I, I, I, I, I, P]),
-    "igcn_nodes_ln_prelu_fwd": (I, [I, I, I, I, F, P, P, P, P, P, P, P, P, P]),
-    "igcn_nodes_ln_prelu_bwd_scratch_floats": (Z, [I, I, I]),
-    "igcn_nodes_ln_prelu_bwd": (I, [I, I, I, I] + [P] * 13),
-    "igcn_bn_prelu_fwd": (I, [I, I, I, I, P, P, P, P, P, P, I, F, F, P, P, P, P, P, P]),
-    "igcn_bn_prelu_bwd_scratch_floats": (Z, [I, I]),
-    "igcn_bn_prelu_bwd": (I, [I, I, I, I] + [P] * 16),
-    "igcn_guide_gate_supported": (I, [I, I, I]),
-    "igcn_guide_gate_fwd": (I, [I, I, I, I, I, P, P, P, F, P, P, P, P, P, P, P, P, P, P]),
-    "igcn_guide_gate_bwd_scratch_floats": (Z, [I, I, I, I]),
-    "igcn_guide_gate_bwd": (I, [I, I, I, I, I, P, P, P, P, F, P, P, P, P, P, P, P, P, P, P]),
-    "igcn_adam_step": (I, [L, P, P, P, P, P, P, F, F, F, F, P]),
-    "igcn_adam_step_multi": (I, [I, P, P, P, P, F, F, F, F, P]),
-    "igcn_adam_step_ticked": (I, [L, P, P, P, P, P, P, F, F, F, F, P]),
-    "igcn_adam_step_multi_ticked": (I, [I, P, P, P, P, F, F, F, F, P]),
-    "igcn_adam_chunk": (I, []),
-    "igcn_adam_step_blocks": (I, [I, P, P, P, P, P, P, F, F, F, F, I, P]),
-    "igcn_pack_grads": (I, [I, P, P, P, P, P]),
-    "igcn_reduce_defer": (I, [P, I]),
-    "igcn_reduce_pending": (I, []),
-    "igcn_reduce_rows_final": (I, [P, L, L, I, P, P]),
-    "igcn_head_loss_supported": (I, [I, I, I]),
-    "igcn_head_loss_blocks": (I, [I, I]),
-    "igcn_head_loss_fwd": (I, [I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, F, F, P, P, P, P, P, P, P, P, P, P]),
-    "igcn_head_loss_gram_fwd": (I, [I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, F, F, P, P, P, P, P, P, P, P, P,
-                                    I, I, I, P, P, I, F, P, P, P, P, P]),
-    "igcn_loss_final": (I, [P, I, P, I, P, I, P, P, P]),
-    "igcn_cluster_head_loss_supported": (I, [I, I, I]),
-    "igcn_cluster_head_loss_blocks": (I, [I, I]),
-    "igcn_cluster_head_loss_fwd": (I, [I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, F, F, F, I, P, P, P, P, P, P, P, P, P]),
-    "igcn_cluster_loss_final": (I, [P, I, P, I, P, P, P]),
-    "igcn_snps_head_supported": (I, [I, I, I, I]),
-    "igcn_snps_head_workspace_bytes": (Z, [I, I, I, I]),
-    "igcn_snps_head_loss_fwd": (I, [I, I, I, I, P, P, P, P, P, P, F, F, I, P, P, P, P, P, P, P, F, P, P, P, P]),
-    "igcn_snps_head_loss_bwd": (I, [I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, F, P, P, P, P, P, P, P, P, P, P]),
-    "igcn_reduce_flush": (I, [P]),
-    "igcn_reduce_flush_tick": (I, [P, P]),
-    "igcn_comm_unique_id_bytes": (I, []),
-    "igcn_comm_get_unique_id": (I, [P]),
-    "igcn_comm_init": (I, [I, I, P, P]),
-    "igcn_comm_allreduce": (I, [P, P, L, P]),
-    "igcn_comm_destroy": (I, [P]),
-    "igcn_loss_head_fwd": (I, [I, I, I, I, P, I, P, P, P, P, P, P, P, I, P, I, P, F, F, P, P, P]),
-    "igcn_loss_head_bwd": (I, [I, I, I, I, P, P, P, P, P, P, P, F, F, P, P, P, P, P, P, P]),
-    "igcn_loss_head_fwd_grads": (I, [I, I, I, I, P, I, P, P, P, P, P, P, P, I, P, I, P, F, F, P, P, P, P, P, P, P, P]),
-    "igcn_gdc_topk_max_rois": (I, []),
-    "igcn_gdc_topk": (I, [I, I, I, ctypes.c_double, P, P, P, P, P]),
-    "igcn_gdc_topk_of": (I, [I, I, I, ctypes.c_double, P, L, P, P, P, P, P]),
-    "igcn_gdc_max_rois": (I, [I]),
-    "igcn_gdc_diffuse": (I, [I, I, I, ctypes.c_double, I, I, ctypes.c_double, P, L, P, P, P, P, P]),
-    "igcn_gdc_tiled_max_rois": (I, []),
-    "igcn_gdc_tiled_workspace_bytes": (Z, [I, I, I]),
-    "igcn_gdc_diffuse_tiled": (I, [I, I, I, ctypes.c_double, I, I, ctypes.c_double, P, L, P, P, P, P, P, Z, P]),
-    "igcn_eval_collect": (I, [I, I, I, I, I, P, P, P, P, P, P, P, P, L, P, P, P, P, P, P, P, P, P, P, P]),
-    "igcn_eval_metrics": (I, [L, I, I, P, P, P, P, P, P, P, P, P, P]),
-    "igcn_knn_impute_stats": (I, [L, I, P, P, L, P, P, P]),
-    "igcn_knn_impute_scratch_floats": (Z, [L, L]),
-    "igcn_knn_impute": (I, [L, I, I, P, P, L, P, L, P, P, P, P, I, I, P, P, P, P, P, P]),
-    "igcn_tsne_sqdist": (I, [I, I, P, P, P]),
-    "igcn_tsne_joint_p_scratch_doubles": (Z, [I]),
-    "igcn_tsne_joint_p": (I, [I, ctypes.c_double, P, P, P, P, P, P]),
-    "igcn_tsne_grad": (I, [I, I, P, P, P, P, P]),
-    "igcn_tsne_update": (I, [I, F, F, F, I, P, P, P, P, P, P, P, P, P]),
-    "igcn_kmeans_scratch_floats": (Z, [L, I, I]),
-    "igcn_kmeans_assign": (I, [L, I, I, P, P, P, P, P, P, P, P, P]),
-    "igcn_kmeans_update": (I, [L, I, I, P, P, P, P, P, P, P, P]),
-    "igcn_kmeanspp_step": (I, [L, I, I, P, P, P, P, P, P]),
-    "igcn_perm_planes_bytes": (Z, [I, I]),
-    "igcn_perm_plane_dims": (I, [I, I, P]),
-    "igcn_perm_prepare": (I, [L, I, I, P, P, I, P, P, P, P, P]),
-    "igcn_perm_maxsum_scratch_bytes": (Z, [I, I]),
-    "igcn_perm_maxsum": (I, [I, I, I, P, L, P, P, P, P, P, P, Z, P]),
-}
-
-_lib = None
+HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "igcn.h"))
 
 
 class IgcnError(RuntimeError):
     pass
+
+
+P, I, L, F, Z = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
+_RESTYPES = {"int": I, "size_t": Z, "constchar*": ctypes.c_char_p}     # (spaces removed)
+_SCALARS = {"int": I, "int64_t": L, "size_t": Z, "float": F, "double": ctypes.c_double, "unsigned": ctypes.c_uint}
+_COMMENT = re.compile(r"/\*.*?\*/|//[^\n]*", re.S)
+_DEFINE = re.compile(r"^[ \t]*#[ \t]*define[ \t]+(IGCN_\w+)[ \t]+\(?[ \t]*(-?\d+)[ \t]*\)?[ \t]*$", re.M)
+_DIRECTIVE = re.compile(r"^[ \t]*#.*$", re.M)
+_DECLARATION = re.compile(r"([^;{}()]*?)\b(igcn_\w+)\s*\(([^()]*)\)\s*;")     # (return type, name, arguments)
+_NAME = re.compile(r"\w+\Z")
+
+
+def _argtype(name, arg):
+    """ctypes type of one argument: `<type> [identifier]` with <type> one of _SCALARS (const ignored), or anything
+    with a `*`.  `unsigned long n`, `float x[4]`, `long n` and the like raise: a guessed width would shift every
+    argument behind it without a word."""
+    words = [w for w in arg.split() if w != "const"]
+    if "[" not in arg:
+        if "*" in arg:
+            return P
+        if words and words[0] in _SCALARS and (len(words) == 1 or len(words) == 2 and _NAME.match(words[1])):
+            return _SCALARS[words[0]]
+    raise IgcnError(f"{name}: argument `{arg.strip()}` is neither a pointer nor `<type> [name]` with <type> one of "
+                    f"{', '.join(_SCALARS)}")
+
+
+def parse_header(text):
+    """``(signatures, limits)`` of a header written like include/igcn.h.  limits: ``IGCN_NAME -> int`` for every
+    ``#define IGCN_NAME <decimal literal>``; no expression is evaluated.  signatures: ``name -> (restype, [argtypes])``
+    for every ``igcn_*(...);`` declaration.  Nothing is guessed and nothing is skipped: a return type other than int,
+    size_t or const char*, an argument _argtype refuses, or an ``igcn_*(`` that is no such declaration (a definition, a
+    function-pointer argument) raises IgcnError naming it."""
+    text = _COMMENT.sub(" ", text)
+    limits = {m.group(1): int(m.group(2)) for m in _DEFINE.finditer(text)}
+    text = _DIRECTIVE.sub(" ", text)
+    signatures = {}
+    for m in _DECLARATION.finditer(text):
+        ret, name, args = "".join(m.group(1).split()), m.group(2), m.group(3).strip()
+        if ret not in _RESTYPES:
+            raise IgcnError(f"{name}: return type `{' '.join(m.group(1).split())}` is none of int, size_t, const char*")
+        args = [] if args in ("", "void") else args.split(",")
+        signatures[name] = (_RESTYPES[ret], [_argtype(name, a) for a in args])
+    unbound = [n for n in re.findall(r"\b(igcn_\w+)\s*\(", text) if n not in signatures]
+    if unbound:
+        raise IgcnError(f"{', '.join(unbound)}: not a plain `<type> igcn_name(<arguments>);` declaration")
+    return signatures, limits
+
+
+def read_header(path=HEADER_PATH):
+    try:
+        with open(path) as fh:
+            return parse_header(fh.read())
+    except OSError as e:
+        raise IgcnError(f"{path}: the C header this binding is derived from cannot be read ({e.strerror})") from None
+
+
+# name -> (restype, argtypes) and IGCN_NAME -> value: include/igcn.h is the only place either is written down
+SIGNATURES, LIMITS = read_header()
+ABI_VERSION = LIMITS["IGCN_ABI_VERSION"]
+COPY_MULTI_MAX = LIMITS["IGCN_COPY_MULTI_MAX"]
+
+_lib = None
 
 
 def load():
@@ -339,8 +144,8 @@ def call(name, *args):
 
 def copy_multi(pairs):
     """``dst.copy_(src)`` for every (dst, src) pair of same-shape, same-dtype contiguous DEVICE tensors as one launch
-    per 16 pairs (igcn_copy_multi) on the current stream.  Anything else (a host tensor, a dtype change, a strided
-    view) goes through ``Tensor.copy_``."""
+    per COPY_MULTI_MAX (16) pairs (igcn_copy_multi) on the current stream.  Anything else (a host tensor, a dtype change,
+    a strided view) goes through ``Tensor.copy_``."""
     fast = []
     for dst, src in pairs:
         if (dst.is_cuda and src.is_cuda and dst.device == src.device and dst.dtype == src.dtype
@@ -349,8 +154,8 @@ def copy_multi(pairs):
                 fast.append((dst, src))
         else:
             dst.copy_(src, non_blocking=True)
-    for k in range(0, len(fast), 16):
-        chunk = fast[k:k + 16]
+    for k in range(0, len(fast), COPY_MULTI_MAX):
+        chunk = fast[k:k + COPY_MULTI_MAX]
         n = len(chunk)
         d = (ctypes.c_void_p * n)(*[t.data_ptr() for t, _ in chunk])
         s = (ctypes.c_void_p * n)(*[t.data_ptr() for _, t in chunk])

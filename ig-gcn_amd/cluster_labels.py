@@ -19,8 +19,9 @@ largest-magnitude loading is positive; equal distances go to the lower centre / 
 perplexity search, the scans and the cluster sums in fp64.  The gradient descent is chaotic: a run agrees with sklearn's
 in what it optimises (KL divergence, recovered clusters), not in coordinates.
 
-Supported: 4 <= S <= 4096 subjects, 1 <= D <= 1024 features, 2 embedding dimensions, 1 <= k <= 16 clusters, KMeans input
-width 1 <= d <= 1024; anything else raises ``ValueError``.
+Supported: 4 <= S <= 4096 subjects, 1 <= D <= 1024 features (ops.TSNE_MIN_S, TSNE_MAX_S, TSNE_MAX_D), 2 embedding
+dimensions, 1 <= k <= 16 clusters (ops.KMEANS_MAX_K), KMeans input width 1 <= d <= 1024 (ops.KMEANS_MAX_D); anything else
+raises ``ValueError``.
 """
 import numpy as np
 import torch
@@ -141,7 +142,7 @@ class TSNE:
             raise ValueError(f"TSNE: perplexity ({self.perplexity}) must be less than n_samples ({X.shape[0]})")
         if self.perplexity <= 0:
             raise ValueError("TSNE: perplexity must be positive")
-        x, s, _ = _points(X, "TSNE", 4, ops.TSNE_MAX_S, ops.TSNE_MAX_D)
+        x, s, _ = _points(X, "TSNE", ops.TSNE_MIN_S, ops.TSNE_MAX_S, ops.TSNE_MAX_D)
         if torch.is_tensor(self.init):
             y0 = _points(self.init, "TSNE init", s, s, 2)[0].to(x.device)
             if y0.shape[1] != 2:

@@ -633,7 +633,7 @@ size_t igcn_attn_mfma_lds_bytes(int D, int H, int Lq, int Lk, int backward) {
   const int hd = D / H;
   if (hd > 96) return 0;
   const size_t bytes = am_lds_bytes(hd, Lq, Lk, backward);
-  return bytes <= 150 * 1024 ? bytes : 0;
+  return bytes <= IGCN_LDS_BUDGET_BYTES ? bytes : 0;
 }
 
 static int am_vec(int D, int hd, const void* a, const void* b, const void* c, const void* d) {
@@ -686,7 +686,7 @@ int igcn_attn_mfma_bwd(int B, int D, int H, int Lq, int Lk, const float* q, cons
     const int nqt = (Lq + 15) / 16, nkt = (Lk + 15) / 16;
     const size_t lds2 = lds + (size_t)8 * 16 * AM_TLD * sizeof(float);
     if (vec && hd == 16 && nqt <= 8 && nkt >= 8 && (size_t)8 * nqt * 16 * 16 <= (size_t)2 * nkt * 16 * 17 &&
-        lds2 <= 150 * 1024 && !igcn_opt(IGCN_OPT_ATTN_BWD_TWICE)) {
+        lds2 <= IGCN_LDS_BUDGET_BYTES && !igcn_opt(IGCN_OPT_ATTN_BWD_TWICE)) {
 #define CALLS(NQTV)                                                                                              \
   case NQTV:                                                                                                     \
     IGCN_ALLOW_BIG_LDS((k_attn_mfma_bwd_shared<NQTV>));                                                          \

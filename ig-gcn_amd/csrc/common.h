@@ -51,7 +51,8 @@ static inline bool igcn_first_on_device(IgcnPerDevice& f) {
   do {                                                                                                          \
     static IgcnPerDevice f_ = {};                                                                               \
     if (igcn_first_on_device(f_))                                                                               \
-      (void)hipFuncSetAttribute((const void*)(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
+      (void)hipFuncSetAttribute((const void*)(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,             \
+                                IGCN_LDS_MAX_BYTES);                                                            \
   } while (0)
 
 #define IGCN_CHECK_LAUNCH(name)                                          \
@@ -62,6 +63,11 @@ static inline bool igcn_first_on_device(IgcnPerDevice& f) {
       return IGCN_ERR_LAUNCH;                                            \
     }                                                                    \
   } while (0)
+
+// Layer widths of the LDS-resident GCN / GAT stacks: the powers of two in the header's range (one kernel instance each)
+static inline bool igcn_stack_width_ok(int F) {
+  return F >= IGCN_STACK_MIN_WIDTH && F <= IGCN_STACK_MAX_WIDTH && (F & (F - 1)) == 0;
+}
 
 static inline int64_t igcn_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

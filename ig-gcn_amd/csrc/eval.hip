@@ -8,7 +8,6 @@
 
 #define EVAL_THREADS 256
 #define EVAL_MAX_CLASSES 16             // confusion matrix in LDS
-#define EVAL_MAX_ROWS 65536             // pairwise AUC: n_pos * n_neg comparisons, one workgroup per 256 rows
 
 // =================================================================================================
 // igcn_eval_collect: one workgroup.  Every thread reads the cursor before the barrier; thread 0 advances it after the
@@ -258,7 +257,9 @@ k_eval_final(int64_t n, int C, int NR, const int64_t* __restrict__ pred, const i
 extern "C" int igcn_eval_metrics(int64_t n, int C, int NR, const float* logp, const int64_t* pred, const int64_t* y,
                                  const float* reg, const float* clin, const int64_t* state, const double* loss_sum,
                                  int64_t* parts, double* out, void* stream) {
-  IGCN_REQUIRE(n >= 1 && n <= EVAL_MAX_ROWS, "eval_metrics: %lld rows outside [1, %d]", (long long)n, EVAL_MAX_ROWS);
+  // (pairwise AUC: n_pos * n_neg comparisons, one workgroup per 256 rows)
+  IGCN_REQUIRE(n >= 1 && n <= IGCN_EVAL_MAX_ROWS, "eval_metrics: %lld rows outside [1, %d]", (long long)n,
+               IGCN_EVAL_MAX_ROWS);
   IGCN_REQUIRE(C >= 1 && C <= EVAL_MAX_CLASSES && NR >= 0, "eval_metrics: C=%d (1..%d), NR=%d", C, EVAL_MAX_CLASSES, NR);
   IGCN_REQUIRE(logp && pred && y && state && loss_sum && parts && out && (NR == 0 || (reg && clin)),
                "eval_metrics: null pointer");

@@ -25,12 +25,11 @@
 #include "gcn_lds.h"
 
 #define GT_T 256
-#define GT_MAXL 4
-#define GT_MAXH0 8
 #define GT_SLOPE 0.2f
 
 struct GtParams {
-  const float* p[6 * GT_MAXL];   // per layer: W [F, Fin] | bias [F] | att_src [F] | att_dst [F] | lin_edge [F] | att_edge [F]
+  // per layer: W [F, Fin] | bias [F] | att_src [F] | att_dst [F] | lin_edge [F] | att_edge [F]
+  const float* p[6 * IGCN_STACK_MAX_LAYERS];
 };
 
 // offset of layer l's block in the flat parameter list (and in a gradient row): W | b | att_src | att_dst | le | ae
@@ -271,7 +270,7 @@ k_gat_stack_fwd(int R, int Emax, int H0, int L, const float* __restrict__ x_in, 
 static int gt_alpha_tile(int R, int Emax, int H0, int F, int L) {
   const size_t base = (size_t)gt_layout(R, Emax, H0, F, L, 0).total * 4;
   for (int tc = 64; tc >= 1; tc >>= 1)
-    if (base + (size_t)R * tc * 4 <= 150 * 1024) return tc;
+    if (base + (size_t)R * tc * 4 <= IGCN_LDS_BUDGET_BYTES) return tc;
   return 0;
 }
 
@@ -528,12 +527,16 @@ k_gat_stack_bwd(int R, int Emax, int H0, int L, const float* __restrict__ x_in, 
   for (int e = tid; e < P; e += GT_T) dpar_partial[(int64_t)blockIdx.x * P + e] = prow[e];
 }
 
+// The launch switches below instantiate F = 4, 8, 16 and 32 only (default: 32): igcn_stack_width_ok must admit no other
+static_assert(IGCN_STACK_MIN_WIDTH == 4 && IGCN_STACK_MAX_WIDTH == 32,
+              "a new layer width needs a kernel instance and a case in every launch switch of this file");
 static int gt_check(const char* nm, int64_t n_graphs, int R, int max_edges, int H0, int F, int L, int backward) {
   IGCN_REQUIRE(n_graphs > 0 && R > 0 && max_edges >= 0, "%s: bad sizes", nm);
-  if (!(F == 4 || F == 8 || F == 16 || F == 32) || H0 < 1 || H0 > GT_MAXH0 || L < 1 || L > GT_MAXL ||
-      igcn_gat_stack_lds_bytes(R, max_edges, H0, F, L, backward) > 150 * 1024) {
-    igcn_set_error("%s: needs F in {4, 8, 16, 32}, 1 <= H0 <= %d, 1 <= L <= %d and a graph that fits 150 KB of LDS "
-                   "(R=%d, E<=%d, H0=%d, F=%d, L=%d)", nm, GT_MAXH0, GT_MAXL, R, max_edges, H0, F, L);
+  if (!igcn_stack_width_ok(F) || H0 < 1 || H0 > IGCN_MAX_H0 || L < 1 || L > IGCN_STACK_MAX_LAYERS ||
+      igcn_gat_stack_lds_bytes(R, max_edges, H0, F, L, backward) > IGCN_LDS_BUDGET_BYTES) {
+    igcn_set_error("%s: needs F in {4, 8, 16, 32}, 1 <= H0 <= %d, 1 <= L <= %d and a graph that fits %d KB of LDS "
+                   "(R=%d, E<=%d, H0=%d, F=%d, L=%d)", nm, IGCN_MAX_H0, IGCN_STACK_MAX_LAYERS, IGCN_LDS_BUDGET_BYTES / 1024,
+                   R, max_edges, H0, F, L);
     return IGCN_ERR_UNSUPPORTED;
   }
   return IGCN_OK;
@@ -573,8 +576,8 @@ extern "C" int igcn_gat_stack_fwd(int64_t n_graphs, int R, int max_edges, int H0
 }
 
 extern "C" int igcn_gat_stack_alpha_tile(int R, int max_edges, int H0, int F, int L) {
-  if (R <= 0 || max_edges < 0 || !(F == 4 || F == 8 || F == 16 || F == 32) || H0 < 1 || H0 > GT_MAXH0 || L < 1 ||
-      L > GT_MAXL)
+  if (R <= 0 || max_edges < 0 || !igcn_stack_width_ok(F) || H0 < 1 || H0 > IGCN_MAX_H0 || L < 1 ||
+      L > IGCN_STACK_MAX_LAYERS)
     return 0;
   return gt_alpha_tile(R, max_edges, H0, F, L);
 }
@@ -587,8 +590,8 @@ extern "C" int igcn_gat_stack_alpha(int64_t n_graphs, int R, int max_edges, int 
   if (rc) return rc;
   const int tc = gt_alpha_tile(R, max_edges, H0, F, L);
   if (tc == 0) {
-    igcn_set_error("gat_stack_alpha: no column of the [R, R] map fits beside the stack in 150 KB of LDS (R=%d, E<=%d, "
-                   "H0=%d, F=%d, L=%d)", R, max_edges, H0, F, L);
+    igcn_set_error("gat_stack_alpha: no column of the [R, R] map fits beside the stack in %d KB of LDS (R=%d, E<=%d, "
+                   "H0=%d, F=%d, L=%d)", IGCN_LDS_BUDGET_BYTES / 1024, R, max_edges, H0, F, L);
     return IGCN_ERR_UNSUPPORTED;
   }
   IGCN_REQUIRE(x_in && ew_in && src32 && dst32 && tgt_ptr && tgt_perm && params && G, "gat_stack_alpha: null argument");

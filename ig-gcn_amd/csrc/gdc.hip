@@ -494,7 +494,7 @@ static size_t gdc_lds_bytes(int R) {
 
 extern "C" int igcn_gdc_topk_max_rois(void) {
   int r = 8;
-  while (r < 128 && gdc_lds_bytes(r + 1) <= 160 * 1024) ++r;       // (128: two row slices of 64 register rows)
+  while (r < 128 && gdc_lds_bytes(r + 1) <= IGCN_LDS_MAX_BYTES) ++r;  // (128: two row slices of 64 register rows)
   return r;
 }
 
@@ -508,7 +508,7 @@ extern "C" int igcn_gdc_max_rois(int kernel) {
   if (kernel == IGCN_GDC_PPR) return igcn_gdc_topk_max_rois();
   if (kernel != IGCN_GDC_HEAT) return 0;
   int r = 16;
-  while (r < 128 && gdc_heat_lds_bytes(r + 1) <= 160 * 1024) ++r;  // (128: the selection's row bit set)
+  while (r < 128 && gdc_heat_lds_bytes(r + 1) <= IGCN_LDS_MAX_BYTES) ++r;  // (128: the selection's row bit set)
   return r;
 }
 

@@ -298,7 +298,7 @@ static SpmmRoute spmm_list_route(int C, int n_out, int L, int64_t nnz, int sum_c
   const bool longlists = nnz > (int64_t)8 * n_out;
   const size_t vec_bytes = spmm_long_lds_bytes(C, L, nnz, sum_c);
   const int64_t row_floats = sum_c ? (int64_t)C * L : L;
-  if (!spmm_no_lds() && longlists && vec_bytes <= 150 * 1024) return {IGCN_SPMM_LONG_LDS, 1, vec_bytes};
+  if (!spmm_no_lds() && longlists && vec_bytes <= IGCN_LDS_BUDGET_BYTES) return {IGCN_SPMM_LONG_LDS, 1, vec_bytes};
   if (!spmm_no_lds() && !longlists && row_floats <= 1024)
     return {IGCN_SPMM_ROWS_TILED, SPMM_SB, (size_t)SPMM_SB * row_floats * sizeof(float)};
   return {longlists ? IGCN_SPMM_WAVE : IGCN_SPMM_THREAD, 1, 0};
@@ -1657,7 +1657,7 @@ static bool go_attn_force_cm(void) { return igcn_opt(IGCN_OPT_GO_ATTN_CM); }
 static bool go_ln_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 static bool go_attn_bwd_in_lds(int N, int fin, int fout) {
   const int TT = go_abl_threads(N, fin, fout);
-  return !go_attn_force_cm() && go_abl_lds_bytes(N, fin, fout, TT) <= 160 * 1024 && N <= TT * GO_ABL_MAXIT;
+  return !go_attn_force_cm() && go_abl_lds_bytes(N, fin, fout, TT) <= IGCN_LDS_MAX_BYTES && N <= TT * GO_ABL_MAXIT;
 }
 // 1 when igcn_go_attn_ln_bwd runs for these sizes (the LDS-resident kernel takes the layer and LnFuse's shape
 // preconditions hold); otherwise call igcn_nodes_ln_bwd* and igcn_go_attn_bwd
@@ -2233,7 +2233,7 @@ extern "C" size_t igcn_go_decode_bwd_scratch_floats(int B, int Nin, int fin, int
 
 static bool go_decode_bwd_in_lds(int Nin, int Nout, int fin, int fout) {
   const int TT = go_dbl_threads(Nin, Nout, fin, fout);
-  return !go_attn_force_cm() && go_dbl_lds_bytes(Nout, fin, fout, TT) <= 160 * 1024 && 2 * fout >= 4;
+  return !go_attn_force_cm() && go_dbl_lds_bytes(Nout, fin, fout, TT) <= IGCN_LDS_MAX_BYTES && 2 * fout >= 4;
 }
 // 1 when igcn_go_decode_ln_bwd runs for these sizes (see igcn_go_attn_ln_fused_ok; the decoder's LayerNorm has no pooling)
 extern "C" int igcn_go_decode_ln_fused_ok(int Nin, int Nout, int fin, int fout) {

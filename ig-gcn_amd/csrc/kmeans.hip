@@ -15,16 +15,13 @@
 //   igcn_kmeanspp_step   one step of _kmeans_plusplus: t candidates by an fp64 inclusive scan of the closest distances
 //                        (stable_cumsum) and a left search of u_c * potential, each candidate's new potential, the best
 //                        one kept (equal potentials: the first), the closest distances updated.
-// No atomics, one writer per element, fixed orders: the same bits every run.  N <= 65536, d <= 1024, k <= 16.
+// No atomics, one writer per element, fixed orders: the same bits every run.  N <= 65536, d <= 1024, k <= 16
+// (IGCN_KMEANS_MAX_N, IGCN_KMEANS_MAX_D, IGCN_KMEANS_MAX_K).
 #include "common.h"
 
 #define KM_T 256
 #define KM_PTS 64               /* points per workgroup of the assignment */
-#define KM_MAX_N 65536
-#define KM_MAX_D 1024
-#define KM_MAX_K 16
 #define KMPP_T 1024
-#define KMPP_MAX_TRIALS 8
 
 __global__ void __launch_bounds__(KM_T)
 k_kmeans_assign(int N, int d, int k, const float* __restrict__ X, const float* __restrict__ centers,
@@ -120,7 +117,7 @@ __global__ void __launch_bounds__(KM_T)
 k_kmeans_update(int N, int d, int k, const float* __restrict__ X, const int64_t* __restrict__ labels,
                 const float* __restrict__ mind, const int64_t* __restrict__ counts, double* __restrict__ sums,
                 float* __restrict__ centers, double* __restrict__ stats) {
-  __shared__ long long s_cnt[KM_MAX_K];
+  __shared__ long long s_cnt[IGCN_KMEANS_MAX_K];
   __shared__ unsigned long long s_key[KM_T];
   __shared__ double s_red[KM_T];
   __shared__ int s_big;
@@ -193,9 +190,9 @@ __global__ void __launch_bounds__(KMPP_T)
 k_kmeanspp_step(int N, int d, int t, const float* __restrict__ X, const double* __restrict__ u,
                 float* __restrict__ closest, double* __restrict__ pot, int64_t* __restrict__ chosen) {
   __shared__ double s_sum[KMPP_T];
-  __shared__ double s_pot[KMPP_MAX_TRIALS];
+  __shared__ double s_pot[IGCN_KMEANSPP_MAX_TRIALS];
   __shared__ int s_cnt[KMPP_T];
-  __shared__ int s_id[KMPP_MAX_TRIALS];
+  __shared__ int s_id[IGCN_KMEANSPP_MAX_TRIALS];
   __shared__ int s_best;
   const int tid = threadIdx.x, chunk = (N + KMPP_T - 1) / KMPP_T;
   const int lo = min(N, tid * chunk), hi = min(N, lo + chunk);
@@ -274,7 +271,7 @@ k_kmeanspp_step(int N, int d, int t, const float* __restrict__ X, const double* 
 }
 
 static bool km_sizes_ok(int64_t N, int d, int k) {
-  return N >= 1 && N <= KM_MAX_N && d >= 1 && d <= KM_MAX_D && k >= 1 && k <= KM_MAX_K;
+  return N >= 1 && N <= IGCN_KMEANS_MAX_N && d >= 1 && d <= IGCN_KMEANS_MAX_D && k >= 1 && k <= IGCN_KMEANS_MAX_K;
 }
 
 // in 4-byte words: part_inertia [nblk] fp64, part_sums [nblk, k, d] fp64, part_cnt [nblk, k], part_chg [nblk]
@@ -288,7 +285,7 @@ extern "C" int igcn_kmeans_assign(int64_t N, int d, int k, const float* X, const
                                   float* mind, int64_t* counts, double* sums, double* stats, float* scratch,
                                   void* stream) {
   IGCN_REQUIRE(km_sizes_ok(N, d, k), "kmeans_assign: N=%lld d=%d k=%d outside 1 <= N <= %d, 1 <= d <= %d, 1 <= k <= %d",
-               (long long)N, d, k, KM_MAX_N, KM_MAX_D, KM_MAX_K);
+               (long long)N, d, k, IGCN_KMEANS_MAX_N, IGCN_KMEANS_MAX_D, IGCN_KMEANS_MAX_K);
   IGCN_REQUIRE(X && centers && labels && mind && stats && scratch, "kmeans_assign: a NULL argument");
   IGCN_REQUIRE((counts != nullptr) == (sums != nullptr), "kmeans_assign: counts and sums come together");
   IGCN_REQUIRE(((uintptr_t)scratch & 7) == 0, "kmeans_assign: the scratch is not 8-byte aligned");
@@ -310,7 +307,7 @@ extern "C" int igcn_kmeans_assign(int64_t N, int d, int k, const float* X, const
 extern "C" int igcn_kmeans_update(int64_t N, int d, int k, const float* X, const int64_t* labels, const float* mind,
                                   const int64_t* counts, double* sums, float* centers, double* stats, void* stream) {
   IGCN_REQUIRE(km_sizes_ok(N, d, k), "kmeans_update: N=%lld d=%d k=%d outside 1 <= N <= %d, 1 <= d <= %d, 1 <= k <= %d",
-               (long long)N, d, k, KM_MAX_N, KM_MAX_D, KM_MAX_K);
+               (long long)N, d, k, IGCN_KMEANS_MAX_N, IGCN_KMEANS_MAX_D, IGCN_KMEANS_MAX_K);
   IGCN_REQUIRE(X && labels && mind && counts && sums && centers && stats, "kmeans_update: a NULL argument");
   hipLaunchKernelGGL(k_kmeans_update, dim3(1), dim3(KM_T), 0, (hipStream_t)stream, (int)N, d, k, X, labels, mind, counts,
                      sums, centers, stats);
@@ -321,8 +318,9 @@ extern "C" int igcn_kmeans_update(int64_t N, int d, int k, const float* X, const
 extern "C" int igcn_kmeanspp_step(int64_t N, int d, int t, const float* X, const double* u, float* closest, double* pot,
                                   int64_t* chosen, void* stream) {
   IGCN_REQUIRE(km_sizes_ok(N, d, 1), "kmeanspp_step: N=%lld d=%d outside 1 <= N <= %d, 1 <= d <= %d", (long long)N, d,
-               KM_MAX_N, KM_MAX_D);
-  IGCN_REQUIRE(t >= 1 && t <= KMPP_MAX_TRIALS, "kmeanspp_step: t=%d outside 1..%d", t, KMPP_MAX_TRIALS);
+               IGCN_KMEANS_MAX_N, IGCN_KMEANS_MAX_D);
+  IGCN_REQUIRE(t >= 1 && t <= IGCN_KMEANSPP_MAX_TRIALS, "kmeanspp_step: t=%d outside 1..%d", t,
+               IGCN_KMEANSPP_MAX_TRIALS);
   IGCN_REQUIRE(X && u && closest && pot && chosen, "kmeanspp_step: a NULL argument");
   hipLaunchKernelGGL(k_kmeanspp_step, dim3(1), dim3(KMPP_T), 0, (hipStream_t)stream, (int)N, d, t, X, u, closest, pot,
                      chosen);

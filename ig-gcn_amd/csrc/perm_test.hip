@@ -26,11 +26,6 @@
 #define PT_BK 32                                       // subjects per step: one v_mfma_f32_16x16x32_bf16 deep
 #define PT_LD (PT_BK + 8)                              // LDS row: 32 bf16 + 8 pad (80 B), as k_gemm_bf16 (csrc/gemm.hip)
 #define PT_T 256
-#define PT_MIN_S 4
-#define PT_MAX_S 4096
-#define PT_MAX_E (1 << 20)
-#define PT_MAX_P 65536
-#define PT_MAX_G_ROWS 8                                // g is written for P <= 8 (the observed pass: P = 1)
 
 typedef __bf16 pt_bf16x8 __attribute__((ext_vector_type(8)));
 typedef float pt_f32x4 __attribute__((ext_vector_type(4)));
@@ -197,7 +192,7 @@ k_perm_maxsum(int P, int S, int E, int Sp, const uint8_t* __restrict__ member, i
 
   // ---- epilogue: G stays in registers ----
   const int prow = m0 + w * 32 + lg * 4;                // + 16 a + r
-  if (g_obs == nullptr) {                               // the observed pass: G itself, P <= PT_MAX_G_ROWS
+  if (g_obs == nullptr) {                               // the observed pass: G itself, P <= IGCN_PERM_MAX_G_ROWS
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -273,7 +268,9 @@ k_perm_fold_cnt(int E, int tiles_p, const int32_t* __restrict__ pcnt, int32_t* _
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------
-static bool pt_sizes_ok(int S, int E) { return S >= PT_MIN_S && S <= PT_MAX_S && E >= 1 && E <= PT_MAX_E; }
+static bool pt_sizes_ok(int S, int E) {
+  return S >= IGCN_PERM_MIN_S && S <= IGCN_PERM_MAX_S && E >= 1 && E <= IGCN_PERM_MAX_E;
+}
 
 extern "C" size_t igcn_perm_planes_bytes(int S, int E) {
   if (!pt_sizes_ok(S, E)) return 0;
@@ -282,8 +279,8 @@ extern "C" size_t igcn_perm_planes_bytes(int S, int E) {
 
 extern "C" int igcn_perm_plane_dims(int S, int E, int* dims) {
   IGCN_REQUIRE(dims != nullptr, "perm_plane_dims: dims is null");
-  IGCN_REQUIRE(pt_sizes_ok(S, E), "perm_plane_dims: S=%d outside [%d,%d] or E=%d outside [1,%d]", S, PT_MIN_S, PT_MAX_S,
-               E, PT_MAX_E);
+  IGCN_REQUIRE(pt_sizes_ok(S, E), "perm_plane_dims: S=%d outside [%d,%d] or E=%d outside [1,%d]", S, IGCN_PERM_MIN_S,
+               IGCN_PERM_MAX_S, E, IGCN_PERM_MAX_E);
   dims[0] = pt_ep(E);
   dims[1] = pt_sp(S);
   return IGCN_OK;
@@ -292,8 +289,9 @@ extern "C" int igcn_perm_plane_dims(int S, int E, int* dims) {
 extern "C" int igcn_perm_prepare(int64_t S_all, int S, int E, const float* x, const int64_t* rows, int standardize,
                                  double* mean, double* sd, uint8_t* constant, void* planes, void* stream) {
   const char* who = "perm_prepare";
-  IGCN_REQUIRE(S >= PT_MIN_S && S <= PT_MAX_S, "%s: S=%d subjects outside [%d,%d]", who, S, PT_MIN_S, PT_MAX_S);
-  IGCN_REQUIRE(E >= 1 && E <= PT_MAX_E, "%s: E=%d map entries outside [1,%d]", who, E, PT_MAX_E);
+  IGCN_REQUIRE(S >= IGCN_PERM_MIN_S && S <= IGCN_PERM_MAX_S, "%s: S=%d subjects outside [%d,%d]", who, S, IGCN_PERM_MIN_S,
+               IGCN_PERM_MAX_S);
+  IGCN_REQUIRE(E >= 1 && E <= IGCN_PERM_MAX_E, "%s: E=%d map entries outside [1,%d]", who, E, IGCN_PERM_MAX_E);
   IGCN_REQUIRE(S_all >= 1, "%s: S_all=%lld rows in the table", who, (long long)S_all);
   IGCN_REQUIRE(x && rows && mean && sd && constant && planes, "%s: a null buffer", who);
   IGCN_REQUIRE(((uintptr_t)planes & 15) == 0, "%s: the planes must be 16-byte aligned", who);
@@ -305,7 +303,7 @@ extern "C" int igcn_perm_prepare(int64_t S_all, int S, int E, const float* x, co
 }
 
 extern "C" size_t igcn_perm_maxsum_scratch_bytes(int P, int E) {
-  if (P < 1 || P > PT_MAX_P || E < 1 || E > PT_MAX_E) return 0;
+  if (P < 1 || P > IGCN_PERM_MAX_P || E < 1 || E > IGCN_PERM_MAX_E) return 0;
   const size_t tiles_p = (P + PT_BM - 1) / PT_BM, tiles_e = (E + PT_BN - 1) / PT_BN;
   return (size_t)P * tiles_e * sizeof(float) + tiles_p * (size_t)E * sizeof(int32_t);
 }
@@ -314,16 +312,18 @@ extern "C" int igcn_perm_maxsum(int P, int S, int E, const uint8_t* member, int6
                                 const float* g_obs, float* maxabs, int32_t* exceed, float* g, void* scratch,
                                 size_t scratch_bytes, void* stream) {
   const char* who = "perm_maxsum";
-  IGCN_REQUIRE(S >= PT_MIN_S && S <= PT_MAX_S, "%s: S=%d subjects outside [%d,%d]", who, S, PT_MIN_S, PT_MAX_S);
-  IGCN_REQUIRE(E >= 1 && E <= PT_MAX_E, "%s: E=%d map entries outside [1,%d]", who, E, PT_MAX_E);
-  IGCN_REQUIRE(P >= 1 && P <= PT_MAX_P, "%s: P=%d relabellings in one launch outside [1,%d]", who, P, PT_MAX_P);
+  IGCN_REQUIRE(S >= IGCN_PERM_MIN_S && S <= IGCN_PERM_MAX_S, "%s: S=%d subjects outside [%d,%d]", who, S, IGCN_PERM_MIN_S,
+               IGCN_PERM_MAX_S);
+  IGCN_REQUIRE(E >= 1 && E <= IGCN_PERM_MAX_E, "%s: E=%d map entries outside [1,%d]", who, E, IGCN_PERM_MAX_E);
+  IGCN_REQUIRE(P >= 1 && P <= IGCN_PERM_MAX_P, "%s: P=%d relabellings in one launch outside [1,%d]", who, P,
+               IGCN_PERM_MAX_P);
   IGCN_REQUIRE(ldm >= S, "%s: member row stride %lld below S=%d", who, (long long)ldm, S);
   IGCN_REQUIRE(member && planes && maxabs && scratch, "%s: a null buffer", who);
   if (g_obs) {
     IGCN_REQUIRE(exceed != nullptr, "%s: g_obs without an exceed buffer", who);
   } else {
-    IGCN_REQUIRE(g != nullptr && P <= PT_MAX_G_ROWS, "%s: without g_obs the call writes g itself, for P <= %d (P=%d)", who,
-                 PT_MAX_G_ROWS, P);
+    IGCN_REQUIRE(g != nullptr && P <= IGCN_PERM_MAX_G_ROWS, "%s: without g_obs the call writes g itself, for P <= %d (P=%d)",
+                 who, IGCN_PERM_MAX_G_ROWS, P);
   }
   IGCN_REQUIRE(((uintptr_t)planes & 15) == 0 && ((uintptr_t)scratch & 15) == 0,
                "%s: the planes and the scratch must be 16-byte aligned", who);

@@ -489,8 +489,6 @@ extern "C" int igcn_graph_plan_replicate(int64_t n_nodes, int64_t n_edges, int c
 // whole stable grouping fits in LDS: integer histogram -> scan -> each node's thread walks the graph's edges in
 // stored order and appends its own (so the order inside a group is the stored order: bit-identical to a stable
 // sort), for targets and for sources.  One launch replaces two device-wide radix sorts (~14 launches).
-#define SEG_MAXE 4096
-#define SEG_MAXN 1024
 // `rep`: the plan of `copies` disjoint copies of the batch (what igcn_graph_plan_replicate derives from the plan: the
 // two passes of a train step as one block-diagonal problem), written by the same workgroups — one launch less per step.
 struct PlanRep { int copies; int32_t *src32, *dst32, *tgt_ptr, *tgt_perm, *src_ptr, *src_perm, *loop_edge; };
@@ -501,14 +499,14 @@ plan_segmented_body(const int g, int64_t n_nodes, int64_t n_edges, int n_graphs,
                     int32_t* __restrict__ tgt_perm, int32_t* __restrict__ src_ptr, int32_t* __restrict__ src_perm,
                     int32_t* __restrict__ loop_edge, int32_t* __restrict__ status, const PlanRep& rep) {
   const int32_t N32 = (int32_t)n_nodes, E32 = (int32_t)n_edges;
-  __shared__ int16_t ls[SEG_MAXE], ld[SEG_MAXE];        // local (graph-relative) endpoints
-  __shared__ int32_t ct[SEG_MAXN + 1], cs[SEG_MAXN + 1], lp[SEG_MAXN];
+  __shared__ int16_t ls[IGCN_SEG_MAX_EDGES], ld[IGCN_SEG_MAX_EDGES];        // local (graph-relative) endpoints
+  __shared__ int32_t ct[IGCN_SEG_MAX_NODES + 1], cs[IGCN_SEG_MAX_NODES + 1], lp[IGCN_SEG_MAX_NODES];
   const int tid = threadIdx.x;
   const int64_t nb = node_ptr[g], eb = edge_ptr[g];
   const int nn = (int)(node_ptr[g + 1] - nb), ne = (int)(edge_ptr[g + 1] - eb);
   // host checked the maxima; the offsets themselves come from device memory (a loader may have handed over garbage):
   // refuse anything that does not lie inside the batch, don't read or write out of bounds
-  if (nn > SEG_MAXN || ne > SEG_MAXE || nn < 0 || ne < 0 || nb < 0 || eb < 0 || nb + nn > n_nodes ||
+  if (nn > IGCN_SEG_MAX_NODES || ne > IGCN_SEG_MAX_EDGES || nn < 0 || ne < 0 || nb < 0 || eb < 0 || nb + nn > n_nodes ||
       eb + ne > n_edges) {
     if (tid == 0) atomicExch(status, 1);
     return;
@@ -637,9 +635,9 @@ static int plan_build_segmented(int64_t n_nodes, int64_t n_edges, int n_graphs, 
   IGCN_REQUIRE(rep.copies >= 0 && n_nodes * (rep.copies > 0 ? rep.copies : 1) < ((int64_t)1 << 31) &&
                    n_edges * (rep.copies > 0 ? rep.copies : 1) < ((int64_t)1 << 31),
                "graph_plan_build_segmented: replica sizes out of int32 range");
-  if (max_nodes_per_graph > SEG_MAXN || max_edges_per_graph > SEG_MAXE) {
+  if (max_nodes_per_graph > IGCN_SEG_MAX_NODES || max_edges_per_graph > IGCN_SEG_MAX_EDGES) {
     igcn_set_error("graph_plan_build_segmented: graphs too large for the LDS path (max %d nodes / %d edges per graph)",
-                   SEG_MAXN, SEG_MAXE);
+                   IGCN_SEG_MAX_NODES, IGCN_SEG_MAX_EDGES);
     return IGCN_ERR_UNSUPPORTED;
   }
   DropJob job;

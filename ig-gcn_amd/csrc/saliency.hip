@@ -13,7 +13,7 @@
 // maximum is a fixed tree, and every element of attr / roi is stored exactly once, zeros included: one writer per
 // element, no atomics, the same bits every run.  x, base and every dx[m] are read once, consecutive lanes on
 // consecutive elements.  LDS budget: 34 KB static (8192 + 512 floats + the reduction scratch), so R <= 512,
-// R * H0 <= 8192 and 1 <= M <= 4096 — IGCN_ERR_UNSUPPORTED outside, nothing is truncated.  R = 54, H0 = 1 is the SNP
+// R * H0 <= 8192 and 1 <= M <= 4096 (IGCN_SALIENCY_MAX_ROIS, _MAX_ELEMS, _MAX_STEPS) — IGCN_ERR_UNSUPPORTED outside, nothing is truncated.  R = 54, H0 = 1 is the SNP
 // vector.
 //
 // k_grad_cam — the Grad-CAM map of the taps:
@@ -24,14 +24,11 @@
 // wave per row — lane l adds columns l, l + 64, l + 128 in order, then a fixed xor tree.  LDS budget: 4 KB static
 // (alpha, its partials, the R cam values, the reduction scratch): neither tile is staged — grads and acts are each
 // streamed from global memory exactly once, so nothing is re-read however large R * K is.  Bounds: 1 <= R <= 512 (the
-// configs[4] size), 1 <= K <= 160; IGCN_ERR_UNSUPPORTED outside.  Every element of cam / alpha is stored exactly once.
+// configs[4] size), 1 <= K <= 160 (IGCN_GRAD_CAM_MAX_WIDTH); IGCN_ERR_UNSUPPORTED outside.  Every element of cam / alpha is
+// stored exactly once.
 #include "common.h"
 
 #define SAL_T 256
-#define SAL_MAX_R 512
-#define SAL_MAX_ELEMS 8192
-#define SAL_MAX_M 4096
-#define CAM_MAX_K 160
 
 // Block-wide maximum of non-negative values (blockDim.x = SAL_T); `red` holds >= 4 floats.  Result in all threads.
 __device__ __forceinline__ float sal_block_max(float v, float* red) {
@@ -50,8 +47,8 @@ __global__ void __launch_bounds__(SAL_T)
 k_saliency_maps(int R, int H0, int M, int64_t total, const float* __restrict__ x, const float* __restrict__ base,
                 int base_mode, const float* __restrict__ dx, int norm, float* __restrict__ attr,
                 float* __restrict__ roi) {
-  __shared__ float s_attr[SAL_MAX_ELEMS];
-  __shared__ float s_roi[SAL_MAX_R];
+  __shared__ float s_attr[IGCN_SALIENCY_MAX_ELEMS];
+  __shared__ float s_roi[IGCN_SALIENCY_MAX_ROIS];
   __shared__ float s_red[SAL_T / 64];
   const int tid = threadIdx.x;
   const int n = R * H0;                                       // elements of one subject
@@ -84,9 +81,9 @@ k_saliency_maps(int R, int H0, int M, int64_t total, const float* __restrict__ x
 extern "C" int igcn_saliency_maps(int B, int R, int H0, int M, const float* x, const float* base, int base_per_subject,
                                   const float* dx, int norm, float* attr, float* roi, void* stream) {
   IGCN_REQUIRE(B > 0 && R > 0 && H0 > 0 && M > 0, "saliency_maps: B=%d R=%d H0=%d M=%d", B, R, H0, M);
-  if (R > SAL_MAX_R || (int64_t)R * H0 > SAL_MAX_ELEMS || M > SAL_MAX_M) {
+  if (R > IGCN_SALIENCY_MAX_ROIS || (int64_t)R * H0 > IGCN_SALIENCY_MAX_ELEMS || M > IGCN_SALIENCY_MAX_STEPS) {
     igcn_set_error("saliency_maps: R=%d H0=%d M=%d: needs R <= %d, R * H0 <= %d (the subject's tile in LDS) and M <= %d",
-                   R, H0, M, SAL_MAX_R, SAL_MAX_ELEMS, SAL_MAX_M);
+                   R, H0, M, IGCN_SALIENCY_MAX_ROIS, IGCN_SALIENCY_MAX_ELEMS, IGCN_SALIENCY_MAX_STEPS);
     return IGCN_ERR_UNSUPPORTED;
   }
   IGCN_REQUIRE(x && dx && attr && roi, "saliency_maps: null argument");
@@ -103,8 +100,8 @@ __global__ void __launch_bounds__(SAL_T)
 k_grad_cam(int R, int K, const float* __restrict__ acts, const float* __restrict__ grads, int norm,
            float* __restrict__ cam, float* __restrict__ alpha) {
   __shared__ float s_part[SAL_T];                             // [P][K] partial column sums, P * K <= 256
-  __shared__ float s_alpha[CAM_MAX_K];
-  __shared__ float s_cam[SAL_MAX_R];
+  __shared__ float s_alpha[IGCN_GRAD_CAM_MAX_WIDTH];
+  __shared__ float s_cam[IGCN_SALIENCY_MAX_ROIS];
   __shared__ float s_red[SAL_T / 64];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int64_t off = (int64_t)blockIdx.x * R * K;
@@ -145,8 +142,9 @@ k_grad_cam(int R, int K, const float* __restrict__ acts, const float* __restrict
 extern "C" int igcn_grad_cam(int B, int R, int K, const float* acts, const float* grads, int norm, float* cam,
                              float* alpha, void* stream) {
   IGCN_REQUIRE(B > 0 && R > 0 && K > 0, "grad_cam: B=%d R=%d K=%d", B, R, K);
-  if (R > SAL_MAX_R || K > CAM_MAX_K) {
-    igcn_set_error("grad_cam: R=%d K=%d: needs R <= %d and K <= %d", R, K, SAL_MAX_R, CAM_MAX_K);
+  if (R > IGCN_SALIENCY_MAX_ROIS || K > IGCN_GRAD_CAM_MAX_WIDTH) {
+    igcn_set_error("grad_cam: R=%d K=%d: needs R <= %d and K <= %d", R, K, IGCN_SALIENCY_MAX_ROIS,
+                   IGCN_GRAD_CAM_MAX_WIDTH);
     return IGCN_ERR_UNSUPPORTED;
   }
   IGCN_REQUIRE(acts && grads && cam && alpha, "grad_cam: null argument");

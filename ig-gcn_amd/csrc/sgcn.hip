@@ -3,8 +3,6 @@
 // sums run in the same order as the reference's sequential scatter_add.
 #include "common.h"
 
-#define MAX_H0 8
-
 // =================================================================================================
 // Long edge lists (dense graphs: hundreds of edges per node): per-node sums over a list reached through a permutation
 // (tgt_perm / src_perm) gather 4-byte values at the list's stride — one 64-byte sector per value.  In a dense or
@@ -167,7 +165,7 @@ k_edge_mask_bwd_nodes_tiled(int64_t n_nodes, int rois, int h0, const float* __re
                             float inv_ne) {
   __shared__ int32_t tiles[TL_WAVES][TL_NODES][TL_POS + 1];
   __shared__ float red[TL_WAVES][TL_NODES];
-  __shared__ float pbred[TL_NODES][2 * MAX_H0];
+  __shared__ float pbred[TL_NODES][2 * IGCN_MAX_H0];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t n0 = (int64_t)blockIdx.x * TL_NODES, node = n0 + lane;
   const float gre = rg.greg ? rg.greg[0] * inv_ne : 0.f;
@@ -184,7 +182,7 @@ k_edge_mask_bwd_nodes_tiled(int64_t n_nodes, int rois, int h0, const float* __re
   T = tl_combine(T, red, wave, lane);                   // (its barriers also publish bysrc)
   const float S = bysrc[lane];
   if (wave == 0) {
-    for (int j = 0; j < 2 * MAX_H0; ++j) pbred[lane][j] = 0.f;
+    for (int j = 0; j < 2 * IGCN_MAX_H0; ++j) pbred[lane][j] = 0.f;
     if (node < n_nodes) {
       const int64_t r = (node % rois) * h0;
       for (int h = 0; h < h0; ++h) {
@@ -193,15 +191,15 @@ k_edge_mask_bwd_nodes_tiled(int64_t n_nodes, int rois, int h0, const float* __re
         dx[node * h0 + h] = g * pv + (d_x_plain ? d_x_plain[node * h0 + h] : 0.f);
         gx[node * h0 + h] = g * xv;
         pbred[lane][h] = xv * pv * S;
-        pbred[lane][MAX_H0 + h] = xv * pv * T;
+        pbred[lane][IGCN_MAX_H0 + h] = xv * pv * T;
       }
     }
   }
   __syncthreads();
-  if (threadIdx.x < 2 * MAX_H0) {
+  if (threadIdx.x < 2 * IGCN_MAX_H0) {
     float t = 0.f;
     for (int l = 0; l < TL_NODES; ++l) t += pbred[l][threadIdx.x];
-    pb_partial[(int64_t)blockIdx.x * 2 * MAX_H0 + threadIdx.x] = t;
+    pb_partial[(int64_t)blockIdx.x * 2 * IGCN_MAX_H0 + threadIdx.x] = t;
   }
 }
 
@@ -263,8 +261,8 @@ extern "C" int igcn_edge_mask_fwd(int64_t n_nodes, int64_t n_edges, int rois, in
                                   const float* prob, const float* prob_bias, const float* ew, const int32_t* src32,
                                   const int32_t* dst32, float* xm, float* e, float* ewm, float* x_plain,
                                   float* ew_plain, void* stream) {
-  IGCN_REQUIRE(rois > 0 && h0 > 0 && h0 <= MAX_H0 && n_nodes % rois == 0,
-               "edge_mask_fwd: need n_nodes %% rois == 0 and 0 < h0 <= %d (n_nodes=%lld rois=%d h0=%d)", MAX_H0,
+  IGCN_REQUIRE(rois > 0 && h0 > 0 && h0 <= IGCN_MAX_H0 && n_nodes % rois == 0,
+               "edge_mask_fwd: need n_nodes %% rois == 0 and 0 < h0 <= %d (n_nodes=%lld rois=%d h0=%d)", IGCN_MAX_H0,
                (long long)n_nodes, rois, h0);
   const int64_t n = em_fwd_items(n_nodes, n_edges, h0, 0);
   if (n == 0) return IGCN_OK;
@@ -289,8 +287,8 @@ extern "C" int igcn_edge_mask_fwd_reg(int64_t n_nodes, int64_t n_edges, int rois
                                       float* ew_plain, const float* snps_logits, int n_snps, float l1_x, float ent_x,
                                       float l1_e, float ent_e, float eps, float* reg_partial, const float* snps_feat,
                                       int snps_rows, float* snps_full, void* stream) {
-  IGCN_REQUIRE(rois > 0 && h0 > 0 && h0 <= MAX_H0 && n_nodes % rois == 0 && n_nodes > 0 && n_edges > 0 && reg_partial &&
-                   n_snps >= 0 && (snps_feat == nullptr || (snps_logits && snps_full && snps_rows > 0)),
+  IGCN_REQUIRE(rois > 0 && h0 > 0 && h0 <= IGCN_MAX_H0 && n_nodes % rois == 0 && n_nodes > 0 && n_edges > 0 &&
+                   reg_partial && n_snps >= 0 && (snps_feat == nullptr || (snps_logits && snps_full && snps_rows > 0)),
                "edge_mask_fwd_reg: bad arguments");
   const int ns = snps_logits ? n_snps : 0;
   const int64_t n = em_fwd_items(n_nodes, n_edges, h0, (int64_t)(snps_feat ? snps_rows : 1) * ns);
@@ -323,11 +321,11 @@ k_edge_mask_bwd_nodes(int64_t n_nodes, int rois, int h0, const float* __restrict
                       const int32_t* __restrict__ src_perm, float* __restrict__ dx,
                       float* __restrict__ gx /*[N,h0]*/, float* __restrict__ pb_partial /*[nblk,2h0]*/, EmReg rg,
                       float inv_ne) {
-  __shared__ float red[4 * 2 * MAX_H0];
+  __shared__ float red[4 * 2 * IGCN_MAX_H0];
   const float gre = rg.greg ? rg.greg[0] * inv_ne : 0.f;
-  float acc[2 * MAX_H0];
+  float acc[2 * IGCN_MAX_H0];
 #pragma unroll
-  for (int j = 0; j < 2 * MAX_H0; ++j) acc[j] = 0.f;
+  for (int j = 0; j < 2 * IGCN_MAX_H0; ++j) acc[j] = 0.f;
   const int sub = threadIdx.x % LPN;
   const int64_t i = (int64_t)blockIdx.x * (256 / LPN) + threadIdx.x / LPN;
   if (i < n_nodes) {                               // uniform over the LPN lanes of a node (the wave for LPN=64)
@@ -337,9 +335,9 @@ k_edge_mask_bwd_nodes(int64_t n_nodes, int rois, int h0, const float* __restrict
     const int32_t s0 = src_ptr[i], s1 = src_ptr[i + 1], t0 = tgt_ptr[i], t1 = tgt_ptr[i + 1];
     // the node's own operands ride with the pointer loads (they are not needed before the list sums are done)
     const int64_t r = (i % rois) * h0;
-    float nx[MAX_H0], npv[MAX_H0], ndxm[MAX_H0], ndxp[MAX_H0];
+    float nx[IGCN_MAX_H0], npv[IGCN_MAX_H0], ndxm[IGCN_MAX_H0], ndxp[IGCN_MAX_H0];
 #pragma unroll
-    for (int h = 0; h < MAX_H0; ++h) {
+    for (int h = 0; h < IGCN_MAX_H0; ++h) {
       const bool on = sub == 0 && h < h0;
       nx[h] = on ? x[i * h0 + h] : 0.f;
       npv[h] = on ? prob[r + h] : 0.f;
@@ -369,18 +367,18 @@ k_edge_mask_bwd_nodes(int64_t n_nodes, int rois, int h0, const float* __restrict
     T = group_sum_all<LPN>(T);
     if (sub == 0) {
 #pragma unroll
-      for (int h = 0; h < MAX_H0; ++h)
+      for (int h = 0; h < IGCN_MAX_H0; ++h)
         if (h < h0) {
           const float xv = nx[h], pv = npv[h];
           const float g = ndxm[h] + pb[h] * S + pb[h0 + h] * T;
           dx[i * h0 + h] = g * pv + ndxp[h];                                       // + the plain half of a stacked batch
           gx[i * h0 + h] = g * xv;
           acc[h] += xv * pv * S;
-          acc[MAX_H0 + h] += xv * pv * T;
+          acc[IGCN_MAX_H0 + h] += xv * pv * T;
         }
     }
   }
-  block_reduce_vec<2 * MAX_H0>(acc, red, pb_partial + (int64_t)blockIdx.x * 2 * MAX_H0);
+  block_reduce_vec<2 * IGCN_MAX_H0>(acc, red, pb_partial + (int64_t)blockIdx.x * 2 * IGCN_MAX_H0);
 }
 
 // dprob[r,h] = sum_b gx[(b*rois + r), h]: one block per (roi, feature).  One MORE block sums the node kernel's block
@@ -410,9 +408,9 @@ k_edge_mask_bwd_prob(int64_t n_graphs, int rois, int h0, const float* __restrict
     const int rl = threadIdx.x >> 4, cs = threadIdx.x & 15;
     float t = 0.f;
     if (cs < 2 * h0) {
-      const int col = cs < h0 ? cs : MAX_H0 + (cs - h0);
+      const int col = cs < h0 ? cs : IGCN_MAX_H0 + (cs - h0);
 #pragma unroll 4
-      for (int64_t r = rl; r < nblk; r += 16) t += partial[r * 2 * MAX_H0 + col];
+      for (int64_t r = rl; r < nblk; r += 16) t += partial[r * 2 * IGCN_MAX_H0 + col];
     }
     red[rl * 16 + cs] = t;
     __syncthreads();
@@ -445,7 +443,7 @@ static int em_bwd_impl(int64_t n_nodes, int64_t n_edges, int rois, int h0, const
   const int64_t nblk = tiled ? igcn_cdiv(n_nodes, TL_NODES) : igcn_cdiv(n_nodes, dense ? 4 : 64);
   const float inv_ne = n_edges > 0 ? 1.0f / (float)n_edges : 0.f;
   float* gx = scratch;
-  float* part = scratch + n_nodes * h0;  // [nblk, 2*MAX_H0]
+  float* part = scratch + n_nodes * h0;  // [nblk, 2*IGCN_MAX_H0]
   if (tiled)                                       // dense graphs: lanes own nodes, permutation tiles through LDS
     hipLaunchKernelGGL(k_edge_mask_bwd_nodes_tiled, dim3((unsigned)nblk), dim3(TL_T), 0, st, n_nodes, rois, h0, x, prob,
                        prob_bias, ew, e, d_xm, d_ewm, d_e, d_x_plain, tgt_ptr, tgt_perm, src_ptr, src_perm, dx, gx, part, rg,
@@ -458,7 +456,7 @@ static int em_bwd_impl(int64_t n_nodes, int64_t n_edges, int rois, int h0, const
     hipLaunchKernelGGL(k_edge_mask_bwd_nodes<4>, dim3((unsigned)nblk), dim3(256), 0, st, n_nodes, rois, h0, x, prob,
                        prob_bias, ew, e, d_xm, d_ewm, d_e, d_x_plain, tgt_ptr, tgt_perm, src_ptr, src_perm, dx, gx, part, rg,
                        inv_ne);
-  static_assert(2 * MAX_H0 <= 16, "k_edge_mask_bwd_prob: the bias-gradient block has 16 column slots");
+  static_assert(2 * IGCN_MAX_H0 <= 16, "k_edge_mask_bwd_prob: the bias-gradient block has 16 column slots");
   const bool snps_block = rg.greg && rg.snps && rg.dsnps && rg.n_snps > 0;
   hipLaunchKernelGGL(k_edge_mask_bwd_prob, dim3((unsigned)(rois * h0 + 1 + (snps_block ? rg.n_snps : 0))), dim3(256), 0, st,
                      n_nodes / rois, rois, h0, gx, dprob, nblk, part, dprob_bias, prob, rg);
@@ -472,7 +470,7 @@ extern "C" int igcn_edge_mask_bwd(int64_t n_nodes, int64_t n_edges, int rois, in
                                   const int32_t* tgt_ptr, const int32_t* tgt_perm, const int32_t* src_ptr,
                                   const int32_t* src_perm, float* dx, float* dprob, float* dprob_bias, float* scratch,
                                   void* stream) {
-  IGCN_REQUIRE(rois > 0 && h0 > 0 && h0 <= MAX_H0 && n_nodes % rois == 0, "edge_mask_bwd: bad rois/h0");
+  IGCN_REQUIRE(rois > 0 && h0 > 0 && h0 <= IGCN_MAX_H0 && n_nodes % rois == 0, "edge_mask_bwd: bad rois/h0");
   return em_bwd_impl(n_nodes, n_edges, rois, h0, x, prob, prob_bias, ew, e, d_xm, d_ewm, d_e, d_x_plain, tgt_ptr, tgt_perm,
                      src_ptr, src_perm, dx, dprob, dprob_bias, scratch, EmReg{}, (hipStream_t)stream);
 }
@@ -488,7 +486,8 @@ extern "C" int igcn_edge_mask_bwd_reg(int64_t n_nodes, int64_t n_edges, int rois
                                       float l1_x, float ent_x, float l1_e, float ent_e, float eps, float* dx, float* dprob,
                                       float* dprob_bias, float* dsnps, float* scratch, const float* snps_feat,
                                       int snps_rows, const float* d_snps_full, void* stream) {
-  IGCN_REQUIRE(rois > 0 && h0 > 0 && h0 <= MAX_H0 && n_nodes % rois == 0 && d_reg, "edge_mask_bwd_reg: bad arguments");
+  IGCN_REQUIRE(rois > 0 && h0 > 0 && h0 <= IGCN_MAX_H0 && n_nodes % rois == 0 && d_reg,
+               "edge_mask_bwd_reg: bad arguments");
   const EmReg rg = {d_reg, snps_logits, dsnps, snps_logits ? n_snps : 0, l1_x, ent_x, l1_e, ent_e, eps, snps_feat, nullptr,
                     d_snps_full, snps_feat ? snps_rows : 0};
   return em_bwd_impl(n_nodes, n_edges, rois, h0, x, prob, prob_bias, ew, e, d_xm, d_ewm, d_e, d_x_plain, tgt_ptr, tgt_perm,
@@ -1497,7 +1496,7 @@ extern "C" int igcn_gcn_propagate_bwd(int64_t n_nodes, int64_t n_edges, int F, i
     if (dbias)                                                                                                    \
       hipLaunchKernelGGL((k_colsum_partial_q<FQV>), dim3((unsigned)nblk), dim3(256), 0, st, n_nodes, dout, ld_dout, \
                          scratch);                                                                                 \
-    if (need_dw && 2 * (size_t)R * (4 * FQV + 4) * sizeof(float) <= 150 * 1024) {                                 \
+    if (need_dw && 2 * (size_t)R * (4 * FQV + 4) * sizeof(float) <= IGCN_LDS_BUDGET_BYTES) {                      \
       IGCN_ALLOW_BIG_LDS((k_gcn_propagate_bwd_dw_lds<FQV>));                                                      \
       hipLaunchKernelGGL((k_gcn_propagate_bwd_dw_lds<FQV>), dim3((unsigned)igcn_cdiv(n_edges, DW_CHUNK)),          \
                          dim3(DW_THREADS), 2 * (size_t)R * (4 * FQV + 4) * sizeof(float), st, n_nodes, n_edges, R, \

@@ -23,7 +23,8 @@
 // Six edge passes of 4 B per edge per train step instead of ~30 passes of 4-20 B (sort, replicate, mask, norm, two
 // record streams, four aggregations, three backward walks): DESIGN.md §4.
 //
-// Needs: uniform complete graphs, R % 64 == 0, R <= 1024, F == 16, L <= 4, H0 <= 8 (igcn_dense_sgcn_supported);
+// Needs: uniform complete graphs, R % 64 == 0, R <= 1024, F == 16, L <= 4 (IGCN_STACK_MAX_LAYERS), H0 <= 8
+// (IGCN_MAX_H0) (igcn_dense_sgcn_supported);
 // anything else takes the general kernels (csrc/sgcn.hip).  Summation order: a target's incoming messages are added
 // in matrix-core / tree order, not the reference's sequential scatter order (fp32 rounding ~1e-7, like the LDS-staged
 // aggregation it replaces at this shape).
@@ -33,12 +34,10 @@
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #define DS_F 16
-#define DS_MAXL 4
-#define DS_MAXH0 8
 
 struct DsParams {
-  const float* W[DS_MAXL];
-  const float* b[DS_MAXL];
+  const float* W[IGCN_STACK_MAX_LAYERS];
+  const float* b[IGCN_STACK_MAX_LAYERS];
 };
 
 struct DsReg {                                   // loss_probability's constants (sgcn_hyperparameters.py:18-21)
@@ -179,7 +178,8 @@ __host__ __device__ inline DsWs ds_ws(int64_t GR, int L, int NC) {
 }
 
 extern "C" int igcn_dense_sgcn_supported(int R, int H0, int F, int L) {
-  return R >= 64 && R <= 1024 && R % 64 == 0 && F == DS_F && L >= 1 && L <= DS_MAXL && H0 >= 1 && H0 <= DS_MAXH0;
+  return R >= 64 && R <= 1024 && R % 64 == 0 && F == DS_F && L >= 1 && L <= IGCN_STACK_MAX_LAYERS && H0 >= 1 &&
+         H0 <= IGCN_MAX_H0;
 }
 
 extern "C" size_t igcn_dense_sgcn_ws_floats(int64_t n_graphs, int R, int L, int copies) {
@@ -986,9 +986,9 @@ k_ds_mask_nodes(int64_t GR, int R, int H0, const float* __restrict__ x, const fl
   constexpr bool ANYM = NC == 2 || M0;
   constexpr int CM = NC - 1;                                     // index of the masked copy when there is one
   const int64_t node = (int64_t)blockIdx.x * 64 + threadIdx.x;
-  float da[2 * DS_MAXH0];
+  float da[2 * IGCN_MAX_H0];
 #pragma unroll
-  for (int h = 0; h < 2 * DS_MAXH0; ++h) da[h] = 0.f;
+  for (int h = 0; h < 2 * IGCN_MAX_H0; ++h) da[h] = 0.f;
   if (node < GR) {
     const int r = (int)(node % R);
     float du = 0.f, dvv = 0.f;
@@ -999,7 +999,7 @@ k_ds_mask_nodes(int64_t GR, int R, int H0, const float* __restrict__ x, const fl
       dvv = dv[node];
     }
 #pragma unroll
-    for (int h = 0; h < DS_MAXH0; ++h)
+    for (int h = 0; h < IGCN_MAX_H0; ++h)
       if (h < H0) {
         const float xv = x[node * H0 + h], pv = prob[r * H0 + h];
         float g = 0.f;
@@ -1009,17 +1009,17 @@ k_ds_mask_nodes(int64_t GR, int R, int H0, const float* __restrict__ x, const fl
           dxm[node * H0 + h] = m;
           g += m * pv;
           da[h] = du * xv * pv;
-          da[DS_MAXH0 + h] = dvv * xv * pv;
+          da[IGCN_MAX_H0 + h] = dvv * xv * pv;
         }
         dx[node * H0 + h] = g;
       }
   }
   if (!ANYM) return;
 #pragma unroll
-  for (int h = 0; h < 2 * DS_MAXH0; ++h) {
+  for (int h = 0; h < 2 * IGCN_MAX_H0; ++h) {
     const float s = wave_sum(da[h]);                             // valid in lane 0
-    if (threadIdx.x == 0 && (h < H0 || (h >= DS_MAXH0 && h - DS_MAXH0 < H0)))
-      da_partial[(int64_t)blockIdx.x * 2 * H0 + (h < DS_MAXH0 ? h : H0 + h - DS_MAXH0)] = s;
+    if (threadIdx.x == 0 && (h < H0 || (h >= IGCN_MAX_H0 && h - IGCN_MAX_H0 < H0)))
+      da_partial[(int64_t)blockIdx.x * 2 * H0 + (h < IGCN_MAX_H0 ? h : H0 + h - IGCN_MAX_H0)] = s;
   }
 }
 
@@ -1056,7 +1056,7 @@ static int ds_check_args(const char* nm, int64_t G, int R, int H0, int F, int L,
   IGCN_REQUIRE(G > 0 && (copies == 1 || copies == 2), "%s: bad sizes", nm);
   if (!igcn_dense_sgcn_supported(R, H0, F, L)) {
     igcn_set_error("%s: needs 64 <= R <= 1024, R %% 64 == 0, F == 16, L <= %d, H0 <= %d (R=%d, H0=%d, F=%d, L=%d)", nm,
-                   DS_MAXL, DS_MAXH0, R, H0, F, L);
+                   IGCN_STACK_MAX_LAYERS, IGCN_MAX_H0, R, H0, F, L);
     return IGCN_ERR_UNSUPPORTED;
   }
   return IGCN_OK;

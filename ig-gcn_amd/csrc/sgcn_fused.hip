@@ -37,12 +37,10 @@ extern "C" int igcn_debug_sf_probe(long long* out) {
 // 256 / 512 / 1024 threads.
 #define SF_T 512           // forward
 #define SF_TB 512          // backward
-#define SF_MAXL 4
-#define SF_MAXH0 8
 
 struct SfParams {
-  const float* W[SF_MAXL];     // W_l [F, Fin_l] row-major (Fin_0 = H0, then F)
-  const float* b[SF_MAXL];     // b_l [F]
+  const float* W[IGCN_STACK_MAX_LAYERS];     // W_l [F, Fin_l] row-major (Fin_0 = H0, then F)
+  const float* b[IGCN_STACK_MAX_LAYERS];     // b_l [F]
 };
 
 // LDS carve-out shared by both kernels (all offsets in 4-byte words)
@@ -285,7 +283,7 @@ __device__ __forceinline__ void sf_layer(float* lds, const SfLayout& o, int R, i
       const int i = e / FQ, q = e - i * FQ;
       float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-      for (int fi = 0; fi < SF_MAXH0; ++fi)
+      for (int fi = 0; fi < IGCN_MAX_H0; ++fi)
         if (fi < fin) {
           const float xv = xin[i * ldx + fi];
           const float4 w4 = *reinterpret_cast<const float4*>(Wt + fi * F + q * 4);
@@ -832,13 +830,17 @@ k_sgcn_stack_bwd(int R, int Emax, int H0, int L, const float* __restrict__ x_in,
   SF_PROBE(14);
 }
 
+// The launch switches below instantiate F = 4, 8, 16 and 32 only (default: 32): igcn_stack_width_ok must admit no other
+static_assert(IGCN_STACK_MIN_WIDTH == 4 && IGCN_STACK_MAX_WIDTH == 32,
+              "a new layer width needs a kernel instance and a case in every launch switch of this file");
 static int sf_check(const char* nm, int64_t n_graphs, int R, int max_edges, int H0, int F, int L, int backward) {
-  IGCN_REQUIRE(n_graphs > 0 && R > 0 && max_edges >= 0 && H0 >= 1 && H0 <= SF_MAXH0 && L >= 1 && L <= SF_MAXL,
-               "%s: bad sizes (1 <= H0 <= %d, 1 <= L <= %d)", nm, SF_MAXH0, SF_MAXL);
-  if (!(F == 4 || F == 8 || F == 16 || F == 32) ||
-      igcn_sgcn_stack_lds_bytes(R, max_edges, H0, F, L, backward) > 150 * 1024) {
-    igcn_set_error("%s: needs F in {4, 8, 16, 32} and a graph that fits 150 KB of LDS (R=%d, E<=%d, F=%d, L=%d)", nm,
-                   R, max_edges, F, L);
+  IGCN_REQUIRE(n_graphs > 0 && R > 0 && max_edges >= 0 && H0 >= 1 && H0 <= IGCN_MAX_H0 && L >= 1 &&
+                   L <= IGCN_STACK_MAX_LAYERS,
+               "%s: bad sizes (1 <= H0 <= %d, 1 <= L <= %d)", nm, IGCN_MAX_H0, IGCN_STACK_MAX_LAYERS);
+  if (!igcn_stack_width_ok(F) ||
+      igcn_sgcn_stack_lds_bytes(R, max_edges, H0, F, L, backward) > IGCN_LDS_BUDGET_BYTES) {
+    igcn_set_error("%s: needs F in {4, 8, 16, 32} and a graph that fits %d KB of LDS (R=%d, E<=%d, F=%d, L=%d)", nm,
+                   IGCN_LDS_BUDGET_BYTES / 1024, R, max_edges, F, L);
     return IGCN_ERR_UNSUPPORTED;
   }
   return IGCN_OK;
@@ -903,7 +905,7 @@ extern "C" int igcn_sgcn_front_fwd(int64_t n_nodes, int64_t n_edges, int n_graph
                "sgcn_front_fwd: the SNP mask needs logits and an output");
   for (int i = 0; i < 7; ++i) IGCN_REQUIRE(plan[i] && plan2[i], "sgcn_front_fwd: null plan array %d", i);
   const size_t lds = igcn_sgcn_front_lds_bytes(R, max_edges, H0, F, L);
-  if (lds > 150 * 1024) {
+  if (lds > IGCN_LDS_BUDGET_BYTES) {
     igcn_set_error("sgcn_front_fwd: a graph of %d nodes / %d edges does not fit LDS", R, max_edges);
     return IGCN_ERR_UNSUPPORTED;
   }

@@ -16,8 +16,6 @@
 #include "gcn_lds.h"
 
 #define SO_T 512
-#define SO_MAXH0 8
-#define SO_MAXF 32
 #define SO_DB_PARTS 8         // thread groups that share the node range of a bias gradient
 
 struct SoLayout {
@@ -58,7 +56,7 @@ __host__ __device__ inline SoLayout so_layout(int R, int Emax, int H0, int F1, i
     o.dy3 = take(R * P3);                          // d z's h3 block, then G3 = the gradient at the tap in place
     o.dh = take(R * PM);
     o.dx0 = take(R * H0);
-    o.redb = take(SO_DB_PARTS * SO_MAXF);
+    o.redb = take(SO_DB_PARTS * IGCN_STACK_MAX_WIDTH);
     o.redw = take(2 * SO_T);                       // dW partials: parts * outputs <= 2 * SO_T (so_dw_parts)
     o.prow = take(so_param_floats(H0, F1, F3));
     // gcn_norm backward's per-position products go into G1 / the first transform, dead by then, when they fit
@@ -134,7 +132,7 @@ __device__ __forceinline__ void so_transform(int R, int fin, const float* X, int
       }
     } else {
 #pragma unroll
-      for (int fi = 0; fi < SO_MAXH0; ++fi)
+      for (int fi = 0; fi < IGCN_MAX_H0; ++fi)
         if (fi < fin) {
           const float xv = X[i * ldx + fi];
           const float4 w4 = *reinterpret_cast<const float4*>(Wt + fi * P + q * 4);
@@ -359,10 +357,11 @@ k_sgcn_ori_bwd(const SoArgs a, const float* __restrict__ dz, const float* __rest
 static int so_check(const char* nm, int64_t n_graphs, int R, int max_edges, int H0, int F1, int F3, int backward) {
   IGCN_REQUIRE(n_graphs > 0 && n_graphs < ((int64_t)1 << 31) && R > 0 && max_edges >= 0, "%s: bad sizes", nm);
   IGCN_REQUIRE(n_graphs * R < ((int64_t)1 << 31), "%s: the batch's nodes must fit int32", nm);
-  if (H0 < 1 || H0 > SO_MAXH0 || F1 < 1 || F1 > SO_MAXF || F3 < 1 || F3 > SO_MAXF ||
-      igcn_sgcn_ori_lds_bytes(R, max_edges, H0, F1, F3, backward) > 150 * 1024) {
-    igcn_set_error("%s: needs 1 <= H0 <= %d, 1 <= F1, F3 <= %d and a graph that fits 150 KB of LDS (R=%d, E<=%d, "
-                   "H0=%d, F1=%d, F3=%d)", nm, SO_MAXH0, SO_MAXF, R, max_edges, H0, F1, F3);
+  if (H0 < 1 || H0 > IGCN_MAX_H0 || F1 < 1 || F1 > IGCN_STACK_MAX_WIDTH || F3 < 1 || F3 > IGCN_STACK_MAX_WIDTH ||
+      igcn_sgcn_ori_lds_bytes(R, max_edges, H0, F1, F3, backward) > IGCN_LDS_BUDGET_BYTES) {
+    igcn_set_error("%s: needs 1 <= H0 <= %d, 1 <= F1, F3 <= %d and a graph that fits %d KB of LDS (R=%d, E<=%d, "
+                   "H0=%d, F1=%d, F3=%d)", nm, IGCN_MAX_H0, IGCN_STACK_MAX_WIDTH, IGCN_LDS_BUDGET_BYTES / 1024, R, max_edges,
+                   H0, F1, F3);
     return IGCN_ERR_UNSUPPORTED;
   }
   return IGCN_OK;

@@ -16,11 +16,10 @@
 //                      sum_j P_ij log max(num_ij / Z, eps) in fp64 (it needs Z, so it follows the first; every 50th step).
 //   igcn_tsne_update   one workgroup: Z in a fixed order, grad = 4 (e attr - rep / Z), sklearn's _gradient_descent step
 //                      on (Y, update, gains) in place, and on check iterations the status record.
-// No atomics, one writer per element, fixed-order reductions: the same bits every run.  S <= 4096, D <= 1024.
+// No atomics, one writer per element, fixed-order reductions: the same bits every run.  S <= 4096
+// (IGCN_TSNE_MAX_S), D <= 1024 (IGCN_TSNE_MAX_D).
 #include "common.h"
 
-#define TSNE_MAX_S 4096
-#define TSNE_MAX_D 1024
 #define TSNE_T 256              /* threads of every kernel here */
 #define TSNE_EPS 2.220446049250313e-16   /* np.finfo(np.double).eps: sklearn's MACHINE_EPSILON */
 
@@ -71,7 +70,7 @@ k_tsne_sqdist(int S, int D, const float* __restrict__ X, float* __restrict__ dis
 __global__ void __launch_bounds__(TSNE_T)
 k_tsne_beta(int S, double desired_entropy, const float* __restrict__ dist, double* __restrict__ betas,
             double* __restrict__ rownorm, double* __restrict__ rowtot) {
-  __shared__ float s_d[TSNE_MAX_S];
+  __shared__ float s_d[IGCN_TSNE_MAX_S];
   __shared__ double s_red[2 * (TSNE_T / 64)];
   const int i = blockIdx.x, tid = threadIdx.x;
   for (int j = tid; j < S; j += TSNE_T) s_d[j] = dist[(int64_t)i * S + j];
@@ -148,7 +147,7 @@ k_tsne_psym(int S, const float* __restrict__ dist, const double* __restrict__ be
 // rowacc: [5][S] = attr_x, attr_y, rep_x, rep_y, z
 __global__ void __launch_bounds__(TSNE_T)
 k_tsne_grad(int S, const float* __restrict__ P, const float* __restrict__ Y, float* __restrict__ rowacc) {
-  __shared__ float2 s_y[TSNE_MAX_S];
+  __shared__ float2 s_y[IGCN_TSNE_MAX_S];
   const int tid = threadIdx.x, lane = tid & 63;
   for (int j = tid; j < S; j += TSNE_T) s_y[j] = reinterpret_cast<const float2*>(Y)[j];
   __syncthreads();
@@ -194,7 +193,7 @@ __device__ __forceinline__ float tsne_z(const float* __restrict__ zrow, int S, f
 __global__ void __launch_bounds__(TSNE_T)
 k_tsne_kl(int S, const float* __restrict__ P, const float* __restrict__ Y, const float* __restrict__ rowacc,
           double* __restrict__ klpart) {
-  __shared__ float2 s_y[TSNE_MAX_S];
+  __shared__ float2 s_y[IGCN_TSNE_MAX_S];
   __shared__ float s_red[16];
   const int tid = threadIdx.x, lane = tid & 63;
   for (int j = tid; j < S; j += TSNE_T) s_y[j] = reinterpret_cast<const float2*>(Y)[j];
@@ -255,11 +254,12 @@ k_tsne_update(int S, float ex, float momentum, float lr, int check, const float*
   }
 }
 
-static bool tsne_s_ok(int S) { return S >= 4 && S <= TSNE_MAX_S; }
+static bool tsne_s_ok(int S) { return S >= IGCN_TSNE_MIN_S && S <= IGCN_TSNE_MAX_S; }
 
 extern "C" int igcn_tsne_sqdist(int S, int D, const float* X, float* dist, void* stream) {
-  IGCN_REQUIRE(tsne_s_ok(S) && D >= 1 && D <= TSNE_MAX_D, "tsne_sqdist: S=%d D=%d outside 4 <= S <= %d, 1 <= D <= %d", S, D,
-               TSNE_MAX_S, TSNE_MAX_D);
+  IGCN_REQUIRE(tsne_s_ok(S) && D >= 1 && D <= IGCN_TSNE_MAX_D,
+               "tsne_sqdist: S=%d D=%d outside %d <= S <= %d, 1 <= D <= %d", S, D, IGCN_TSNE_MIN_S, IGCN_TSNE_MAX_S,
+               IGCN_TSNE_MAX_D);
   IGCN_REQUIRE(X && dist, "tsne_sqdist: a NULL matrix or output");
   const unsigned t = (unsigned)igcn_cdiv(S, 16);
   hipLaunchKernelGGL(k_tsne_sqdist, dim3(t, t), dim3(TSNE_T), 0, (hipStream_t)stream, S, D, X, dist);
@@ -272,7 +272,8 @@ extern "C" size_t igcn_tsne_joint_p_scratch_doubles(int S) { return S < 1 ? 0 : 
 
 extern "C" int igcn_tsne_joint_p(int S, double perplexity, const float* dist, float* P, double* betas, double* pstats,
                                  double* scratch, void* stream) {
-  IGCN_REQUIRE(tsne_s_ok(S), "tsne_joint_p: S=%d outside 4 <= S <= %d", S, TSNE_MAX_S);
+  IGCN_REQUIRE(tsne_s_ok(S), "tsne_joint_p: S=%d outside %d <= S <= %d", S, IGCN_TSNE_MIN_S,
+               IGCN_TSNE_MAX_S);
   IGCN_REQUIRE(perplexity > 0.0 && perplexity < (double)S, "tsne_joint_p: perplexity %g must lie in (0, S=%d)", perplexity, S);
   IGCN_REQUIRE(dist && P && betas && pstats && scratch, "tsne_joint_p: a NULL argument");
   hipStream_t st = (hipStream_t)stream;
@@ -291,7 +292,8 @@ extern "C" int igcn_tsne_joint_p(int S, double perplexity, const float* dist, fl
 
 extern "C" int igcn_tsne_grad(int S, int want_kl, const float* P, const float* Y, float* rowacc, double* klpart,
                               void* stream) {
-  IGCN_REQUIRE(tsne_s_ok(S), "tsne_grad: S=%d outside 4 <= S <= %d", S, TSNE_MAX_S);
+  IGCN_REQUIRE(tsne_s_ok(S), "tsne_grad: S=%d outside %d <= S <= %d", S, IGCN_TSNE_MIN_S,
+               IGCN_TSNE_MAX_S);
   IGCN_REQUIRE(P && Y && rowacc && (!want_kl || klpart), "tsne_grad: a NULL argument");
   hipStream_t st = (hipStream_t)stream;
   const unsigned blocks = (unsigned)igcn_cdiv(S, TSNE_T / 64);
@@ -307,7 +309,8 @@ extern "C" int igcn_tsne_grad(int S, int want_kl, const float* P, const float* Y
 extern "C" int igcn_tsne_update(int S, float exaggeration, float momentum, float lr, int check, const float* rowacc,
                                 const double* klpart, const double* pstats, float* Y, float* update, float* gains,
                                 float* grad_out, double* status, void* stream) {
-  IGCN_REQUIRE(tsne_s_ok(S), "tsne_update: S=%d outside 4 <= S <= %d", S, TSNE_MAX_S);
+  IGCN_REQUIRE(tsne_s_ok(S), "tsne_update: S=%d outside %d <= S <= %d", S, IGCN_TSNE_MIN_S,
+               IGCN_TSNE_MAX_S);
   IGCN_REQUIRE(exaggeration >= 1.0f, "tsne_update: exaggeration %g below 1", (double)exaggeration);
   IGCN_REQUIRE(rowacc && Y && update && gains, "tsne_update: a NULL argument");
   IGCN_REQUIRE(!check || (klpart && pstats && status), "tsne_update: a check iteration needs klpart, pstats and status");

@@ -13,6 +13,13 @@ from . import _lib
 from . import switches
 from ._lib import call, ptr, stream_ptr
 
+# Limits of the kernels: each is a #define of include/igcn.h (read by _lib), written as a number nowhere else
+_L = _lib.LIMITS
+LDS_BUDGET_BYTES = _L["IGCN_LDS_BUDGET_BYTES"]       # what an LDS-resident stack or attention kernel may ask for
+MAX_H0, STACK_MAX_LAYERS = _L["IGCN_MAX_H0"], _L["IGCN_STACK_MAX_LAYERS"]
+STACK_MAX_WIDTH = _L["IGCN_STACK_MAX_WIDTH"]
+STACK_WIDTHS = tuple(w for w in range(_L["IGCN_STACK_MIN_WIDTH"], STACK_MAX_WIDTH + 1) if w & (w - 1) == 0)
+
 
 def _f32(t):
     if t.dtype != torch.float32:
@@ -171,12 +178,12 @@ class _immediate:
 class GraphPlan:
     """Stable by-target / by-source grouping of a batch's edges (igcn_graph_plan_build)."""
 
-    SEG_MAX_NODES, SEG_MAX_EDGES = 1024, 4096
+    SEG_MAX_NODES, SEG_MAX_EDGES = _L["IGCN_SEG_MAX_NODES"], _L["IGCN_SEG_MAX_EDGES"]
 
     def __init__(self, edge_index, n_nodes, node_ptr=None, edge_ptr=None, max_nodes=None, max_edges=None):
         """``node_ptr``/``edge_ptr`` (int64 device tensors [G+1]) + the host-known per-graph maxima select a per-graph
-        build (graphs of at most 1024 nodes: in LDS up to 4096 edges per graph, tiled counting sort beyond);
-        otherwise the general radix-sort build.  All three are hand-written and hipGraph-capturable."""
+        build (graphs of at most SEG_MAX_NODES = 1024 nodes: in LDS up to SEG_MAX_EDGES = 4096 edges per graph, tiled
+        counting sort beyond); otherwise the general radix-sort build.  All three are hand-written and hipGraph-capturable."""
         if edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.shape[0] != 2:
             raise _lib.IgcnError("edge_index must be int64 [2,E]")
         ei = edge_index.contiguous()
@@ -609,10 +616,11 @@ def sgcn_stack_supported(plan, rois, h0, f, layers):
     """The LDS-resident SGCN stack (igcn_sgcn_stack_*) covers this batch: per-graph plan of uniform graphs (block
     diagonal, verified by the builder), supported widths, and the graph fits LDS."""
     seg = getattr(plan, "_stack_dims", None)
-    if seg is None or seg[0] != rois or f not in (4, 8, 16, 32) or not (1 <= layers <= 4) or not (1 <= h0 <= 8):
+    if (seg is None or seg[0] != rois or f not in STACK_WIDTHS or not (1 <= layers <= STACK_MAX_LAYERS)
+            or not (1 <= h0 <= MAX_H0)):
         return False
     lib = _lib.load()
-    return int(lib.igcn_sgcn_stack_lds_bytes(rois, seg[1], h0, f, layers, 1)) <= 150 * 1024
+    return int(lib.igcn_sgcn_stack_lds_bytes(rois, seg[1], h0, f, layers, 1)) <= LDS_BUDGET_BYTES
 
 
 class SgcnStack(torch.autograd.Function):
@@ -688,13 +696,15 @@ def _sgcn_stack_backward(x_in, ew_in, wb, plan, rois, final, dxcat, dxcat2):
 
 
 def sgcn_ori_supported(plan, rois, h0, f1, f3):
-    """The LDS-resident SGCN_Ori stack (igcn_sgcn_ori_*) covers this batch: per-graph plan of uniform graphs, 1 <= h0 <= 8,
-    1 <= f1, f3 <= 32 (any width, not only the grid), and the graph fits LDS in both directions."""
+    """The LDS-resident SGCN_Ori stack (igcn_sgcn_ori_*) covers this batch: per-graph plan of uniform graphs, 1 <= h0 <= 8
+    (MAX_H0), 1 <= f1, f3 <= 32 (STACK_MAX_WIDTH; any width, not only the grid), and the graph fits LDS in both
+    directions."""
     seg = getattr(plan, "_stack_dims", None)
-    if seg is None or seg[0] != rois or not (1 <= h0 <= 8) or not (1 <= f1 <= 32) or not (1 <= f3 <= 32):
+    if (seg is None or seg[0] != rois or not (1 <= h0 <= MAX_H0) or not (1 <= f1 <= STACK_MAX_WIDTH)
+            or not (1 <= f3 <= STACK_MAX_WIDTH)):
         return False
     lib = _lib.load()
-    return int(lib.igcn_sgcn_ori_lds_bytes(rois, seg[1], h0, f1, f3, 1)) <= 150 * 1024
+    return int(lib.igcn_sgcn_ori_lds_bytes(rois, seg[1], h0, f1, f3, 1)) <= LDS_BUDGET_BYTES
 
 
 class TapGrads:
@@ -763,10 +773,7 @@ class SgcnOriStack(torch.autograd.Function):
         return (dx, dew, None, None, None, dpar[:o1].view(f1, h0), dpar[o1:o2], dpar[o2:o3].view(f3, f1), dpar[o3:])
 
 
-GAT_WIDTHS = (4, 8, 16, 32)
-GAT_MAX_LAYERS = 4
-GAT_MAX_H0 = 8
-GAT_LDS_BYTES = 150 * 1024
+GAT_WIDTHS, GAT_MAX_LAYERS, GAT_MAX_H0, GAT_LDS_BYTES = STACK_WIDTHS, STACK_MAX_LAYERS, MAX_H0, LDS_BUDGET_BYTES
 
 
 def gat_stack_limits(plan, rois, h0, f, layers, ew_grad=False):
@@ -868,7 +875,7 @@ def sgcn_front_supported(plan, rois, h0, f, layers, snps_feat, snps_logits):
         return False
     if snps_feat is None or snps_feat.dim() != 2 or snps_logits is None or snps_feat.shape[1] != snps_logits.numel():
         return False
-    return int(_lib.load().igcn_sgcn_front_lds_bytes(rois, plan._stack_dims[1], h0, f, layers)) <= 150 * 1024
+    return int(_lib.load().igcn_sgcn_front_lds_bytes(rois, plan._stack_dims[1], h0, f, layers)) <= LDS_BUDGET_BYTES
 
 
 class SgcnFront(torch.autograd.Function):
@@ -3214,8 +3221,8 @@ def attention_map_accumulate(w, y, sums, counts, state):
     call("igcn_attn_map_accumulate", b, lq, lk, c, ptr(w), ptr(y), ptr(sums), ptr(counts), ptr(state), stream_ptr())
 
 
-SALIENCY_MAX_ROIS, SALIENCY_MAX_ELEMS, SALIENCY_MAX_STEPS = 512, 8192, 4096      # csrc/saliency.hip
-GRAD_CAM_MAX_WIDTH = 160
+SALIENCY_MAX_ROIS, SALIENCY_MAX_ELEMS = _L["IGCN_SALIENCY_MAX_ROIS"], _L["IGCN_SALIENCY_MAX_ELEMS"]
+SALIENCY_MAX_STEPS, GRAD_CAM_MAX_WIDTH = _L["IGCN_SALIENCY_MAX_STEPS"], _L["IGCN_GRAD_CAM_MAX_WIDTH"]
 
 
 def saliency_maps(x, dx, rois, base=None, normalize=False):
@@ -3616,7 +3623,9 @@ def knn_impute(x, means, k, rows_fit=None, rows_q=None, scale=None, shift=None, 
 # =================================================================================================
 # Cluster labels: exact t-SNE and KMeans (csrc/tsne.hip, csrc/kmeans.hip); the algorithms live in cluster_labels.py
 # =================================================================================================
-TSNE_MAX_S, TSNE_MAX_D, KMEANS_MAX_N, KMEANS_MAX_D, KMEANS_MAX_K = 4096, 1024, 65536, 1024, 16
+TSNE_MIN_S, TSNE_MAX_S, TSNE_MAX_D = _L["IGCN_TSNE_MIN_S"], _L["IGCN_TSNE_MAX_S"], _L["IGCN_TSNE_MAX_D"]
+KMEANS_MAX_N, KMEANS_MAX_D, KMEANS_MAX_K = _L["IGCN_KMEANS_MAX_N"], _L["IGCN_KMEANS_MAX_D"], _L["IGCN_KMEANS_MAX_K"]
+KMEANSPP_MAX_TRIALS = _L["IGCN_KMEANSPP_MAX_TRIALS"]
 
 
 def cl_matrix(x, what, lo_rows, hi_rows, hi_cols):
@@ -3642,7 +3651,7 @@ def _f64(n, dev):
 def tsne_sqdist(x):
     """[S, S] squared Euclidean distances of x [S, D] by direct differences (igcn_tsne_sqdist): symmetric bits, the
     diagonal exactly 0."""
-    x = cl_matrix(x, "tsne_sqdist", 4, TSNE_MAX_S, TSNE_MAX_D)
+    x = cl_matrix(x, "tsne_sqdist", TSNE_MIN_S, TSNE_MAX_S, TSNE_MAX_D)
     s, d = x.shape
     dist = torch.empty(s, s, dtype=torch.float32, device=x.device)
     call("igcn_tsne_sqdist", s, d, ptr(x), ptr(dist), stream_ptr())
@@ -3653,7 +3662,7 @@ def tsne_joint_p(dist, perplexity):
     """sklearn's ``_joint_probabilities`` of the squared distances dist [S, S] — symmetric bit for bit, as
     ``tsne_sqdist`` returns them: d_ji is read as d_ij — (igcn_tsne_joint_p): (P [S, S] float32
     with a zero diagonal, betas [S] float64, pstats [2] float64 = (sum P log P, sum P))."""
-    dist = cl_matrix(dist, "tsne_joint_p", 4, TSNE_MAX_S, TSNE_MAX_S)
+    dist = cl_matrix(dist, "tsne_joint_p", TSNE_MIN_S, TSNE_MAX_S, TSNE_MAX_S)
     s = dist.shape[0]
     if dist.shape[1] != s:
         raise ValueError("tsne_joint_p: the distances must be [S, S]")
@@ -3674,8 +3683,9 @@ class TsneState:
 
     def __init__(self, p, pstats, y):
         s = int(p.shape[0])
-        if tuple(p.shape) != (s, s) or tuple(y.shape) != (s, 2) or not 4 <= s <= TSNE_MAX_S:
-            raise ValueError(f"TsneState: P {tuple(p.shape)} / Y {tuple(y.shape)} are not [S, S] / [S, 2], 4 <= S <= 4096")
+        if tuple(p.shape) != (s, s) or tuple(y.shape) != (s, 2) or not TSNE_MIN_S <= s <= TSNE_MAX_S:
+            raise ValueError(f"TsneState: P {tuple(p.shape)} / Y {tuple(y.shape)} are not [S, S] / [S, 2], "
+                             f"{TSNE_MIN_S} <= S <= {TSNE_MAX_S}")
         dev = p.device
         self.s, self.p, self.pstats = s, _f32(p), pstats
         self.y = _f32(y.detach()).clone()
@@ -3749,15 +3759,16 @@ def kmeanspp_step(x, u, closest, pot, chosen):
     """One greedy k-means++ step (igcn_kmeanspp_step): ``u`` float64 [t] uniform numbers on the device; ``closest`` [N]
     float32, ``pot`` float64 [1] and ``chosen`` int64 [1] are updated in place."""
     x = cl_matrix(x, "kmeanspp_step", 1, KMEANS_MAX_N, KMEANS_MAX_D)
-    if u.dtype != torch.float64 or u.dim() != 1 or not 1 <= u.numel() <= 8 or u.device != x.device:
-        raise ValueError("kmeanspp_step: u must hold 1..8 float64 numbers on the points' device")
+    if u.dtype != torch.float64 or u.dim() != 1 or not 1 <= u.numel() <= KMEANSPP_MAX_TRIALS or u.device != x.device:
+        raise ValueError(f"kmeanspp_step: u must hold 1..{KMEANSPP_MAX_TRIALS} float64 numbers on the points' device")
     call("igcn_kmeanspp_step", x.shape[0], x.shape[1], int(u.numel()), ptr(x), ptr(u.contiguous()), ptr(closest), ptr(pot),
          ptr(chosen), stream_ptr())
 
 
 from .gdc import _empty as _buffer  # noqa: E402  (the package's one device-buffer helper: (shape, dtype, device))
 
-PERM_MIN_S, PERM_MAX_S, PERM_MAX_E, PERM_MAX_P, PERM_MAX_G_ROWS = 4, 4096, 1 << 20, 65536, 8      # csrc/perm_test.hip
+PERM_MIN_S, PERM_MAX_S, PERM_MAX_E = _L["IGCN_PERM_MIN_S"], _L["IGCN_PERM_MAX_S"], _L["IGCN_PERM_MAX_E"]
+PERM_MAX_P, PERM_MAX_G_ROWS = _L["IGCN_PERM_MAX_P"], _L["IGCN_PERM_MAX_G_ROWS"]
 
 
 def perm_plane_dims(s, e):
@@ -3798,7 +3809,7 @@ def perm_maxsum(member, planes, e, g_obs=None):
     """The relabelled group sums of igcn_perm_maxsum, never stored: member [P, S] uint8 (0/1; row p = group A of
     relabelling p; any row stride), planes of ``perm_prepare`` for the same S and ``e`` entries.  With ``g_obs`` [E] fp32:
     (maxabs [P], exceed [E] int32) = (max_e |G[p, e]|, #{p : |G[p, e]| >= |g_obs[e]|}).  Without: (maxabs [P], g [P, E])
-    for P <= 8, the observed pass."""
+    for P <= 8 (PERM_MAX_G_ROWS), the observed pass."""
     if member.dtype != torch.uint8 or member.dim() != 2 or member.stride(1) != 1 or member.device != planes.device:
         raise TypeError("perm_maxsum: member must be uint8 [P, S] with unit column stride on the planes' device")
     p, s, e, dev = int(member.shape[0]), int(member.shape[1]), int(e), planes.device

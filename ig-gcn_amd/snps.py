@@ -34,6 +34,7 @@ from .capture import GradTable, ShapeCache, _capture, kept_trainer, rolled_back
 
 SNPS_LAMBDA0 = 1e-5                      # kernel/train_eval_snps.py:169
 SNPS_TERMS = ("class", "recon")
+EVAL_MAX_ROWS = _lib.LIMITS["IGCN_EVAL_MAX_ROWS"]      # rows one igcn_eval_metrics call takes
 
 
 def _head(model):
@@ -297,15 +298,15 @@ def eval_scores_snps(model, loader, device=None, criterion_class=None, criterion
                      lambda0=SNPS_LAMBDA0):
     """eval_scores() :388-423 with its 7-tuple (true_label, pred_label, accuracy, auc, f1, sensitivity, specificity);
     the two label arrays are numpy bool, as the reference's.  The prediction is ``y_hat > 0.5`` (a score of exactly 0.5 is
-    class 0).  Routes: on the GPU with at most 65536 rows every metric comes from igcn_eval_metrics (C = 2, scores
-    [log(1 - y_hat), log y_hat], whose order is y_hat's: auc = the Mann-Whitney statistic with ties 1/2, which is what
+    class 0).  Routes: on the GPU with at most 65536 (EVAL_MAX_ROWS) rows every metric comes from igcn_eval_metrics (C =
+    2, scores [log(1 - y_hat), log y_hat], whose order is y_hat's: auc = the Mann-Whitney statistic with ties 1/2, which is what
     roc_curve + auc compute; weighted f1, sensitivity and specificity from its confusion counts) — the thresholding, the
     correct count and the two logarithms are torch launches in front of it; anywhere else (CPU, more rows) the same
     definitions on the host in numpy.  No sklearn.  As in the reference, a NaN score gives auc 0."""
     y_hat, label = _scores(model, loader, device, temperature)
     truth, pred = label > 0.5, y_hat > 0.5
     n = int(y_hat.numel())
-    if y_hat.is_cuda and n <= 65536:
+    if y_hat.is_cuda and n <= EVAL_MAX_ROWS:
         logp = torch.stack((torch.log1p(-y_hat), torch.log(y_hat)), 1).contiguous()
         p64, t64 = pred.long(), truth.long()
         state = torch.stack((torch.tensor(n, device=y_hat.device), torch.tensor(0, device=y_hat.device),

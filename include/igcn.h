@@ -40,6 +40,24 @@ const char* igcn_last_error(void);
  * attention kernels (sweeps).  No launch path reads the environment. */
 int igcn_configure(unsigned options, int gemm_bn_cap, int attn_chunk_rows);
 
+/* Limits.  Every `#define IGCN_<NAME> <decimal literal>` of this header is the ONE place that number is written: the
+ * kernels use the macro, and the Python binding reads it from this file (igcn_amd/_lib.py: LIMITS), as it reads the
+ * prototypes.  Plain literals only (1048576, not 1 << 20): the binding evaluates no expression.  A limit stands next
+ * to the entry points it bounds; the ones below bound several families.
+ *   IGCN_LDS_BUDGET_BYTES  150 KB: what an LDS-resident graph stack (igcn_sgcn_stack_*, igcn_sgcn_ori_*,
+ *                          igcn_gat_stack_*), the staged attention kernels and the long-list SpMM may ask for.
+ *   IGCN_LDS_MAX_BYTES     160 KB: the dynamic-LDS ceiling of a gfx950 workgroup, raised per kernel on first use.
+ *   IGCN_MAX_H0            input features per node of the edge masks and of every graph stack.
+ *   IGCN_STACK_MAX_LAYERS  layers of igcn_sgcn_stack_*, igcn_gat_stack_*, igcn_dense_sgcn_*.
+ *   IGCN_STACK_MIN_WIDTH, IGCN_STACK_MAX_WIDTH  layer widths: the powers of two in this range for igcn_sgcn_stack_* and
+ *                          igcn_gat_stack_* (F in {4,8,16,32}), any width up to the maximum for igcn_sgcn_ori_*. */
+#define IGCN_LDS_BUDGET_BYTES 153600
+#define IGCN_LDS_MAX_BYTES 163840
+#define IGCN_MAX_H0 8
+#define IGCN_STACK_MAX_LAYERS 4
+#define IGCN_STACK_MIN_WIDTH 4
+#define IGCN_STACK_MAX_WIDTH 32
+
 /* ------------------------------------------------------------------------------------------------
  * Graph plan: replaces the index work PyG's gcn_norm/propagate redo in every GCNConv call
  * (mask src!=dst, cat, arange, scatter index math; call sites kernel/sgcn_img_snp.py:218,221).
@@ -60,7 +78,8 @@ size_t igcn_graph_plan_workspace_bytes(int64_t n_nodes, int64_t n_edges);
  * h = x W^T, z_e = leaky_relu(h[src].att_src + h[i].att_dst + ea_e (lin_edge[:,0].att_edge)) over i's stored incoming
  * edges with src != dst plus one virtual loop whose ea is the mean of those edges' ea (0 if none), alpha = the edge
  * softmax over them (max-subtracted, + 1e-16 in the denominator), y_i = relu(sum alpha h[src] + bias).
- * F in {4,8,16,32}, L <= 4, H0 <= 8 and igcn_gat_stack_lds_bytes(...) <= 150 KB (IGCN_ERR_UNSUPPORTED otherwise).
+ * F in {4,8,16,32}, L <= 4 (IGCN_STACK_MAX_LAYERS), H0 <= 8 (IGCN_MAX_H0) and igcn_gat_stack_lds_bytes(...) <= 150 KB
+ * (IGCN_LDS_BUDGET_BYTES), IGCN_ERR_UNSUPPORTED otherwise.
  * params: HOST array of 6 L device pointers, per layer W [F, Fin_l] (Fin_0 = H0, then F), bias [F], att_src [F],
  * att_dst [F], lin_edge [F], att_edge [F].  ew_in [E]: the scalar edge attributes (igcn_gat_stack_bwd: data, no gradient).
  * Backward recomputes the forward in LDS; outputs dx_in [N, H0] (or NULL: not computed) and dparams
@@ -97,8 +116,8 @@ int igcn_gat_stack_bwd_ew(int64_t n_graphs, int R, int max_edges, int H0, int F,
  * Arguments and limits of igcn_gat_stack_fwd, G in place of xcat.  One workgroup per graph runs the forward's own
  * staging and layer functions on the forward's LDS layout and, after each layer, builds that layer's block one tile
  * of igcn_gat_stack_alpha_tile(...) target columns at a time in LDS (one [R, tile] block behind the layout, the whole
- * within 150 KB; 0 = nothing fits: IGCN_ERR_UNSUPPORTED): every element stored exactly once, zeros included, one writer
- * per element, no atomics, copies added in list order: bit-identical from run to run. */
+ * within 150 KB = IGCN_LDS_BUDGET_BYTES; 0 = nothing fits: IGCN_ERR_UNSUPPORTED): every element stored exactly once,
+ * zeros included, one writer per element, no atomics, copies added in list order: bit-identical from run to run. */
 int igcn_gat_stack_alpha_tile(int R, int max_edges, int H0, int F, int L);
 int igcn_gat_stack_alpha(int64_t n_graphs, int R, int max_edges, int H0, int F, int L, const float* x_in,
                          const float* ew_in, const int32_t* src32, const int32_t* dst32, const int32_t* tgt_ptr,
@@ -111,9 +130,12 @@ int igcn_graph_plan_build(int64_t n_nodes, int64_t n_edges, const int64_t* edge_
 /* Same plan for a block-diagonal PyG batch of SMALL graphs, one workgroup per graph, everything in LDS (no
  * device-wide sort): graph g owns nodes [node_ptr[g],node_ptr[g+1]) and edges [edge_ptr[g],edge_ptr[g+1]) (int64
  * device arrays of n_graphs+1 entries, as Batch.from_data_list records them; batch.py:24-123).  Limits: 1024 nodes
- * and 4096 edges per graph (IGCN_ERR_UNSUPPORTED otherwise: use igcn_graph_plan_build_tiled / igcn_graph_plan_build).
+ * (IGCN_SEG_MAX_NODES) and 4096 edges (IGCN_SEG_MAX_EDGES) per graph (IGCN_ERR_UNSUPPORTED otherwise: use
+ * igcn_graph_plan_build_tiled / igcn_graph_plan_build).
  * `status` (device int32, zeroed by the caller) is set non-zero if a graph exceeds the limits or an edge leaves its
  * graph. */
+#define IGCN_SEG_MAX_NODES 1024
+#define IGCN_SEG_MAX_EDGES 4096
 int igcn_graph_plan_build_segmented(int64_t n_nodes, int64_t n_edges, int n_graphs, const int64_t* edge_index,
                                     const int64_t* node_ptr, const int64_t* edge_ptr,
                                     int64_t max_nodes_per_graph, int64_t max_edges_per_graph,
@@ -185,10 +207,16 @@ int igcn_edge_dense_map(int64_t n_graphs, int R, int64_t n_edges, const float* v
  *   norm = 1: cam divided by the subject's maximum; a subject whose maximum is 0 stays at zero.
  * Both: one workgroup per subject, fixed-order reductions, no atomics, every output element stored exactly once (zeros
  * included), bit-identical from run to run.  LDS: igcn_saliency_maps holds the subject's attr tile and roi, 34 KB static
- * — R <= 512, R * H0 <= 8192, M <= 4096; igcn_grad_cam holds alpha, its partial sums and the R cam values, 4 KB static,
- * and streams acts and grads from global memory once each (no tile is staged, nothing re-read) — R <= 512, K <= 160.
+ * — R <= 512 (IGCN_SALIENCY_MAX_ROIS), R * H0 <= 8192 (IGCN_SALIENCY_MAX_ELEMS), M <= 4096
+ * (IGCN_SALIENCY_MAX_STEPS); igcn_grad_cam holds alpha, its partial sums and the R cam values, 4 KB static,
+ * and streams acts and grads from global memory once each (no tile is staged, nothing re-read) — R <= 512, K <= 160
+ * (IGCN_GRAD_CAM_MAX_WIDTH).
  * IGCN_ERR_UNSUPPORTED outside these bounds, before anything runs; nothing is truncated.  Per-class cohort sums:
  * igcn_attn_map_accumulate with Lq = R, Lk = H0 (or 1). */
+#define IGCN_SALIENCY_MAX_ROIS 512
+#define IGCN_SALIENCY_MAX_ELEMS 8192
+#define IGCN_SALIENCY_MAX_STEPS 4096
+#define IGCN_GRAD_CAM_MAX_WIDTH 160
 int igcn_saliency_maps(int B, int R, int H0, int M, const float* x, const float* base /*or NULL*/, int base_per_subject,
                        const float* dx, int norm, float* attr, float* roi, void* stream);
 int igcn_grad_cam(int B, int R, int K, const float* acts, const float* grads, int norm, float* cam, float* alpha,
@@ -304,8 +332,9 @@ int igcn_gcn_propagate_bwd(int64_t n_nodes, int64_t n_edges, int F, int nodes_pe
  * compulsory traffic of SURVEY §8d's "fused SGCN forward lower bound": x_in [n_graphs*R, H0], the graph's edges and
  * ew_in in, xcat [n_graphs*R, L*F] out.  Needs a block-diagonal batch (graph g = nodes [gR, (g+1)R), its edges
  * contiguous in stored order — what the per-graph plan builders verify), at most `max_edges` edges per graph,
- * F in {4,8,16,32}, L <= 4, H0 <= 8 and igcn_sgcn_stack_lds_bytes(...) <= 150 KB (IGCN_ERR_UNSUPPORTED otherwise: use
- * igcn_gcn_norm_* / igcn_gemm_f32 / igcn_gcn_propagate_*).  W / b: HOST arrays of L device pointers, W_l [F, Fin_l]
+ * F in {4,8,16,32}, L <= 4 (IGCN_STACK_MAX_LAYERS), H0 <= 8 (IGCN_MAX_H0) and igcn_sgcn_stack_lds_bytes(...) <= 150 KB
+ * (IGCN_LDS_BUDGET_BYTES), IGCN_ERR_UNSUPPORTED otherwise: use
+ * igcn_gcn_norm_* / igcn_gemm_f32 / igcn_gcn_propagate_*.  W / b: HOST arrays of L device pointers, W_l [F, Fin_l]
  * row-major (Fin_0 = H0, then F), b_l [F].
  * Backward recomputes the forward in LDS; outputs dx_in [N, H0], dew_in [E] and dparams
  * [igcn_sgcn_stack_param_floats] = dW_0 | db_0 | dW_1 | db_1 | ... (scratch: n_graphs * that many floats; the sum over
@@ -349,8 +378,9 @@ int igcn_sgcn_front_fwd(int64_t n_nodes, int64_t n_edges, int n_graphs, int R, i
  * like igcn_sgcn_stack_* and on the same per-graph plan, with two layers of INDEPENDENT width: per graph
  *   h1 = relu(GCNConv1(x)) [R, F1],  acts = GCNConv3(h1) [R, F3] (no ReLU: final_conv_acts, :124),  h3 = relu(acts);
  * gcn_norm runs once.  Row g of z [n_graphs, R*F1 + R*F3] = [h1 of graph g node-major | h3 of graph g node-major]: the
- * reference's final_z (:128-138) written in place; acts [n_graphs*R, F3].  1 <= H0 <= 8, 1 <= F1, F3 <= 32 (any value:
- * a width is rounded up to a multiple of 4 inside LDS only) and igcn_sgcn_ori_lds_bytes(...) <= 150 KB, otherwise
+ * reference's final_z (:128-138) written in place; acts [n_graphs*R, F3].  1 <= H0 <= 8 (IGCN_MAX_H0), 1 <= F1, F3 <= 32
+ * (IGCN_STACK_MAX_WIDTH; any value: a width is rounded up to a multiple of 4 inside LDS only) and
+ * igcn_sgcn_ori_lds_bytes(...) <= 150 KB (IGCN_LDS_BUDGET_BYTES), otherwise
  * IGCN_ERR_UNSUPPORTED.  W1 [F1, H0], b1 [F1], W3 [F3, F1], b3 [F3].  A graph with more than max_edges edges sets status
  * bit 1 and leaves its outputs unwritten.
  * Backward recomputes the forward in LDS: dx_in [N, H0], dew_in [E] (every element written), dparams
@@ -1380,14 +1410,15 @@ int igcn_gdc_diffuse_tiled(int B, int R, int kernel, double param, int sparsify,
  * rows_out_lin [cap, F], rows_lin_f [cap, H], rows_sbj [cap] int64), adds loss * B to loss_sum[0] (fp64) and the correct
  * count to state[2], then advances the cursor.  If state[1] (overflow) is set or c + B > capacity it writes nothing and
  * sets state[1] = 1.  state int64 [3] and loss_sum are zeroed by the caller before the first batch.
- * igcn_eval_metrics: one call after the last batch, over the first n rows (1 <= n <= 65536; C <= 16).  parts: int64
- * workspace of 2 * ceil(n / 256).  out [8 + 3 NR + C C] fp64 = {rows written (state[0]), overflow (state[1]), loss =
+ * igcn_eval_metrics: one call after the last batch, over the first n rows (1 <= n <= 65536 = IGCN_EVAL_MAX_ROWS;
+ * C <= 16).  parts: int64 workspace of 2 * ceil(n / 256).  out [8 + 3 NR + C C] fp64 = {rows written (state[0]), overflow (state[1]), loss =
  * loss_sum / n, accuracy = correct / n, auc, weighted f1, sensitivity, specificity, corr[NR], r2[NR], rmse[NR],
  * confusion[C][C] (true-major counts)}.  auc / sensitivity / specificity only for C = 2 (else 0): auc is the Mann-Whitney
  * statistic of logp[:, 1] (ties 1/2; NaN when a class is absent, 0 when a score is NaN, as the reference's except
  * makes sklearn's error); sensitivity / specificity NaN on a zero denominator.  Per target: predictions' NaN -> 0,
  * pearsonr (NaN for a constant input), r2_score with force_finite, RMSE.  Integer counts and fixed-order fp64 sums:
  * bitwise reproducible. */
+#define IGCN_EVAL_MAX_ROWS 65536
 int igcn_eval_collect(int B, int C, int NR, int F, int H, const float* loss, const float* logp, const float* reg,
                       const float* out_lin, const float* lin_f, const int64_t* y, const float* clin, const int64_t* sbj,
                       int64_t capacity, int64_t* state, double* loss_sum, float* rows_logp, int64_t* rows_pred,
@@ -1493,7 +1524,8 @@ int igcn_knn_impute(int64_t S, int F, int k, const float* X, const int64_t* rows
  * Cluster labels (csrc/tsne.hip, csrc/kmeans.hip): util/image_cluster.py:148-282 — sklearn's exact t-SNE of the image
  * features (tsne_fdim), KMeans on the embedding (clust_y) and the inertia curve (calculate_WSS), restated on fp32 device
  * tensors.  4 <= S <= 4096 subjects, 1 <= D <= 1024 features, 2 embedding dimensions; KMeans: 1 <= N <= 65536 points of
- * width 1 <= d <= 1024, 1 <= k <= 16 clusters.  No atomics, one writer per element, fixed-order reductions.
+ * width 1 <= d <= 1024, 1 <= k <= 16 clusters (the IGCN_TSNE_* and IGCN_KMEANS_* limits below).  No atomics, one writer per
+ * element, fixed-order reductions.
  * igcn_tsne_sqdist: dist [S, S] = squared Euclidean distances of X [S, D] by direct differences (fp32 fma chain in feature
  *   order; dist[i][j] and dist[j][i] hold the same bits, the diagonal is exactly 0).
  * igcn_tsne_joint_p: _binary_search_perplexity (fp64, at most 100 bisection steps on beta against log(perplexity),
@@ -1517,9 +1549,16 @@ int igcn_knn_impute(int64_t S, int F, int k, const float* X, const int64_t* rows
  *   without points takes the centre of the largest one.  stats[2] = the total squared centre shift, stats[3] = 1 when
  *   the assignment before it changed a label (stats[1] != 0), else 0.
  * igcn_kmeanspp_step: one greedy k-means++ step from closest [N] (squared distance to the nearest chosen centre), pot [1]
- *   fp64 (their sum) and u [t] fp64 uniform numbers on the device, 1 <= t <= 8: candidates = left search of u_c pot in the
- *   fp64 inclusive scan of closest, clipped to N - 1; the candidate with the smallest new potential (ties: the first) is
- *   written to chosen [1], closest and pot are updated in place. */
+ *   fp64 (their sum) and u [t] fp64 uniform numbers on the device, 1 <= t <= 8 (IGCN_KMEANSPP_MAX_TRIALS): candidates =
+ *   left search of u_c pot in the fp64 inclusive scan of closest, clipped to N - 1; the candidate with the smallest new
+ *   potential (ties: the first) is written to chosen [1], closest and pot are updated in place. */
+#define IGCN_TSNE_MIN_S 4
+#define IGCN_TSNE_MAX_S 4096
+#define IGCN_TSNE_MAX_D 1024
+#define IGCN_KMEANS_MAX_N 65536
+#define IGCN_KMEANS_MAX_D 1024
+#define IGCN_KMEANS_MAX_K 16
+#define IGCN_KMEANSPP_MAX_TRIALS 8
 int igcn_tsne_sqdist(int S, int D, const float* X, float* dist, void* stream);
 size_t igcn_tsne_joint_p_scratch_doubles(int S);
 int igcn_tsne_joint_p(int S, double perplexity, const float* dist, float* P, double* betas, double* pstats,
@@ -1550,15 +1589,21 @@ int igcn_kmeanspp_step(int64_t N, int d, int t, const float* X, const double* u,
  *   stride ldm bytes (non-zero = 1; row p = group A of relabelling p), widened to bf16 0.0 / 1.0 while it is staged;
  *   the three planes accumulate into the same fp32 accumulators, so every product is exact and the only rounding is the
  *   fp32 accumulation.  G is never stored: maxabs[p] = max_e |G[p, e]| and, with g_obs [E] given,
- *   exceed[e] = #{p : |G[p, e]| >= |g_obs[e]|} (int32).  With g_obs NULL the call writes g [P, E] itself, for P <= 8 (the
- *   observed pass, P = 1, through the same tile code), and exceed is not touched.  Rows of member that start 16-byte
+ *   exceed[e] = #{p : |G[p, e]| >= |g_obs[e]|} (int32).  With g_obs NULL the call writes g [P, E] itself, for P <= 8
+ *   (IGCN_PERM_MAX_G_ROWS; the observed pass, P = 1, through the same tile code), and exceed is not touched.  Rows of member that start 16-byte
  *   aligned (ldm % 16 == 0, aligned base: all ldm bytes of every row must then be readable) are staged with 16-byte
  *   loads; the result does not depend on it.
  *   Per-tile partials ([P, tiles_E] maxima, [tiles_P, E] counts) in `scratch` (device, 16-byte aligned,
  *   igcn_perm_maxsum_scratch_bytes(P, E); 0 outside the limits) are folded in tile order by two small kernels.  One
  *   writer per element, no atomics: two runs give the same bits, and a row's results do not depend on the tile, the
  *   launch or the chunk it sits in (the accumulation order along S is the same for every row).  The library allocates
- *   nothing.  Limits: 4 <= S <= 4096, 1 <= E <= 2^20, 1 <= P <= 65536 per launch. */
+ *   nothing.  Limits: 4 <= S <= 4096, 1 <= E <= 2^20, 1 <= P <= 65536 per launch
+ *   (IGCN_PERM_MIN_S, IGCN_PERM_MAX_S, IGCN_PERM_MAX_E, IGCN_PERM_MAX_P). */
+#define IGCN_PERM_MIN_S 4
+#define IGCN_PERM_MAX_S 4096
+#define IGCN_PERM_MAX_E 1048576
+#define IGCN_PERM_MAX_P 65536
+#define IGCN_PERM_MAX_G_ROWS 8
 size_t igcn_perm_planes_bytes(int S, int E);
 int igcn_perm_plane_dims(int S, int E, int* dims);
 int igcn_perm_prepare(int64_t S_all, int S, int E, const float* x, const int64_t* rows, int standardize, double* mean,

@@ -368,16 +368,16 @@ EXEMPT = {
     "ig-gcn_amd/sgcn_img_snp.py:33": _PARAM, "ig-gcn_amd/sgcn_img_snp.py:214": _PARAM,
     "ig-gcn_amd/sgcn_img_snp.py:215": _PARAM, "ig-gcn_amd/sgcn_img_snp.py:216": _PARAM,
     "ig-gcn_amd/sgcn_img_snp.py:217": _PARAM,
-    "ig-gcn_amd/ops.py:1801": _CPU + "Csr builds its row pointers on the host before the upload",
-    "ig-gcn_amd/ops.py:1804": _CPU + "Csr builds its transposed row pointers on the host before the upload",
-    "ig-gcn_amd/ops.py:1807": _CPU + "Csr pads an empty host index list before the upload",
-    "ig-gcn_amd/ops.py:1823": _CPU + "the GO attention walk order is laid out in a host buffer, then uploaded",
+    "ig-gcn_amd/ops.py:1808": _CPU + "Csr builds its row pointers on the host before the upload",
+    "ig-gcn_amd/ops.py:1811": _CPU + "Csr builds its transposed row pointers on the host before the upload",
+    "ig-gcn_amd/ops.py:1814": _CPU + "Csr pads an empty host index list before the upload",
+    "ig-gcn_amd/ops.py:1830": _CPU + "the GO attention walk order is laid out in a host buffer, then uploaded",
     "ig-gcn_amd/train.py:116": _CPU + "FlatAdam's pinned host copies of the pointer table",
     "ig-gcn_amd/train.py:1500": _CPU + "eval_scores_of works on .cpu() copies of the evaluation's rows",
-    "ig-gcn_amd/ops.py:662": _ABSENT + "test_front_kernel_equals_plan_build_mask_and_stack",
-    "ig-gcn_amd/ops.py:3518": _ABSENT + "test_gate_encoder_vs_fp64 (test_gpu_guide.py)",
+    "ig-gcn_amd/ops.py:670": _ABSENT + "test_front_kernel_equals_plan_build_mask_and_stack",
+    "ig-gcn_amd/ops.py:3525": _ABSENT + "test_gate_encoder_vs_fp64 (test_gpu_guide.py)",
     "ig-gcn_amd/saliency.py:131": _ABSENT[:24] + ": a zeros stand-in for an input the model does not read, returned, no kernel",
-    "ig-gcn_amd/snps.py:98": "no kernel operand: the zero-dim reconstruction term of the unfused route when lambda0 == 0.0; "
+    "ig-gcn_amd/snps.py:99": "no kernel operand: the zero-dim reconstruction term of the unfused route when lambda0 == 0.0; "
                              "composed by torch, handed to no kernel",
     "ig-gcn_amd/train.py:592": "no kernel operand: a zero-dim placeholder taken once per process (whichever test first "
                                "runs a train step), only its device, dtype and shape are read",
