@@ -185,14 +185,12 @@ __device__ __forceinline__ void gcn_norm_bwd_products(float* lds, const GraphLds
 
 // second half: short sums of consecutive words per node -> d deg, a barrier, then d(edge weight) of every stored edge
 // of the graph to dew_in[eb + k].  Of a node's stored loops only the one that counted (n.loop) gets the loop's gradient.
-__device__ __forceinline__ void gcn_norm_bwd_edges(float* lds, const GraphLds& t, const GcnNormLds& n, int R, int ne,
-                                                   int32_t eb, float* __restrict__ dew_in, int nt) {
-  const int tid = threadIdx.x;
-  const int32_t* ssrc = lds_i32(lds, t.src);
-  const int32_t* sdst = lds_i32(lds, t.dst);
+// Its two steps are functions of their own for a caller that consumes the edge gradients instead of storing them
+// (k_sgcn_stack_bwd's masked copy, csrc/sgcn_fused.hip).
+__device__ __forceinline__ void gcn_norm_bwd_ddeg(float* lds, const GraphLds& t, const GcnNormLds& n, int R, int nt) {
   const int32_t* ssptr = lds_i32(lds, t.sptr);
   const int32_t* stptr = lds_i32(lds, t.tptr);
-  for (int i = tid; i < R; i += nt) {
+  for (int i = threadIdx.x; i < R; i += nt) {
     float dd = 0.f;
     for (int p = ssptr[i]; p < ssptr[i + 1]; ++p) dd += lds[n.v1 + p];     // list order; stored loops add an exact 0
     for (int p = stptr[i]; p < stptr[i + 1]; ++p) dd += lds[n.v2 + p];
@@ -200,18 +198,27 @@ __device__ __forceinline__ void gcn_norm_bwd_edges(float* lds, const GraphLds& t
     dd += 2.f * lds[n.dwloop + i] * lds[n.wl + i] * di;
     lds[n.ddeg + i] = -0.5f * di * di * di * dd;
   }
-  __syncthreads();
-  for (int k = tid; k < ne; k += nt) {
-    const int s = ssrc[k], tn = sdst[k];
-    float g;
-    if (s != tn) {
-      g = lds[n.dis + s] * lds[n.dis + tn] * lds[n.dwhat + k] + lds[n.ddeg + tn];
-    } else {
-      g = (lds_i32(lds, n.loop)[s] == eb + k) ? lds[n.ddeg + s] + lds[n.dis + s] * lds[n.dis + s] * lds[n.dwloop + s]
-                                              : 0.f;
-    }
-    dew_in[eb + k] = g;
+}
+
+// d(edge weight) of stored edge k of the graph (behind gcn_norm_bwd_ddeg and a barrier)
+__device__ __forceinline__ float gcn_norm_bwd_edge(const float* lds, const GraphLds& t, const GcnNormLds& n, int32_t eb,
+                                                   int k) {
+  const int s = lds_i32(lds, t.src)[k], tn = lds_i32(lds, t.dst)[k];
+  float g;
+  if (s != tn) {
+    g = lds[n.dis + s] * lds[n.dis + tn] * lds[n.dwhat + k] + lds[n.ddeg + tn];
+  } else {
+    g = (lds_i32(lds, n.loop)[s] == eb + k) ? lds[n.ddeg + s] + lds[n.dis + s] * lds[n.dis + s] * lds[n.dwloop + s]
+                                            : 0.f;
   }
+  return g;
+}
+
+__device__ __forceinline__ void gcn_norm_bwd_edges(float* lds, const GraphLds& t, const GcnNormLds& n, int R, int ne,
+                                                   int32_t eb, float* __restrict__ dew_in, int nt) {
+  gcn_norm_bwd_ddeg(lds, t, n, R, nt);
+  __syncthreads();
+  for (int k = threadIdx.x; k < ne; k += nt) dew_in[eb + k] = gcn_norm_bwd_edge(lds, t, n, eb, k);
 }
 
 // ---- the list walks of one layer -------------------------------------------------------------------------------------

@@ -138,19 +138,6 @@ k_gcn_norm_bwd_deg_tiled(int64_t n_nodes, const float* __restrict__ ew, const fl
 }
 
 #include "mask_reg.h"
-struct EmReg {                    // greg == NULL: no regulariser in this launch
-  const float* greg;              // backward: d loss / d (regulariser), device scalar
-  const float* snps;              // SNP mask logits [n_snps] (may be NULL)
-  float* dsnps;                   // backward: their gradient (regulariser part + mask part)
-  int n_snps;
-  float l1_x, ent_x, l1_e, ent_e, eps;
-  // the SNP mask itself (cal_probability :147-151) for the stacked sweep: feat [B, n_snps] -> full [2B, n_snps] =
-  // (feat | feat * sigmoid(logits)); backward: d_full [2B, n_snps] (its masked half is read)
-  const float* feat;
-  float* full;
-  const float* d_full;
-  int B;
-};
 
 // edge-mask backward node pass, dense graphs (formula: k_edge_mask_bwd_nodes); partial row layout identical
 __global__ void __launch_bounds__(TL_T)
@@ -384,12 +371,23 @@ k_edge_mask_bwd_nodes(int64_t n_nodes, int rois, int h0, const float* __restrict
 // dprob[r,h] = sum_b gx[(b*rois + r), h]: one block per (roi, feature).  One MORE block sums the node kernel's block
 // partials into the bias gradient dpb [2 h0] (16 row lanes x 16 column slots, lanes combined in order) — that sum used
 // to be two further launches (column sums of the partial rows, then the pick-and-store).
+// Behind a node pass that left g_i and not dx_i (k_sgcn_stack_bwd's masked copy, csrc/sgcn_fused.hip) the workgroups from
+// dx_first on write dx = g * prob + dx_plain, EM_DX_ITEMS elements each: the node kernel's expression, one fused
+// multiply-add as there.
+#define EM_DX_ITEMS 1024
 __global__ void __launch_bounds__(256)
 k_edge_mask_bwd_prob(int64_t n_graphs, int rois, int h0, const float* __restrict__ gx, float* __restrict__ dprob,
                      int64_t nblk, const float* __restrict__ partial, float* __restrict__ dpb,
-                     const float* __restrict__ prob, EmReg rg) {
+                     const float* __restrict__ prob, EmReg rg, int dx_first, const float* __restrict__ g_part,
+                     const float* __restrict__ dx_plain, float* __restrict__ dx) {
   __shared__ float red[16 * 16];
   const int j = blockIdx.x;
+  if (j >= dx_first) {
+    const int64_t n = n_graphs * rois * h0;
+    for (int64_t t = (int64_t)(j - dx_first) * EM_DX_ITEMS + threadIdx.x, end = t + EM_DX_ITEMS; t < end && t < n; t += 256)
+      dx[t] = __fmaf_rn(g_part[t], prob[t % (rois * h0)], dx_plain[t]);
+    return;
+  }
   if (j > rois * h0) {                               // one extra workgroup per SNP: the mask logit's gradient —
     const int k = j - (rois * h0 + 1);               // regulariser part + (stacked sweep) sum_b d_masked[b,k] feat[b,k]
     float acc = 0.f;
@@ -456,11 +454,21 @@ static int em_bwd_impl(int64_t n_nodes, int64_t n_edges, int rois, int h0, const
     hipLaunchKernelGGL(k_edge_mask_bwd_nodes<4>, dim3((unsigned)nblk), dim3(256), 0, st, n_nodes, rois, h0, x, prob,
                        prob_bias, ew, e, d_xm, d_ewm, d_e, d_x_plain, tgt_ptr, tgt_perm, src_ptr, src_perm, dx, gx, part, rg,
                        inv_ne);
+  IGCN_CHECK_LAUNCH("edge_mask_bwd");
+  return igcn_launch_edge_mask_bwd_tail(n_nodes, rois, h0, gx, part, nblk, nullptr, nullptr, nullptr, dprob, dprob_bias, prob,
+                                        rg, st);                     // (dx is the node kernel's here)
+}
+
+int igcn_launch_edge_mask_bwd_tail(int64_t n_nodes, int rois, int h0, const float* gx, const float* partial, int64_t rows,
+                                   const float* g_part, const float* dx_plain, float* dx, float* dprob, float* dprob_bias,
+                                   const float* prob, const EmReg& rg, hipStream_t st) {
   static_assert(2 * IGCN_MAX_H0 <= 16, "k_edge_mask_bwd_prob: the bias-gradient block has 16 column slots");
   const bool snps_block = rg.greg && rg.snps && rg.dsnps && rg.n_snps > 0;
-  hipLaunchKernelGGL(k_edge_mask_bwd_prob, dim3((unsigned)(rois * h0 + 1 + (snps_block ? rg.n_snps : 0))), dim3(256), 0, st,
-                     n_nodes / rois, rois, h0, gx, dprob, nblk, part, dprob_bias, prob, rg);
-  IGCN_CHECK_LAUNCH("edge_mask_bwd");
+  const int dx_first = rois * h0 + 1 + (snps_block ? rg.n_snps : 0);
+  const int dx_blocks = dx ? (int)igcn_cdiv(n_nodes * h0, EM_DX_ITEMS) : 0;
+  hipLaunchKernelGGL(k_edge_mask_bwd_prob, dim3((unsigned)(dx_first + dx_blocks)), dim3(256), 0, st, n_nodes / rois, rois,
+                     h0, gx, dprob, rows, partial, dprob_bias, prob, rg, dx_first, g_part, dx_plain, dx);
+  IGCN_CHECK_LAUNCH("edge_mask_bwd_tail");
   return IGCN_OK;
 }
 

@@ -618,7 +618,57 @@ __host__ __device__ inline int sf_param_offset(int l, int H0, int F) {
 
 extern "C" int igcn_sgcn_stack_param_floats(int H0, int F, int L) { return sf_param_offset(L, H0, F); }
 
-template <int F>
+// The edge-mask backward's node pass (k_edge_mask_bwd_nodes<4> of csrc/sgcn.hip) for the stacked (plain | masked) batch
+// of a train step, done by the masked copy's workgroups of k_sgcn_stack_bwd<F, true>: graph g of the masked copy is
+// workgroup n_graphs + g, and what that pass fetches — the lists, d_xm (dX of layer 0) and d_ewm (gcn_norm's edge
+// gradients) — is in its LDS already, in graph-local numbering.  x, prob, ew, e, d_e are the batch's own (plain) arrays.
+struct SfMaskBwd {
+  int n_graphs, n_edges;                           // of ONE copy
+  const float *x, *prob, *pb, *ew, *e;
+  const float* d_e;                                // or NULL
+  const float* greg;                               // d loss / d (regulariser), device scalar; or NULL
+  float l1_e, ent_e, eps, inv_ne;
+  float* gx;                                       // [N, H0]  g_i * x_i
+  float* g_part;                                   // [N, H0]  g_i: the tail launch writes dx = g * prob + dx_plain
+  float* pb_partial;                               // [n_graphs, 2 IGCN_MAX_H0]  (sum_i x_i prob S_i | sum_i x_i prob T_i)
+};
+
+// dz_k = up_k e_k (1 - e_k) as its two factors, a_k = up_k e_k into A and b_k = 1 - e_k into Bf: a lane of the node pass
+// takes its first list entry as a_k b_k and every further one as one fused multiply-add onto its sum, and the sums
+// here are held to those bits — so the roundings are spelled out and nothing is left to contraction.
+__device__ __forceinline__ void sf_mask_edge_term(const SfMaskBwd& mk, float gre, float d_ewm, float ewk, float ek,
+                                                  float dek, float& a, float& b) {
+  float up;
+  {
+#pragma clang fp contract(off)
+    up = d_ewm * ewk + dek;
+  }
+  if (mk.greg) up = __fmaf_rn(gre, em_reg_grad(ek, mk.l1_e, mk.ent_e, mk.eps), up);
+  {
+#pragma clang fp contract(off)
+    a = up * ek;
+    b = 1.f - ek;
+  }
+}
+
+// one lane's share of a node's list [p0, p1) (entries p0 + sub, p0 + sub + 4, ... in list order)
+__device__ __forceinline__ float sf_mask_list_sum(const int32_t* perm, const float* A, const float* Bf, int p0, int p1,
+                                                  int sub) {
+  float s = 0.f;
+  int p = p0 + sub;
+  if (p < p1) {
+#pragma clang fp contract(off)
+    const int k = perm[p];
+    s = A[k] * Bf[k];
+  }
+  for (p += 4; p < p1; p += 4) {
+    const int k = perm[p];
+    s = __fmaf_rn(A[k], Bf[k], s);
+  }
+  return s;
+}
+
+template <int F, bool MASK>
 __global__ void __launch_bounds__(SF_TB)
 k_sgcn_stack_bwd(int R, int Emax, int H0, int L, const float* __restrict__ x_in, const float* __restrict__ ew_in,
                  const int32_t* __restrict__ src32, const int32_t* __restrict__ dst32,
@@ -627,11 +677,14 @@ k_sgcn_stack_bwd(int R, int Emax, int H0, int L, const float* __restrict__ x_in,
                  const int32_t* __restrict__ loop_edge, SfParams prm, const float* __restrict__ dxcat,
                  const float* __restrict__ dxcat2 /*a second consumer's gradient, added on load; or NULL*/,
                  float* __restrict__ dx_in, float* __restrict__ dew_in, float* __restrict__ dpar_partial, int P,
-                 int32_t* __restrict__ status) {
+                 int32_t* __restrict__ status, SfMaskBwd mk) {
   extern __shared__ float sf_lds[];
   const SfLayout o = sf_layout(R, Emax, H0, F, L, 1);
   const int tid = threadIdx.x;
   const int64_t nb = (int64_t)blockIdx.x * R;
+  // MASK: the masked copy's workgroups consume d_xm / d_ewm themselves (below) instead of storing dx_in / dew_in
+  const bool masked = MASK && (int)blockIdx.x >= mk.n_graphs;
+  const int64_t nbp = nb - (int64_t)mk.n_graphs * R;   // the graph's first node in the batch's own numbering
   SF_PROBE(8);
   const int32_t eb = tgt_ptr[nb];
   const int D = L * F;
@@ -652,7 +705,12 @@ k_sgcn_stack_bwd(int R, int Emax, int H0, int L, const float* __restrict__ x_in,
   const int ne = sf_stage<true>(sf_lds, o, R, Emax, H0, nb, x_in, ew_in, src32, dst32, tgt_ptr, tgt_perm, src_ptr,
                                 src_perm, loop_edge, prm, F, L, status);
   if (ne < 0) {                                        // refused graph: defined (zero) outputs, flagged in `status`
-    for (int e = tid; e < R * H0; e += SF_TB) dx_in[nb * H0 + e] = 0.f;
+    if (masked) {
+      for (int e = tid; e < R * H0; e += SF_TB) mk.gx[nbp * H0 + e] = mk.g_part[nbp * H0 + e] = 0.f;
+      if (tid < 2 * IGCN_MAX_H0) mk.pb_partial[(int64_t)((int)blockIdx.x - mk.n_graphs) * 2 * IGCN_MAX_H0 + tid] = 0.f;
+    } else {
+      for (int e = tid; e < R * H0; e += SF_TB) dx_in[nb * H0 + e] = 0.f;
+    }
     for (int e = tid; e < P; e += SF_TB) dpar_partial[(int64_t)blockIdx.x * P + e] = 0.f;
     return;
   }
@@ -821,11 +879,110 @@ k_sgcn_stack_bwd(int R, int Emax, int H0, int L, const float* __restrict__ x_in,
     prow[pend_off + e] = acc;
   }
   SF_PROBE(13);
+  // the masked copy's own operands — this thread's edge and this thread's (node, feature) element — are requested here,
+  // three phases ahead of their first use, and cost no register during the layer loop
+  const int32_t ebp = eb - mk.n_edges;                 // the graph's first edge in the batch's own numbering
+  float m_e = 0.f, m_ew = 0.f, m_de = 0.f, m_x = 0.f, m_p = 0.f;
+  if (masked) {
+    if (tid < ne) {
+      m_e = mk.e[ebp + tid];
+      m_ew = mk.ew[ebp + tid];
+      if (mk.d_e) m_de = mk.d_e[ebp + tid];
+    }
+    if (tid < R * H0) {
+      m_x = mk.x[nbp * H0 + tid];
+      m_p = mk.prob[tid];
+    }
+  }
   // ---- gcn_norm backward (k_gcn_norm_bwd_deg / _edge of sgcn.hip, per graph)
   gcn_norm_bwd_products(sf_lds, o.t, o.n, ne, SF_TB);
   __syncthreads();
-  gcn_norm_bwd_edges(sf_lds, o.t, o.n, R, ne, eb, dew_in, SF_TB);
-  for (int e = tid; e < R * H0; e += SF_TB) dx_in[nb * H0 + e] = dX[e];
+  if (!masked) {
+    gcn_norm_bwd_edges(sf_lds, o.t, o.n, R, ne, eb, dew_in, SF_TB);
+    for (int e = tid; e < R * H0; e += SF_TB) dx_in[nb * H0 + e] = dX[e];
+  } else {
+    // ---- edge-mask backward, node pass (formula and order of summation: k_edge_mask_bwd_nodes<4> of csrc/sgcn.hip).
+    // v1 / v2, ddeg, dwloop and dX are reused as their last readers finish: the edge factors a_k | b_k, S_i, T_i and
+    // x_i prob.
+    gcn_norm_bwd_ddeg(sf_lds, o.t, o.n, R, SF_TB);
+    __syncthreads();
+    float* A = sf_lds + o.n.v1;
+    float* Bf = sf_lds + o.n.v2;
+    const float gre = mk.greg ? mk.greg[0] * mk.inv_ne : 0.f;
+    for (int k = tid; k < ne; k += SF_TB) {
+      const float d_ewm = gcn_norm_bwd_edge(sf_lds, o.t, o.n, eb, k);
+      const bool own = k == tid;
+      const float ek = own ? m_e : mk.e[ebp + k], ewk = own ? m_ew : mk.ew[ebp + k];
+      const float dek = own ? m_de : (mk.d_e ? mk.d_e[ebp + k] : 0.f);
+      float a, b;
+      sf_mask_edge_term(mk, gre, d_ewm, ewk, ek, dek, a, b);
+      A[k] = a;
+      Bf[k] = b;
+    }
+    __syncthreads();
+    float* Ss = sf_lds + o.n.ddeg;                     // S_i = sum_{k: src = i} dz_k, T_i = sum_{k: dst = i} dz_k:
+    float* Ts = sf_lds + o.n.dwloop;                   // four lanes per node, combined as group_sum_all<4> does
+    const int32_t* stptr = lds_i32(sf_lds, o.t.tptr);
+    for (int idx = tid; idx < 4 * R; idx += SF_TB) {
+      const int i = idx >> 2, sub = idx & 3;
+      float S = sf_mask_list_sum(lds_i32(sf_lds, o.t.sperm), A, Bf, ssptr[i], ssptr[i + 1], sub);
+      float T = sf_mask_list_sum(lds_i32(sf_lds, o.t.tperm), A, Bf, stptr[i], stptr[i + 1], sub);
+      S = group_sum_all<4>(S);
+      T = group_sum_all<4>(T);
+      if (sub == 0) {
+        Ss[i] = S;
+        Ts[i] = T;
+      }
+    }
+    __syncthreads();
+    // g_i = d_xm_i + pb[:h0] S_i + pb[h0:] T_i per (node, feature) element; the first element of a thread leaves with
+    // the last stores of the kernel (nothing is stored in front of a barrier)
+    float g0 = 0.f, gx0 = 0.f;
+    for (int e = tid; e < R * H0; e += SF_TB) {
+      const int i = e / H0, h = e - i * H0;
+      const bool own = e == tid;
+      const float xv = own ? m_x : mk.x[nbp * H0 + e], pv = own ? m_p : mk.prob[e];
+      float g, gxv, xp;
+      {
+#pragma clang fp contract(off)
+        g = dX[e] + mk.pb[h] * Ss[i] + mk.pb[H0 + h] * Ts[i];
+        gxv = g * xv;
+        xp = xv * pv;
+      }
+      dX[e] = xp;
+      if (own) {
+        g0 = g;
+        gx0 = gxv;
+      } else {
+        mk.g_part[nbp * H0 + e] = g;
+        mk.gx[nbp * H0 + e] = gxv;
+      }
+    }
+    __syncthreads();
+    // the graph's bias-gradient partial row: 16 row lanes x 16 column slots, lanes combined in order (the layout
+    // k_edge_mask_bwd_prob sums: S columns at [0, h0), T columns at [IGCN_MAX_H0, IGCN_MAX_H0 + h0))
+    static_assert(2 * IGCN_MAX_H0 <= 16 && SF_TB >= 256, "the bias-gradient partials take 16 x 16 threads");
+    const int rl = tid >> 4, cs = tid & 15;
+    if (tid < 256) {
+      float t = 0.f;
+      if (cs < 2 * H0) {
+        const int h = cs < H0 ? cs : cs - H0;
+        const float* st = cs < H0 ? Ss : Ts;
+        for (int i = rl; i < R; i += 16) t += dX[i * H0 + h] * st[i];
+      }
+      red_db[tid] = t;
+    }
+    __syncthreads();
+    if (tid < 2 * H0) {
+      float a = 0.f;
+      for (int l = 0; l < 16; ++l) a += red_db[l * 16 + tid];
+      mk.pb_partial[(int64_t)((int)blockIdx.x - mk.n_graphs) * 2 * IGCN_MAX_H0 + (tid < H0 ? tid : IGCN_MAX_H0 + tid - H0)] = a;
+    }
+    if (tid < R * H0) {
+      mk.g_part[nbp * H0 + tid] = g0;
+      mk.gx[nbp * H0 + tid] = gx0;
+    }
+  }
   for (int e = tid; e < P; e += SF_TB) dpar_partial[(int64_t)blockIdx.x * P + e] = prow[e];
   SF_PROBE(14);
 }
@@ -937,6 +1094,42 @@ extern "C" int igcn_sgcn_front_fwd(int64_t n_nodes, int64_t n_edges, int n_graph
   return IGCN_OK;
 }
 
+// one launch of k_sgcn_stack_bwd: mk == NULL the plain kernel, else the one whose masked copy does the mask's node pass
+static int sf_launch_bwd(const char* nm, int64_t n_graphs, int R, int max_edges, int H0, int F, int L, const float* x_in,
+                         const float* ew_in, const int32_t* src32, const int32_t* dst32, const int32_t* tgt_ptr,
+                         const int32_t* tgt_perm, const int32_t* src_ptr, const int32_t* src_perm,
+                         const int32_t* loop_edge, const float* const* W, const float* const* b, const float* dxcat,
+                         const float* dxcat2, float* dx_in, float* dew_in, float* dparams, float* scratch,
+                         int32_t* status, const SfMaskBwd* mk, hipStream_t st) {
+  int rc = sf_check(nm, n_graphs, R, max_edges, H0, F, L, 1);
+  if (rc) return rc;
+  IGCN_REQUIRE(((uintptr_t)dxcat & 15) == 0 && ((uintptr_t)dxcat2 & 15) == 0,
+               "%s: dxcat / dxcat2 must be 16-byte aligned", nm);
+  SfParams prm = {};
+  for (int l = 0; l < L; ++l) { prm.W[l] = W[l]; prm.b[l] = b[l]; }
+  const size_t lds = igcn_sgcn_stack_lds_bytes(R, max_edges, H0, F, L, 1);
+  const int P = igcn_sgcn_stack_param_floats(H0, F, L);
+#define SF_BWD(FV, MV)                                                                                            \
+  {                                                                                                               \
+    if (lds > 64 * 1024) IGCN_ALLOW_BIG_LDS((k_sgcn_stack_bwd<FV, MV>));                                          \
+    hipLaunchKernelGGL((k_sgcn_stack_bwd<FV, MV>), dim3((unsigned)n_graphs), dim3(SF_TB), lds, st, R, max_edges,  \
+                       H0, L, x_in, ew_in, src32, dst32, tgt_ptr, tgt_perm, src_ptr, src_perm, loop_edge, prm,    \
+                       dxcat, dxcat2, dx_in, dew_in, scratch, P, status, mk ? *mk : SfMaskBwd{});                \
+  }
+#define SF_BWD_F(MV)                                                                                              \
+  switch (F) {                                                                                                    \
+    case 4: SF_BWD(4, MV) break;                                                                                  \
+    case 8: SF_BWD(8, MV) break;                                                                                  \
+    case 16: SF_BWD(16, MV) break;                                                                                \
+    default: SF_BWD(32, MV) break;                                                                                \
+  }
+  if (mk) SF_BWD_F(true) else SF_BWD_F(false)
+#undef SF_BWD_F
+#undef SF_BWD
+  IGCN_CHECK_LAUNCH(nm);
+  return igcn_launch_reduce_rows_final(scratch, n_graphs, P, P, dparams, st);
+}
+
 extern "C" int igcn_sgcn_stack_bwd(int64_t n_graphs, int R, int max_edges, int H0, int F, int L, const float* x_in,
                                    const float* ew_in, const int32_t* src32, const int32_t* dst32,
                                    const int32_t* tgt_ptr, const int32_t* tgt_perm, const int32_t* src_ptr,
@@ -945,29 +1138,43 @@ extern "C" int igcn_sgcn_stack_bwd(int64_t n_graphs, int R, int max_edges, int H
                                    float* dew_in,
                                    float* dparams /*[param_floats]*/, float* scratch /*[n_graphs * param_floats]*/,
                                    int32_t* status /*device word or NULL*/, void* stream) {
-  int rc = sf_check("sgcn_stack_bwd", n_graphs, R, max_edges, H0, F, L, 1);
-  if (rc) return rc;
-  IGCN_REQUIRE(((uintptr_t)dxcat & 15) == 0 && ((uintptr_t)dxcat2 & 15) == 0,
-               "sgcn_stack_bwd: dxcat / dxcat2 must be 16-byte aligned");
-  SfParams prm = {};
-  for (int l = 0; l < L; ++l) { prm.W[l] = W[l]; prm.b[l] = b[l]; }
-  const size_t lds = igcn_sgcn_stack_lds_bytes(R, max_edges, H0, F, L, 1);
-  const int P = igcn_sgcn_stack_param_floats(H0, F, L);
+  return sf_launch_bwd("sgcn_stack_bwd", n_graphs, R, max_edges, H0, F, L, x_in, ew_in, src32, dst32, tgt_ptr, tgt_perm,
+                       src_ptr, src_perm, loop_edge, W, b, dxcat, dxcat2, dx_in, dew_in, dparams, scratch, status, nullptr,
+                       (hipStream_t)stream);
+}
+
+// igcn_sgcn_stack_bwd on the 2-copy (plain | masked) plan of a train step + igcn_edge_mask_bwd_reg, as TWO launches
+// instead of three: the masked copy's workgroups do the mask's node pass (SfMaskBwd), k_edge_mask_bwd_prob stays the tail
+// and also writes dx.  n_graphs / n_edges: of ONE copy.  dx_plain [N, H0] and dew_plain [E] receive the plain copy's
+// stack gradients; mask_scratch: 2 N H0 + n_graphs * 2 IGCN_MAX_H0 floats (gx | g | the graphs' bias-gradient rows).
+extern "C" int igcn_sgcn_stack_bwd_mask(int64_t n_graphs, int64_t n_edges, int R, int max_edges, int H0, int F, int L,
+                                        const float* x_in, const float* ew_in, const int32_t* src32, const int32_t* dst32,
+                                        const int32_t* tgt_ptr, const int32_t* tgt_perm, const int32_t* src_ptr,
+                                        const int32_t* src_perm, const int32_t* loop_edge, const float* const* W,
+                                        const float* const* b, const float* dxcat, const float* dxcat2, float* dx_plain,
+                                        float* dew_plain, float* dparams, float* scratch, int32_t* status, const float* x,
+                                        const float* prob, const float* prob_bias, const float* ew, const float* e,
+                                        const float* d_e, const float* d_reg, const float* snps_logits, int n_snps,
+                                        float l1_x, float ent_x, float l1_e, float ent_e, float eps, float* dx,
+                                        float* dprob, float* dprob_bias, float* dsnps, float* mask_scratch,
+                                        const float* snps_feat, int snps_rows, const float* d_snps_full, void* stream) {
+  IGCN_REQUIRE(n_graphs > 0 && n_edges > 0 && 2 * n_graphs * R < ((int64_t)1 << 31) && 2 * n_edges < ((int64_t)1 << 31) &&
+                   n_edges < 16 * n_graphs * R,
+               "sgcn_stack_bwd_mask: a sparse batch whose 2-copy sizes stay inside int32");
+  IGCN_REQUIRE(x && prob && prob_bias && ew && e && dx_plain && dew_plain && dprob && dprob_bias && mask_scratch,
+               "sgcn_stack_bwd_mask: null argument");
+  const int64_t n = n_graphs * R;
+  float* gx = mask_scratch;
+  float* g_part = gx + n * H0;
+  float* part = g_part + n * H0;
+  const SfMaskBwd mk = {(int)n_graphs, (int)n_edges, x, prob, prob_bias, ew, e, d_e, d_reg, l1_e, ent_e, eps,
+                        1.0f / (float)n_edges, gx, g_part, part};
   hipStream_t st = (hipStream_t)stream;
-#define SF_BWD(FV)                                                                                                \
-  {                                                                                                               \
-    if (lds > 64 * 1024) IGCN_ALLOW_BIG_LDS((k_sgcn_stack_bwd<FV>));                                              \
-    hipLaunchKernelGGL((k_sgcn_stack_bwd<FV>), dim3((unsigned)n_graphs), dim3(SF_TB), lds, st, R, max_edges, H0, L, \
-                       x_in, ew_in, src32, dst32, tgt_ptr, tgt_perm, src_ptr, src_perm, loop_edge, prm, dxcat,     \
-                       dxcat2, dx_in, dew_in, scratch, P, status);                                                 \
-  }
-  switch (F) {
-    case 4: SF_BWD(4) break;
-    case 8: SF_BWD(8) break;
-    case 16: SF_BWD(16) break;
-    default: SF_BWD(32) break;
-  }
-#undef SF_BWD
-  IGCN_CHECK_LAUNCH("sgcn_stack_bwd");
-  return igcn_launch_reduce_rows_final(scratch, n_graphs, P, P, dparams, st);
+  int rc = sf_launch_bwd("sgcn_stack_bwd_mask", 2 * n_graphs, R, max_edges, H0, F, L, x_in, ew_in, src32, dst32, tgt_ptr,
+                         tgt_perm, src_ptr, src_perm, loop_edge, W, b, dxcat, dxcat2, dx_plain, dew_plain, dparams, scratch,
+                         status, &mk, st);
+  if (rc) return rc;
+  const EmReg rg = {d_reg, snps_logits, dsnps, snps_logits ? n_snps : 0, l1_x, ent_x, l1_e, ent_e, eps, snps_feat, nullptr,
+                    d_snps_full, snps_feat ? snps_rows : 0};
+  return igcn_launch_edge_mask_bwd_tail(n, R, H0, gx, part, n_graphs, g_part, dx_plain, dx, dprob, dprob_bias, prob, rg, st);
 }

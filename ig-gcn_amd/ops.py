@@ -488,7 +488,7 @@ def _edge_mask_reg_backward(x, prob, pb, ew, e, snps, feat, reg, plan, rois, d_x
     n, h0 = x.shape
     d_xm, d_ewm, d_e, d_xp, d_full = (_f32(t) if t is not None else None for t in (d_xm, d_ewm, d_e, d_xp, d_full))
     # the partials' gradient is one scalar, repeated (ops.LossHead); none: the regulariser was not used
-    greg = _f32(d_regp[:1]).reshape(1) if d_regp is not None else torch.zeros(1, dtype=torch.float32, device=x.device)
+    greg = _reg_upstream(d_regp, x.device)
     dx, dprob, dpb = torch.empty_like(x), torch.empty_like(prob), torch.empty_like(pb)
     dsnps = torch.empty(snps_shape, dtype=torch.float32, device=x.device) if snps is not None else None
     scratch = torch.empty(n * h0 + 16 * ((n + 3) // 4) + 16, dtype=torch.float32, device=x.device)
@@ -661,31 +661,31 @@ class SgcnStack(torch.autograd.Function):
         return (dx, dew, None, None, *grads)
 
 
-def _sgcn_stack_backward(x_in, ew_in, wb, plan, rois, final, dxcat, dxcat2):
-    """igcn_sgcn_stack_bwd on the batched plan ``plan``: (dx_in, dew_in, [dW_0, db_0, dW_1, ...])."""
+def _sgcn_stack_backward(x_in, ew_in, wb, plan, rois, final, dxcat, dxcat2, mask_call=None):
+    """igcn_sgcn_stack_bwd on ``plan``: (dx_in, dew_in, [dW_0, db_0, ...]); ``mask_call``: ops._front_backward's launch."""
     ws, bs = wb[0::2], wb[1::2]
     if dxcat is None:
         dxcat, dxcat2 = dxcat2, None
     if dxcat is None:
         dxcat = torch.zeros(x_in.shape[0], len(ws) * ws[0].shape[0], dtype=torch.float32, device=x_in.device)
-    dxcat = _f32(dxcat)
-    dxcat2 = _f32(dxcat2) if dxcat2 is not None else None
+    dxcat, dxcat2 = _f32(dxcat), (_f32(dxcat2) if dxcat2 is not None else None)
     n, h0 = x_in.shape
     f, layers = ws[0].shape[0], len(ws)
-    emax = plan._stack_dims[1]
-    g = n // rois
-    lib = _lib.load()
-    npar = int(lib.igcn_sgcn_stack_param_floats(h0, f, layers))
-    dx, dew = torch.empty_like(x_in), torch.empty_like(ew_in)
+    emax, g = plan._stack_dims[1], n // rois
+    npar = int(_lib.load().igcn_sgcn_stack_param_floats(h0, f, layers))
     dpar = torch.empty(npar, dtype=torch.float32, device=x_in.device)
     scratch = _keep(torch.empty(g * npar, dtype=torch.float32, device=x_in.device))
     wp = (ctypes.c_void_p * layers)(*[w.data_ptr() for w in ws])
     bp = (ctypes.c_void_p * layers)(*[b.data_ptr() for b in bs])
+    head = (rois, emax, h0, f, layers, ptr(x_in), ptr(ew_in), ptr(plan.src32), ptr(plan.dst32), ptr(plan.tgt_ptr),
+            ptr(plan.tgt_perm), ptr(plan.src_ptr), ptr(plan.src_perm), ptr(plan.loop_edge), wp, bp, ptr(dxcat), ptr(dxcat2))
     with _immediate(final):
-        call("igcn_sgcn_stack_bwd", g, rois, emax, h0, f, layers, ptr(x_in), ptr(ew_in), ptr(plan.src32),
-             ptr(plan.dst32), ptr(plan.tgt_ptr), ptr(plan.tgt_perm), ptr(plan.src_ptr), ptr(plan.src_perm),
-             ptr(plan.loop_edge), wp, bp, ptr(dxcat), ptr(dxcat2), ptr(dx), ptr(dew), ptr(dpar), ptr(scratch),
-             ptr(plan.status), stream_ptr())
+        if mask_call is not None:          # (graphs per copy, the leading arguments, dparams, scratch) -> stands for dx_in
+            dx, dew = mask_call(g // 2, head, ptr(dpar), ptr(scratch)), None
+        else:
+            dx, dew = torch.empty_like(x_in), torch.empty_like(ew_in)
+            call("igcn_sgcn_stack_bwd", g, *head, ptr(dx), ptr(dew), ptr(dpar), ptr(scratch), ptr(plan.status),
+                 stream_ptr())
     grads, off = [], 0
     for l in range(layers):
         fin = h0 if l == 0 else f
@@ -882,8 +882,8 @@ class SgcnFront(torch.autograd.Function):
     """The front of the image branch of a train step — graph plan, cal_probability for the stacked (plain | masked) batch,
     loss_probability, the SNP mask and the GCNConv stack of both passes (kernel/sgcn_img_snp.py:133-181,218-224; train()
     :521-523) — as ONE launch (igcn_sgcn_front_fwd) instead of plan build -> EdgeMaskStacked -> SgcnStack.  Outputs
-    (xcat, xcat alias, e, reg partials, stacked SNP mask); backward = the two existing backward launches (igcn_sgcn_stack_bwd
-    on the 2-copy plan, igcn_edge_mask_bwd_reg), which walk the plan arrays this launch wrote."""
+    (xcat, xcat alias, e, reg partials, stacked SNP mask); backward = ops._front_backward, whose launches walk the plan
+    arrays this launch wrote."""
 
     @staticmethod
     def forward(ctx, x, prob, prob_bias, ew, plan, rois, snps_logits, reg_hp, snps_feat, edge_index, *wb):
@@ -926,11 +926,11 @@ class SgcnFront(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dxcat, dxcat2, d_e, d_regp, d_full):
-        x, prob, pb, ew, e, snps, feat, x_in, ew_in, *wb = ctx.saved_tensors
-        n, ne = x.shape[0], ew.shape[0]
-        dx_in, dew_in, grads = _sgcn_stack_backward(x_in, ew_in, wb, ctx.plan_g, ctx.rois, ctx.final, dxcat, dxcat2)
-        dx, dprob, dpb, dsnps = _edge_mask_reg_backward(x, prob, pb, ew, e, snps, feat, ctx.reg, ctx.plan, ctx.rois,
-                                                        dx_in[n:], dew_in[ne:], d_e, dx_in[:n], d_regp, d_full)
+        # sparse (k-NN) graphs: igcn_sgcn_stack_bwd_mask on the 2-copy plan, whose masked copy does the mask's node pass
+        # out of LDS (``mask_bwd_fused_supported``); else the two launches it replaces, igcn_sgcn_stack_bwd on the 2-copy
+        # plan and igcn_edge_mask_bwd_reg.  Every gradient has the same bits on both routes but prob_bias's, whose partial
+        # sums are one per graph on the first
+        (dx, dprob, dpb, dsnps), grads = _front_backward(ctx, dxcat, dxcat2, d_e, d_regp, d_full)
         return (dx, dprob, dpb, None, None, None, dsnps, None, None, None, *grads)
 
 
@@ -3841,3 +3841,51 @@ def perm_maxsum(member, planes, e, g_obs=None):
     call("igcn_perm_maxsum", p, s, e, mptr, ldm, ptr(planes), ptr(g_obs), ptr(maxabs), ptr(exceed), None,
          ptr(scratch), nbytes, stream_ptr())
     return maxabs, exceed
+
+
+# =================================================================================================
+# backward of ops.SgcnFront
+# =================================================================================================
+def _reg_upstream(d_regp, device):
+    """d(loss)/d(regulariser partials) as the device scalar the mask backward reads: the partials' gradient is one scalar,
+    repeated (ops.LossHead); None (the regulariser was not used): a zero."""
+    return _f32(d_regp[:1]).reshape(1) if d_regp is not None else torch.zeros(1, dtype=torch.float32, device=device)
+
+
+def mask_bwd_fused_supported(plan, rois, h0, f, layers):
+    """SgcnFront's backward is the one call igcn_sgcn_stack_bwd_mask: the LDS stack covers the batch and the plan is the
+    sparse (k-NN) kind whose mask backward runs four lanes per node — not complete graphs, not 16 or more edges per node.
+    IGCN_NO_MASK_BWD_FUSED=1 keeps igcn_sgcn_stack_bwd + igcn_edge_mask_bwd_reg."""
+    return (not switches.on("IGCN_NO_MASK_BWD_FUSED") and not getattr(plan, "dense_blocks", False)
+            and plan.n_edges < 16 * plan.n_nodes and sgcn_stack_supported(plan, rois, h0, f, layers))
+
+
+def _front_backward(ctx, dxcat, dxcat2, d_e, d_regp, d_full):
+    """((dx, dprob, dpb, dsnps), [dW_0, db_0, ...]) of ops.SgcnFront."""
+    x, prob, pb, ew, e, snps, feat, x_in, ew_in, *wb = ctx.saved_tensors
+    n, ne = x.shape[0], ew.shape[0]
+    stack = (x_in, ew_in, wb, ctx.plan_g, ctx.rois, ctx.final, dxcat, dxcat2)
+    if not mask_bwd_fused_supported(ctx.plan, ctx.rois, x.shape[1], wb[0].shape[0], len(wb) // 2):
+        dx_in, dew_in, grads = _sgcn_stack_backward(*stack)
+        return _edge_mask_reg_backward(x, prob, pb, ew, e, snps, feat, ctx.reg, ctx.plan, ctx.rois, dx_in[n:], dew_in[ne:],
+                                       d_e, dx_in[:n], d_regp, d_full), grads
+    # neither dx_in[n:] nor dew_in[ne:] makes the round trip through memory: the stack's call takes the mask's operands
+    hp, ns, snps_shape, rows = ctx.reg
+    h0 = x.shape[1]
+    d_e, d_full = (_f32(t) if t is not None else None for t in (d_e, d_full))
+    f32 = dict(dtype=torch.float32, device=x.device)
+    greg = _reg_upstream(d_regp, x.device)
+    dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+    dprob, dpb, dsnps = torch.empty_like(prob), torch.empty_like(pb), torch.empty(snps_shape, **f32)
+    use_feat = d_full is not None
+
+    def mask_call(g, head, dpar, scratch):
+        dx_plain, dew_plain = torch.empty(n, h0, **f32), torch.empty(ne, **f32)
+        mscratch = torch.empty(2 * n * h0 + 2 * MAX_H0 * g, **f32)
+        call("igcn_sgcn_stack_bwd_mask", g, ne, *head, ptr(dx_plain), ptr(dew_plain), dpar, scratch,
+             ptr(ctx.plan_g.status), ptr(x), ptr(prob), ptr(pb), ptr(ew), ptr(e), ptr(d_e), ptr(greg), ptr(snps), ns, *hp,
+             ptr(dx), ptr(dprob), ptr(dpb), ptr(dsnps), ptr(mscratch), ptr(feat) if use_feat else None,
+             rows if use_feat else 0, ptr(d_full) if use_feat else None, stream_ptr())
+        return dx
+
+    return (dx, dprob, dpb, dsnps), _sgcn_stack_backward(*stack, mask_call)[2]

@@ -11,6 +11,7 @@ import os
 HOST = {
     "IGCN_NO_FUSED_SGCN": "per-layer SGCN kernels instead of the LDS-resident stack",
     "IGCN_NO_FRONT_FUSED": "plan build, mask launch and SGCN stack forward as three launches, not igcn_sgcn_front_fwd",
+    "IGCN_NO_MASK_BWD_FUSED": "front backward: the mask's node pass as its own launch, not in the stack backward's masked copy",
     "IGCN_PLAN_REPLICATE_LAUNCH": "LDS plans: the two-pass replica by a launch of its own after each build, not filled by it",
     "IGCN_NO_DENSE_BLOCKS": "complete graphs: the general sorted-plan kernels instead of the dense-block path",
     "IGCN_NO_DROPOUT_RIDER": "captured step: the dropout masks as a launch of their own, not riding in the plan build",

@@ -352,6 +352,25 @@ int igcn_sgcn_stack_bwd(int64_t n_graphs, int R, int max_edges, int H0, int F, i
                         const int32_t* loop_edge, const float* const* W, const float* const* b, const float* dxcat,
                         const float* dxcat2, float* dx_in, float* dew_in, float* dparams, float* scratch,
                         int32_t* status, void* stream);
+/* igcn_sgcn_stack_bwd on the 2-copy (plain | masked) plan of a train step together with igcn_edge_mask_bwd_reg, as two
+ * launches instead of three: the masked copy's workgroups of the stack kernel hold the mask backward's per-node operands
+ * in LDS (lists, d_xm, d_ewm) and do its node pass themselves, in the summation order of the sparse node kernel; the tail
+ * launch sums dprob / dprob_bias / dsnps and writes dx.  Sparse batches only (n_edges < 16 nodes).  n_graphs, n_edges: of
+ * ONE copy; the plan arrays, x_in, ew_in, dxcat, dxcat2 and scratch (2 n_graphs * param_floats) are the 2-copy ones.
+ * dx_plain [N, H0] / dew_plain [E]: the plain copy's stack gradients (dx_plain is added into dx).  d_e, d_reg, dx, dsnps
+ * may be NULL.  mask_scratch: 2 N H0 + 16 n_graphs floats.  Every output but dprob_bias has the bits of the two calls;
+ * dprob_bias is summed per graph and not per 64 nodes. */
+int igcn_sgcn_stack_bwd_mask(int64_t n_graphs, int64_t n_edges, int R, int max_edges, int H0, int F, int L,
+                             const float* x_in, const float* ew_in, const int32_t* src32, const int32_t* dst32,
+                             const int32_t* tgt_ptr, const int32_t* tgt_perm, const int32_t* src_ptr,
+                             const int32_t* src_perm, const int32_t* loop_edge, const float* const* W,
+                             const float* const* b, const float* dxcat, const float* dxcat2, float* dx_plain,
+                             float* dew_plain, float* dparams, float* scratch, int32_t* status, const float* x,
+                             const float* prob, const float* prob_bias, const float* ew, const float* e,
+                             const float* d_e, const float* d_reg, const float* snps_logits, int n_snps, float l1_x,
+                             float ent_x, float l1_e, float ent_e, float eps, float* dx, float* dprob,
+                             float* dprob_bias, float* dsnps, float* mask_scratch, const float* snps_feat,
+                             int snps_rows, const float* d_snps_full, void* stream);
 /* THE FRONT OF THE IMAGE BRANCH OF A TRAIN STEP AS ONE LAUNCH (kernel/sgcn_img_snp.py:133-151 cal_probability, :153-181
  * loss_probability, :218-224 the GCNConv stack; train() :521-523 runs them for the plain and the masked pass): for a batch
  * of n_graphs uniform graphs of R nodes (at most max_edges edges each, edge_index int64 [2, n_edges] with per-graph
