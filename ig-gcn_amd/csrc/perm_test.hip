@@ -17,6 +17,9 @@
 // Launch sequence of igcn_perm_maxsum: k_perm_maxsum (per-tile partials) -> k_perm_fold_max, k_perm_fold_cnt.
 // One writer per element, no atomics, fixed order: the accumulation order along S of a row is k-steps ascending, planes
 // hi, mid, lo inside a step, whichever tile or launch the row sits in.
+//
+// igcn_perm_maxf (k_perm_maxf, below the two-group kernels) is the same product for K = 2..5 groups: K - 1 indicator
+// operands read off one label byte, one statistic B of which the one-way ANOVA F is an increasing function.
 #include <math.h>
 
 #include "common.h"
@@ -130,6 +133,12 @@ __device__ __forceinline__ void pt_load(PtStage& st, const uint8_t* __restrict__
   for (int q = 0; q < 3; ++q) st.b[q] = *reinterpret_cast<const uint4*>(src + q * plane);
 }
 
+__device__ __forceinline__ void pt_store_planes(const PtStage& st, unsigned short (*Bs)[PT_BN][PT_LD], int tid) {
+  const int br = tid >> 2, bk = (tid & 3) * 8;
+#pragma unroll
+  for (int q = 0; q < 3; ++q) *reinterpret_cast<uint4*>(&Bs[q][br][bk]) = st.b[q];
+}
+
 __device__ __forceinline__ void pt_store(const PtStage& st, unsigned short (*As)[PT_LD],
                                          unsigned short (*Bs)[PT_BN][PT_LD], int S, int k0, int tid) {
   const int ar = tid >> 1, ah = (tid & 1) * 16, ak = k0 + ah;
@@ -144,9 +153,7 @@ __device__ __forceinline__ void pt_store(const PtStage& st, unsigned short (*As)
   uint4* ad = reinterpret_cast<uint4*>(&As[ar][ah]);
   ad[0] = make_uint4(o[0], o[1], o[2], o[3]);
   ad[1] = make_uint4(o[4], o[5], o[6], o[7]);
-  const int br = tid >> 2, bk = (tid & 3) * 8;
-#pragma unroll
-  for (int q = 0; q < 3; ++q) *reinterpret_cast<uint4*>(&Bs[q][br][bk]) = st.b[q];
+  pt_store_planes(st, Bs, tid);
 }
 
 __global__ void __launch_bounds__(PT_T)
@@ -267,6 +274,195 @@ k_perm_fold_cnt(int E, int tiles_p, const int32_t* __restrict__ pcnt, int32_t* _
   exceed[e] = c;
 }
 
+// ---- K groups: the max-F product and its epilogue ------------------------------------------------------------------------
+// labels [P, S] uint8: byte g puts the subject in group g of the relabelling.  For the NG = K - 1 accumulated groups
+//   G_g[p, e] = sum_s (labels[p, s] == g) z[s, e]
+// on the same tile as k_perm_maxsum: wave w owns rows 32 w .. 32 w + 31 and all 64 columns, for every group,
+//   acc[g][a][b][r] = G_g[m0 + 32 w + 16 a + 4 (lane >> 4) + r][n0 + 16 b + (lane & 15)].
+// The label bytes stay RAW in LDS (PF_LDL bytes a row) and a lane widens the 8 bytes of its A fragment into NG
+// fragments of bf16 0.0 / 1.0 in registers, so LDS does not grow with NG and every B fragment is read once for all
+// 2 NG accumulators it feeds.  Rows behind P and bytes behind S are staged as PF_NONE, which is no group.
+// The statistic, with the last group's sum DEFINED as minus the sum of the others (the column sum of the fp32 z is
+// zero only to rounding):  B = sum_{g < NG} w_g G_g^2 + w_NG (sum_{g < NG} G_g)^2, in fp32, g ascending, the last term
+// last.  With w_g = 1 / n_g this is the between-groups sum of squares, every column's total is S, and
+// F = (B / (K - 1)) / ((S - B) / (S - K)) is ONE increasing function of B: comparing B is comparing F.
+// maxstat[p] = max_e B[p, e] and exceed[e] = #{p : B[p, e] >= b_obs[e]} through the partials and folds of k_perm_maxsum.
+#define PF_LDL 48                                      // LDS label row: 32 bytes + 16 pad (12 dwords: no bank conflicts)
+#define PF_NONE 0xFFu
+
+struct PfWeights {
+  float w[IGCN_PERM_MAX_GROUPS];
+};
+
+__device__ __forceinline__ void pf_store(const PtStage& st, uint8_t (*Ls)[PF_LDL], unsigned short (*Bs)[PT_BN][PT_LD],
+                                         bool row_ok, int S, int k0, int tid) {
+  const int ar = tid >> 1, ah = (tid & 1) * 16;
+  int n = row_ok ? S - (k0 + ah) : 0;                   // label bytes of this half that are real
+  n = n < 0 ? 0 : n > 16 ? 16 : n;
+  unsigned w[4] = {st.a.x, st.a.y, st.a.z, st.a.w};
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    const int nv = n - 4 * d;
+    const unsigned keep = nv >= 4 ? 0xFFFFFFFFu : nv <= 0 ? 0u : (1u << (8 * nv)) - 1u;
+    w[d] = (w[d] & keep) | ~keep;                       // PF_NONE in every byte behind S
+  }
+  *reinterpret_cast<uint4*>(&Ls[ar][ah]) = make_uint4(w[0], w[1], w[2], w[3]);
+  pt_store_planes(st, Bs, tid);
+}
+
+// the A fragment of group g from 8 label bytes: bf16 1.0 (0x3F80) where the byte is g
+__device__ __forceinline__ pt_bf16x8 pf_widen(uint2 l, unsigned g) {
+  const unsigned w[2] = {l.x, l.y};
+  unsigned o[4];
+#pragma unroll
+  for (int j = 0; j < 8; j += 2) {
+    const unsigned lo = ((w[j >> 2] >> (8 * (j & 3))) & 0xFFu) == g ? 0x3F80u : 0u;
+    const unsigned hi = ((w[j >> 2] >> (8 * ((j + 1) & 3))) & 0xFFu) == g ? 0x3F80u : 0u;
+    o[j >> 1] = lo | (hi << 16);
+  }
+  return __builtin_bit_cast(pt_bf16x8, make_uint4(o[0], o[1], o[2], o[3]));
+}
+
+template <int NG>
+__global__ void __launch_bounds__(PT_T, 2)              // two waves a SIMD: NG = 4 then fits 208 registers, no spill
+k_perm_maxf(int P, int S, int E, int Sp, const uint8_t* __restrict__ labels, int64_t ldl, int vec,
+            const unsigned short* __restrict__ planes, size_t plane, PfWeights wt, const float* __restrict__ b_obs,
+            float* __restrict__ pmax, int tiles_e, int32_t* __restrict__ pcnt, float* __restrict__ b,
+            float* __restrict__ g) {
+  __shared__ __attribute__((aligned(16))) uint8_t Ls[2][PT_BM][PF_LDL];
+  __shared__ __attribute__((aligned(16))) unsigned short Bs[2][3][PT_BN][PT_LD];
+  __shared__ int cnt_s[PT_T / 64][PT_BN];
+  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lr = lane & 15, lg = lane >> 4;
+  const int m0 = blockIdx.x * PT_BM, n0 = blockIdx.y * PT_BN;
+  const bool row_ok = m0 + (tid >> 1) < P;              // the row this thread stages
+
+  pt_f32x4 acc[NG][2][4];
+#pragma unroll
+  for (int q = 0; q < NG; ++q)
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) acc[q][a][c] = (pt_f32x4){0.f, 0.f, 0.f, 0.f};
+
+  PtStage st;
+  pt_load(st, labels, ldl, vec != 0, P, S, m0, planes, plane, Sp, n0, 0, tid);
+  pf_store(st, Ls[0], Bs[0], row_ok, S, 0, tid);
+  __syncthreads();
+  int buf = 0;
+  for (int k0 = 0; k0 < Sp; k0 += PT_BK) {
+    const bool more = k0 + PT_BK < Sp;
+    if (more) pt_load(st, labels, ldl, vec != 0, P, S, m0, planes, plane, Sp, n0, k0 + PT_BK, tid);
+    pt_bf16x8 fa[NG][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+      const uint2 l = *reinterpret_cast<const uint2*>(&Ls[buf][w * 32 + a * 16 + lr][lg * 8]);
+#pragma unroll
+      for (int q = 0; q < NG; ++q) fa[q][a] = pf_widen(l, (unsigned)q);
+    }
+#pragma unroll
+    for (int q = 0; q < 3; ++q)                         // planes hi, mid, lo into the same accumulators
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {                     // one read of a B fragment feeds all 2 NG accumulators
+        const pt_bf16x8 fb = *reinterpret_cast<const pt_bf16x8*>(&Bs[buf][q][c * 16 + lr][lg * 8]);
+#pragma unroll
+        for (int gi = 0; gi < NG; ++gi)
+#pragma unroll
+          for (int a = 0; a < 2; ++a)
+            acc[gi][a][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[gi][a], fb, acc[gi][a][c], 0, 0, 0);
+      }
+    if (more) pf_store(st, Ls[buf ^ 1], Bs[buf ^ 1], row_ok, S, k0 + PT_BK, tid);
+    __syncthreads();
+    buf ^= 1;
+  }
+
+  // ---- epilogue: the group sums and B stay in registers ----
+  const int prow = m0 + w * 32 + lg * 4;                // + 16 a + r
+  if (b_obs == nullptr && g != nullptr) {               // the observed pass: the sums themselves, g [P, NG, E]
+#pragma unroll
+    for (int gi = 0; gi < NG; ++gi)
+#pragma unroll
+      for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int p = prow + 16 * a + r, e = n0 + 16 * c + lr;
+            if (p < P && e < E) g[((size_t)p * NG + gi) * E + e] = acc[gi][a][c][r];
+          }
+  }
+  pt_f32x4 bv[2][4];                                    // B: g ascending, the last group's term last
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float sum = acc[0][a][c][r];
+        float v = wt.w[0] * sum * sum;
+#pragma unroll
+        for (int gi = 1; gi < NG; ++gi) {
+          const float x = acc[gi][a][c][r];
+          v += wt.w[gi] * x * x;
+          sum += x;
+        }
+        v += wt.w[NG] * sum * sum;
+        bv[a][c][r] = v;
+      }
+  if (b_obs == nullptr) {                               // the observed pass: B itself, P <= IGCN_PERM_MAX_G_ROWS
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int p = prow + 16 * a + r, e = n0 + 16 * c + lr;
+          if (p < P && e < E) b[(size_t)p * E + e] = bv[a][c][r];
+        }
+  }
+  // max partial: over the tile's real columns, for each of the lane's 8 rows; lanes of one 16-group hold the columns
+  float mx[2][4];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float v = 0.f;
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        if (n0 + 16 * c + lr < E) v = fmaxf(v, bv[a][c][r]);
+#pragma unroll
+      for (int o = 8; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+      mx[a][r] = v;
+    }
+  if (lr == 0) {
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int p = prow + 16 * a + r;
+        if (p < P) pmax[(size_t)p * tiles_e + blockIdx.y] = mx[a][r];
+      }
+  }
+  if (b_obs != nullptr) {                               // exceedance partial: over the tile's real rows, per column
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int e = n0 + 16 * c + lr;
+      const float thr = e < E ? b_obs[e] : 0.f;
+      int n = 0;
+#pragma unroll
+      for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) n += (prow + 16 * a + r < P && bv[a][c][r] >= thr) ? 1 : 0;
+      n += __shfl_xor(n, 16, 64);
+      n += __shfl_xor(n, 32, 64);
+      if (lg == 0) cnt_s[w][16 * c + lr] = n;
+    }
+    __syncthreads();
+    if (tid < PT_BN && n0 + tid < E)
+      pcnt[(size_t)blockIdx.x * E + n0 + tid] = cnt_s[0][tid] + cnt_s[1][tid] + cnt_s[2][tid] + cnt_s[3][tid];
+  }
+}
+
 // ---- host -------------------------------------------------------------------------------------------------------------
 static bool pt_sizes_ok(int S, int E) {
   return S >= IGCN_PERM_MIN_S && S <= IGCN_PERM_MAX_S && E >= 1 && E <= IGCN_PERM_MAX_E;
@@ -342,6 +538,67 @@ extern "C" int igcn_perm_maxsum(int P, int S, int E, const uint8_t* member, int6
                      (const unsigned short*)planes, (size_t)Ep * Sp, g_obs, pmax, tiles_e, pcnt, g);
   hipLaunchKernelGGL(k_perm_fold_max, dim3((P + 255) / 256), dim3(256), 0, st, P, tiles_e, pmax, maxabs);
   if (g_obs)
+    hipLaunchKernelGGL(k_perm_fold_cnt, dim3((E + 255) / 256), dim3(256), 0, st, E, tiles_p, pcnt, exceed);
+  IGCN_CHECK_LAUNCH(who);
+  return IGCN_OK;
+}
+
+template <int NG>
+static void pf_launch(dim3 grid, hipStream_t st, int P, int S, int E, int Sp, const uint8_t* labels, int64_t ldl, int vec,
+                      const unsigned short* planes, size_t plane, const PfWeights& wt, const float* b_obs, float* pmax,
+                      int tiles_e, int32_t* pcnt, float* b, float* g) {
+  hipLaunchKernelGGL(k_perm_maxf<NG>, grid, dim3(PT_T), 0, st, P, S, E, Sp, labels, ldl, vec, planes, plane, wt, b_obs,
+                     pmax, tiles_e, pcnt, b, g);
+}
+
+extern "C" int igcn_perm_maxf(int P, int S, int E, int K, const uint8_t* labels, int64_t ldl, const void* planes,
+                              const float* weights, const float* b_obs, float* maxstat, int32_t* exceed, float* b,
+                              float* g, void* scratch, size_t scratch_bytes, void* stream) {
+  const char* who = "perm_maxf";
+  IGCN_REQUIRE(S >= IGCN_PERM_MIN_S && S <= IGCN_PERM_MAX_S, "%s: S=%d subjects outside [%d,%d]", who, S, IGCN_PERM_MIN_S,
+               IGCN_PERM_MAX_S);
+  IGCN_REQUIRE(E >= 1 && E <= IGCN_PERM_MAX_E, "%s: E=%d map entries outside [1,%d]", who, E, IGCN_PERM_MAX_E);
+  IGCN_REQUIRE(P >= 1 && P <= IGCN_PERM_MAX_P, "%s: P=%d relabellings in one launch outside [1,%d]", who, P,
+               IGCN_PERM_MAX_P);
+  IGCN_REQUIRE(K >= 2 && K <= IGCN_PERM_MAX_GROUPS, "%s: K=%d groups outside [2,%d]", who, K, IGCN_PERM_MAX_GROUPS);
+  IGCN_REQUIRE(ldl >= S, "%s: labels row stride %lld below S=%d", who, (long long)ldl, S);
+  IGCN_REQUIRE(labels && planes && weights && maxstat && scratch, "%s: a null buffer", who);
+  PfWeights wt = {};
+  for (int k = 0; k < K; ++k) {
+    IGCN_REQUIRE(isfinite(weights[k]) && weights[k] > 0.f, "%s: weight %d is %g (finite and > 0)", who, k,
+                 (double)weights[k]);
+    wt.w[k] = weights[k];
+  }
+  if (b_obs) {
+    IGCN_REQUIRE(exceed != nullptr, "%s: b_obs without an exceed buffer", who);
+  } else {
+    IGCN_REQUIRE(b != nullptr && P <= IGCN_PERM_MAX_G_ROWS, "%s: without b_obs the call writes b itself, for P <= %d (P=%d)",
+                 who, IGCN_PERM_MAX_G_ROWS, P);
+  }
+  IGCN_REQUIRE(((uintptr_t)planes & 15) == 0 && ((uintptr_t)scratch & 15) == 0,
+               "%s: the planes and the scratch must be 16-byte aligned", who);
+  const size_t need = igcn_perm_maxsum_scratch_bytes(P, E);
+  if (scratch_bytes < need) {
+    igcn_set_error("%s: the scratch holds %zu bytes, P=%d E=%d needs %zu bytes", who, scratch_bytes, P, E, need);
+    return IGCN_ERR_UNSUPPORTED;
+  }
+  const int Ep = pt_ep(E), Sp = pt_sp(S);
+  const int tiles_p = (P + PT_BM - 1) / PT_BM, tiles_e = Ep / PT_BN;
+  float* pmax = (float*)scratch;
+  int32_t* pcnt = (int32_t*)(pmax + (size_t)P * tiles_e);
+  const int vec = (ldl % 16 == 0 && ((uintptr_t)labels & 15) == 0) ? 1 : 0;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(tiles_p, tiles_e);
+  const unsigned short* pl = (const unsigned short*)planes;
+  const size_t plane = (size_t)Ep * Sp;
+  switch (K - 1) {
+    case 1: pf_launch<1>(grid, st, P, S, E, Sp, labels, ldl, vec, pl, plane, wt, b_obs, pmax, tiles_e, pcnt, b, g); break;
+    case 2: pf_launch<2>(grid, st, P, S, E, Sp, labels, ldl, vec, pl, plane, wt, b_obs, pmax, tiles_e, pcnt, b, g); break;
+    case 3: pf_launch<3>(grid, st, P, S, E, Sp, labels, ldl, vec, pl, plane, wt, b_obs, pmax, tiles_e, pcnt, b, g); break;
+    default: pf_launch<4>(grid, st, P, S, E, Sp, labels, ldl, vec, pl, plane, wt, b_obs, pmax, tiles_e, pcnt, b, g); break;
+  }
+  hipLaunchKernelGGL(k_perm_fold_max, dim3((P + 255) / 256), dim3(256), 0, st, P, tiles_e, pmax, maxstat);
+  if (b_obs)
     hipLaunchKernelGGL(k_perm_fold_cnt, dim3((E + 255) / 256), dim3(256), 0, st, E, tiles_p, pcnt, exceed);
   IGCN_CHECK_LAUNCH(who);
   return IGCN_OK;

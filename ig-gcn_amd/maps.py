@@ -249,7 +249,11 @@ def group_difference(model, loader, quantity="association", groups=(0, 1), permu
     ``weighted``; ``target``, ``inputs``, ``normalize``).  A pass of its own: every batch's maps are copied into one
     preallocated [S_all, E] device buffer, the labels beside it, and nothing is summed per class.  Returns the dict of
     ``stats.permutation_test`` in the map's shape plus ``significant`` (int64: the flat indices of the entries with
-    ``p_fwe <= 0.05``, largest |t| first, at most ``top_k``).  A group with fewer than 2 subjects raises ValueError."""
+    ``p_fwe <= 0.05``, largest |t| first, at most ``top_k``).  A group with fewer than 2 subjects raises ValueError.
+
+    With three to five labels in ``groups`` (``groups=(0, 1, 2)``) the question is where the groups differ at all: the
+    max-F permutation test ``stats.permutation_anova``, whose dict is returned instead; ``members`` then carries its
+    label rows (uint8 [P, S], codes in the order of ``groups``) and ``significant`` lists the largest F first."""
     from . import stats
     if quantity not in QUANTITIES:
         raise ValueError(f"group_difference: quantity={quantity!r} (one of {QUANTITIES})")
@@ -276,9 +280,14 @@ def group_difference(model, loader, quantity="association", groups=(0, 1), permu
         n += b
     if n == 0:
         raise ValueError("group_difference: the loader is empty")
-    out = stats.permutation_test(buf[:n].view(n, *shape), labels[:n], groups=groups, permutations=permutations, seed=seed,
-                                 members=members)
-    t_abs = out["t"].reshape(-1).abs()
+    if len(groups) > 2:
+        out = stats.permutation_anova(buf[:n].view(n, *shape), labels[:n], groups=groups, permutations=permutations,
+                                      seed=seed, labels=members)
+        t_abs = out["f"].reshape(-1)
+    else:
+        out = stats.permutation_test(buf[:n].view(n, *shape), labels[:n], groups=groups, permutations=permutations,
+                                     seed=seed, members=members)
+        t_abs = out["t"].reshape(-1).abs()
     hit = torch.nonzero(out["p_fwe"].reshape(-1) <= 0.05).view(-1)
     order = torch.argsort(t_abs[hit], descending=True, stable=True)[:max(int(top_k), 0)]
     out["significant"] = hit[order]

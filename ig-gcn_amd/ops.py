@@ -3769,6 +3769,7 @@ from .gdc import _empty as _buffer  # noqa: E402  (the package's one device-buff
 
 PERM_MIN_S, PERM_MAX_S, PERM_MAX_E = _L["IGCN_PERM_MIN_S"], _L["IGCN_PERM_MAX_S"], _L["IGCN_PERM_MAX_E"]
 PERM_MAX_P, PERM_MAX_G_ROWS = _L["IGCN_PERM_MAX_P"], _L["IGCN_PERM_MAX_G_ROWS"]
+PERM_MAX_GROUPS = _L["IGCN_PERM_MAX_GROUPS"]
 
 
 def perm_plane_dims(s, e):
@@ -3841,6 +3842,51 @@ def perm_maxsum(member, planes, e, g_obs=None):
     call("igcn_perm_maxsum", p, s, e, mptr, ldm, ptr(planes), ptr(g_obs), ptr(maxabs), ptr(exceed), None,
          ptr(scratch), nbytes, stream_ptr())
     return maxabs, exceed
+
+
+def perm_maxf(labels, planes, e, weights, b_obs=None, want_g=False):
+    """The K-group statistic of igcn_perm_maxf, never stored: labels [P, S] uint8 (byte g = group g of relabelling p; any
+    row stride), planes of ``perm_prepare`` for the same S and ``e`` entries, ``weights`` K = 2..5 positive finite
+    numbers (1 / n_g for the ANOVA between-groups sum of squares).  B = sum_{g<K-1} w_g G_g^2 + w_{K-1} (sum G_g)^2:
+    the last group's sum is minus the sum of the others, so a byte >= K - 1 counts for the last group.  With ``b_obs``
+    [E] fp32: (maxstat [P], exceed [E] int32) = (max_e B[p, e], #{p : B[p, e] >= b_obs[e]}).  Without, for P <= 8
+    (PERM_MAX_G_ROWS), the observed pass: (maxstat [P], b [P, E]), or with ``want_g`` (maxstat, b, g [P, K-1, E])."""
+    if labels.dtype != torch.uint8 or labels.dim() != 2 or labels.stride(1) != 1 or labels.device != planes.device:
+        raise TypeError("perm_maxf: labels must be uint8 [P, S] with unit column stride on the planes' device")
+    p, s, e, dev = int(labels.shape[0]), int(labels.shape[1]), int(e), planes.device
+    w = [float(v) for v in weights]
+    k = len(w)
+    if not 2 <= k <= PERM_MAX_GROUPS or not all(0 < v < float("inf") for v in w):
+        raise ValueError(f"perm_maxf: weights {w} must be 2..{PERM_MAX_GROUPS} positive finite numbers")
+    if not 1 <= p <= PERM_MAX_P:
+        raise ValueError(f"perm_maxf: P={p} relabellings in one launch outside [1, {PERM_MAX_P}]")
+    if not PERM_MIN_S <= s <= PERM_MAX_S or not 1 <= e <= PERM_MAX_E:
+        raise ValueError(f"perm_maxf: S={s} outside [{PERM_MIN_S}, {PERM_MAX_S}] or E={e} outside [1, {PERM_MAX_E}]")
+    if (planes.dtype != torch.bfloat16 or not planes.is_contiguous() or tuple(planes.shape) != (3,) + perm_plane_dims(s, e)):
+        raise ValueError(f"perm_maxf: planes {tuple(planes.shape)} are not those of perm_prepare for S={s}, E={e}")
+    ldl = int(labels.stride(0)) if p > 1 else max(int(labels.stride(0)), s)
+    if ldl < s:
+        raise ValueError("perm_maxf: the rows of labels overlap")
+    if not labels.is_cuda:
+        raise _lib.IgcnError("libigcn operates on device memory only; got a CPU tensor")
+    wbuf = (ctypes.c_float * k)(*w)                              # (a host array: the launch takes a copy)
+    maxstat = _buffer((p,), torch.float32, dev)
+    nbytes = int(_lib.load().igcn_perm_maxsum_scratch_bytes(p, e))
+    scratch = _buffer(((nbytes + 3) // 4,), torch.int32, dev)
+    if b_obs is None:
+        if p > PERM_MAX_G_ROWS:
+            raise ValueError(f"perm_maxf: without b_obs the statistic itself is returned, for P <= {PERM_MAX_G_ROWS}")
+        b = _buffer((p, e), torch.float32, dev)
+        g = _buffer((p, k - 1, e), torch.float32, dev) if want_g else None
+        call("igcn_perm_maxf", p, s, e, k, labels.data_ptr(), ldl, ptr(planes), ctypes.addressof(wbuf), None,
+             ptr(maxstat), None, ptr(b), ptr(g), ptr(scratch), nbytes, stream_ptr())
+        return (maxstat, b, g) if want_g else (maxstat, b)
+    if b_obs.dtype != torch.float32 or b_obs.numel() != e or b_obs.device != dev or not b_obs.is_contiguous():
+        raise ValueError(f"perm_maxf: b_obs must be a contiguous float32 [{e}] on the planes' device")
+    exceed = _buffer((e,), torch.int32, dev)
+    call("igcn_perm_maxf", p, s, e, k, labels.data_ptr(), ldl, ptr(planes), ctypes.addressof(wbuf), ptr(b_obs),
+         ptr(maxstat), ptr(exceed), None, None, ptr(scratch), nbytes, stream_ptr())
+    return maxstat, exceed
 
 
 # =================================================================================================

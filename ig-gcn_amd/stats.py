@@ -8,6 +8,9 @@ For S subjects of two groups (n_a + n_b = S) and E map entries the statistic of 
 ``r = G / sqrt(n_a n_b)`` and ``t = r sqrt((S - 2) / (1 - r^2))``: |t| is ONE increasing function of |G| for every column
 and every relabelling, so comparing |G| is comparing |t| and the kernel (csrc/perm_test.hip, igcn_perm_maxsum) never
 forms t.  Two-sided only.
+
+``permutation_anova`` below is the counterpart for three to five groups: the one-way ANOVA F with the same max-statistic
+correction (igcn_perm_maxf).
 """
 import math
 
@@ -117,3 +120,116 @@ def permutation_test(x, y, groups=(0, 1), permutations=10000, seed=0, members=No
     t = (r * torch.sqrt((s - 2) / (1 - r * r))).masked_fill(const, 0.0)
     return {"diff": diff.view(shape), "t": t.view(shape), "p_unc": p_unc.view(shape), "p_fwe": p_fwe.view(shape),
             "constant": const.view(shape), "null_max": null_max, "n": (n_a, n_b), "permutations": p_total}
+
+
+# ---- more than two groups: the max-F test --------------------------------------------------------------------------------
+# One-way ANOVA over K groups of sizes n_g on the same standardised column (sum z = 0, sum z^2 = S): the between-groups
+# sum of squares is B = sum_g G_g^2 / n_g with G_g the group sums, the total is S, and
+#   F = (B / (K - 1)) / ((S - B) / (S - K))
+# is ONE increasing function of B for every column and every relabelling, so the kernel (igcn_perm_maxf) compares B and
+# never forms F.  The LAST group's sum is DEFINED as minus the sum of the others: the column sum of the fp32 z is zero
+# only to rounding, and the definition is the same in the kernel, here and in the tests' restatement.
+def draw_labels(observed, permutations, seed=0, device="cuda"):
+    """uint8 [permutations, S]: every row a uniformly drawn permutation of the group codes ``observed`` [S] (0..K-1), by
+    the argsort of one ``torch.rand(permutations, S)`` of a ``torch.Generator`` on ``device`` seeded with ``seed`` — one
+    draw for all rows, so the rows do not depend on how a caller chunks them.  Rows start 16-byte aligned."""
+    observed = torch.as_tensor(observed).view(-1)
+    n, p = int(observed.numel()), int(permutations)
+    if n < 2 or p < 1:
+        raise ValueError(f"draw_labels: {n} subjects, {p} relabellings")
+    gen = torch.Generator(device=device)
+    gen.manual_seed(int(seed))
+    u = torch.rand(p, n, generator=gen, device=device)
+    codes = observed.to(device=u.device, dtype=torch.uint8)
+    labels = _padded_rows(p, n, u.device)
+    labels.copy_(codes[torch.argsort(u, dim=1)])
+    return labels
+
+
+def permutation_anova(x, y, groups=(0, 1, 2), permutations=10000, seed=0, labels=None, chunk=None):
+    """Max-F permutation test of a difference between the K = 2..5 diagnosis groups ``groups`` for every entry of the
+    per-subject maps ``x`` [S_all, ...] (fp32, on the device) with labels ``y`` [S_all].  The rows with another label are
+    left out; a kept row's code is the position of its label in ``groups``.  ``labels`` (uint8 [P, S], every row a
+    rearrangement of the kept rows' codes, in the order of the kept rows) replaces the ``permutations`` relabellings
+    drawn by ``draw_labels(codes, permutations, seed)``.  The relabellings run in chunks of ``chunk`` rows (4096); the
+    result has the same bits for any chunking.
+
+    Returns a dict, the per-entry tensors in the shape of one map and fp64 unless noted: ``f`` (the one-way ANOVA F of
+    the observed labelling), ``eta2`` = B / S (the share of the variance between the groups), ``means`` [K, ...] (the
+    group means in original units, mean + sd G_g / n_g; the last group's G is minus the sum of the others),
+    ``p_unc`` = (1 + #{p : F_p[e] >= F_obs[e]}) / (1 + P), ``p_fwe`` = (1 + #{p : max_e' F_p[e'] >= F_obs[e]}) / (1 + P),
+    ``constant`` (bool: the entry has one value over the kept rows; f 0 and p-values 1 there); ``null_max`` [P] (fp32:
+    max_e B_p[e], the null distribution of the maximum in the units of B), ``n`` (the K group sizes),
+    ``df`` = (K - 1, S - K) and ``permutations`` = P."""
+    if not torch.is_tensor(x) or x.dim() < 2 or x.dtype != torch.float32:
+        raise TypeError("permutation_anova: x must be a float32 tensor [S_all, ...]")
+    shape = tuple(x.shape[1:])
+    x2 = x.reshape(x.shape[0], -1).contiguous()
+    dev = x2.device
+    y = torch.as_tensor(y).view(-1).to(device=dev, dtype=torch.int64)
+    if y.numel() != x2.shape[0]:
+        raise ValueError(f"permutation_anova: {y.numel()} labels for {x2.shape[0]} subjects")
+    groups = tuple(int(v) for v in groups)
+    k = len(groups)
+    if not 2 <= k <= ops.PERM_MAX_GROUPS:
+        raise ValueError(f"permutation_anova: {k} groups (2 to {ops.PERM_MAX_GROUPS})")
+    if len(set(groups)) != k:
+        raise ValueError(f"permutation_anova: a label is repeated in groups={groups}")
+    code = torch.full_like(y, k)
+    for c, label in enumerate(groups):
+        code[y == label] = c
+    rows = torch.nonzero(code < k).view(-1)
+    codes = code[rows].to(torch.uint8)
+    s = int(rows.numel())
+    n = tuple(int(v) for v in torch.bincount(codes.long(), minlength=k).tolist())
+    if min(n) < 2:
+        raise ValueError(f"permutation_anova: groups {groups} have {n} subjects (at least 2 each)")
+    if not ops.PERM_MIN_S <= s <= ops.PERM_MAX_S:
+        raise ValueError(f"permutation_anova: S={s} subjects outside [{ops.PERM_MIN_S}, {ops.PERM_MAX_S}]")
+    e = int(x2.shape[1])
+    if labels is None:
+        labels = draw_labels(codes, permutations, seed, dev)
+    else:
+        if (not torch.is_tensor(labels) or labels.dim() != 2 or labels.shape[1] != s or labels.shape[0] < 1
+                or labels.dtype != torch.uint8):
+            raise ValueError(f"permutation_anova: labels must be uint8 [P, {s}]")
+        labels = labels.to(dev)
+        if any(bool(((labels == c).sum(1, dtype=torch.int64) != n[c]).any()) for c in range(k)):
+            raise ValueError(f"permutation_anova: every row of labels must hold the codes 0..{k - 1} {n} times")
+        if labels.stride(1) != 1 or labels.stride(0) % 16 or labels.data_ptr() % 16:
+            padded = _padded_rows(labels.shape[0], s, dev)
+            padded.copy_(labels)
+            labels = padded
+    p_total = int(labels.shape[0])
+    chunk = DEFAULT_CHUNK if chunk is None else int(chunk)
+    if not 1 <= chunk <= ops.PERM_MAX_P:
+        raise ValueError(f"permutation_anova: chunk={chunk} outside [1, {ops.PERM_MAX_P}]")
+
+    mean, sd, constant, planes = ops.perm_prepare(x2, rows, standardize=True)
+    if not (bool(torch.isfinite(mean).all()) and bool(torch.isfinite(sd).all())):
+        raise ValueError("permutation_anova: x holds non-finite values in the rows under test")
+    weights = [1.0 / v for v in n]
+    observed = _padded_rows(1, s, dev)
+    observed.copy_(codes.view(1, s))
+    _, b, g = ops.perm_maxf(observed, planes, e, weights, want_g=True)
+    b_obs = b.view(-1).contiguous()
+    null_max = ops._buffer((p_total,), torch.float32, dev)
+    exceed = ops._buffer((e,), torch.int64, dev).zero_()
+    for p0 in range(0, p_total, chunk):
+        mx, ex = ops.perm_maxf(labels[p0:p0 + chunk], planes, e, weights, b_obs)
+        null_max[p0:p0 + mx.numel()] = mx
+        exceed += ex
+    const = constant.bool()
+    srt = torch.sort(null_max).values
+    fwe = p_total - torch.searchsorted(srt, b_obs, right=False)                   # #{p : null_max[p] >= b_obs[e]}
+    den = torch.tensor(float(1 + p_total), dtype=torch.float64, device=dev)      # (a tensor divisor: a true division)
+    p_unc = ((1 + exceed).double() / den).masked_fill(const, 1.0)
+    p_fwe = ((1 + fwe).double() / den).masked_fill(const, 1.0)
+    eta2 = (b_obs.double() / s).clamp(0.0, 1.0).masked_fill(const, 0.0)
+    f = ((eta2 / (k - 1)) / ((1 - eta2) / (s - k))).masked_fill(const, 0.0)
+    gd = g.view(k - 1, e).double()
+    gd = torch.cat([gd, -gd.sum(0, keepdim=True)])                                # the last group: minus the others
+    means = mean + sd * gd / torch.tensor(n, dtype=torch.float64, device=dev).view(k, 1)
+    return {"f": f.view(shape), "eta2": eta2.view(shape), "means": means.view(k, *shape), "p_unc": p_unc.view(shape),
+            "p_fwe": p_fwe.view(shape), "constant": const.view(shape), "null_max": null_max, "n": n,
+            "df": (k - 1, s - k), "permutations": p_total}

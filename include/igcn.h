@@ -1631,6 +1631,26 @@ size_t igcn_perm_maxsum_scratch_bytes(int P, int E);
 int igcn_perm_maxsum(int P, int S, int E, const uint8_t* member, int64_t ldm, const void* planes, const float* g_obs,
                      float* maxabs, int32_t* exceed, float* g, void* scratch, size_t scratch_bytes, void* stream);
 
+/* Max-F permutation test of a difference between K = 2..5 groups (IGCN_PERM_MAX_GROUPS), on the planes of
+ * igcn_perm_prepare.  labels [P, S] uint8 with row stride ldl bytes: byte g puts subject s in group g of relabelling p.
+ * igcn_perm_maxf: for the K - 1 accumulated groups G_g[p, e] = sum_s (labels[p, s] == g) z[s, e], the indicator as bf16
+ *   0.0 / 1.0 on v_mfma_f32_16x16x32_bf16 (exact products, fp32 accumulation, planes hi, mid, lo and subjects ascending
+ *   for every row, as igcn_perm_maxsum; the label bytes stay raw in LDS and are widened in registers, and one read of a
+ *   plane fragment feeds all groups).  The LAST group's sum is DEFINED as minus the sum of the others — the column sum of
+ *   the fp32 z is zero only to rounding — so a label byte >= K - 1, whatever its value, counts for the last group.
+ *   With weights [K] (a HOST array, copied into the launch; finite and > 0; 1 / n_g gives the between-groups sum of
+ *   squares of a one-way ANOVA, of which F is one increasing function for every column)
+ *     B[p, e] = sum_{g < K-1} w_g G_g^2 + w_{K-1} (sum_{g < K-1} G_g)^2      (fp32, g ascending, the last term last),
+ *   maxstat[p] = max_e B[p, e] and, with b_obs [E] given, exceed[e] = #{p : B[p, e] >= b_obs[e]} (int32).  With b_obs
+ *   NULL the call writes b [P, E] itself and, when g is not NULL, g [P, K-1, E], for P <= 8 (IGCN_PERM_MAX_G_ROWS: the
+ *   observed pass through the same tile code, so a relabelling equal to the observed one ties exactly); exceed is not
+ *   touched.  scratch, alignment, limits and the guarantees (one writer per element, no atomics, no allocation, same
+ *   bits for any tile, launch or chunk) are those of igcn_perm_maxsum; scratch: igcn_perm_maxsum_scratch_bytes(P, E). */
+#define IGCN_PERM_MAX_GROUPS 5
+int igcn_perm_maxf(int P, int S, int E, int K, const uint8_t* labels, int64_t ldl, const void* planes,
+                   const float* weights /* HOST, [K], copied into the launch */, const float* b_obs, float* maxstat,
+                   int32_t* exceed, float* b, float* g /* or NULL */, void* scratch, size_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
