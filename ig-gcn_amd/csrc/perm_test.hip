@@ -20,6 +20,9 @@
 //
 // igcn_perm_maxf (k_perm_maxf, below the two-group kernels) is the same product for K = 2..5 groups: K - 1 indicator
 // operands read off one label byte, one statistic B of which the one-way ANOVA F is an increasing function.
+//
+// igcn_perm_supra (k_perm_supra, below k_perm_maxsum) is the two-group product once more with an epilogue that keeps one
+// bit per (relabelling, entry), |G| >= thr: the input of the network-based statistic (csrc/nbs.hip labels the graphs).
 #include <math.h>
 
 #include "common.h"
@@ -250,6 +253,90 @@ k_perm_maxsum(int P, int S, int E, int Sp, const uint8_t* __restrict__ member, i
     __syncthreads();
     if (tid < PT_BN && n0 + tid < E)
       pcnt[(size_t)blockIdx.x * E + n0 + tid] = cnt_s[0][tid] + cnt_s[1][tid] + cnt_s[2][tid] + cnt_s[3][tid];
+  }
+}
+
+// ---- suprathreshold bits: the network-based statistic's first half ----------------------------------------------------------
+// The tile and the main loop of k_perm_maxsum (the accumulators hold the bits igcn_perm_maxsum writes to g), and an
+// epilogue that keeps ONE BIT per (relabelling, entry): bit e & 31 of word e >> 5 of row p is set iff tested[e] and
+// v >= thr, v = |G| (tail 0), G (tail +1) or -G (tail -1).  For one accumulator register (a, b, r) a wave-wide ballot
+// holds four 16-bit pieces, piece lane >> 4 the 16 columns of fragment b of row 16 a + 4 (lane >> 4) + r; the four b
+// pieces of a row are the tile's two words.  Lane (lg, lr = 4 a + r) keeps them, so lanes lr < 8 store the wave's 32
+// rows at once: one writer per word, no atomics, no scratch, and no LDS beyond the staging buffers.  The block of the
+// last column tile also clears the words of its rows between Ep / 32 and ldw.
+__global__ void __launch_bounds__(PT_T)
+k_perm_supra(int P, int S, int E, int Sp, const uint8_t* __restrict__ member, int64_t ldm, int vec,
+             const unsigned short* __restrict__ planes, size_t plane, float thr, int tail,
+             const uint8_t* __restrict__ tested, unsigned* __restrict__ bits, int64_t ldw) {
+  __shared__ __attribute__((aligned(16))) unsigned short As[2][PT_BM][PT_LD];
+  __shared__ __attribute__((aligned(16))) unsigned short Bs[2][3][PT_BN][PT_LD];
+  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lr = lane & 15, lg = lane >> 4;
+  const int m0 = blockIdx.x * PT_BM, n0 = blockIdx.y * PT_BN;
+
+  pt_f32x4 acc[2][4];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[a][b] = (pt_f32x4){0.f, 0.f, 0.f, 0.f};
+
+  PtStage st;
+  pt_load(st, member, ldm, vec != 0, P, S, m0, planes, plane, Sp, n0, 0, tid);
+  pt_store(st, As[0], Bs[0], S, 0, tid);
+  __syncthreads();
+  int buf = 0;
+  for (int k0 = 0; k0 < Sp; k0 += PT_BK) {
+    const bool more = k0 + PT_BK < Sp;
+    if (more) pt_load(st, member, ldm, vec != 0, P, S, m0, planes, plane, Sp, n0, k0 + PT_BK, tid);
+    pt_bf16x8 fa[2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a) fa[a] = *reinterpret_cast<const pt_bf16x8*>(&As[buf][w * 32 + a * 16 + lr][lg * 8]);
+#pragma unroll
+    for (int q = 0; q < 3; ++q)                         // planes hi, mid, lo into the same accumulators
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        const pt_bf16x8 fb = *reinterpret_cast<const pt_bf16x8*>(&Bs[buf][q][b * 16 + lr][lg * 8]);
+#pragma unroll
+        for (int a = 0; a < 2; ++a) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[a], fb, acc[a][b], 0, 0, 0);
+      }
+    if (more) pt_store(st, As[buf ^ 1], Bs[buf ^ 1], S, k0 + PT_BK, tid);
+    __syncthreads();
+    buf ^= 1;
+  }
+
+  // ---- epilogue: G stays in registers, one bit of it leaves ----
+  bool on[4];                                           // the lane's four columns: real and tested
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    const int e = n0 + 16 * b + lr;
+    on[b] = e < E && tested[e] != 0;
+  }
+  const float sgn = (float)tail;                        // (+-1: the product is exact)
+  unsigned w0 = 0u, w1 = 0u;                            // the two words of row 16 a + 4 lg + r, kept by lane lr = 4 a + r
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      unsigned piece[4];
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        const float x = acc[a][b][r];
+        const float v = tail == 0 ? fabsf(x) : sgn * x;
+        const unsigned long long m = __ballot(on[b] && v >= thr);
+        piece[b] = (unsigned)(m >> (16 * lg)) & 0xFFFFu;
+      }
+      if (lr == 4 * a + r) {
+        w0 = piece[0] | (piece[1] << 16);
+        w1 = piece[2] | (piece[3] << 16);
+      }
+    }
+  const int p = m0 + w * 32 + 16 * (lr >> 2) + 4 * lg + (lr & 3);
+  if (lr < 8 && p < P) {
+    unsigned* row = bits + (int64_t)p * ldw;
+    row[2 * blockIdx.y] = w0;
+    row[2 * blockIdx.y + 1] = w1;
+    if (blockIdx.y == gridDim.y - 1)
+      for (int64_t x = 2 * (int64_t)gridDim.y; x < ldw; ++x) row[x] = 0u;
   }
 }
 
@@ -539,6 +626,31 @@ extern "C" int igcn_perm_maxsum(int P, int S, int E, const uint8_t* member, int6
   hipLaunchKernelGGL(k_perm_fold_max, dim3((P + 255) / 256), dim3(256), 0, st, P, tiles_e, pmax, maxabs);
   if (g_obs)
     hipLaunchKernelGGL(k_perm_fold_cnt, dim3((E + 255) / 256), dim3(256), 0, st, E, tiles_p, pcnt, exceed);
+  IGCN_CHECK_LAUNCH(who);
+  return IGCN_OK;
+}
+
+extern "C" int igcn_perm_supra(int P, int S, int E, const uint8_t* member, int64_t ldm, const void* planes, float thr,
+                               int tail, const uint8_t* tested, void* bits, int64_t ldw, void* stream) {
+  const char* who = "perm_supra";
+  IGCN_REQUIRE(S >= IGCN_PERM_MIN_S && S <= IGCN_PERM_MAX_S, "%s: S=%d subjects outside [%d,%d]", who, S, IGCN_PERM_MIN_S,
+               IGCN_PERM_MAX_S);
+  IGCN_REQUIRE(E >= 1 && E <= IGCN_PERM_MAX_E, "%s: E=%d map entries outside [1,%d]", who, E, IGCN_PERM_MAX_E);
+  IGCN_REQUIRE(P >= 1 && P <= IGCN_PERM_MAX_P, "%s: P=%d relabellings in one launch outside [1,%d]", who, P,
+               IGCN_PERM_MAX_P);
+  IGCN_REQUIRE(ldm >= S, "%s: member row stride %lld below S=%d", who, (long long)ldm, S);
+  IGCN_REQUIRE(member && planes && tested && bits, "%s: a null buffer", who);
+  IGCN_REQUIRE(isfinite(thr) && thr > 0.f, "%s: the threshold is %g (finite and > 0)", who, (double)thr);
+  IGCN_REQUIRE(tail >= -1 && tail <= 1, "%s: tail=%d (-1, 0 or 1)", who, tail);
+  const int Ep = pt_ep(E), Sp = pt_sp(S);
+  IGCN_REQUIRE(ldw >= Ep / 32, "%s: bits row stride %lld words below %d (E=%d rounded up to %d, 32 entries a word)", who,
+               (long long)ldw, Ep / 32, E, PT_BN);
+  IGCN_REQUIRE(((uintptr_t)planes & 15) == 0 && ((uintptr_t)bits & 15) == 0,
+               "%s: the planes and the bits must be 16-byte aligned", who);
+  const int tiles_p = (P + PT_BM - 1) / PT_BM, tiles_e = Ep / PT_BN;
+  const int vec = (ldm % 16 == 0 && ((uintptr_t)member & 15) == 0) ? 1 : 0;
+  hipLaunchKernelGGL(k_perm_supra, dim3(tiles_p, tiles_e), dim3(PT_T), 0, (hipStream_t)stream, P, S, E, Sp, member, ldm,
+                     vec, (const unsigned short*)planes, (size_t)Ep * Sp, thr, tail, tested, (unsigned*)bits, ldw);
   IGCN_CHECK_LAUNCH(who);
   return IGCN_OK;
 }

@@ -2,7 +2,8 @@
 — over one per-class accumulator (``ClassSums``).  Every pass runs a model method per batch, sums what it returns per
 class of ``data.y`` on the device (igcn_attn_map_accumulate: fp64, sample order; one call per quantity and batch) and
 reads the device once at the end.  ``group_difference`` is a pass of its own: it keeps every subject's map and hands the
-table to the max-T permutation test of ``igcn_amd.stats``.  None of them trains; ``igcn_amd.train`` re-exports the five names.
+table to the max-T permutation test of ``igcn_amd.stats``; ``network_difference`` hands the ROI x ROI tables to its
+network-based statistic.  None of them trains; ``igcn_amd.train`` re-exports the six names.
 """
 import torch
 
@@ -239,6 +240,29 @@ def _subject_maps(model, data, quantity, kw):
                                 inputs=kw.get("inputs", "image"), normalize=kw.get("normalize", True))["attr"]
 
 
+def _stack_subject_maps(who, loader, device, subject_maps):
+    """(x [n, ...] fp32, labels [n] int64): the per-subject maps ``subject_maps(data)`` [B, ...] of every batch copied
+    into one preallocated [S_all, E] device buffer, ``data.y`` beside it."""
+    total = len(loader.dataset) if hasattr(loader, "dataset") else sum(int(d.num_graphs) for d in loader)
+    buf = labels = None
+    n = 0
+    for data in _batches(loader, device):
+        m = subject_maps(data).detach()
+        b = int(m.shape[0])
+        if buf is None:
+            shape = tuple(m.shape[1:])
+            buf = ops._buffer((total, m[0].numel()), torch.float32, m.device)
+            labels = ops._buffer((total,), torch.int64, m.device)
+        if n + b > total:
+            raise ValueError(f"{who}: the loader yields more than its {total} subjects")
+        buf[n:n + b] = m.reshape(b, -1)
+        labels[n:n + b] = data.y.view(-1)
+        n += b
+    if n == 0:
+        raise ValueError(f"{who}: the loader is empty")
+    return buf[:n].view(n, *shape), labels[:n]
+
+
 def group_difference(model, loader, quantity="association", groups=(0, 1), permutations=10000, seed=0, members=None,
                      top_k=10, **pass_kw):
     """Which entries of a cohort map differ between two diagnosis groups, corrected over the whole map: the two-sample
@@ -263,32 +287,38 @@ def group_difference(model, loader, quantity="association", groups=(0, 1), permu
         raise TypeError(f"group_difference: {quantity!r} takes no {sorted(set(pass_kw) - known)}")
     if pass_kw.get("source", "mask") not in ("mask", "gat"):
         raise ValueError(f"group_difference: source={pass_kw['source']!r} ('mask' or 'gat')")
-    total = len(loader.dataset) if hasattr(loader, "dataset") else sum(int(d.num_graphs) for d in loader)
-    buf = labels = None
-    n = 0
-    for data in _batches(loader, pass_kw.get("device")):
-        m = _subject_maps(model, data, quantity, pass_kw).detach()
-        b = int(m.shape[0])
-        if buf is None:
-            shape = tuple(m.shape[1:])
-            buf = ops._buffer((total, m[0].numel()), torch.float32, m.device)
-            labels = ops._buffer((total,), torch.int64, m.device)
-        if n + b > total:
-            raise ValueError(f"group_difference: the loader yields more than its {total} subjects")
-        buf[n:n + b] = m.reshape(b, -1)
-        labels[n:n + b] = data.y.view(-1)
-        n += b
-    if n == 0:
-        raise ValueError("group_difference: the loader is empty")
+    x, labels = _stack_subject_maps("group_difference", loader, pass_kw.get("device"),
+                                    lambda data: _subject_maps(model, data, quantity, pass_kw))
     if len(groups) > 2:
-        out = stats.permutation_anova(buf[:n].view(n, *shape), labels[:n], groups=groups, permutations=permutations,
-                                      seed=seed, labels=members)
+        out = stats.permutation_anova(x, labels, groups=groups, permutations=permutations, seed=seed, labels=members)
         t_abs = out["f"].reshape(-1)
     else:
-        out = stats.permutation_test(buf[:n].view(n, *shape), labels[:n], groups=groups, permutations=permutations,
-                                     seed=seed, members=members)
+        out = stats.permutation_test(x, labels, groups=groups, permutations=permutations, seed=seed, members=members)
         t_abs = out["t"].reshape(-1).abs()
     hit = torch.nonzero(out["p_fwe"].reshape(-1) <= 0.05).view(-1)
     order = torch.argsort(t_abs[hit], descending=True, stable=True)[:max(int(top_k), 0)]
     out["significant"] = hit[order]
+    return out
+
+
+def network_difference(model, loader, source="mask", groups=(0, 1), threshold=3.1, tail="both", permutations=5000,
+                       seed=0, members=None, symmetric=False, weighted=False, layer=-1, isExplain=False, device=None):
+    """Which connected sub-networks of the ROI x ROI connectivity maps differ between two diagnosis groups: the
+    network-based statistic (``stats.network_based_statistic``) on the per-subject maps of ``source`` — "mask"
+    (``model.edge_importance``, with ``weighted``) or "gat" (layer ``layer`` of ``model.gat_attention``, with
+    ``isExplain``).  A pass of its own, like ``group_difference``: every subject's map is kept.  ``threshold``, ``tail``,
+    ``permutations``, ``seed``, ``members`` and ``symmetric`` are those of the statistic.  Returns its dict plus
+    ``significant`` (int64: the labels of the components with ``p_fwe <= 0.05``, largest extent first).  A group with fewer
+    than 2 subjects raises ValueError."""
+    from . import stats
+    if source not in ("mask", "gat"):
+        raise ValueError(f"network_difference: source={source!r} ('mask' or 'gat')")
+    subject_maps = ((lambda data: model.edge_importance(data, weighted=weighted)) if source == "mask" else
+                    (lambda data: model.gat_attention(data, isExplain=isExplain)[:, layer]))
+    x, labels = _stack_subject_maps("network_difference", loader, device, subject_maps)
+    out = stats.network_based_statistic(x, labels, groups=groups, threshold=threshold, tail=tail,
+                                        permutations=permutations, seed=seed, members=members, symmetric=symmetric)
+    comp, extent = out["component"], out["extent"]
+    roots = torch.nonzero((comp == torch.arange(comp.numel(), device=comp.device)) & (out["p_fwe"] <= 0.05)).view(-1)
+    out["significant"] = roots[torch.argsort(extent[roots], descending=True, stable=True)]
     return out

@@ -3889,6 +3889,84 @@ def perm_maxf(labels, planes, e, weights, b_obs=None, want_g=False):
     return maxstat, exceed
 
 
+NBS_MAX_ROIS = _L["IGCN_NBS_MAX_ROIS"]
+
+
+def perm_supra(member, planes, e, thr, tail, tested):
+    """One bit per (relabelling, entry) of igcn_perm_supra: member [P, S] uint8 and planes as for ``perm_maxsum``,
+    ``thr`` a finite positive threshold on G, ``tail`` 0 (|G| >= thr), +1 (G >= thr) or -1 (-G >= thr), ``tested`` [E]
+    uint8 / bool (an entry that is not tested never sets its bit).  Returns bits int32 [P, Ep / 32] (Ep = E rounded up to
+    64): bit e & 31 of word e >> 5 of row p; every word is written and the bits at or behind E are 0."""
+    if member.dtype != torch.uint8 or member.dim() != 2 or member.stride(1) != 1 or member.device != planes.device:
+        raise TypeError("perm_supra: member must be uint8 [P, S] with unit column stride on the planes' device")
+    p, s, e, dev = int(member.shape[0]), int(member.shape[1]), int(e), planes.device
+    thr, tail = float(thr), int(tail)
+    if not 0 < thr < float("inf"):
+        raise ValueError(f"perm_supra: the threshold is {thr} (finite and > 0)")
+    if tail not in (-1, 0, 1):
+        raise ValueError(f"perm_supra: tail={tail} (-1, 0 or 1)")
+    if not 1 <= p <= PERM_MAX_P:
+        raise ValueError(f"perm_supra: P={p} relabellings in one launch outside [1, {PERM_MAX_P}]")
+    if not PERM_MIN_S <= s <= PERM_MAX_S or not 1 <= e <= PERM_MAX_E:
+        raise ValueError(f"perm_supra: S={s} outside [{PERM_MIN_S}, {PERM_MAX_S}] or E={e} outside [1, {PERM_MAX_E}]")
+    ep = perm_plane_dims(s, e)[0]
+    if (planes.dtype != torch.bfloat16 or not planes.is_contiguous() or tuple(planes.shape) != (3,) + perm_plane_dims(s, e)):
+        raise ValueError(f"perm_supra: planes {tuple(planes.shape)} are not those of perm_prepare for S={s}, E={e}")
+    if tested.dtype not in (torch.uint8, torch.bool) or tested.numel() != e or tested.device != dev:
+        raise ValueError(f"perm_supra: tested must be uint8 or bool with {e} entries on the planes' device")
+    tested = tested.reshape(-1).to(torch.uint8).contiguous()
+    ldm = int(member.stride(0)) if p > 1 else max(int(member.stride(0)), s)
+    if ldm < s:
+        raise ValueError("perm_supra: the rows of member overlap")
+    if not member.is_cuda:
+        raise _lib.IgcnError("libigcn operates on device memory only; got a CPU tensor")
+    ldw = ep // 32
+    bits = _buffer((p, ldw), torch.int32, dev)
+    call("igcn_perm_supra", p, s, e, member.data_ptr(), ldm, ptr(planes), thr, tail, ptr(tested), ptr(bits), ldw,
+         stream_ptr())
+    return bits
+
+
+def nbs_pack(mask):
+    """bool [P, R, R] (source row, target column) as the bits of ``perm_supra``: int32 [P, Ep / 32] with Ep = R R rounded
+    up to 64, entry e = i R + j at bit e & 31 of word e >> 5.  torch ops only, on the mask's device."""
+    if mask.dim() != 3 or mask.shape[1] != mask.shape[2] or mask.dtype != torch.bool:
+        raise ValueError("nbs_pack: mask must be bool [P, R, R]")
+    p, e, dev = int(mask.shape[0]), int(mask.shape[1]) ** 2, mask.device
+    ldw = -(-e // 64) * 2
+    flat = torch.nn.functional.pad(mask.reshape(p, e), (0, ldw * 32 - e)).long()
+    words = (flat.view(p, ldw, 32) << torch.arange(32, dtype=torch.int64, device=dev)).sum(2)
+    bits = _buffer((p, ldw), torch.int32, dev)
+    bits.copy_(torch.where(words >= 2 ** 31, words - 2 ** 32, words))           # (the bit pattern, as a signed word)
+    return bits
+
+
+def nbs_components(bits, r, want_labels=False):
+    """The connected components of P graphs on ``r`` nodes (igcn_nbs_components): bits int32 [P, >= ceil(r r / 32)], row p
+    the [r, r] entry set of relabelling p as ``perm_supra`` / ``nbs_pack`` lay it out.  Nodes i != j are joined when bit
+    (i, j) or bit (j, i) is set; a component's extent is the number of set bits whose source row lies in it.  Returns
+    max_extent int32 [P], or with ``want_labels`` (max_extent, label int32 [P, r]: the smallest node index of the
+    node's component, extent int32 [P, r]: the extent of the node's component)."""
+    r = int(r)
+    if not 2 <= r <= NBS_MAX_ROIS:
+        raise ValueError(f"nbs_components: R={r} regions outside [2, {NBS_MAX_ROIS}]")
+    if bits.dtype != torch.int32 or bits.dim() != 2 or bits.stride(1) != 1 or bits.shape[1] < -(-r * r // 32):
+        raise ValueError(f"nbs_components: bits must be int32 [P, >= {-(-r * r // 32)}] with unit column stride")
+    p, dev = int(bits.shape[0]), bits.device
+    if not 1 <= p <= PERM_MAX_P:
+        raise ValueError(f"nbs_components: P={p} relabellings in one launch outside [1, {PERM_MAX_P}]")
+    ldw = int(bits.stride(0)) if p > 1 else max(int(bits.stride(0)), int(bits.shape[1]))
+    if ldw < bits.shape[1]:
+        raise ValueError("nbs_components: the rows of bits overlap")
+    if not bits.is_cuda:
+        raise _lib.IgcnError("libigcn operates on device memory only; got a CPU tensor")
+    max_extent = _buffer((p,), torch.int32, dev)
+    label = _buffer((p, r), torch.int32, dev) if want_labels else None
+    extent = _buffer((p, r), torch.int32, dev) if want_labels else None
+    call("igcn_nbs_components", p, r, bits.data_ptr(), ldw, ptr(max_extent), ptr(label), ptr(extent), stream_ptr())
+    return (max_extent, label, extent) if want_labels else max_extent
+
+
 # =================================================================================================
 # backward of ops.SgcnFront
 # =================================================================================================

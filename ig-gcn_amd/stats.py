@@ -10,9 +10,12 @@ and every relabelling, so comparing |G| is comparing |t| and the kernel (csrc/pe
 forms t.  Two-sided only.
 
 ``permutation_anova`` below is the counterpart for three to five groups: the one-way ANOVA F with the same max-statistic
-correction (igcn_perm_maxf).
+correction (igcn_perm_maxf).  ``network_based_statistic`` at the end is the cluster-level test for the ROI x ROI
+connectivity maps: connected components of the suprathreshold graph, corrected by the largest component's extent
+(igcn_perm_supra, igcn_nbs_components).
 """
 import math
+from types import SimpleNamespace
 
 import torch
 
@@ -43,6 +46,67 @@ def draw_members(n, n_a, permutations, seed=0, device="cuda"):
     return members
 
 
+def _two_groups(who, x, y, groups, permutations, seed, members, chunk):
+    """What the two-group tests share up to the observed labelling: the kept rows, the checked (or drawn) and aligned
+    ``members``, the chunk, the statistics and planes of ``ops.perm_prepare`` and ``g_obs`` [E] (``ops.perm_maxsum`` on the
+    observed labelling).  ``who`` names the caller in the messages."""
+    x2 = x.reshape(x.shape[0], -1).contiguous()
+    dev = x2.device
+    y = torch.as_tensor(y).view(-1).to(device=dev, dtype=torch.int64)
+    if y.numel() != x2.shape[0]:
+        raise ValueError(f"{who}: {y.numel()} labels for {x2.shape[0]} subjects")
+    ga, gb = int(groups[0]), int(groups[1])
+    if ga == gb:
+        raise ValueError(f"{who}: the two groups are the same label")
+    rows = torch.nonzero((y == ga) | (y == gb)).view(-1)
+    in_a = (y[rows] == ga)
+    s = int(rows.numel())
+    n_a = int(in_a.sum())
+    n_b = s - n_a
+    if n_a < 2 or n_b < 2:
+        raise ValueError(f"{who}: groups {ga} / {gb} have {n_a} / {n_b} subjects (at least 2 each)")
+    if not ops.PERM_MIN_S <= s <= ops.PERM_MAX_S:
+        raise ValueError(f"{who}: S={s} subjects outside [{ops.PERM_MIN_S}, {ops.PERM_MAX_S}]")
+    e = int(x2.shape[1])
+    if members is None:
+        members = draw_members(s, n_a, permutations, seed, dev)
+    else:
+        if (not torch.is_tensor(members) or members.dim() != 2 or members.shape[1] != s or members.shape[0] < 1
+                or members.dtype != torch.uint8):
+            raise ValueError(f"{who}: members must be uint8 [P, {s}]")
+        members = members.to(dev)
+        if bool((members > 1).any()) or bool((members.sum(1, dtype=torch.int64) != n_a).any()):
+            raise ValueError(f"{who}: every row of members must hold {n_a} ones and {n_b} zeros")
+        if members.stride(1) != 1 or members.stride(0) % 16 or members.data_ptr() % 16:
+            padded = _padded_rows(members.shape[0], s, dev)
+            padded.copy_(members)
+            members = padded
+    p_total = int(members.shape[0])
+    chunk = DEFAULT_CHUNK if chunk is None else int(chunk)
+    if not 1 <= chunk <= ops.PERM_MAX_P:
+        raise ValueError(f"{who}: chunk={chunk} outside [1, {ops.PERM_MAX_P}]")
+
+    mean, sd, constant, planes = ops.perm_prepare(x2, rows, standardize=True)
+    if not (bool(torch.isfinite(mean).all()) and bool(torch.isfinite(sd).all())):
+        raise ValueError(f"{who}: x holds non-finite values in the rows under test")
+    observed = _padded_rows(1, s, dev)
+    observed.copy_(in_a.view(1, s))
+    _, g = ops.perm_maxsum(observed, planes, e)
+    return SimpleNamespace(dev=dev, s=s, n_a=n_a, n_b=n_b, e=e, members=members, p_total=p_total, chunk=chunk, sd=sd,
+                           constant=constant, planes=planes, observed=observed, g_obs=g.view(-1).contiguous())
+
+
+def _t_and_diff(c):
+    """(t, diff) [E] fp64 of the observed labelling of ``_two_groups``: the pooled-variance Student t and the group-A
+    mean minus the group-B mean in original units; 0 for a constant entry."""
+    const = c.constant.bool()
+    gd = c.g_obs.double()
+    diff = (c.sd * gd * (c.s / (c.n_a * c.n_b))).masked_fill(const, 0.0)
+    r = (gd / math.sqrt(c.n_a * c.n_b)).clamp(-1.0, 1.0)
+    t = (r * torch.sqrt((c.s - 2) / (1 - r * r))).masked_fill(const, 0.0)
+    return t, diff
+
+
 def permutation_test(x, y, groups=(0, 1), permutations=10000, seed=0, members=None, chunk=None):
     """Max-T permutation test of ``groups[0]`` against ``groups[1]`` for every entry of the per-subject maps
     ``x`` [S_all, ...] (fp32, on the device) with labels ``y`` [S_all].  The rows with another label are left out.
@@ -58,49 +122,9 @@ def permutation_test(x, y, groups=(0, 1), permutations=10000, seed=0, members=No
     if not torch.is_tensor(x) or x.dim() < 2 or x.dtype != torch.float32:
         raise TypeError("permutation_test: x must be a float32 tensor [S_all, ...]")
     shape = tuple(x.shape[1:])
-    x2 = x.reshape(x.shape[0], -1).contiguous()
-    dev = x2.device
-    y = torch.as_tensor(y).view(-1).to(device=dev, dtype=torch.int64)
-    if y.numel() != x2.shape[0]:
-        raise ValueError(f"permutation_test: {y.numel()} labels for {x2.shape[0]} subjects")
-    ga, gb = int(groups[0]), int(groups[1])
-    if ga == gb:
-        raise ValueError("permutation_test: the two groups are the same label")
-    rows = torch.nonzero((y == ga) | (y == gb)).view(-1)
-    in_a = (y[rows] == ga)
-    s = int(rows.numel())
-    n_a = int(in_a.sum())
-    n_b = s - n_a
-    if n_a < 2 or n_b < 2:
-        raise ValueError(f"permutation_test: groups {ga} / {gb} have {n_a} / {n_b} subjects (at least 2 each)")
-    if not ops.PERM_MIN_S <= s <= ops.PERM_MAX_S:
-        raise ValueError(f"permutation_test: S={s} subjects outside [{ops.PERM_MIN_S}, {ops.PERM_MAX_S}]")
-    e = int(x2.shape[1])
-    if members is None:
-        members = draw_members(s, n_a, permutations, seed, dev)
-    else:
-        if (not torch.is_tensor(members) or members.dim() != 2 or members.shape[1] != s or members.shape[0] < 1
-                or members.dtype != torch.uint8):
-            raise ValueError(f"permutation_test: members must be uint8 [P, {s}]")
-        members = members.to(dev)
-        if bool((members > 1).any()) or bool((members.sum(1, dtype=torch.int64) != n_a).any()):
-            raise ValueError(f"permutation_test: every row of members must hold {n_a} ones and {n_b} zeros")
-        if members.stride(1) != 1 or members.stride(0) % 16 or members.data_ptr() % 16:
-            padded = _padded_rows(members.shape[0], s, dev)
-            padded.copy_(members)
-            members = padded
-    p_total = int(members.shape[0])
-    chunk = DEFAULT_CHUNK if chunk is None else int(chunk)
-    if not 1 <= chunk <= ops.PERM_MAX_P:
-        raise ValueError(f"permutation_test: chunk={chunk} outside [1, {ops.PERM_MAX_P}]")
-
-    mean, sd, constant, planes = ops.perm_prepare(x2, rows, standardize=True)
-    if not (bool(torch.isfinite(mean).all()) and bool(torch.isfinite(sd).all())):
-        raise ValueError("permutation_test: x holds non-finite values in the rows under test")
-    observed = _padded_rows(1, s, dev)
-    observed.copy_(in_a.view(1, s))
-    _, g = ops.perm_maxsum(observed, planes, e)
-    g_obs = g.view(-1).contiguous()
+    c = _two_groups("permutation_test", x, y, groups, permutations, seed, members, chunk)
+    dev, n_a, n_b, e, members, p_total, chunk = c.dev, c.n_a, c.n_b, c.e, c.members, c.p_total, c.chunk
+    constant, planes, g_obs = c.constant, c.planes, c.g_obs
     null_max = ops._buffer((p_total,), torch.float32, dev)
     exceed = ops._buffer((e,), torch.int64, dev).zero_()
     for p0 in range(0, p_total, chunk):
@@ -114,10 +138,7 @@ def permutation_test(x, y, groups=(0, 1), permutations=10000, seed=0, members=No
     den = torch.tensor(float(1 + p_total), dtype=torch.float64, device=dev)      # (a tensor divisor: a true division)
     p_unc = ((1 + exceed).double() / den).masked_fill(const, 1.0)
     p_fwe = ((1 + fwe).double() / den).masked_fill(const, 1.0)
-    gd = g_obs.double()
-    diff = (sd * gd * (s / (n_a * n_b))).masked_fill(const, 0.0)
-    r = (gd / math.sqrt(n_a * n_b)).clamp(-1.0, 1.0)
-    t = (r * torch.sqrt((s - 2) / (1 - r * r))).masked_fill(const, 0.0)
+    t, diff = _t_and_diff(c)
     return {"diff": diff.view(shape), "t": t.view(shape), "p_unc": p_unc.view(shape), "p_fwe": p_fwe.view(shape),
             "constant": const.view(shape), "null_max": null_max, "n": (n_a, n_b), "permutations": p_total}
 
@@ -233,3 +254,85 @@ def permutation_anova(x, y, groups=(0, 1, 2), permutations=10000, seed=0, labels
     return {"f": f.view(shape), "eta2": eta2.view(shape), "means": means.view(k, *shape), "p_unc": p_unc.view(shape),
             "p_fwe": p_fwe.view(shape), "constant": const.view(shape), "null_max": null_max, "n": n,
             "df": (k - 1, s - k), "permutations": p_total}
+
+
+# ---- cluster level, on the one map that is a graph: the network-based statistic ---------------------------------------------
+# Zalesky, Fornito & Bullmore 2010: threshold the edge-wise t map of the ROI x ROI connectivity maps at a primary
+# threshold t0, take the connected components of the suprathreshold graph, measure each by its extent (its number of
+# suprathreshold entries) and correct with the permutation distribution of the LARGEST extent.  |t| is one increasing
+# function of |G|, so t0 is the one threshold  thr = sqrt(n_a n_b) t0 / sqrt(S - 2 + t0^2)  on G for every entry and
+# every relabelling: igcn_perm_supra keeps one bit per (relabelling, entry) of the product igcn_perm_maxsum forms, and
+# igcn_nbs_components labels the P graphs, one wave each.
+TAILS = {"both": 0, "greater": 1, "less": -1}
+
+
+def _unpack_bits(bits, e):
+    """bool [P, e] from the int32 words of ``ops.perm_supra``."""
+    shifts = torch.arange(32, dtype=torch.int32, device=bits.device)
+    return ((bits.unsqueeze(-1) >> shifts) & 1).bool().view(bits.shape[0], -1)[:, :e]
+
+
+def network_based_statistic(x, y, groups=(0, 1), threshold=3.1, tail="both", permutations=5000, seed=0, members=None,
+                            chunk=None, tested=None, symmetric=False):
+    """Network-based statistic of ``groups[0]`` against ``groups[1]`` on the per-subject ROI x ROI maps ``x``
+    [S_all, R, R] (fp32, on the device; entry (i, j): source row i, target column j, like ``data.A``) with labels ``y``.
+    Rows, ``members``, ``permutations`` / ``seed`` and ``chunk`` are those of ``permutation_test``.  ``threshold`` is the
+    primary threshold t0 on the pooled-variance Student t; ``tail`` "both" (|t| >= t0), "greater" (t >= t0: group A above
+    group B) or "less".  Tested are the entries of ``tested`` (bool [R, R], default all) off the diagonal that are not
+    constant over the kept rows; ``symmetric=True`` also drops the entries with i >= j, so that a symmetric map counts
+    every undirected edge once.  Regions i != j are joined when entry (i, j) or (j, i) is suprathreshold; a component's
+    extent is the number of suprathreshold entries whose source row lies in it.  R <= 128 (``ops.NBS_MAX_ROIS``).
+
+    Returns a dict: ``t``, ``diff`` [R, R] (fp64, as ``permutation_test`` forms them), ``supra`` (bool [R, R]: the
+    suprathreshold entries of the observed labelling), ``component`` (int64 [R]: the smallest region index of the
+    region's component, -1 where its extent is 0), ``extent`` (int64 [R]: of the region's component), ``p_fwe`` (fp64 [R]:
+    (1 + #{p : null_max[p] >= extent}) / (1 + P), 1 where the extent is 0), ``edge_p_fwe`` (fp64 [R, R]: the component's
+    p on the ``supra`` entries, 1 elsewhere), ``null_max`` (int32 [P]: the largest extent of every relabelling),
+    ``tested`` (bool [R, R]), ``threshold`` = (t0, the fp32 threshold on G), ``n`` = (n_a, n_b), ``permutations`` = P.
+    The result has the same bits for any chunking."""
+    who = "network_based_statistic"
+    if not torch.is_tensor(x) or x.dim() != 3 or x.shape[1] != x.shape[2] or x.dtype != torch.float32:
+        raise ValueError(f"{who}: x must be a float32 tensor [S_all, R, R]")
+    r = int(x.shape[1])
+    if not 2 <= r <= ops.NBS_MAX_ROIS:
+        raise ValueError(f"{who}: R={r} regions outside [2, {ops.NBS_MAX_ROIS}]")
+    t0 = float(threshold)
+    if not 0 < t0 < float("inf"):
+        raise ValueError(f"{who}: threshold={threshold} (finite and > 0)")
+    if tail not in TAILS:
+        raise ValueError(f"{who}: tail={tail!r} (one of {tuple(TAILS)})")
+    if tested is not None and (not torch.is_tensor(tested) or tested.dtype != torch.bool or tuple(tested.shape) != (r, r)):
+        raise ValueError(f"{who}: tested must be bool [{r}, {r}]")
+    c = _two_groups(who, x, y, groups, permutations, seed, members, chunk)
+    dev, e, p_total = c.dev, c.e, c.p_total
+    # the threshold on G: fp64 on the host, rounded once to fp32
+    thr = float(torch.tensor(math.sqrt(c.n_a * c.n_b) * t0 / math.sqrt(c.s - 2 + t0 * t0), dtype=torch.float64).float())
+    if not 0 < thr < float("inf"):
+        raise ValueError(f"{who}: threshold={threshold} gives the threshold {thr} on G")
+    keep = torch.ones(r, r, dtype=torch.bool, device=dev) if tested is None else tested.to(dev).clone()
+    keep &= ~torch.eye(r, dtype=torch.bool, device=dev)
+    if symmetric:
+        keep &= torch.ones(r, r, dtype=torch.bool, device=dev).triu(1)
+    keep &= ~c.constant.bool().view(r, r)
+    flags = keep.view(-1).to(torch.uint8)
+
+    bits_obs = ops.perm_supra(c.observed, c.planes, e, thr, TAILS[tail], flags)
+    _, label, extent = ops.nbs_components(bits_obs, r, want_labels=True)
+    null_max = ops._buffer((p_total,), torch.int32, dev)
+    for p0 in range(0, p_total, c.chunk):
+        bits = ops.perm_supra(c.members[p0:p0 + c.chunk], c.planes, e, thr, TAILS[tail], flags)
+        mx = ops.nbs_components(bits, r)
+        null_max[p0:p0 + mx.numel()] = mx
+    extent = extent.view(r).long()
+    empty = extent == 0
+    srt = torch.sort(null_max).values.long()
+    fwe = p_total - torch.searchsorted(srt, extent.contiguous(), right=False)     # #{p : null_max[p] >= extent[i]}
+    den = torch.tensor(float(1 + p_total), dtype=torch.float64, device=dev)      # (a tensor divisor: a true division)
+    p_fwe = ((1 + fwe).double() / den).masked_fill(empty, 1.0)
+    supra = _unpack_bits(bits_obs, e).view(r, r)
+    edge_p = torch.where(supra, p_fwe.view(r, 1).expand(r, r), torch.ones((), dtype=torch.float64, device=dev))
+    t, diff = _t_and_diff(c)
+    return {"t": t.view(r, r), "diff": diff.view(r, r), "supra": supra,
+            "component": label.view(r).long().masked_fill(empty, -1), "extent": extent, "p_fwe": p_fwe,
+            "edge_p_fwe": edge_p, "null_max": null_max, "tested": keep, "threshold": (t0, thr), "n": (c.n_a, c.n_b),
+            "permutations": p_total}

@@ -15,7 +15,7 @@ from . import switches
 from ._lib import call, ptr, stream_ptr
 from .capture import GradTable, ShapeCache, _capture, kept_trainer, rolled_back
 from .data import _batches
-from .maps import association_maps, attention_maps, connectivity_maps, group_difference, saliency_maps  # noqa: F401  (re-exported)
+from .maps import association_maps, attention_maps, connectivity_maps, group_difference, network_difference, saliency_maps  # noqa: F401  (re-exported)
 
 # sgcn_hyperparameters.py:18-23
 HP = SimpleNamespace(lamda_x_l1=0.1, lamda_e_l1=0.1, lamda_x_ent=0.1, lamda_e_ent=0.1, lamda_mi=1, lamda_ce=1)

@@ -1651,6 +1651,33 @@ int igcn_perm_maxf(int P, int S, int E, int K, const uint8_t* labels, int64_t ld
                    const float* weights /* HOST, [K], copied into the launch */, const float* b_obs, float* maxstat,
                    int32_t* exceed, float* b, float* g /* or NULL */, void* scratch, size_t scratch_bytes, void* stream);
 
+/* Network-based statistic (Zalesky, Fornito & Bullmore 2010) of a two-group difference over ROI x ROI connectivity maps,
+ * on the planes of igcn_perm_prepare: threshold the edge-wise statistic, take the connected components of what is left,
+ * correct with the permutation distribution of the largest component's extent.
+ * igcn_perm_supra (csrc/perm_test.hip): the product, the tile and the accumulation order of igcn_perm_maxsum — the
+ *   accumulators hold exactly the bits igcn_perm_maxsum writes to g — and ONE BIT per (relabelling, entry) leaves: with
+ *   v = |G[p, e]| for tail 0, G for tail +1 and -G for tail -1, bit e & 31 of word e >> 5 of row p of bits (uint32
+ *   [P, ldw], ldw >= Ep / 32 words, Ep = E rounded up to 64) is set iff tested[e] != 0 (uint8 [E], device) and v >= thr.
+ *   |t| is one increasing function of |G| for every column, so a primary threshold t0 on t is the ONE threshold
+ *   thr = sqrt(n_a n_b) t0 / sqrt(S - 2 + t0^2) on G.  Every word of every row below P is written, all-zero words and
+ *   the words behind Ep / 32 included; bits at or behind E are 0.  A row's words are assembled from wave ballots: one
+ *   writer per word, no atomics, no scratch, no fold launch.  thr finite and > 0, tail in {-1, 0, 1}, bits 16-byte
+ *   aligned; the other limits and guarantees are those of igcn_perm_maxsum.
+ * igcn_nbs_components (csrc/nbs.hip): row p of bits is the [R, R] entry set of relabelling p, row-major (entry i R + j:
+ *   source row i, target column j; E = R R), 2 <= R <= 128 (IGCN_NBS_MAX_ROIS), ldw >= ceil(R R / 32), 1 <= P <= 65536.
+ *   Nodes i != j are joined when bit (i, j) OR bit (j, i) is set (undirected; a diagonal bit joins nothing).  The extent
+ *   of a component is the number of set bits whose source row lies in it: every set entry counts once, diagonal bits
+ *   included, and with only the upper triangle tested every undirected edge counts once.  One wave per relabelling labels
+ *   the graph by minimum-label propagation in LDS.  max_extent[p] is the largest extent (0 for an empty graph);
+ *   label [P, R] (or NULL) the smallest node index of the node's component; extent [P, R] (or NULL) the extent of the
+ *   node's component, 0 for a node without a set entry in its row and without a neighbour.  All int32; one writer per
+ *   element; the extent sums are integer LDS atomics (one result in any order).  The library allocates nothing. */
+#define IGCN_NBS_MAX_ROIS 128
+int igcn_perm_supra(int P, int S, int E, const uint8_t* member, int64_t ldm, const void* planes, float thr, int tail,
+                    const uint8_t* tested /* [E] */, void* bits /* uint32 [P, ldw] */, int64_t ldw, void* stream);
+int igcn_nbs_components(int P, int R, const void* bits, int64_t ldw, int32_t* max_extent /* [P] */,
+                        int32_t* label /* [P, R] or NULL */, int32_t* extent /* [P, R] or NULL */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
