@@ -992,15 +992,16 @@ extern "C" int igcn_node_linear_bn_fwd(int B, int F, int N, int D, int groups, c
 // (ro_affine / ro_apply_kept: the apply pass's expression), stores it to LDS and to out_d (both backward passes read
 // it), and walks the lists (spmm_long_walk: the map kernel's sums).
 template <int F>
-__global__ void __launch_bounds__(SPMM_LT, 4)
-k_nlbn_apply_map(int B, int N, int groups, const float* __restrict__ x, const float* __restrict__ W,
-                 const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ mean,
-                 const float* __restrict__ rstd, const float* __restrict__ keep /*[B,N] or NULL*/,
-                 float* __restrict__ out_d, int n_out, int64_t vs, const int32_t* __restrict__ row_ptr,
-                 const int32_t* __restrict__ col, const float* __restrict__ val, float* __restrict__ y) {
+__device__ __forceinline__ void
+nlbn_apply_map_body(const int b /*the workgroup's sample*/, int B, int N, int groups, const float* __restrict__ x,
+                    const float* __restrict__ W, const float* __restrict__ gamma, const float* __restrict__ beta,
+                    const float* __restrict__ mean, const float* __restrict__ rstd,
+                    const float* __restrict__ keep /*[B,N] or NULL*/, float* __restrict__ out_d, int n_out, int64_t vs,
+                    const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
+                    const float* __restrict__ val, float* __restrict__ y) {
   extern __shared__ float ro_vec[];                    // [N]
   const float* __restrict__ w = W;
-  const int b = blockIdx.x, g = b / (B / groups);
+  const int g = b / (B / groups);
   for (int n = threadIdx.x; n < N; n += SPMM_LT) {
     const RoAffine af = ro_affine(rstd[(int64_t)g * N + n], gamma[n], beta[n], mean[(int64_t)g * N + n]);
     float xv[F], pre[1];
@@ -1014,6 +1015,16 @@ k_nlbn_apply_map(int B, int N, int groups, const float* __restrict__ x, const fl
   }
   __syncthreads();
   spmm_long_walk(ro_vec, b, 1, N, n_out, vs, 0, row_ptr, col, (const int32_t*)nullptr, val, y);
+}
+template <int F>
+__global__ void __launch_bounds__(SPMM_LT, 4)
+k_nlbn_apply_map(int B, int N, int groups, const float* __restrict__ x, const float* __restrict__ W,
+                 const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ mean,
+                 const float* __restrict__ rstd, const float* __restrict__ keep /*[B,N] or NULL*/,
+                 float* __restrict__ out_d, int n_out, int64_t vs, const int32_t* __restrict__ row_ptr,
+                 const int32_t* __restrict__ col, const float* __restrict__ val, float* __restrict__ y) {
+  nlbn_apply_map_body<F>((int)blockIdx.x, B, N, groups, x, W, gamma, beta, mean, rstd, keep, out_d, n_out, vs, row_ptr,
+                         col, val, y);
 }
 
 // host only: the fused launch covers this read-out (F inputs, D outputs per node, N nodes) in front of a one-channel
@@ -1417,15 +1428,18 @@ k_bn1d_bwd(int B, int C, int groups, int training, int relu, const float* __rest
 // narrow product itself — the latent MLP's 32 -> 32 layer, every channel's workgroup reading all of h — was measured at
 // 12.0 us against 4.7 + 4.9 for product + BatchNorm and removed: 32 workgroups cannot read 64 KB each, a row per lane,
 // in less than the 8-workgroup product and its launch take.]
+// The bodies take their channel `c` as a parameter: the workgroup is blockIdx.x of the kernels below, or one of the first
+// C workgroups of a read-out launch that carries the stage as a passenger (k_nlbn_*_ride).  `on`: the thread takes part;
+// the upper half of a 512-thread host workgroup walks through the barriers with on == false and adds 0.f for its waves.
 template <int PRODUCER>
-__global__ void __launch_bounds__(256)
-k_bn1d_fwd_reg(int B, int C, int groups, int training, float momentum, float eps, int relu,
-               const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
-               const float* __restrict__ keep, float* __restrict__ running_mean, float* __restrict__ running_var,
-               float* __restrict__ y, float* __restrict__ save_mean, float* __restrict__ save_rstd, int n_slabs,
-               float* __restrict__ x_out) {
+__device__ __forceinline__ void
+bn1d_fwd_reg_body(const int c, const bool on, int B, int C, int groups, int training, float momentum, float eps, int relu,
+                  const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
+                  const float* __restrict__ keep, float* __restrict__ running_mean, float* __restrict__ running_var,
+                  float* __restrict__ y, float* __restrict__ save_mean, float* __restrict__ save_rstd, int n_slabs,
+                  float* __restrict__ x_out) {
   __shared__ float red[32];
-  const int c = blockIdx.x, bg = B / groups;
+  const int bg = on ? B / groups : 0;                  // (an idle thread owns no sample)
   float rm = running_mean[c], rv = running_var[c];
   const float ga = gamma[c], be = beta[c];
   float xv[2][BN1_VP], kv[2][BN1_VP];
@@ -1508,14 +1522,25 @@ k_bn1d_fwd_reg(int B, int C, int groups, int training, float momentum, float eps
     running_var[c] = rv;
   }
 }
-
+template <int PRODUCER>
 __global__ void __launch_bounds__(256)
-k_bn1d_bwd_reg(int B, int C, int groups, int training, int relu, const float* __restrict__ x,
-               const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ save_mean,
-               const float* __restrict__ save_rstd, const float* __restrict__ dy, const float* __restrict__ keep,
-               float* __restrict__ dx, float* __restrict__ dgamma, float* __restrict__ dbeta) {
+k_bn1d_fwd_reg(int B, int C, int groups, int training, float momentum, float eps, int relu,
+               const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
+               const float* __restrict__ keep, float* __restrict__ running_mean, float* __restrict__ running_var,
+               float* __restrict__ y, float* __restrict__ save_mean, float* __restrict__ save_rstd, int n_slabs,
+               float* __restrict__ x_out) {
+  bn1d_fwd_reg_body<PRODUCER>((int)blockIdx.x, true, B, C, groups, training, momentum, eps, relu, x, gamma, beta, keep,
+                              running_mean, running_var, y, save_mean, save_rstd, n_slabs, x_out);
+}
+
+__device__ __forceinline__ void
+bn1d_bwd_reg_body(const int c, const bool on, int B, int C, int groups, int training, int relu,
+                  const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
+                  const float* __restrict__ save_mean, const float* __restrict__ save_rstd,
+                  const float* __restrict__ dy, const float* __restrict__ keep, float* __restrict__ dx,
+                  float* __restrict__ dgamma, float* __restrict__ dbeta) {
   __shared__ float red[32];
-  const int c = blockIdx.x, bg = B / groups;
+  const int bg = on ? B / groups : 0;                  // (an idle thread owns no sample)
   const float ga = gamma[c], be = beta[c];
   float xh[2][BN1_VP], dv[2][BN1_VP], mean[2], rstd[2];
 #pragma unroll
@@ -1567,6 +1592,14 @@ k_bn1d_bwd_reg(int B, int C, int groups, int training, int relu, const float* __
     dbeta[c] = db_tot;
   }
 }
+__global__ void __launch_bounds__(256)
+k_bn1d_bwd_reg(int B, int C, int groups, int training, int relu, const float* __restrict__ x,
+               const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ save_mean,
+               const float* __restrict__ save_rstd, const float* __restrict__ dy, const float* __restrict__ keep,
+               float* __restrict__ dx, float* __restrict__ dgamma, float* __restrict__ dbeta) {
+  bn1d_bwd_reg_body((int)blockIdx.x, true, B, C, groups, training, relu, x, gamma, beta, save_mean, save_rstd, dy, keep,
+                    dx, dgamma, dbeta);
+}
 
 extern "C" int igcn_bn1d_fwd(int B, int C, int groups, const float* x, const float* gamma, const float* beta,
                              float* running_mean, float* running_var, int training, float momentum, float eps,
@@ -1617,4 +1650,231 @@ extern "C" int igcn_bn1d_bwd(int B, int C, int groups, int training, int relu, c
                        beta, save_mean, save_rstd, dy, keep, dx, dgamma, dbeta);
   IGCN_CHECK_LAUNCH("bn1d_bwd");
   return IGCN_OK;
+}
+
+// =================================================================================================
+// The gene read-out's launches carry the latent MLP's BatchNorm stages (go_model.py:278-285).
+// A k_bn1d_*_reg stage is 32 workgroups and one 5-us latency chain; the gene read-out's passes between the same two
+// points of the step (after the paired read-outs, before the heads) have chip-wide grids and do not depend on it.  In a
+// `_ride` launch the FIRST job.C workgroups (dispatch order: the longer chain per workgroup starts first) run the
+// BatchNorm body for channel blockIdx.x, the others the read-out body with their coordinates shifted by job.C: the same
+// bodies, so the same bits as the two launches.  A read-out without passengers keeps igcn_node_linear_bn_* and the plain
+// kernels above.
+// =================================================================================================
+enum { BN1D_NONE = 0, BN1D_FWD = 1, BN1D_FWD_SLABS = 2, BN1D_BWD = 3 };
+// One BatchNorm1d stage: the arguments of k_bn1d_fwd_reg<0> (FWD), k_bn1d_fwd_reg<1> (FWD_SLABS: x = the slabs) or
+// k_bn1d_bwd_reg (BWD: mean / rstd are the saved ones, y = dx, x_out unused).  Travels by value in the kernel arguments.
+struct Bn1dJob {
+  int kind, B, C, groups, training, relu, n_slabs;
+  float momentum, eps;
+  const float *x, *gamma, *beta, *keep, *dy;
+  float *running_mean, *running_var, *y, *mean, *rstd, *x_out, *dgamma, *dbeta;
+};
+template <int KIND>
+__device__ __forceinline__ void bn1d_job_body(const Bn1dJob& j, const int c, const bool on) {
+  if constexpr (KIND == BN1D_BWD)
+    bn1d_bwd_reg_body(c, on, j.B, j.C, j.groups, j.training, j.relu, j.x, j.gamma, j.beta, j.mean, j.rstd, j.dy, j.keep,
+                      j.y, j.dgamma, j.dbeta);
+  else
+    bn1d_fwd_reg_body<KIND == BN1D_FWD_SLABS ? 1 : 0>(c, on, j.B, j.C, j.groups, j.training, j.momentum, j.eps, j.relu,
+                                                      j.x, j.gamma, j.beta, j.keep, j.running_mean, j.running_var, j.y,
+                                                      j.mean, j.rstd, j.n_slabs, j.x_out);
+}
+// the host's block of workgroup `wg` behind job.C passengers, in a 1-D grid of job.C + gx * gy
+#define RO_RIDE_BLK(job, gxv, gyv) \
+  RoBlk{((int)blockIdx.x - (job).C) % (gxv), ((int)blockIdx.x - (job).C) / (gxv), (int)(gxv), (int)(gyv)}
+
+template <int KIND>
+__global__ void __launch_bounds__(RO_T)
+k_nlbn_stats_ride(Bn1dJob job, int gx, int gy, int B, int N, int groups, const float* __restrict__ x,
+                  const float* __restrict__ W, float* __restrict__ partial) {
+  if ((int)blockIdx.x < job.C) return bn1d_job_body<KIND>(job, (int)blockIdx.x, true);
+  nlbn_stats_body<2, 1>(RO_RIDE_BLK(job, gx, gy), B, N, groups, x, W, partial);
+}
+// 512-thread workgroups (SPMM_LT): the upper half of a passenger's workgroup only takes part in the barriers
+template <int KIND>
+__global__ void __launch_bounds__(SPMM_LT, 4)
+k_nlbn_apply_map_ride(Bn1dJob job, int B, int N, int groups, const float* __restrict__ x, const float* __restrict__ W,
+                      const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ mean,
+                      const float* __restrict__ rstd, const float* __restrict__ keep, float* __restrict__ out_d,
+                      int n_out, int64_t vs, const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
+                      const float* __restrict__ val, float* __restrict__ y) {
+  if ((int)blockIdx.x < job.C) return bn1d_job_body<KIND>(job, (int)blockIdx.x, threadIdx.x < 256);
+  nlbn_apply_map_body<2>((int)blockIdx.x - job.C, B, N, groups, x, W, gamma, beta, mean, rstd, keep, out_d, n_out, vs,
+                         row_ptr, col, val, y);
+}
+__global__ void __launch_bounds__(RO_T, 8)     // (the parent's eight waves per SIMD: at most 64 VGPRs)
+k_nlbn_bwd_stats_ride(Bn1dJob job, int gx, int gy, int B, int N, int groups, const float* __restrict__ x,
+                      const float* __restrict__ W, const float* __restrict__ gamma, const float* __restrict__ beta,
+                      const float* __restrict__ mean, const float* __restrict__ rstd, const float* __restrict__ dout,
+                      const float* __restrict__ keep, float* __restrict__ partial) {
+  if ((int)blockIdx.x < job.C) return bn1d_job_body<BN1D_BWD>(job, (int)blockIdx.x, true);
+  nlbn_bwd_stats_body<2, 1>(RO_RIDE_BLK(job, gx, gy), B, N, groups, x, W, gamma, beta, mean, rstd, dout, keep, partial);
+}
+__global__ void __launch_bounds__(RO_T, 8)     // (the parent's eight waves per SIMD: at most 64 VGPRs)
+k_nlbn_bwd_apply_ride(Bn1dJob job, int gx, int gy, int B, int N, int groups, int training,
+                      const float* __restrict__ x, const float* __restrict__ W, const float* __restrict__ gamma,
+                      const float* __restrict__ beta, const float* __restrict__ mean, const float* __restrict__ rstd,
+                      const float* __restrict__ dout, const float* __restrict__ keep,
+                      const float* __restrict__ partial, int nchunks, float* __restrict__ dpre_out,
+                      float* __restrict__ dx, float* __restrict__ wpartial) {
+  if ((int)blockIdx.x < job.C) return bn1d_job_body<BN1D_BWD>(job, (int)blockIdx.x, true);
+  nlbn_bwd_apply_body<2, 1>(RO_RIDE_BLK(job, gx, gy), B, N, groups, training, x, W, gamma, beta, mean, rstd, dout, keep,
+                            partial, nchunks, dpre_out, dx, wpartial);
+}
+
+// ---- host side: the word table of igcn_gene_tail_{fwd,bwd} ---------------------------------------------------------
+// Records of GT_REC int64 words.  A BatchNorm stage: {kind, B, C, groups, relu, n_slabs, momentum, eps (the bits of a
+// double each), x, gamma, beta, keep, dy, running_mean, running_var, y, mean, rstd, x_out, dgamma, dbeta}.  A product
+// stage: {form, ...}: 1 = igcn_gemm_f32 of the 16 words behind it (igcn_gemm_f32_grouped's record), 2 = {n, n such
+// records} as one igcn_gemm_f32_grouped, 3 = igcn_small_linear_fwd {R, K, C, x, keep, W, b, y}, 4 = igcn_small_linear_bwd
+// {R, K, C, x, keep, W, dy, dx, dwb, scratch}.
+#define GT_REC 40
+static float gt_float(int64_t w) {
+  double d;
+  memcpy(&d, &w, sizeof d);
+  return (float)d;
+}
+static int gt_job(const int64_t* t, int training, int want_fwd, Bn1dJob* j) {
+  j->kind = (int)t[0];
+  j->B = (int)t[1]; j->C = (int)t[2]; j->groups = (int)t[3]; j->training = training; j->relu = (int)t[4];
+  j->n_slabs = (int)t[5];
+  j->momentum = gt_float(t[6]); j->eps = gt_float(t[7]);
+  j->x = (const float*)t[8]; j->gamma = (const float*)t[9]; j->beta = (const float*)t[10];
+  j->keep = (const float*)t[11]; j->dy = (const float*)t[12];
+  j->running_mean = (float*)t[13]; j->running_var = (float*)t[14]; j->y = (float*)t[15];
+  j->mean = (float*)t[16]; j->rstd = (float*)t[17]; j->x_out = (float*)t[18];
+  j->dgamma = (float*)t[19]; j->dbeta = (float*)t[20];
+  const bool fwd = j->kind == BN1D_FWD || j->kind == BN1D_FWD_SLABS;
+  IGCN_REQUIRE(want_fwd ? fwd : j->kind == BN1D_BWD, "gene_tail: BatchNorm stage of kind %d in a %s table", j->kind,
+               want_fwd ? "forward" : "backward");
+  IGCN_REQUIRE(j->C > 0 && igcn_bn1d_fwd_supported(j->B, j->groups) && (!fwd || !training || j->B / j->groups > 1),
+               "gene_tail: BatchNorm stage not covered (B=%d C=%d groups=%d; igcn_bn1d_fwd_supported)", j->B, j->C,
+               j->groups);
+  IGCN_REQUIRE(j->x && j->gamma && j->beta && j->y && j->mean && j->rstd, "gene_tail: BatchNorm stage: NULL tensor");
+  IGCN_REQUIRE(fwd ? (j->running_mean && j->running_var) : (j->dy && j->dgamma && j->dbeta),
+               "gene_tail: BatchNorm stage: NULL tensor");
+  IGCN_REQUIRE(j->kind != BN1D_FWD_SLABS || (j->n_slabs >= 1 && j->x_out), "gene_tail: slab stage without slabs");
+  return IGCN_OK;
+}
+// the stage in a launch of its own: the kernels and launch shapes of igcn_bn1d_fwd / _fwd_slabs / _bwd
+static void gt_job_alone(const Bn1dJob& j, hipStream_t st) {
+  if (j.kind == BN1D_BWD)
+    hipLaunchKernelGGL(k_bn1d_bwd_reg, dim3(j.C), dim3(256), 0, st, j.B, j.C, j.groups, j.training, j.relu, j.x, j.gamma,
+                       j.beta, (const float*)j.mean, (const float*)j.rstd, j.dy, j.keep, j.y, j.dgamma, j.dbeta);
+  else if (j.kind == BN1D_FWD_SLABS)
+    hipLaunchKernelGGL(k_bn1d_fwd_reg<1>, dim3(j.C), dim3(256), 0, st, j.B, j.C, j.groups, j.training, j.momentum, j.eps,
+                       j.relu, j.x, j.gamma, j.beta, j.keep, j.running_mean, j.running_var, j.y, j.mean, j.rstd,
+                       j.n_slabs, j.x_out);
+  else
+    hipLaunchKernelGGL(k_bn1d_fwd_reg<0>, dim3(j.C), dim3(256), 0, st, j.B, j.C, j.groups, j.training, j.momentum, j.eps,
+                       j.relu, j.x, j.gamma, j.beta, j.keep, j.running_mean, j.running_var, j.y, j.mean, j.rstd, 0,
+                       (float*)nullptr);
+}
+static int gt_product(const int64_t* t, void* stream) {
+  switch ((int)t[0]) {
+    case 1: {
+      const int64_t* p = t + 1;
+      IGCN_REQUIRE(p[15] == 0, "gene_tail: fp32 products only");
+      return igcn_gemm_f32(p[0], p[1], p[2], (const float*)p[3], p[4], p[5], (const float*)p[6], p[7], p[8],
+                           (const float*)p[9], (float*)p[10], p[11], (int)p[12], (int)p[13], (float*)p[14], stream);
+    }
+    case 2:
+      IGCN_REQUIRE(t[1] >= 1 && 2 + 16 * t[1] <= GT_REC, "gene_tail: at most two products per group");
+      return igcn_gemm_f32_grouped((int)t[1], t + 2, stream);
+    case 3:
+      return igcn_small_linear_fwd(t[1], (int)t[2], (int)t[3], (const float*)t[4], (const float*)t[5],
+                                   (const float*)t[6], (const float*)t[7], (float*)t[8], stream);
+    case 4:
+      return igcn_small_linear_bwd(t[1], (int)t[2], (int)t[3], (const float*)t[4], (const float*)t[5],
+                                   (const float*)t[6], (const float*)t[7], (float*)t[8], (float*)t[9], (float*)t[10],
+                                   stream);
+    default:
+      igcn_set_error("gene_tail: product stage of form %d", (int)t[0]);
+      return IGCN_ERR_BADARG;
+  }
+}
+
+// host only: the fused tail covers this gene read-out (igcn_node_linear_bn_apply_map_ok) and BatchNorm stages of Bl
+// samples in `groups` groups (igcn_bn1d_fwd_supported)
+extern "C" int igcn_gene_tail_supported(int F, int D, int N, int J, int64_t nnz, int Bl, int groups) {
+  return igcn_node_linear_bn_apply_map_ok(F, D, N, J, nnz) && igcn_bn1d_fwd_supported(Bl, groups) &&
+         groups <= RO_FIN_MAXG;
+}
+
+// igcn_node_linear_bn_apply_map_fwd (its arguments, its launches) with the latent MLP behind the first product riding:
+// table = {BatchNorm 1, product 2, BatchNorm 2} (GT_REC words each).
+//   training:  k_nlbn_stats + BatchNorm 1 | k_nlbn_finalize | product 2 | k_nlbn_apply_map + BatchNorm 2
+//   else (no statistics pass):  BatchNorm 1 alone | k_nlbn_finalize | product 2 | k_nlbn_apply_map + BatchNorm 2
+extern "C" int igcn_gene_tail_fwd(int B, int F, int N, int groups, const float* x, const float* W, const float* gamma,
+                                  const float* beta, float* running_mean, float* running_var, int training,
+                                  float momentum, float eps, const float* keep, float* out, float* save_mean,
+                                  float* save_rstd, float* scratch, int J, int64_t nnz, const int32_t* row_ptr,
+                                  const int32_t* col, const float* val, int64_t val_stride, float* y,
+                                  const int64_t* table, void* stream) {
+  IGCN_REQUIRE(B > 0 && N > 0 && groups >= 1 && groups <= RO_FIN_MAXG && B % groups == 0,
+               "gene_tail_fwd: bad sizes (1 <= groups <= 8, B divisible by groups)");
+  IGCN_REQUIRE(!training || B / groups > 1, "gene_tail_fwd: need more than one value per node and group to train");
+  IGCN_REQUIRE(val_stride >= nnz && table != nullptr, "gene_tail_fwd: val_stride < nnz, or no table");
+  if (!igcn_node_linear_bn_apply_map_ok(F, 1, N, J, nnz)) {
+    igcn_set_error("gene_tail_fwd: shape not covered (igcn_gene_tail_supported)");
+    return IGCN_ERR_UNSUPPORTED;
+  }
+  Bn1dJob j1, j2;
+  int rc;
+  if ((rc = gt_job(table, training, 1, &j1)) || (rc = gt_job(table + 2 * GT_REC, training, 1, &j2))) return rc;
+  IGCN_REQUIRE(j2.kind == BN1D_FWD, "gene_tail_fwd: the second BatchNorm reads the product as written");
+  hipStream_t st = (hipStream_t)stream;
+  const int cpg = ro_cpg(B, groups);
+  const int gx = igcn_cdiv(N, RO_NL), gy = groups * cpg;
+  if (training) {
+    const dim3 g1((unsigned)(j1.C + gx * gy));
+    if (j1.kind == BN1D_FWD_SLABS)
+      hipLaunchKernelGGL((k_nlbn_stats_ride<BN1D_FWD_SLABS>), g1, dim3(RO_T), 0, st, j1, gx, gy, B, N, groups, x, W, scratch);
+    else
+      hipLaunchKernelGGL((k_nlbn_stats_ride<BN1D_FWD>), g1, dim3(RO_T), 0, st, j1, gx, gy, B, N, groups, x, W, scratch);
+  } else {
+    gt_job_alone(j1, st);
+  }
+  hipLaunchKernelGGL((k_nlbn_finalize<2, 1>), dim3((unsigned)igcn_cdiv(N, 64)), dim3(256), 0, st, B, N, groups, cpg,
+                     training, eps, momentum, x, W, scratch, running_mean, running_var, save_mean, save_rstd);
+  IGCN_CHECK_LAUNCH("gene_tail_fwd");
+  if ((rc = gt_product(table + GT_REC, stream))) return rc;
+  hipLaunchKernelGGL((k_nlbn_apply_map_ride<BN1D_FWD>), dim3((unsigned)(j2.C + B)), dim3(SPMM_LT),
+                     (size_t)N * sizeof(float), st, j2, B, N, groups, x, W, gamma, beta, save_mean, save_rstd, keep, out,
+                     J, val_stride, row_ptr, col, val, y);
+  IGCN_CHECK_LAUNCH("gene_tail_fwd");
+  return IGCN_OK;
+}
+
+// igcn_node_linear_bn_bwd of that read-out (F = 2, D = 1: its arguments, its launches) with the latent MLP's backward
+// riding: table = {BatchNorm 2, products of layer 2 (dX | dW), BatchNorm 1, products of layer 1}.
+//   k_nlbn_bwd_stats + BatchNorm 2 | products 2 | chunk sum | k_nlbn_bwd_apply + BatchNorm 1 | products 1 | final sums
+extern "C" int igcn_gene_tail_bwd(int B, int F, int N, int groups, int training, const float* x, const float* W,
+                                  const float* gamma, const float* beta, const float* save_mean,
+                                  const float* save_rstd, const float* dout, const float* keep, float* dx, float* dW,
+                                  float* dgb, float* scratch, const int64_t* table, void* stream) {
+  IGCN_REQUIRE(B > 0 && N > 0 && groups >= 1 && B % groups == 0 && F == 2 && table != nullptr,
+               "gene_tail_bwd: bad sizes (F = 2, B divisible by groups)");
+  Bn1dJob j2, j1;
+  int rc;
+  if ((rc = gt_job(table, training, 0, &j2)) || (rc = gt_job(table + 2 * GT_REC, training, 0, &j1))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int cpg = ro_cpg(B, groups);
+  const int gx = igcn_cdiv(N, RO_NL), gy = groups * cpg;
+  float* stats = scratch;                                    // the layout of igcn_node_linear_bn_bwd
+  float* dgg = stats + (size_t)groups * cpg * 2 * N;
+  float* aux = scratch + (((size_t)(dgg - scratch) + (size_t)groups * 2 * N + 3) & ~(size_t)3);
+  hipLaunchKernelGGL(k_nlbn_bwd_stats_ride, dim3((unsigned)(j2.C + gx * gy)), dim3(RO_T), 0, st, j2, gx, gy, B, N,
+                     groups, x, W, gamma, beta, save_mean, save_rstd, dout, keep, stats);
+  IGCN_CHECK_LAUNCH("gene_tail_bwd");
+  if ((rc = gt_product(table + GT_REC, stream))) return rc;
+  if ((rc = igcn_launch_reduce_rows(stats, cpg, (int64_t)groups * 2 * N, groups * 2 * N, dgg, 0, st))) return rc;
+  hipLaunchKernelGGL(k_nlbn_bwd_apply_ride, dim3((unsigned)(j1.C + gx * gy)), dim3(RO_T), 0, st, j1, gx, gy, B, N,
+                     groups, training, x, W, gamma, beta, save_mean, save_rstd, dout, keep, (const float*)dgg, 1, aux, dx,
+                     aux);
+  IGCN_CHECK_LAUNCH("gene_tail_bwd");
+  if ((rc = gt_product(table + 3 * GT_REC, stream))) return rc;
+  if ((rc = igcn_launch_reduce_rows_final(dgg, groups, 2 * (int64_t)N, 2 * N, dgb, st))) return rc;
+  return igcn_launch_reduce_rows_final(aux, (int64_t)gx * gy, 2, 2, dW, st);
 }

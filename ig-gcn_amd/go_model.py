@@ -89,6 +89,11 @@ class Gene_ontology_network(nn.Module):
         self._dropout_enabled = True        # parity tests switch every dropout off
 
     # ---------------------------------------------------------------------------------------------
+    # The gene read-out's launches carry the latent MLP's BatchNorm stages (ops.GeneTail, where ops.gene_tail_supported)
+    # in the CAPTURED step, whose launches run back to back; False: never.  The eager step keeps the separate ops (it
+    # is bound by the host, and its tests observe the three ops one by one); forward(tail_ride=True) rides there too.
+    tail_ride = True
+
     def _batch_counters(self):
         """num_batches_tracked of the BatchNorms this forward runs in training mode (go_model.py:119-146)."""
         bns = (self.conc_for_attention[1], self.B[0], self.B_D[0], self.latent[1], self.latent[5])
@@ -172,12 +177,44 @@ class Gene_ontology_network(nn.Module):
                                         bn.momentum, bn.eps, groups, keep)
         return self._bn_relu(ops.linear(x, lin.weight, lin.bias), bn, groups, keep)
 
-    def forward(self, data, T=None, device=None, groups=1, extra_dropout=()):
+    def _gene_tail(self, x, inp2, masks, groups, tail_ride):
+        """Gene decoding of the decoder output ``x`` [B,f,N] (:278-282) and the latent projection of the read-out
+        ``inp2`` [B,n_top] (:138-146,285) -> (x_d [B,54], latent [B,l_dim])."""
+        # on the CSR route (from 256 samples up) the read-out's apply pass runs inside the map's forward launch
+        rider = (self.gene_t_csr, self.t_D[0]) \
+            if ops.node_linear_bn_map_supported(x, self.conc_D.weight, self.gene_t_csr, self.t_D[0]) else None
+        bn_d, (lin1, bn1, lin2, bn2) = self.B_D[0], (self.latent[i] for i in (0, 1, 4, 5))
+        latent = None
+        if tail_ride and rider is not None and ops.gene_tail_supported(x, inp2, self.conc_D.weight, bn_d, *rider, lin1,
+                                                                       bn1, lin2, bn2, groups):
+            # the read-out's launches carry the latent MLP's BatchNorm stages (ops.GeneTail): one op for both
+            if self.training:
+                self._tracked += [bn.num_batches_tracked for bn in (bn_d, bn1, bn2) if bn.track_running_stats]
+            out_d3, latent = ops.GeneTail.apply(
+                x, inp2, self.conc_D.weight, bn_d.weight, bn_d.bias, bn_d.running_mean, bn_d.running_var, bn_d.momentum,
+                bn_d.eps, masks["out_d"], *rider, lin1.weight, bn1.weight, bn1.bias, bn1.running_mean, bn1.running_var,
+                bn1.momentum, bn1.eps, masks["h"], lin2.weight, bn2.weight, bn2.bias, bn2.running_mean, bn2.running_var,
+                bn2.momentum, bn2.eps, self.training, groups)
+        else:
+            out_d3 = self._node_linear_bn(x, self.conc_D.weight, bn_d, groups, masks["out_d"], rider)
+        out_d = out_d3.squeeze(2)                                                                # [B,N]
+        if rider is not None:
+            out_d._igcn_map_fwd = rider + (out_d3._igcn_map_y,)
+        x_d = ops.SparseMap.apply(out_d, self.gene_t_csr, self.t_D[0]).squeeze(1)               # [B, 54]
+        if latent is None:
+            h = self._lin_bn_relu(inp2, lin1, bn1, groups, masks["h"])
+            latent = self._lin_bn_relu(h, lin2, bn2, groups)
+        return x_d, latent
+
+    def forward(self, data, T=None, device=None, groups=1, extra_dropout=(), tail_ride=None):
         """``groups`` > 1: ``data`` holds that many equally sized batches stacked along dim 0 that are treated as
         successive forward calls (own BatchNorm statistics, running statistics updated in order).
         ``extra_dropout`` [(shape, p), ...]: dropout sites of the caller drawn by the same launch; their factors are
-        left in ``self.extra_masks``."""
+        left in ``self.extra_masks``.  ``tail_ride``: True / False decide for this call; None: the class attribute, inside
+        a stream capture (the genetics-only trainer passes False: it keeps the separate ops)."""
         bsz, dev = data.shape[0], data.device
+        if tail_ride is None:
+            tail_ride = self.tail_ride and data.is_cuda and torch.cuda.is_current_stream_capturing()
         self._tracked = []
         self._counters_done = False
         masks, self.extra_masks = self._dropout_masks(bsz, dev, extra_dropout, groups)
@@ -229,18 +266,8 @@ class Gene_ontology_network(nn.Module):
             csr = self.dec_csr[j]
             x = ops.GoDecodeLN.apply(x, self.w_out[j].weight, self.w_s_loop_out[j].weight, csr, self.G_B_D[j].weight,
                                      self.G_B_D[j].bias, keeps[self.n_l + j], self.G_B_D[j].eps)
-        # gene decoding (:278-282)
-        # on the CSR route (from 256 samples up) the read-out's apply pass runs inside the map's forward launch
-        rider = (self.gene_t_csr, self.t_D[0]) \
-            if ops.node_linear_bn_map_supported(x, self.conc_D.weight, self.gene_t_csr, self.t_D[0]) else None
-        out_d3 = self._node_linear_bn(x, self.conc_D.weight, self.B_D[0], groups, masks["out_d"], rider)
-        out_d = out_d3.squeeze(2)                                                                # [B,N]
-        if rider is not None:
-            out_d._igcn_map_fwd = rider + (out_d3._igcn_map_y,)
-        x_d = ops.SparseMap.apply(out_d, self.gene_t_csr, self.t_D[0]).squeeze(1)               # [B, 54]
-        # latent projection (:138-146,285)
-        h = self._lin_bn_relu(inp_out.view(bsz, -1), self.latent[0], self.latent[1], groups, masks["h"])
-        latent = self._lin_bn_relu(h, self.latent[4], self.latent[5], groups)
+        # gene decoding (:278-282) and latent projection (:138-146,285)
+        x_d, latent = self._gene_tail(x, inp_out.view(bsz, -1), masks, groups, tail_ride)
         if self._tracked and not self._counters_done:  # num_batches_tracked of the five BatchNorms: one launch (with
             torch._foreach_add_(self._tracked, groups)  # dropout on, the mask launch has advanced them already)
         self._tracked = []

@@ -4013,3 +4013,7 @@ def _front_backward(ctx, dxcat, dxcat2, d_e, d_regp, d_full):
         return dx
 
     return (dx, dprob, dpb, dsnps), _sgcn_stack_backward(*stack, mask_call)[2]
+
+
+# the gene read-out that carries the latent MLP: its own module (it is built from the ops above)
+from .gene_tail import GeneTail, gene_tail_supported  # noqa: E402,F401

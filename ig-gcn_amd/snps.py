@@ -82,7 +82,7 @@ def losses_snps(model, data, label, lambda0=SNPS_LAMBDA0, temperature=None, lazy
     if training and b == 1:
         raise ValueError("losses_snps: training mode needs more than one sample per batch (BatchNorm1d over the batch)")
     extra = [((b, bn.num_features), float(d1.p)), ((b, lin1.weight.shape[0]), float(d2.p))]
-    latent, x_hat = model(data, temperature, data.device, extra_dropout=extra)[:2]
+    latent, x_hat = model(data, temperature, data.device, extra_dropout=extra, tail_ride=False)[:2]
     keep1, keep2 = model.extra_masks
     y = label.reshape(-1).to(data.dtype)
     lam = float(lambda0)

@@ -819,6 +819,34 @@ int igcn_bn1d_fwd_slabs(int B, int C, int groups, const float* slabs, int n_slab
                         const float* beta, float* running_mean, float* running_var, int training, float momentum,
                         float eps, int relu, const float* keep, float* y, float* save_mean, float* save_rstd,
                         void* stream);
+/* The gene read-out (igcn_node_linear_bn_apply_map_fwd / igcn_node_linear_bn_bwd with F = 2, D = 1: the leading
+ * arguments are theirs) whose launches carry the latent MLP's BatchNorm1d stages (kernel/go_model.py:278-285): the
+ * first C workgroups of a carrying launch run a stage's channels, the others the read-out pass — the same kernel
+ * bodies as the separate launches, so every output is theirs bit for bit; the products between the stages are launched
+ * by the same call.  A stage whose carrier does not launch (forward without training: no statistics pass) gets the
+ * launch it has in igcn_bn1d_*.  igcn_gene_tail_supported: igcn_node_linear_bn_apply_map_ok for the read-out and
+ * igcn_bn1d_fwd_supported for stages of Bl samples.
+ * `table` (host): records of 40 int64 words.
+ *   BatchNorm stage {kind, B, C, groups, relu, n_slabs, momentum, eps, x, gamma, beta, keep, dy, running_mean,
+ *     running_var, y, mean, rstd, x_out, dgamma, dbeta}: kind 1 = igcn_bn1d_fwd, 2 = igcn_bn1d_fwd_slabs (x = slabs),
+ *     3 = igcn_bn1d_bwd (mean / rstd = the saved ones, y = dx); momentum and eps as the bit pattern of a double.
+ *   product stage {form, ...}: 1 = igcn_gemm_f32 of the igcn_gemm_f32_grouped record behind it, 2 = {n <= 2, n such
+ *     records} as one igcn_gemm_f32_grouped, 3 = igcn_small_linear_fwd {R, K, C, x, keep, W, b, y},
+ *     4 = igcn_small_linear_bwd {R, K, C, x, keep, W, dy, dx, dwb, scratch}.
+ * forward  table = {BatchNorm 1, product 2, BatchNorm 2}: statistics + BatchNorm 1 | finalize | product 2 |
+ *          apply-and-map + BatchNorm 2 (product 1 is the caller's, launched before).
+ * backward table = {BatchNorm 2, products 2, BatchNorm 1, products 1}: statistics + BatchNorm 2 | products 2 | chunk
+ *          sum | apply + BatchNorm 1 | products 1 | the read-out's parameter-gradient sums (deferred as usual). */
+int igcn_gene_tail_supported(int F, int D, int N, int J, int64_t nnz, int Bl, int groups);
+int igcn_gene_tail_fwd(int B, int F, int N, int groups, const float* x, const float* W, const float* gamma,
+                       const float* beta, float* running_mean, float* running_var, int training, float momentum,
+                       float eps, const float* keep, float* out, float* save_mean, float* save_rstd, float* scratch,
+                       int J, int64_t nnz, const int32_t* row_ptr, const int32_t* col, const float* val,
+                       int64_t val_stride, float* y, const int64_t* table, void* stream);
+int igcn_gene_tail_bwd(int B, int F, int N, int groups, int training, const float* x, const float* W,
+                       const float* gamma, const float* beta, const float* save_mean, const float* save_rstd,
+                       const float* dout, const float* keep, float* dx, float* dW, float* dgb, float* scratch,
+                       const int64_t* table, void* stream);
 
 /* Dropout factors of every site of a forward pass in ONE launch (the reference draws them site by site: nn.Dropout /
  * nn.Dropout2d / F.dropout, kernel/go_model.py:104,113,128,136,143, kernel/sgcn_img_snp.py:289,299).  out [total]:
